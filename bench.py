@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Newton steps/sec on the dense KKT hot path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one Full Newton step (NewtonType.Full, StepSolverType.Symmetric,
 SURVEY.md 8d): evaluate c, g at the device point -> active-set mask -> gather-assemble
@@ -14,7 +14,12 @@ N > 1: one process per GPU (launched by torch.distributed.run); each rank owns a
 independent instance of the same size (seed = rank): weak scaling over instances, and
 per step ONE RCCL all-gather of the ranks' residual norms ||F(z)||_2.
 
-Prints one JSON line (rank 0) with `roofline` (dominant launch = k_chain_update, the
+A plain run sets up, warms up, times the K steps and prints one JSON line (rank 0) whose
+`value` and `ms_per_step` come from those steps; `--dump-outputs DIR` also writes what the
+last timed step left for its caller (rank 0's point, active mask and residual norms) as
+DIR/<name>.npy.  Everything else is measured only with `--full`:
+
+With `--full` the line also carries `roofline` (dominant launch = k_chain_update, the
 diagonal chain beside the FP64-MFMA trailing update, timed with HIP events on the solver's
 stream around the PRODUCTION launches in an instrumented pass over the same steps; the
 per-kernel view of the unfused schedule rides along under its own key) and `cpu_baseline`
@@ -96,6 +101,23 @@ def pmc_traffic(kernel):
         return None
 
 
+# --dump-outputs: at most this many bytes in all (the largest workload, batch256, writes ~4 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Write each array as path/<name>.npy: float64 as computed, boolean masks as float32 0 / 1,
+    so that two builds can be compared output for output on the same seeded inputs."""
+    out = {k: (np.asarray(a, dtype=np.float32) if np.asarray(a).dtype == np.bool_
+               else np.asarray(a, dtype=np.float64)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def bench_batched(args, wl, rank, local_rank, world, dist, torch, emit=True, steps=None, warmup=None):
     """BASELINE configs[3]: B independent instances, contiguous shards per rank; every rank
     advances its shard as ONE device batch (pgf_batch_*), one all-gather of norms per step."""
@@ -120,9 +142,9 @@ def bench_batched(args, wl, rank, local_rank, world, dist, torch, emit=True, ste
             bd.advance_outer()
         return bd.step()
 
-    # parity of instance 0's first step against the CPU restatement (rank 0, bounded)
+    # parity of instance 0's first step against the CPU restatement (rank 0, bounded; --full)
     parity = cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and emit:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and emit:
         rate, recs, csteps, cel = cpu_baseline(problems.dense_qp(n, m, seed=0), args.cpu_seconds)
         bd.step_local()
         xg, yg = bd.points()
@@ -172,13 +194,18 @@ def bench_batched(args, wl, rank, local_rank, world, dist, torch, emit=True, ste
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # EVERY rank walks the same steps (each one ends in the all-gather); only rank 0 records
+    if emit and rank == 0 and args.dump_outputs:
+        xg, yg = bd.points()
+        dump_outputs(args.dump_outputs, dict(x=xg, y=yg, mask=bd.masks(),
+                                             residual_norms=norms.cpu().numpy()))
+    # --full: EVERY rank walks the same steps (each one ends in the all-gather); only rank 0 records
     roof = None
-    if rank == 0:
-        bd.profile(True)
-    for i in range(nsteps):
-        one_step(i)
-    if rank == 0:
+    if args.full:
+        if rank == 0:
+            bd.profile(True)
+        for i in range(nsteps):
+            one_step(i)
+    if args.full and rank == 0:
         pr = bd.profile_read()
         bd.profile(False)
         if pr["update_launches"] > 0 and pr["update_ms"] > 0:
@@ -283,12 +310,20 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="dense_qp_n4096_m1024", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU "
+                         "baselines and parity against the oracle, the instrumented roofline "
+                         "passes, the back-solve step and the nested records of the default workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the nested records of the default workload at --gpus 1 "
+                    help="with --full: skip the nested records of the default workload at --gpus 1 "
                          "(batch256, shard32, plugin_step)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -360,10 +395,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    # parity of the first step against the CPU restatement (rank 0 only, bounded)
+    # parity of the first step against the CPU restatement (rank 0 only, bounded; --full)
     parity = None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not wl.get("no_cpu"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not wl.get("no_cpu"):
         rate, recs, csteps, cel = cpu_baseline(problem, args.cpu_seconds)
         dn.step()
         xg, yg = dn.point()
@@ -442,20 +477,26 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        xg, yg = dn.point()
+        dump_outputs(args.dump_outputs, dict(x=xg, y=yg, mask=dn.mask(),
+                                             residual_norms=(norms_all if dist is not None
+                                                             else norms_local).cpu().numpy()))
 
-    # instrumented pass: HIP events around every trailing-update launch (same steps)
+    # --full, instrumented pass: HIP events around every trailing-update launch (same steps)
     # EVERY rank walks the same steps (each one ends in the all-gather); only rank 0 records
     roof = None
-    dn.set_outer(x0, y0, 1.0, 1.0)
-    if rank == 0:
-        dn.profile(True)
-    for i in range(args.steps):
-        one_step(i)
     pr = pp = None
-    if rank == 0:
-        pr = dn.profile_read()
-        dn.profile(False)
-    if not is_sparse:
+    if args.full:
+        dn.set_outer(x0, y0, 1.0, 1.0)
+        if rank == 0:
+            dn.profile(True)
+        for i in range(args.steps):
+            one_step(i)
+        if rank == 0:
+            pr = dn.profile_read()
+            dn.profile(False)
+    if args.full and not is_sparse:
         # the PRODUCTION launches: a second instrumented pass, one span per launch -- walked by
         # every rank as well (a step ends in the all-gather: rank 0 alone would leave the others
         # behind in a different collective)
@@ -467,7 +508,7 @@ def main():
         if rank == 0:
             pp = dn.profile_read()
             dn.profile(False)
-    if rank == 0:
+    if args.full and rank == 0:
         if is_sparse and pr["update_launches"] > 0 and pr["update_ms"] > 0:
             # banded path: the dominant piece is the block-cyclic-reduction solve (one span =
             # extract + log2(N/8) invert/reduce levels + the back-substitution levels); the
@@ -560,9 +601,9 @@ def main():
 
     # SURVEY.md 8d "reported separately": the back-solve step of the Simplified policy
     # (2nd+ Newton step of an outer iteration: residual, reduced rhs, forward + backward
-    # triangular solves, update -- no assembly, no factorisation).  Outside the timed region.
+    # triangular solves, update -- no assembly, no factorisation).  Outside the timed region; --full.
     backsolve = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         dn.close()
         ds = DeviceNewton(problem, "Simplified", x0, y0, 1.0, 1.0, device=local_rank)
         ds.step()  # factorises
@@ -580,9 +621,9 @@ def main():
 
     # BASELINE configs[3] (what north_star names for multi-GPU scaling): at N > 1 the same
     # launch also times the 256-instance batch, 256 / N instances per rank, one all-gather of
-    # 256 residual norms per batched step -- a nested record, strong scaling over N
+    # 256 residual norms per batched step -- a nested record, strong scaling over N (--full)
     batch_rec = shard_rec = plugin_rec = None
-    if args.workload == "dense_qp_n4096_m1024" and not (world == 1 and args.no_extras):
+    if args.full and args.workload == "dense_qp_n4096_m1024" and not (world == 1 and args.no_extras):
         dn.close()
         dn = None
         nb_steps = min(args.steps, 8 if world > 1 else 20)
