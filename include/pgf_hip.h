@@ -139,6 +139,12 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
                            const int *JTrow, const int *JTmap);
+/* block size of the banded solve, after pgf_sparse_set_pattern (which selects B = 0):
+ *   B = 0: automatic -- bw <= 8: 8 x 8 block cyclic reduction; bw 9 .. 10: the sequential band
+ *          walk; bw 11 .. 64: block cyclic reduction with the smallest B in {16, 32, 64} >= bw;
+ *   B = 8, 16, 32, 64: that block size (PGF_INVALID if B < bw).
+ * Invalidates the factorisation; the work arrays are sized for the chosen B. */
+int pgf_sparse_set_block_size(pgf_handle h, int B);
 /* values of H = lag_hess(x, y) and J = cons_jac(x) in pattern order (update_derivs) */
 int pgf_sparse_set_values(pgf_handle h, const double *Hval, const double *Jval);
 /* q and b of a linear-quadratic problem whose Q, A were given through the sparse pattern */

@@ -51,6 +51,7 @@ SIGNATURES = {
     "pgf_get_kkt": (C.c_int, [_h, _dp, C.c_int64]),
     "pgf_sparse_set_pattern": (C.c_int, [_h, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int, _ip, _ip, _ip,
                                          _ip, _ip, _ip]),
+    "pgf_sparse_set_block_size": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_values": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_vectors": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_problem": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,

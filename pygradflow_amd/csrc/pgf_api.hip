@@ -597,16 +597,35 @@ static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
   return hipGetLastError();
 }
 
+// The banded system is solved by block cyclic reduction (B = 8: pgf_sparse.hip, B = 16, 32, 64:
+// pgf_band_wide.hip) or, for B = 0 (bw 9 .. 10) and under PGF_BAND_SEQ at B = 8, by the
+// sequential band walk (k_band_factor; supports bw <= 10 only)
+static bool sp_cyclic(const SparseDev &sp) {
+  return sp.B > 8 || (sp.B == 8 && !getenv("PGF_BAND_SEQ"));
+}
+static void sp_cyclic_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+  if (sp.B > 8)
+    sp_launch_bw_solve(s, sp, N, flags, guard);
+  else
+    sp_launch_bcr_solve(s, sp, N, flags, guard);
+}
+static void sp_cyclic_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
+  if (sp.B > 8)
+    sp_launch_bw_residual(s, sp, N, flags);
+  else
+    sp_launch_band_residual(s, sp, N, flags);
+}
+
 // enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in row N
 static int factor_async(pgf_handle h, bool with_rhs) {
   if (h->sparse) {
     // band assembly + banded LDL^T; the permuted rhs in sp.brhs is forward-substituted on
     // the way (harmless when the caller only wants the factor)
     sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
-    if (h->sp.bw <= 8 && !getenv("PGF_BAND_SEQ")) {
+    if (sp_cyclic(h->sp)) {
       // cyclic-reduction mode keeps the assembled band intact; run one reduction (on
       // whatever right-hand side is there) only to obtain the pivot flags / inertia
-      sp_launch_bcr_solve(h->stream, h->sp, h->n + h->m, h->fac.flags, /*guard=*/false);
+      sp_cyclic_solve(h->stream, h->sp, h->n + h->m, h->fac.flags, /*guard=*/false);
     } else {
       sp_launch_factor(h->stream, h->sp, h->n + h->m, h->fac.flags);
     }
@@ -858,9 +877,9 @@ static int sparse_refine(pgf_handle h, bool swapped, bool with_step) {
   for (int it = 0; it < 2 && rel > h->refine_tol && rel < 1.0; ++it) {
     HIPCHK(h, hipMemcpyAsync(sp.bsol, sp.brhs, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(sp.brhs, sp.bres, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
-    sp_launch_bcr_solve(s, sp, Nf, h->fac.flags, /*guard=*/false);
+    sp_cyclic_solve(s, sp, Nf, h->fac.flags, /*guard=*/false);
     sp_launch_band_axpy(s, Nf, sp.bsol, sp.brhs);
-    sp_launch_band_residual(s, sp, Nf, h->fac.flags);
+    sp_cyclic_residual(s, sp, Nf, h->fac.flags);
     HIPCHK(h, hipMemcpyAsync(h->h_bred, sp.bred, (size_t)2 * sp.nred * sizeof(double), hipMemcpyDeviceToHost, s));
     if (with_step) {
       unswap();
@@ -935,9 +954,9 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
     const int Nf = h->n + h->m;
     sp_launch_rhs(s, h->sp, h->n, h->m, h->mask, h->F, h->b0full, h->fact, h->sp.Hb0, h->sp.Jb0);
     *did_factor = false;
-    if (h->sp.bw <= 8 && !getenv("PGF_BAND_SEQ")) {
+    if (sp_cyclic(h->sp)) {
       // block cyclic reduction: assemble (only when the mask / derivatives changed) and
-      // solve in log2(N/8) parallel levels; the band itself is left untouched, so a
+      // solve in log2(N/B) parallel levels; the band itself is left untouched, so a
       // back-solve step just runs the reduction again on the same band (~1 ms)
       if (!h->fac.factored) sp_launch_assemble(s, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
       hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -952,14 +971,16 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
         }
         (void)hipEventRecord(e0, s);
       }
-      sp_launch_bcr_solve(s, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
+      sp_cyclic_solve(s, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
       h->sp_guarded = h->refine_mode != 0;
       if (e0) {
         (void)hipEventRecord(e1, s);
         h->prof.update_spans.emplace_back(e0, e1);
         // algorithmic bytes of one cyclic-reduction solve: every block (D, L, U, inv D:
-        // 4 x 512 B, rhs + solution 128 B) is written once and read about twice
-        h->prof.update_flops.push_back(3.0 * (double)((Nf + 7) / 8) * (4 * 512 + 128));
+        // 4 x 8 B^2, rhs + solution 16 B) is written once and read about twice
+        const double Bk = (double)h->sp.B;
+        h->prof.update_flops.push_back(3.0 * (double)((Nf + h->sp.B - 1) / h->sp.B) *
+                                       (4 * 8 * Bk * Bk + 16 * Bk));
       }
       if (!h->sp_guarded)
         HIPCHK(h, hipMemcpyAsync(h->fac.h_flags, h->fac.flags, 4 * sizeof(int),
@@ -1111,10 +1132,10 @@ int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
     (void)hipSetDevice(h->device);
     if ((rc = up(h, h->rhs, rhs, (size_t)Nf * sizeof(double)))) return rc;
     sp_launch_permute(h->stream, h->sp, Nf, h->rhs, h->sp.brhs, 0);
-    if (h->sp.bw <= 8 && !getenv("PGF_BAND_SEQ")) {
+    if (sp_cyclic(h->sp)) {
       // cyclic reduction keeps the assembled band intact: (re)assemble only when stale
       if (!h->fac.factored) sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
-      sp_launch_bcr_solve(h->stream, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
+      sp_cyclic_solve(h->stream, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
       h->sp_guarded = h->refine_mode != 0;
       if (h->sp_guarded)
         HIPCHK(h, hipMemcpyAsync(h->h_bred, h->sp.bred, (size_t)2 * h->sp.nred * sizeof(double),
@@ -1219,13 +1240,49 @@ int pgf_get_kkt(pgf_handle h, double *K_out, int64_t ldk_out) {
 }
 
 // ---------------------------------------------------------------- sparse (banded) mode
+// bw <= 8: 8 x 8 cyclic reduction; 9 .. 10: the sequential walk; 11 .. 64: the smallest of
+// 16, 32, 64 that holds the band
+static int auto_block_size(int bw) {
+  if (bw <= 8) return 8;
+  if (bw <= 10) return 0;
+  return bw <= 16 ? 16 : bw <= 32 ? 32 : 64;
+}
+
+// work arrays of the cyclic reduction for block size B (none for the walk, B = 0).  B = 8 keeps
+// two block sets (k_bcr_level2 reads one and writes the other); the wide kernels use one.
+static int sp_alloc_blocks(pgf_handle h, int B) {
+  SparseDev &sp = h->sp;
+  for (double **q : {&sp.bD, &sp.bL, &sp.bU, &sp.bDinv, &sp.bF})
+    if (*q) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+  if (sp.bneg) {
+    (void)hipFree(sp.bneg);
+    sp.bneg = nullptr;
+  }
+  sp.B = B;
+  sp.bX = sp.brhs;  // the back-substitution writes the solution where the step update reads it
+  const int N = h->n + h->m;
+  const size_t nsets = (B == 8) ? 2 : 1, Bk = (size_t)(B ? B : 8);
+  const size_t nbk = ((size_t)N + Bk - 1) / Bk + 1;
+  HIPCHK(h, dalloc(&sp.bD, nsets * nbk * Bk * Bk));
+  HIPCHK(h, dalloc(&sp.bL, nsets * nbk * Bk * Bk));
+  HIPCHK(h, dalloc(&sp.bU, nsets * nbk * Bk * Bk));
+  HIPCHK(h, dalloc(&sp.bDinv, nbk * Bk * Bk));
+  HIPCHK(h, dalloc(&sp.bF, nsets * nbk * Bk));
+  sp.bstride = (int64_t)nbk;
+  HIPCHK(h, dalloc(&sp.bneg, nbk));
+  return PGF_OK;
+}
+
 int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const int *Hptr,
                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
                            const int *JTrow, const int *JTmap) {
   if (!h) return PGF_INVALID;
   if (!h->sparse) return fail(h, PGF_NOT_READY, "handle was not created with PGF_CREATE_SPARSE");
-  if (bw < 0 || bw > 10) return fail(h, PGF_INVALID, "bandwidth must be 0..10 in this version");
+  if (bw < 0 || bw > 64) return fail(h, PGF_INVALID, "bandwidth must be 0..64 in this version");
   if (nnzH < 0 || nnzJ < 0 || !pos || !Hptr || !Jptr || !JTptr)
     return fail(h, PGF_INVALID, "null pattern");
   (void)hipSetDevice(h->device);
@@ -1247,20 +1304,15 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
   if ((rc = up_new(h, &sp.JTptr, JTptr, (size_t)n + 1))) return rc;
   if ((rc = up_new(h, &sp.JTrow, JTrow, (size_t)nnzJ))) return rc;
   if ((rc = up_new(h, &sp.JTmap, JTmap, (size_t)nnzJ))) return rc;
-  for (double **q : {&sp.Hval, &sp.Jval, &sp.band, &sp.brhs, &sp.Hb0, &sp.Jb0, &sp.bD, &sp.bL, &sp.bU,
-                     &sp.bDinv, &sp.bF, &sp.brhs0, &sp.bres, &sp.bsol})
+  for (double **q : {&sp.Hval, &sp.Jval, &sp.band, &sp.brhs, &sp.Hb0, &sp.Jb0, &sp.brhs0, &sp.bres, &sp.bsol})
     if (*q) {
       (void)hipFree(*q);
       *q = nullptr;
     }
-  if (sp.bneg) {
-    (void)hipFree(sp.bneg);
-    sp.bneg = nullptr;
-  }
   HIPCHK(h, dalloc(&sp.Hval, (size_t)nnzH));
   HIPCHK(h, dalloc(&sp.Jval, (size_t)nnzJ));
   HIPCHK(h, dalloc(&sp.band, (size_t)(N + 1) * sp.ldb));
-  HIPCHK(h, dalloc(&sp.brhs, (size_t)N + 16));  // whole 8-row blocks: the cyclic reduction's X
+  HIPCHK(h, dalloc(&sp.brhs, (size_t)N + 64));  // whole B-row blocks: the cyclic reduction's X
   HIPCHK(h, dalloc(&sp.brhs0, (size_t)N + 1));
   HIPCHK(h, dalloc(&sp.bres, (size_t)N + 1));
   HIPCHK(h, dalloc(&sp.bsol, (size_t)N + 1));
@@ -1277,20 +1329,28 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
   HIPCHK(h, hipHostMalloc((void **)&h->h_bred, ((size_t)3 * sp.nred + 4) * sizeof(double)));
   HIPCHK(h, dalloc(&sp.Hb0, (size_t)n + 1));
   HIPCHK(h, dalloc(&sp.Jb0, (size_t)m + 1));
-  {
-    const size_t nbk = (size_t)(N + 7) / 8 + 1;
-    HIPCHK(h, dalloc(&sp.bD, 2 * nbk * 64));
-    HIPCHK(h, dalloc(&sp.bL, 2 * nbk * 64));
-    HIPCHK(h, dalloc(&sp.bU, 2 * nbk * 64));
-    HIPCHK(h, dalloc(&sp.bDinv, nbk * 64));
-    HIPCHK(h, dalloc(&sp.bF, 2 * nbk * 8));
-    sp.bstride = (int64_t)nbk;
-    sp.bX = sp.brhs;  // the back-substitution writes the solution where the step update reads it
-    HIPCHK(h, dalloc(&sp.bneg, nbk));
-  }
+  sp.B = 0;
+  if ((rc = sp_alloc_blocks(h, auto_block_size(bw)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   sp.active = true;
   sp.values_set = false;
+  invalidate_factor(h);
+  return PGF_OK;
+}
+
+int pgf_sparse_set_block_size(pgf_handle h, int B) {
+  if (!h) return PGF_INVALID;
+  if (!h->sparse || !h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
+  if (B != 0 && B != 8 && B != 16 && B != 32 && B != 64)
+    return fail(h, PGF_INVALID, "block size must be 0 (automatic), 8, 16, 32 or 64");
+  if (B != 0 && B < h->sp.bw)
+    return fail(h, PGF_INVALID, "block size is smaller than the half-bandwidth");
+  (void)hipSetDevice(h->device);
+  const int want = B ? B : auto_block_size(h->sp.bw);
+  if (want == h->sp.B) return PGF_OK;
+  int rc;
+  if ((rc = sp_alloc_blocks(h, want))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   invalidate_factor(h);
   return PGF_OK;
 }

@@ -1,0 +1,464 @@
+// Wide block cyclic reduction of the banded KKT system: half-bandwidths 11 .. 64 (or any
+// bw <= B on request), B x B blocks with B in {16, 32, 64}.
+//
+// Same algorithm as the 8 x 8 code in pgf_sparse.hip (see the comment above k_bcr_extract):
+// with B >= bw the permuted band is block tridiagonal, D_i (diagonal), L_i (coupling to the
+// left neighbour), U_i = L_{i+1}^T.  Each level eliminates every other block row:
+//   kept block i, eliminated neighbours i-s, i+s:
+//     alpha = L_i inv(D_{i-s}),  gamma = U_i inv(D_{i+s})
+//     D_i -= alpha U_{i-s} + gamma L_{i+s};  f_i -= alpha f_{i-s} + gamma f_{i+s}
+//     L_i <- -alpha L_{i-s};  U_i <- -gamma U_{i+s}
+// The eliminated blocks are inverted without pivoting (Gauss-Jordan; every principal block and
+// Schur complement of a symmetric permutation of a quasi-definite matrix is quasi-definite, and
+// the residual guard catches the rest).  Their pivots give the inertia (Haynsworth additivity),
+// counted per block in negcnt[i] and summed once at the end.
+//
+// Differences from the 8 x 8 code:
+//   * one 256-thread workgroup per block; the B x B x B products run on v_mfma_f64_16x16x4_f64
+//     (one 16 x 16 output tile per wavefront and pass: 1, 4 or 16 tiles for B = 16, 32, 64);
+//   * no LDS-resident tail: a 64 x 64 f64 block is 32 KiB, so the 32-block tail of the 8 x 8
+//     code would need 4 MiB.  The levels run down to ONE block (tail threshold 1 for every B),
+//     and that block is inverted and solved by a single workgroup (k_bw_last);
+//   * one level per launch pair (invert, then reduce): at B >= 16 the block count, and with it
+//     the number of levels, is 2 .. 8 x smaller than at B = 8, and the levels do real
+//     arithmetic rather than being bound by their launch.
+// Every solve re-runs the reduction on the intact band, as the 8 x 8 code does.
+//
+// Block storage (one set): D, L, U, inv D row-major B x B at block * B * B; F at block * B.
+#include "pgf_sparse.h"
+
+typedef double bw_double4 __attribute__((ext_vector_type(4)));
+
+#define BW_THREADS 256
+
+__device__ __forceinline__ double bw_recip(double d) {
+  double r = __builtin_amdgcn_rcp(d);
+  double e = fma(-d, r, 1.0);
+  r = fma(r, e, r);
+  e = fma(-d, r, 1.0);
+  return fma(r, e, r);
+}
+
+// block extraction from the band (+ identity padding of the last block); the right-hand side
+// is copied to F and, for the guard, to rhs0
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_extract(const double *__restrict__ band, int ldb,
+                                                           int bw, const double *__restrict__ rhs,
+                                                           int N, int nb, double *__restrict__ D,
+                                                           double *__restrict__ L,
+                                                           double *__restrict__ U,
+                                                           double *__restrict__ F,
+                                                           double *__restrict__ rhs0,
+                                                           int *__restrict__ flags) {
+  const int i = blockIdx.x, tid = threadIdx.x;
+  if (i == 0 && tid < 4) flags[tid] = 0;  // (every kernel that sets them runs after this one)
+  const int64_t base = (int64_t)i * B * B;
+  for (int p = tid; p < B * B; p += BW_THREADS) {
+    const int r = p / B, c = p % B;
+    const int gr = i * B + r, gc = i * B + c;
+    double d = (r == c) ? 1.0 : 0.0;
+    if (gr < N && gc < N) {
+      const int hi = max(gr, gc), lo = min(gr, gc);
+      d = (hi - lo <= bw) ? band[(int64_t)hi * ldb + (hi - lo)] : 0.0;
+    }
+    D[base + p] = d;
+    // L_i[r][c] = K[B i + r][B (i-1) + c]
+    double l = 0.0;
+    if (i > 0 && gr < N) {
+      const int dist = gr - ((i - 1) * B + c);
+      if (dist <= bw) l = band[(int64_t)gr * ldb + dist];
+    }
+    L[base + p] = l;
+    // U_i[r][c] = K[B i + r][B (i+1) + c] = K[B (i+1) + c][B i + r]
+    double u = 0.0;
+    if (i + 1 < nb && gr < N) {
+      const int rr = (i + 1) * B + c;
+      const int dist = rr - gr;
+      if (rr < N && dist <= bw) u = band[(int64_t)rr * ldb + dist];
+    }
+    U[base + p] = u;
+  }
+  if (tid < B) {
+    const int g = i * B + tid;
+    const double v = (g < N) ? rhs[g] : 0.0;
+    F[(int64_t)i * B + tid] = v;
+    if (rhs0 && g < N) rhs0[g] = v;
+  }
+}
+
+// In-place Gauss-Jordan inverse of the B x B block M (LDS, row stride B + 1) by the whole
+// workgroup, no pivoting.  Returns (in thread 0) the number of negative pivots; sets *bad on a
+// zero or non-finite pivot.
+template <int B>
+__device__ __forceinline__ int bw_gj_inverse(double *M, int tid, int *bad) {
+  constexpr int LD = B + 1, E = B * B / BW_THREADS > 0 ? B * B / BW_THREADS : 1;
+  int neg = 0;
+  double own[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int p = tid + e * BW_THREADS;
+    own[e] = (p < B * B) ? M[(p / B) * LD + p % B] : 0.0;
+  }
+  for (int k = 0; k < B; ++k) {
+    const double piv = M[k * LD + k];
+    const bool isbad = (piv == 0.0) || !(fabs(piv) <= 1.79e308);
+    *bad |= isbad ? 1 : 0;
+    neg += (piv < 0.0) ? 1 : 0;
+    const double d = isbad ? 0.0 : bw_recip(piv);
+    double v[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int p = tid + e * BW_THREADS;
+      const int r = p / B, c = p % B;
+      const double mrk = M[r * LD + k], mkc = M[k * LD + c];
+      if (r == k && c == k)
+        v[e] = d;
+      else if (r == k)
+        v[e] = mkc * d;
+      else if (c == k)
+        v[e] = -mrk * d;
+      else
+        v[e] = fma(-mrk * d, mkc, own[e]);
+    }
+    __syncthreads();  // every thread has read row / column k
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int p = tid + e * BW_THREADS;
+      if (p < B * B) {
+        M[(p / B) * LD + p % B] = v[e];
+        own[e] = v[e];
+      }
+    }
+    __syncthreads();
+  }
+  return neg;
+}
+
+template <int B>
+__device__ __forceinline__ void bw_invert_block(const double *__restrict__ D,
+                                                double *__restrict__ Dinv, int i, double *M,
+                                                int *__restrict__ flags,
+                                                int *__restrict__ negcnt) {
+  constexpr int LD = B + 1;
+  const int tid = threadIdx.x;
+  const int64_t base = (int64_t)i * B * B;
+  for (int p = tid; p < B * B; p += BW_THREADS) M[(p / B) * LD + p % B] = D[base + p];
+  __syncthreads();
+  int bad = 0;
+  const int neg = bw_gj_inverse<B>(M, tid, &bad);
+  for (int p = tid; p < B * B; p += BW_THREADS) Dinv[base + p] = M[(p / B) * LD + p % B];
+  // (the pivots are the same in every thread: thread 0 reports)
+  if (tid == 0) {
+    if (bad) atomicOr(&flags[0], 1);
+    negcnt[i] = neg;
+  }
+}
+
+// invert the blocks eliminated at this level: i = first, first + stride, ...
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_invert(const double *__restrict__ D,
+                                                          double *__restrict__ Dinv, int nb,
+                                                          int first, int stride,
+                                                          int *__restrict__ flags,
+                                                          int *__restrict__ negcnt) {
+  __shared__ double M[B * (B + 1)];
+  const int i = first + blockIdx.x * stride;
+  if (i >= nb) return;
+  bw_invert_block<B>(D, Dinv, i, M, flags, negcnt);
+}
+
+// One 16 x 16 tile of acc += A[r0.., :] Bm[:, c0..] (K = B) on v_mfma_f64_16x16x4_f64.
+// Operand layout: A: lane l holds A[l & 15][l >> 4], B: B[l >> 4][l & 15];
+// C/D: row (l >> 4) + 4 reg, column l & 15 (pgf_factor2.hip, tile_msub).
+// neg: accumulate -A Bm instead.
+template <int B>
+__device__ __forceinline__ bw_double4 bw_tile(const double *A, int lda, const double *Bm, int ldbm,
+                                              int r0, int c0, bw_double4 acc, int lane, bool neg) {
+  const int l15 = lane & 15, l4 = lane >> 4;
+  const double *pa = A + (int64_t)(r0 + l15) * lda + l4;
+  const double *pb = Bm + (int64_t)l4 * ldbm + c0 + l15;
+#pragma unroll
+  for (int k0 = 0; k0 < B; k0 += 4) {
+    const double a = pa[k0];
+    const double b = pb[(int64_t)k0 * ldbm];
+    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(neg ? -a : a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// Reduce the kept blocks of this level: i = 0, 2s, 4s, ...  The eliminated neighbours are not
+// written at this level, every kept block only writes its own D, L, U, F: no races.
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_reduce(double *__restrict__ D, double *__restrict__ L,
+                                                          double *__restrict__ U, double *__restrict__ F,
+                                                          const double *__restrict__ Dinv, int nb,
+                                                          int s) {
+  constexpr int LD = B + 1, NT = (B / 16) * (B / 16);  // 16 x 16 tiles of a block
+  constexpr int TPW = NT >= 4 ? NT / 4 : 1;            // tiles per wavefront
+  constexpr int BB = B * B;
+  __shared__ double T[B * LD];  // alpha, then gamma
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x * 2 * s;
+  if (i >= nb) return;
+  const int le = i - s, ri = i + s;
+  const int64_t bi = (int64_t)i * BB;
+  const int l4 = lane >> 4, l15 = lane & 15;
+  auto tile_rc = [&](int t, int &r0, int &c0) {
+    const int tt = wave + 4 * t;
+    r0 = (tt / (B / 16)) * 16;
+    c0 = (tt % (B / 16)) * 16;
+  };
+  const bool busy = wave < NT;  // B = 16: one tile, wavefront 0
+  // D_i into the accumulators
+  bw_double4 dacc[TPW];
+#pragma unroll
+  for (int t = 0; t < TPW; ++t) {
+    int r0, c0;
+    tile_rc(t, r0, c0);
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      dacc[t][g] = busy ? D[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] : 0.0;
+  }
+  double fv = (tid < B) ? F[(int64_t)i * B + tid] : 0.0;
+  // two sides: (coupling of i, eliminated neighbour, its coupling further out, output)
+  for (int side = 0; side < 2; ++side) {
+    const int e = side == 0 ? le : ri;
+    double *Ci = side == 0 ? L : U;        // L_i or U_i
+    const double *Ce = side == 0 ? U : L;  // block of e that couples back to i
+    const double *Co = side == 0 ? L : U;  // block of e that couples further out
+    if (e < 0 || e >= nb) {
+      // no neighbour on this side: the coupling stays zero
+      for (int p = tid; p < BB; p += BW_THREADS) Ci[bi + p] = 0.0;
+      continue;
+    }
+    const int64_t be = (int64_t)e * BB;
+    // T = C_i inv(D_e)
+    if (busy) {
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) {
+        int r0, c0;
+        tile_rc(t, r0, c0);
+        bw_double4 acc = {0.0, 0.0, 0.0, 0.0};
+        acc = bw_tile<B>(Ci + bi, B, Dinv + be, B, r0, c0, acc, lane, false);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) T[(r0 + l4 + 4 * g) * LD + c0 + l15] = acc[g];
+      }
+    }
+    __syncthreads();  // T complete; C_i has been read by everyone
+    if (busy) {
+#pragma unroll
+      for (int t = 0; t < TPW; ++t) {
+        int r0, c0;
+        tile_rc(t, r0, c0);
+        // D_i -= T (coupling of e back to i)
+        dacc[t] = bw_tile<B>(T, LD, Ce + be, B, r0, c0, dacc[t], lane, true);
+        // new coupling of i (two blocks out): -T (coupling of e further out)
+        bw_double4 acc = {0.0, 0.0, 0.0, 0.0};
+        acc = bw_tile<B>(T, LD, Co + be, B, r0, c0, acc, lane, true);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) Ci[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] = acc[g];
+      }
+    }
+    if (tid < B) {  // f_i -= T f_e
+      const double *fe = F + (int64_t)e * B;
+      double acc = 0.0;
+#pragma unroll 8
+      for (int k = 0; k < B; ++k) acc = fma(T[tid * LD + k], fe[k], acc);
+      fv -= acc;
+    }
+    __syncthreads();  // T is read by everyone before the other side overwrites it
+  }
+  if (busy) {
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+      int r0, c0;
+      tile_rc(t, r0, c0);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) D[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] = dacc[t][g];
+    }
+  }
+  if (tid < B) F[(int64_t)i * B + tid] = fv;
+}
+
+// y = M v (B x B row-major in global memory, v in LDS), the rows split over 256 / B threads
+// each; the result is valid in the first thread of each row's group
+template <int B>
+__device__ __forceinline__ double bw_matvec(const double *__restrict__ M, const double *v, int tid) {
+  constexpr int P = BW_THREADS / B;  // threads per row (16, 8, 4): inside one wavefront
+  const int r = tid / P, part = tid % P;
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < B / P; ++j) acc = fma(M[(int64_t)r * B + part + j * P], v[part + j * P], acc);
+#pragma unroll
+  for (int off = P / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  return acc;
+}
+
+// x_i = inv(D_i) (f_i - L_i x_{i-s} - U_i x_{i+s}) for the blocks eliminated at stride s
+template <int B>
+__device__ __forceinline__ void bw_back_block(const double *__restrict__ Dinv,
+                                              const double *__restrict__ L,
+                                              const double *__restrict__ U,
+                                              const double *__restrict__ F,
+                                              double *__restrict__ X, int nb, int s, int i,
+                                              double *xl, double *xr, double *t) {
+  constexpr int P = BW_THREADS / B;
+  const int tid = threadIdx.x;
+  const int le = i - s, ri = i + s;
+  const bool hl = (s > 0) && le >= 0, hr = (s > 0) && ri < nb;
+  if (tid < B) {
+    xl[tid] = hl ? X[(int64_t)le * B + tid] : 0.0;
+    xr[tid] = hr ? X[(int64_t)ri * B + tid] : 0.0;
+  }
+  __syncthreads();
+  const int64_t bi = (int64_t)i * B * B;
+  double a = hl ? bw_matvec<B>(L + bi, xl, tid) : 0.0;
+  double b = hr ? bw_matvec<B>(U + bi, xr, tid) : 0.0;
+  if (tid % P == 0) t[tid / P] = F[(int64_t)i * B + tid / P] - a - b;
+  __syncthreads();
+  const double x = bw_matvec<B>(Dinv + bi, t, tid);
+  if (tid % P == 0) X[(int64_t)i * B + tid / P] = x;
+}
+
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_back(const double *__restrict__ Dinv,
+                                                        const double *__restrict__ L,
+                                                        const double *__restrict__ U,
+                                                        const double *__restrict__ F,
+                                                        double *__restrict__ X, int nb, int s) {
+  __shared__ double xl[B], xr[B], t[B];
+  const int i = s + blockIdx.x * 2 * s;
+  if (i >= nb) return;
+  bw_back_block<B>(Dinv, L, U, F, X, nb, s, i, xl, xr, t);
+}
+
+// the last block left (block 0): invert, solve, and sum the per-block negative pivots
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_last(const double *__restrict__ D,
+                                                        double *__restrict__ Dinv,
+                                                        const double *__restrict__ F,
+                                                        double *__restrict__ X, int nb,
+                                                        int *__restrict__ flags,
+                                                        int *__restrict__ negcnt) {
+  __shared__ double M[B * (B + 1)];
+  __shared__ double t[B];
+  __shared__ int part[BW_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  bw_invert_block<B>(D, Dinv, 0, M, flags, negcnt);
+  // x_0 = inv(D_0) f_0 with the inverse still in LDS (block 0 has no neighbours left)
+  if (tid < B) t[tid] = F[tid];
+  __syncthreads();
+  {
+    constexpr int P = BW_THREADS / B;
+    const int r = tid / P, pt = tid % P;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < B / P; ++j) acc = fma(M[r * (B + 1) + pt + j * P], t[pt + j * P], acc);
+#pragma unroll
+    for (int off = P / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (pt == 0) X[r] = acc;
+  }
+  // inertia: every block has been inverted exactly once by now
+  int cnt = 0;
+  for (int i = tid; i < nb; i += BW_THREADS) cnt += negcnt[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+  if (lane == 0) part[wave] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    int tot = 0;
+    for (int w = 0; w < BW_THREADS / 64; ++w) tot += part[w];
+    flags[1] = tot;
+  }
+}
+
+// Accuracy guard for bw <= 64: the same (max |r|, max (|K| |x| + |rhs0|)) pair per 256 rows as
+// k_band_residual (pgf_sparse.hip), which stages its rows in LDS for bw <= 10; here a row reads
+// its band entries straight from memory (up to 2 x 65 of them, L2-resident neighbours).
+__global__ __launch_bounds__(256) void k_bw_residual(const double *__restrict__ band, int ldb, int bw,
+                                                     int N, const double *__restrict__ x,
+                                                     const double *__restrict__ rhs0,
+                                                     double *__restrict__ r,
+                                                     double *__restrict__ rsmax,
+                                                     const int *__restrict__ flags, int nred) {
+  if (blockIdx.x == 0 && threadIdx.x < 4) rsmax[3 * nred + threadIdx.x] = (double)flags[threadIdx.x];
+  __shared__ double pr[4], pb[4];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double ar = 0.0, ab = 0.0;
+  if (i < N) {
+    double acc = rhs0[i];
+    ab = fabs(acc);
+    const double *row = band + (int64_t)i * ldb;
+    for (int d = 0; d <= bw && d <= i; ++d) {
+      const double kx = row[d] * x[i - d];
+      acc = fma(-row[d], x[i - d], acc);
+      ab += fabs(kx);
+    }
+    for (int d = 1; d <= bw && i + d < N; ++d) {
+      const double kv = band[(int64_t)(i + d) * ldb + d];
+      acc = fma(-kv, x[i + d], acc);
+      ab += fabs(kv * x[i + d]);
+    }
+    r[i] = acc;
+    ar = (acc == acc) ? fabs(acc) : __builtin_huge_val();
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    ar = fmax(ar, __shfl_down(ar, off));
+    ab = fmax(ab, __shfl_down(ab, off));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    pr[threadIdx.x >> 6] = ar;
+    pb[threadIdx.x >> 6] = ab;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    rsmax[2 * blockIdx.x] = fmax(fmax(pr[0], pr[1]), fmax(pr[2], pr[3]));
+    rsmax[2 * blockIdx.x + 1] = fmax(fmax(pb[0], pb[1]), fmax(pb[2], pb[3]));
+  }
+}
+
+void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
+  if (N == 0) return;
+  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, N,
+                     sp.brhs, sp.brhs0, sp.bres, sp.bred, flags, sp.nred);
+}
+
+template <int B>
+static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+  const int nb = (N + B - 1) / B;
+  const dim3 blk(BW_THREADS);
+  hipLaunchKernelGGL(k_bw_extract<B>, dim3(nb), blk, 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N, nb, sp.bD,
+                     sp.bL, sp.bU, sp.bF, guard ? sp.brhs0 : nullptr, flags);
+  int levels[32], nlev = 0;
+  for (int st = 1; st < nb; st *= 2) {
+    const int ne = (nb - st + 2 * st - 1) / (2 * st);  // eliminated: st, 3st, ...
+    const int nk = (nb + 2 * st - 1) / (2 * st);       // kept: 0, 2st, ...
+    hipLaunchKernelGGL(k_bw_invert<B>, dim3(ne), blk, 0, s, sp.bD, sp.bDinv, nb, st, 2 * st, flags, sp.bneg);
+    hipLaunchKernelGGL(k_bw_reduce<B>, dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF, sp.bDinv, nb, st);
+    levels[nlev++] = st;
+  }
+  hipLaunchKernelGGL(k_bw_last<B>, dim3(1), blk, 0, s, sp.bD, sp.bDinv, sp.bF, sp.bX, nb, flags,
+                     sp.bneg);
+  for (int q = nlev - 1; q >= 0; --q) {
+    const int st = levels[q];
+    const int ne = (nb - st + 2 * st - 1) / (2 * st);
+    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, sp.bF, sp.bX, nb, st);
+  }
+  if (guard) sp_launch_bw_residual(s, sp, N, flags);
+}
+
+// Solve the banded system in sp.band / sp.brhs with B = sp.B x sp.B blocks (16, 32, 64); the
+// solution replaces sp.brhs (which holds whole blocks: sp.bX).  flags[0] zero pivot, flags[1]
+// negative pivots; guard: keep the right-hand side and finish with the residual (bres, bred).
+void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+  if (N == 0) {
+    (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
+    return;
+  }
+  switch (sp.B) {
+    case 16: bw_solve<16>(s, sp, N, flags, guard); break;
+    case 32: bw_solve<32>(s, sp, N, flags, guard); break;
+    default: bw_solve<64>(s, sp, N, flags, guard); break;
+  }
+}

@@ -7,6 +7,9 @@
 struct SparseDev {
   bool active = false;
   int bw = 0, ldb = 0;
+  // block size of the cyclic reduction: 8 (pgf_sparse.hip), 16 / 32 / 64 (pgf_band_wide.hip),
+  // 0: the sequential band walk (bw 9 .. 10 without a forced block size)
+  int B = 0;
   int nnzH = 0, nnzJ = 0;
   int *pos = nullptr;                       // permuted position of variable i / constraint n + r
   int *Hptr = nullptr, *Hrow = nullptr, *Hcol = nullptr, *Hslot = nullptr;
@@ -23,7 +26,7 @@ struct SparseDev {
   double *bred = nullptr;
   int nred = 0;
   double *Hb0 = nullptr, *Jb0 = nullptr;
-  // block cyclic reduction work arrays: (N/8) blocks of 8 x 8 (D, L, U, inv D), rhs, solution
+  // block cyclic reduction work arrays: (N/B) blocks of B x B (D, L, U, inv D), rhs, solution
   double *bD = nullptr, *bL = nullptr, *bU = nullptr, *bDinv = nullptr, *bF = nullptr, *bX = nullptr;
   int *bneg = nullptr;                      // negative pivots met while inverting block i
   // bD, bL, bU, bF hold TWO sets of blocks, the second bstride blocks behind the first: a launch
@@ -49,6 +52,10 @@ void sp_launch_permute(hipStream_t s, const SparseDev &sp, int N, const double *
 void sp_launch_factor(hipStream_t s, const SparseDev &sp, int N, int *flags);
 void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard = true);
 void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
+// B = 16, 32, 64 (pgf_band_wide.hip): the same contract as sp_launch_bcr_solve /
+// sp_launch_band_residual for half-bandwidths up to 64
+void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard);
+void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 void sp_launch_band_axpy(hipStream_t s, int N, const double *a, double *x);
 void sp_launch_fwdsolve(hipStream_t s, const SparseDev &sp, int N);
 void sp_launch_backsolve(hipStream_t s, const SparseDev &sp, int N);

@@ -202,8 +202,10 @@ class DeviceNewton:
         _lib.check(lib.pgf_set_bounds(h, _lib.dptr(lb), _lib.dptr(ub)), h, "pgf_set_bounds")
         key = residency_key(problem)
         stale = not same_key(key, self._hd.derivs_key)
-        if self.sparse and (stale or not getattr(self._hd, "qp_loaded", False)):
-            plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m)
+        block = getattr(problem, "pgf_band_block", None)
+        replan = self._hd.plan is not None and self._hd.plan.block != (int(block) if block else None)
+        if self.sparse and (stale or replan or not getattr(self._hd, "qp_loaded", False)):
+            plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m, block=block)
             if not plan.supported:
                 raise NotImplementedError(
                     f"banded path: half-bandwidth {plan.bw} > {MAX_BANDWIDTH}; use HipStepSolver "

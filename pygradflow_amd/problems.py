@@ -282,6 +282,47 @@ def box_qp(n=16_384, seed=0, qscale=0.7413, bound=0.5, dense=False) -> LinearQua
     return LinearQuadraticProblem(H, q, A, np.zeros(0), np.full(n, -bound), np.full(n, bound))
 
 
+def multistate_ocp(T, nx, nu, seed=0, ubound=0.3) -> LinearQuadraticProblem:
+    """Optimal control with a state vector: x = [s_1..s_T, u_1..u_T], s_t in R^nx, u_t in R^nu,
+    H = blkdiag(I_T (x) Q, 0.1 I) with Q dense SPD, c_t = s_t - A s_{t-1} - B u_t (s_0 = 0) with
+    A dense (spectral radius 0.95) and B dense, controls boxed |u| <= ubound.  The dense blocks
+    fix the band after RCM (bw 22 for nx = 8, nu = 4; 46 for 16, 8; 58 for 20, 10)."""
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((nx, nx))
+    Q = G @ G.T / nx + np.eye(nx)
+    Q = 0.5 * (Q + Q.T)
+    A = rng.standard_normal((nx, nx))
+    A *= 0.95 / np.max(np.abs(np.linalg.eigvals(A)))
+    Bc = rng.standard_normal((nx, nu)) / np.sqrt(nu)
+    ns, nuu = T * nx, T * nu
+    H = sps.block_diag([sps.kron(sps.identity(T), Q), 0.1 * sps.identity(nuu)], format="csr")
+    Js = sps.identity(ns) - sps.kron(sps.diags([np.ones(T - 1)], [-1], shape=(T, T)), A)
+    Ju = -sps.kron(sps.identity(T), Bc)
+    J = sps.hstack([Js, Ju], format="csr")
+    n, m = ns + nuu, ns
+    q = rng.standard_normal(n)
+    b = 0.1 * rng.standard_normal(m)
+    lb = np.concatenate([np.full(ns, -np.inf), np.full(nuu, -ubound)])
+    ub = np.concatenate([np.full(ns, np.inf), np.full(nuu, ubound)])
+    return LinearQuadraticProblem(H.tocsr(), q, J, b, lb, ub)
+
+
+def grid_box_qp(W, L, seed=0, bound=0.5) -> LinearQuadraticProblem:
+    """Shifted 5-point Laplacian on a W x L grid (H = 4.5 I - adjacency, SPD), m = 0,
+    q ~ N(0, 1), box |x| <= bound; bandwidth about W after RCM."""
+    rng = np.random.default_rng(seed)
+
+    def path(k):
+        e = np.ones(k)
+        return sps.diags([-e[:-1], 2.25 * e, -e[:-1]], [-1, 0, 1], shape=(k, k))
+
+    H = sps.kronsum(path(W), path(L), format="csr")
+    n = W * L
+    q = rng.standard_normal(n)
+    return LinearQuadraticProblem(H, q, sps.csr_matrix((0, n), dtype=np.float64), np.zeros(0),
+                                  np.full(n, -bound), np.full(n, bound))
+
+
 def quartic_nlp(n=12, m=4, seed=0, bounded=True) -> QuarticProblem:
     """Random bounded non-convex NLP (SURVEY.md 8(a) verification case)."""
     rng = np.random.default_rng(seed)

@@ -22,11 +22,31 @@ from scipy.sparse.csgraph import reverse_cuthill_mckee
 
 from . import _lib
 
-MAX_BANDWIDTH = 10  # kernels map one lane to one (row, column) pair of the band window
+MAX_BANDWIDTH = 64  # widest block of the cyclic reduction (csrc/pgf_band_wide.hip)
+BLOCK_SIZES = (8, 16, 32, 64)
+
+
+def block_size_for(bw, forced=None):
+    """Block size of the banded solve for half-bandwidth ``bw``: ``forced`` if given, else
+    8 for bw <= 8 (8 x 8 cyclic reduction), 0 for bw 9 .. 10 (the sequential band walk), the
+    smallest of 16, 32, 64 that is >= bw up to 64, and None beyond (no banded path)."""
+    if forced:
+        return int(forced)
+    if bw <= 8:
+        return 8
+    if bw <= 10:
+        return 0
+    for B in BLOCK_SIZES[1:]:
+        if bw <= B:
+            return B
+    return None
 
 
 class BandPlan:
-    def __init__(self, hess, jac, n, m):
+    def __init__(self, hess, jac, n, m, block=None):
+        if block and int(block) not in BLOCK_SIZES:
+            raise ValueError(f"band block size {block}: must be one of {BLOCK_SIZES}")
+        self.block = int(block) if block else None  # forced block size (problem.pgf_band_block)
         H = sps.csr_matrix(hess, dtype=np.float64)
         J = sps.csr_matrix(jac, dtype=np.float64) if m > 0 else sps.csr_matrix((0, n), dtype=np.float64)
         H.sum_duplicates()
@@ -81,6 +101,11 @@ class BandPlan:
     def supported(self) -> bool:
         return self.bw <= MAX_BANDWIDTH
 
+    @property
+    def block_size(self):
+        """Block size the solve runs with (block_size_for; 0 = sequential band walk)."""
+        return block_size_for(self.bw, self.block)
+
     def values(self, hess, jac):
         """Values of H, J in plan order; raises if the pattern differs from the plan's."""
         H = sps.csr_matrix(hess, dtype=np.float64)
@@ -121,11 +146,15 @@ class BandPlan:
             ip(self.Hslot), self.nnzJ, ip(self.Jptr), ip(self.Jcol), ip(self.Jslot), ip(self.JTptr),
             ip(self.JTrow), ip(self.JTmap))
         _lib.check(rc, handle, "pgf_sparse_set_pattern")
+        rc = lib.pgf_sparse_set_block_size(handle, self.block or 0)
+        _lib.check(rc, handle, f"pgf_sparse_set_block_size (half-bandwidth {self.bw})")
 
 
 def wants_band(problem, hess, n, m, dense_limit=20000):
     """Sparse derivatives take the banded path when the problem is too large for the dense
-    one, or when the problem asks for it (``pgf_force_band``; tests use that)."""
+    one, or when the problem asks for it (``pgf_force_band``; tests use that).  A problem may
+    also force the block size of the banded solve (``pgf_band_block``: 8, 16, 32 or 64, at
+    least the half-bandwidth)."""
     if not sps.issparse(hess):
         return False
     return bool(getattr(problem, "pgf_force_band", False)) or (n + m > dense_limit)

@@ -413,9 +413,12 @@ class HipStepSolver:
         hd = self._hd
         hess = sps.csr_matrix(self._hess)
         jac = sps.csr_matrix(self._jac) if self.m else sps.csr_matrix((0, self.n))
+        block = getattr(self.problem, "pgf_band_block", None)
+        if hd.plan is not None and hd.plan.block != (int(block) if block else None):
+            hd.plan = None  # a different block size was asked for: upload again
         for attempt in (0, 1):
             if hd.plan is None:
-                plan = BandPlan(hess, jac, self.n, self.m)
+                plan = BandPlan(hess, jac, self.n, self.m, block=block)
                 if not plan.supported:
                     return False
                 plan.upload(self._lib, hd.h)
