@@ -370,6 +370,12 @@ int pgf_debug_chain_helpers(int on);
  * condensed system (constraint block eliminated first, pgf_api.hip condensed_wanted), 3 the
  * pivoted LU that took over after a failed residual check. */
 int pgf_debug_factor_kind(pgf_handle h);
+/* Counters of the dense qp steps (tests): host_syncs -- host synchronisations made for the
+ * index-set sizes and the step's status (a Full step: one while |I| keeps its size, two with
+ * PGF_STEP_SPEC=0; an ActiveSet step waits once more for the mask difference before it is
+ * enqueued); redone_steps -- steps enqueued with the previous |I|, |A| that were discarded and
+ * enqueued again by pgf_qp_sync because the sizes had changed.  Either pointer may be NULL. */
+int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,16 @@
 
 #define PGF_GEMVT_PARTS 32
 
+// The status block of a dense step (doubles): every word the host reads after the step, read
+// with ONE device-to-host copy of STAT_COPY doubles into the pinned mirror h_stat.
+//   [0, 8)   rs_red: max |r|, max |rhs|, max |s| of the residual check; [4, 7) the matrix norms
+//   [8, 12)  scal:   [0] step diff, [1] residual norm
+//   [12, 14) counts (int): |I|, |A|, mask difference, size mismatch of a speculative step
+//   [14, 16) status (int): factor flags [0, 3), chained-solve status [3] (DenseLdlt::h_flags)
+//   [16, 17) two tickets of the last-workgroup reductions (never copied)
+#define STAT_COPY 16
+#define STAT_ALLOC 17
+
 struct pgf_solver {
   int n = 0, m = 0, device = 0;
   hipStream_t stream = nullptr;
@@ -72,6 +82,17 @@ struct pgf_solver {
   bool sp_guarded = false;  // banded path: the last solve carried the residual check (k_band_residual)
   double *h_bred = nullptr;  // pinned mirror of sp.bred
   bool sp_stat_pending = false;  // a guarded banded step's status block is on its way to h_bred
+  // status block (STAT_COPY above) and its pinned mirror
+  double *stat = nullptr, *h_stat = nullptr;
+  unsigned *ticket = nullptr;
+  int stat_bits = 0;  // DenseLdlt::status_words gathered into the block by the step update
+  // speculative index-set sizes (pgf_qp_step_async): the step is enqueued with the last known
+  // |I|, |A|; the compaction flags a mismatch in counts[3], and pgf_qp_sync redoes the step
+  bool counts_known = false, spec_pending = false;
+  bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
+  int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
+  uint8_t *h_mask_stage = nullptr;  // pinned staging of pgf_set_active_set's mask
+  hipEvent_t mask_ev = nullptr;
   // the current dense factor is that of the condensed system (constraint block eliminated
   // first, condensed_wanted below); cd_t: its right-hand side
   bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
@@ -173,21 +194,31 @@ int pgf_create(int n, int m, int device, unsigned flags, pgf_handle *out) {
   A_(rhs, N + 1) A_(sol, N + 1) A_(dx, n) A_(dy, m);
   // (partial: two sets of PGF_GEMVT_PARTS row chunks of n: launch_residual_and_eval carries two vectors)
   A_(q, n) A_(b, m) A_(w, m) A_(tmpn, n) A_(partial, (size_t)2 * PGF_GEMVT_PARTS * (n ? n : 1));
-  A_(red, (N + 255) / 256 + 1) A_(scal, 4) A_(meas, 4 * ((N + 255) / 256) + 4);
+  A_(red, (N + 255) / 256 + 1) A_(meas, 4 * ((N + 255) / 256) + 4) A_(stat, STAT_ALLOC);
   if (!sparse) {
-    A_(rs_v, n) A_(rs_lv, n) A_(rs_u, n) A_(rs_wy, m) A_(rs_r, N + 1) A_(rs_d, N + 1) A_(rs_red, 8);
+    A_(rs_v, n) A_(rs_lv, n) A_(rs_u, n) A_(rs_wy, m) A_(rs_r, N + 1) A_(rs_d, N + 1);
     A_(cd_t, n + 1);
   }
-  A_(mask, n) A_(mask_new, n) A_(idxI, n) A_(idxA, n) A_(pos, n) A_(counts, 4);
+  A_(mask, n) A_(mask_new, n) A_(idxI, n) A_(idxA, n) A_(pos, n);
 #undef A_
-  if ((e = hipHostMalloc((void **)&h->h_counts, 4 * sizeof(int))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&h->h_scal, 4 * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&h->h_meas, 4 * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&h->h_rs, 8 * sizeof(double))) != hipSuccess) {
+  // index lists hold valid indices from the start: a step enqueued with stale counts reads them
+  if ((e = hipMemset(h->stat, 0, STAT_ALLOC * sizeof(double))) != hipSuccess ||
+      (n && (e = hipMemset(h->idxI, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
+      (n && (e = hipMemset(h->idxA, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
+      (n && (e = hipMemset(h->pos, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
+      (e = hipHostMalloc((void **)&h->h_stat, STAT_COPY * sizeof(double))) != hipSuccess ||
+      (e = hipHostMalloc((void **)&h->h_meas, 4 * sizeof(double))) != hipSuccess) {
     pgf_destroy(h);
     return PGF_HIP_ERROR + (int)e;
   }
-  for (int i = 0; i < 8; ++i) h->h_rs[i] = 0.0;
+  h->rs_red = h->stat;
+  h->scal = h->stat + 8;
+  h->counts = reinterpret_cast<int *>(h->stat + 12);
+  h->ticket = reinterpret_cast<unsigned *>(h->stat + 16);
+  for (int i = 0; i < STAT_COPY; ++i) h->h_stat[i] = 0.0;
+  h->h_rs = h->h_stat;
+  h->h_scal = h->h_stat + 8;
+  h->h_counts = reinterpret_cast<int *>(h->h_stat + 12);
   h->sparse = sparse;
   if (sparse) {
     // banded mode: no dense N x N storage; only the factor's flag words are shared
@@ -215,16 +246,15 @@ int pgf_destroy(pgf_handle h) {
   void *ptrs[] = {h->csr_ptr, h->csr_idx, h->csr_val, h->Hown, h->Jown, h->lb,  h->ub,   h->slb,  h->sub,      h->xhat, h->yhat,
                   h->x,    h->y,    h->xn,  h->yn,   h->g,    h->c,        h->F,    h->b0full,
                   h->rhs,  h->sol,  h->dx,  h->dy,   h->q,    h->b,        h->w,    h->tmpn,
-                  h->partial, h->red, h->scal, h->mask, h->mask_new, h->idxI, h->idxA, h->pos,
-                  h->counts, h->meas, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->rs_r, h->rs_d,
-                  h->rs_red, h->cd_t};
+                  h->partial, h->red, h->stat, h->mask, h->mask_new, h->idxI, h->idxA, h->pos,
+                  h->meas, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->rs_r, h->rs_d, h->cd_t};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
-  if (h->h_rs) (void)hipHostFree(h->h_rs);
+  if (h->h_stat) (void)hipHostFree(h->h_stat);
+  if (h->h_mask_stage) (void)hipHostFree(h->h_mask_stage);
+  if (h->mask_ev) (void)hipEventDestroy(h->mask_ev);
   if (h->h_bred) (void)hipHostFree(h->h_bred);
   lu_free(h->lu);
-  if (h->h_counts) (void)hipHostFree(h->h_counts);
-  if (h->h_scal) (void)hipHostFree(h->h_scal);
   if (h->h_meas) (void)hipHostFree(h->h_meas);
   {
     SparseDev &sp = h->sp;
@@ -439,18 +469,39 @@ int pgf_active_set(pgf_handle h, const double *x, const double *g, double tau, u
   return PGF_OK;
 }
 
-// compaction of h->mask -> index lists + counts (one host sync)
-static int refresh_index_sets(pgf_handle h) {
-  launch_compact(h->stream, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts);
+// PGF_STEP_SPEC=0: a step waits for the sizes of its index sets (one more host synchronisation
+// per step) instead of running with the last known ones
+static bool step_spec() {
+  static const bool on = !(getenv("PGF_STEP_SPEC") && atoi(getenv("PGF_STEP_SPEC")) == 0);
+  return on;
+}
+
+// After the compaction of h->mask into index lists + counts (enqueued by the caller with
+// expect = h->nI when `spec', else -1).  spec: a step is being enqueued and will run with the last
+// known |I|, |A| -- no host synchronisation here; pgf_qp_sync reads the true counts and the
+// mismatch word with the step's status block and redoes the step if they differ.  Otherwise the
+// counts are awaited (one host sync).
+static int adopt_index_sets(pgf_handle h, bool spec) {
+  h->mask_set = true;
+  invalidate_factor(h);
+  if (spec) {
+    h->spec_pending = true;
+    return PGF_OK;
+  }
   int rc;
   if ((rc = down(h, h->h_counts, h->counts, 2 * sizeof(int)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  ++h->stat_host_syncs;
   h->nI = h->h_counts[0];
   h->nA = h->h_counts[1];
   h->N = h->nI + h->m;
-  h->mask_set = true;
-  invalidate_factor(h);
+  h->counts_known = true;
   return PGF_OK;
+}
+static int refresh_index_sets(pgf_handle h, bool in_step) {
+  const bool spec = in_step && h->counts_known && step_spec();
+  launch_compact(h->stream, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, spec ? h->nI : -1);
+  return adopt_index_sets(h, spec);
 }
 
 int pgf_set_active_set(pgf_handle h, const uint8_t *mask) {
@@ -458,19 +509,34 @@ int pgf_set_active_set(pgf_handle h, const uint8_t *mask) {
   if (h->n && !mask) return fail(h, PGF_INVALID, "null mask");
   (void)hipSetDevice(h->device);
   int rc;
-  if ((rc = up(h, h->mask, mask, h->n))) return rc;
   if (h->sparse) {
+    if ((rc = up(h, h->mask, mask, h->n))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    int na = 0;
-    for (int i = 0; i < h->n; ++i) na += mask[i] ? 1 : 0;
-    h->nA = na;
-    h->nI = h->n - na;
-    h->N = h->nI + h->m;
-    h->mask_set = true;
-    invalidate_factor(h);
-    return PGF_OK;
+  } else if (h->n) {
+    // through a pinned stage (the caller's buffer may go as soon as this returns); the stage is
+    // reused once the previous upload from it has run
+    if (!h->h_mask_stage) {
+      HIPCHK(h, hipHostMalloc((void **)&h->h_mask_stage, (size_t)h->n));
+      HIPCHK(h, hipEventCreateWithFlags(&h->mask_ev, hipEventDisableTiming));
+    } else {
+      HIPCHK(h, hipEventSynchronize(h->mask_ev));
+    }
+    memcpy(h->h_mask_stage, mask, (size_t)h->n);
+    if ((rc = up(h, h->mask, h->h_mask_stage, h->n))) return rc;
+    HIPCHK(h, hipEventRecord(h->mask_ev, h->stream));
   }
-  return refresh_index_sets(h);
+  // the sizes are counted here: no wait for the device's counts
+  int na = 0;
+  for (int i = 0; i < h->n; ++i) na += mask[i] ? 1 : 0;
+  h->nA = na;
+  h->nI = h->n - na;
+  h->N = h->nI + h->m;
+  h->counts_known = true;
+  h->mask_set = true;
+  invalidate_factor(h);
+  if (!h->sparse)
+    launch_compact(h->stream, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, h->nI);
+  return PGF_OK;
 }
 
 int pgf_reduced_dims(pgf_handle h, int *n_inactive, int *n_reduced) {
@@ -645,17 +711,22 @@ static int factor_async(pgf_handle h, bool with_rhs) {
     f.vdepth = mp;
     f.vneg = h->m;  // the eliminated block is -delta I
     // A = H[I,I] + lamb I (the assembly kernel with no constraint rows), V = J_I^T, b_y in row nI
-    launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta);
+    // (the assembly launch also clears the factorisation's flags and copies b_x into row nI)
+    f.flags_zeroed = nI > 0;
+    launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
+                        f.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
+                        f.K + (int64_t)nI * f.ldk, nI);
     launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta,
                       with_rhs ? h->rhs + nI : nullptr);
-    if (with_rhs) launch_copy(h->stream, f.K + (int64_t)nI * f.ldk, h->rhs, nI);
     HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0)));
     f.N = nI;
     return PGF_OK;
   }
-  assemble(h, h->fac.K, h->fac.ldk);
-  if (with_rhs && h->N > 0)
-    launch_copy(h->stream, h->fac.K + (int64_t)h->N * h->fac.ldk, h->rhs, h->N);
+  // (the assembly launch also clears the factorisation's flags and copies the rhs into row N)
+  h->fac.flags_zeroed = h->N > 0;
+  launch_assemble_kkt(h->stream, h->fac.K, h->fac.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, h->nI, h->m,
+                      h->lamb, h->delta, h->fac.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
+                      h->fac.K + (int64_t)h->N * h->fac.ldk, h->N);
   HIPCHK(h, ldlt_factor_async(h->fac, h->N, h->N + (with_rhs ? 1 : 0)));
   return PGF_OK;
 }
@@ -712,10 +783,29 @@ static int factor_sync(pgf_handle h) {
   return fail(h, PGF_HIP_ERROR, k_helper_msg);
 }
 
-static void enqueue_step_update(pgf_handle h) {
+// (expand: also the residual check's expansion of the solution into rs_v, rs_lv and the zeroing of
+// its maxima, launch_residual_and_eval(..., prepared = true))
+static void enqueue_step_update(pgf_handle h, bool expand = false) {
+  DenseLdlt &f = h->fac;
+  const int bits = f.status_words;  // deferred status words go to the status block
+  f.status_words = 0;
+  h->stat_bits |= bits;
   launch_step_update(h->stream, h->n, h->m, h->nI, h->fact, h->rho, h->x, h->y, h->lb, h->ub,
                      h->mask, h->pos, h->b0full, h->F, h->sol, h->dx, h->dy, h->xn, h->yn, h->red,
-                     h->scal);
+                     h->scal, h->ticket, h->lamb, expand ? h->rs_v : nullptr, expand ? h->rs_lv : nullptr,
+                     expand ? h->rs_red : nullptr, (bits & 1) ? f.flags : nullptr,
+                     (bits & 2) ? f.chain + 2 * f.chain_stride + 1 : nullptr,
+                     reinterpret_cast<int *>(h->stat + 14));
+}
+// after the host synchronisation of a step with deferred status words: to DenseLdlt::h_flags,
+// in the order the two separate copies would have left them
+static void absorb_status(pgf_handle h) {
+  const int *w = reinterpret_cast<const int *>(h->h_stat + 14);
+  if (h->stat_bits & 1)
+    for (int k = 0; k < 4; ++k) h->fac.h_flags[k] = w[k];
+  else if (h->stat_bits & 2)
+    h->fac.h_flags[3] = w[3];
+  h->stat_bits = 0;
 }
 
 // r = rhs - K s of the solve just enqueued, with K applied from H, J and the mask (the factor
@@ -948,8 +1038,15 @@ int pgf_factor(pgf_handle h, int *n_neg) {
 // was enqueued (its flags then need checking at the sync).
 static int newton_core_async(pgf_handle h, bool *did_factor) {
   hipStream_t s = h->stream;
-  launch_residual(s, h->n, h->m, h->lamb, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c, h->slb,
-                  h->sub, h->mask, h->F, h->b0full);
+  h->fused_eval_done = false;
+  // dense, |A| = 0: the residual and the reduced right-hand side in one launch
+  const bool rhs_fused = !h->sparse && h->nA == 0;
+  if (rhs_fused)
+    launch_residual_rhs(s, h->n, h->m, h->nI, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y, h->g,
+                        h->c, h->slb, h->sub, h->mask, h->idxI, h->F, h->b0full, h->rhs);
+  else
+    launch_residual(s, h->n, h->m, h->lamb, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c, h->slb,
+                    h->sub, h->mask, h->F, h->b0full);
   if (h->sparse) {
     const int Nf = h->n + h->m;
     sp_launch_rhs(s, h->sp, h->n, h->m, h->mask, h->F, h->b0full, h->fact, h->sp.Hb0, h->sp.Jb0);
@@ -1012,8 +1109,9 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
     launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
     return PGF_OK;
   }
-  launch_reduced_rhs(s, h->n, h->m, h->nI, h->nA, h->fact, h->F, h->idxI, h->idxA, h->H, h->ldh, h->J,
-                     h->ldj, h->b0full, h->partial, PGF_GEMVT_PARTS, h->rhs);
+  if (!rhs_fused)
+    launch_reduced_rhs(s, h->n, h->m, h->nI, h->nA, h->fact, h->F, h->idxI, h->idxA, h->H, h->ldh, h->J,
+                       h->ldj, h->b0full, h->partial, PGF_GEMVT_PARTS, h->rhs);
   *did_factor = false;
   if (!h->fac.factored) {
     int rc;
@@ -1037,12 +1135,14 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   h->fused_eval_done = false;
   h->rs_skipped = !*did_factor && h->factor_clean;
   if (ahead && h->qp_mode && h->refine_mode && !h->rs_skipped) {
-    enqueue_step_update(h);
+    enqueue_step_update(h, /*expand=*/true);
     launch_residual_and_eval(s, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj, h->idxI,
                              h->pos, h->mask, h->rhs, h->sol, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->partial,
                              PGF_GEMVT_PARTS, h->rs_r, h->rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c, h->w,
-                             h->tmpn, h->g);
-    (void)hipMemcpyAsync(h->h_rs, h->rs_red, 3 * sizeof(double), hipMemcpyDeviceToHost, s);
+                             h->tmpn, h->g, /*prepared=*/true);
+    // (a qp step reads the maxima with its whole status block)
+    if (!h->fac.defer_status)
+      (void)hipMemcpyAsync(h->h_rs, h->rs_red, 3 * sizeof(double), hipMemcpyDeviceToHost, s);
     h->fused_eval_done = true;
     return PGF_OK;
   }
@@ -1415,11 +1515,22 @@ int pgf_qp_set_point(pgf_handle h, const double *x, const double *y) {
   return PGF_OK;
 }
 
+// a read of the point while a speculative step is in flight: the step is settled first (one wait,
+// off the production path), so that the point read is never that of a discarded step
+static int settle_spec(pgf_handle h, bool *redone);
+static int settle_before_read(pgf_handle h) {
+  if (h->sparse || !h->step_pending || !h->spec_pending) return PGF_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  bool redone;
+  return settle_spec(h, &redone);
+}
+
 int pgf_qp_get_point(pgf_handle h, double *x, double *y) {
   if (!h) return PGF_INVALID;
   if (!h->point_set) return fail(h, PGF_NOT_READY, "pgf_qp_set_point first");
   (void)hipSetDevice(h->device);
   int rc;
+  if ((rc = settle_before_read(h))) return rc;
   if (x && (rc = down(h, x, h->x, h->n * sizeof(double)))) return rc;
   if (y && (rc = down(h, y, h->y, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1460,12 +1571,21 @@ static int qp_ready(pgf_handle h) {
   return PGF_OK;
 }
 
-// mask at the device point -> mask_new; adopt it if it differs (or none yet).
-static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out) {
+// mask at the device point -> mask_new; adopt it if it differs (or none yet).  in_step: a step is
+// being enqueued (its index-set sizes may be speculative, refresh_index_sets).
+static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, bool in_step) {
   int use_tau;
   double f_x, f_x0, f_d;
   tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
   hipStream_t s = h->stream;
+  if (force && !h->sparse) {
+    // the mask, straight into h->mask, and its compaction in one launch
+    const bool spec = in_step && h->counts_known && step_spec();
+    if (changed_out) *changed_out = 1;
+    launch_mask_compact(s, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->x, h->g, h->slb, h->sub,
+                        h->mask, h->idxI, h->idxA, h->pos, h->counts, spec ? h->nI : -1);
+    return adopt_index_sets(h, spec);
+  }
   launch_active_set(s, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->x, h->g, h->slb, h->sub,
                     h->mask_new);
   int changed = 1;
@@ -1475,6 +1595,7 @@ static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_ou
     int rc;
     if ((rc = down(h, h->h_counts + 2, h->counts + 2, sizeof(int)))) return rc;
     HIPCHK(h, hipStreamSynchronize(s));
+    if (in_step) ++h->stat_host_syncs;
     changed = h->h_counts[2] != 0;
   }
   if (changed_out) *changed_out = changed;
@@ -1485,7 +1606,7 @@ static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_ou
       invalidate_factor(h);
       return PGF_OK;
     }
-    return refresh_index_sets(h);
+    return refresh_index_sets(h, in_step);
   }
   return PGF_OK;
 }
@@ -1496,7 +1617,7 @@ int pgf_qp_update_active_set(pgf_handle h, double tau, int *changed) {
   if ((rc = qp_ready(h))) return rc;
   (void)hipSetDevice(h->device);
   qp_eval(h);
-  return qp_refresh_mask(h, tau, false, changed);
+  return qp_refresh_mask(h, tau, false, changed, false);
 }
 
 int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
@@ -1519,23 +1640,18 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
   return PGF_OK;
 }
 
-int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
-  if (!h) return PGF_INVALID;
-  int rc;
-  if ((rc = qp_ready(h))) return rc;
-  if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the previous step first");
-  (void)hipSetDevice(h->device);
+// newton_core_async at the device point, (x, y) <- (xn, yn), and the read-back of the step's status:
+// dense, ONE copy of the status block (the factorisation's and the chained solve's status words
+// are gathered into it by the step update, DenseLdlt::defer_status).
+static int enqueue_qp_step(pgf_handle h) {
   qp_eval(h);
-  if (policy & PGF_STEP_RECOMPUTE_MASK) {
-    // Full (newton.py:83-89): the mask is always re-set, which drops the factor;
-    // ActiveSet (:203-215): only when it differs elementwise.
-    const bool force = (policy & PGF_STEP_REFACTOR) != 0;
-    if ((rc = qp_refresh_mask(h, tau, force, nullptr))) return rc;
-  }
-  if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first");
-  if (policy & PGF_STEP_REFACTOR) invalidate_factor(h);
   bool did_factor;
-  if ((rc = newton_core_async(h, &did_factor))) return rc;
+  const bool armed = h->fac.inject_helper_failure != 0;
+  h->fac.defer_status = !h->sparse;
+  int rc = newton_core_async(h, &did_factor);
+  h->fac.defer_status = false;
+  h->step_took_inject = armed && !h->fac.inject_helper_failure;
+  if (rc) return rc;
   // (x, y) <- (xn, yn)
   std::swap(h->x, h->xn);
   std::swap(h->y, h->yn);
@@ -1551,7 +1667,59 @@ int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
   } else if (ahead && !h->sparse) {
     qp_eval(h);
   }
-  if (!h->sp_stat_pending && (rc = down(h, h->h_scal, h->scal, sizeof(double)))) return rc;
+  if (!h->sparse) return down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double));
+  if (!h->sp_stat_pending) return down(h, h->h_scal, h->scal, sizeof(double));
+  return PGF_OK;
+}
+
+// A step in flight that was enqueued with speculative index-set sizes, after a host
+// synchronisation that brought its status block: if the compaction found other sizes, the step
+// ran with the previous |I|, |A| and its factor, flags and point are garbage (every index it read
+// was in range).  Nothing of it is reported or acted on -- no PGF_SINGULAR, no refinement, no
+// change of condensed_veto, no switching off of the chain helpers or the chained solves (a
+// chained solve's half-published state is only reset) -- and it is enqueued again from the
+// point it started at, with the true sizes.  *redone: it was.
+static int settle_spec(pgf_handle h, bool *redone) {
+  *redone = false;
+  if (h->sparse || !h->step_pending || !h->spec_pending) return PGF_OK;
+  h->spec_pending = false;
+  if (!h->h_counts[3]) return PGF_OK;
+  ++h->stat_redone;
+  const int *w = reinterpret_cast<const int *>(h->h_stat + 14);
+  ldlt_chain_discard(h->fac, (h->stat_bits & 2) ? w[3] : 0);
+  h->stat_bits = 0;  // (the discarded step's status words are not read)
+  // a test hook's injected helper failure belongs to the step that is kept
+  if (h->step_took_inject) h->fac.inject_helper_failure = 1;
+  h->fac.factored = false;
+  h->lu_active = false;
+  std::swap(h->x, h->xn);
+  std::swap(h->y, h->yn);
+  h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
+  h->nI = h->h_counts[0];
+  h->nA = h->h_counts[1];
+  h->N = h->nI + h->m;
+  int rc;
+  if ((rc = enqueue_qp_step(h))) return rc;
+  *redone = true;
+  return PGF_OK;
+}
+
+int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
+  if (!h) return PGF_INVALID;
+  int rc;
+  if ((rc = qp_ready(h))) return rc;
+  if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the previous step first");
+  (void)hipSetDevice(h->device);
+  qp_eval(h);
+  if (policy & PGF_STEP_RECOMPUTE_MASK) {
+    // Full (newton.py:83-89): the mask is always re-set, which drops the factor;
+    // ActiveSet (:203-215): only when it differs elementwise.
+    const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+    if ((rc = qp_refresh_mask(h, tau, force, nullptr, true))) return rc;
+  }
+  if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first");
+  if (policy & PGF_STEP_REFACTOR) invalidate_factor(h);
+  if ((rc = enqueue_qp_step(h))) return rc;
   h->step_pending = true;
   return PGF_OK;
 }
@@ -1564,6 +1732,21 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   hipError_t e;
   int rc;
   if ((rc = sparse_status_sync(h))) return rc;
+  if (!h->sparse) {
+    // the step's one wait: its status block
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ++h->stat_host_syncs;
+    h->step_pending = true;  // (settle_spec acts on a step in flight)
+    bool redone;
+    rc = settle_spec(h, &redone);
+    h->step_pending = false;
+    if (rc) return rc;
+    if (redone) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      ++h->stat_host_syncs;
+    }
+    absorb_status(h);
+  }
   int st = finish_factor_state(h, &e);  // flags are only rewritten by a factor launch
   if (st == 2) {
     // the chain's helper workgroups failed their checks (off now): the step is computed again
@@ -1571,13 +1754,12 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
     std::swap(h->x, h->xn);
     std::swap(h->y, h->yn);
     h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
-    qp_eval(h);
-    bool did_factor;
-    if ((rc = newton_core_async(h, &did_factor))) return rc;
-    std::swap(h->x, h->xn);
-    std::swap(h->y, h->yn);
-    h->eval_fresh = false;
-    if ((rc = down(h, h->h_scal, h->scal, sizeof(double)))) return rc;
+    if ((rc = enqueue_qp_step(h))) return rc;
+    if (!h->sparse) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      ++h->stat_host_syncs;
+      absorb_status(h);
+    }
     st = finish_factor_state(h, &e);
     if (st == 2) return fail(h, PGF_HIP_ERROR, k_helper_msg);
   }
@@ -1623,6 +1805,13 @@ int pgf_debug_fail_next_helper(pgf_handle h) {
   return PGF_OK;
 }
 
+int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps) {
+  if (!h) return PGF_INVALID;
+  if (host_syncs) *host_syncs = h->stat_host_syncs;
+  if (redone_steps) *redone_steps = h->stat_redone;
+  return PGF_OK;
+}
+
 int pgf_debug_factor_kind(pgf_handle h) {
   if (!h || h->sparse) return 0;
   if (h->lu_active) return 3;
@@ -1651,13 +1840,19 @@ int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev) {
   if ((rc = qp_ready(h))) return rc;
   (void)hipSetDevice(h->device);
   qp_eval(h);
-  launch_unscaled_res_norm(h->stream, h->n, h->m, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c,
-                           h->lb, h->ub, h->red, h->scal + 1);
-  if (norm_out_dev)
-    HIPCHK(h, hipMemcpyAsync(norm_out_dev, h->scal + 1, sizeof(double), hipMemcpyDeviceToDevice,
-                             h->stream));
-  if ((rc = down(h, h->h_scal + 1, h->scal + 1, sizeof(double)))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // (the norm also reaches norm_out_dev from the launch itself).  Between pgf_qp_step_async and
+  // pgf_qp_sync the point is that of the step in flight; if that step turns out to have run with
+  // stale index-set sizes (settle_spec), it is redone and the norm taken again at its new point.
+  for (int pass = 0; pass < 2; ++pass) {
+    launch_unscaled_res_norm(h->stream, h->n, h->m, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c,
+                             h->lb, h->ub, h->red, h->scal + 1, norm_out_dev, h->ticket + 1);
+    if ((rc = down(h, h->h_scal + 1, h->scal + 1, sizeof(double)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    bool redone;
+    if ((rc = settle_spec(h, &redone))) return rc;
+    if (!redone) break;
+    qp_eval(h);
+  }
   if (norm_out) *norm_out = h->h_scal[1];
   return PGF_OK;
 }
@@ -2457,6 +2652,8 @@ int pgf_qp_measures(pgf_handle h, double active_tol, double *out) {
   if (!h->qp_mode || !h->point_set || !h->bounds_set)
     return fail(h, PGF_NOT_READY, "pgf_set_bounds, pgf_qp_set_problem, pgf_qp_set_point first");
   (void)hipSetDevice(h->device);
+  int rc0;
+  if ((rc0 = settle_before_read(h))) return rc0;
   hipStream_t s = h->stream;
   const int n = h->n, m = h->m;
   // c = A x - b and r = Q x + q + A'y (no rho term: iterate.py:141, 176)

@@ -2164,7 +2164,9 @@ hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
   f.factored = false;
   hipStream_t s = f.stream;
   // flags [0, 4) and the update launches' tile counters behind them
-  hipError_t e = hipMemsetAsync(f.flags, 0, (4 + LDLT_UPD_COUNTERS) * sizeof(int), s);
+  hipError_t e = hipSuccess;
+  if (!f.flags_zeroed) e = hipMemsetAsync(f.flags, 0, (4 + LDLT_UPD_COUNTERS) * sizeof(int), s);
+  f.flags_zeroed = false;
   if (e != hipSuccess) return e;
   static const int ncu = []() {
     int dev = 0, n = 256;
@@ -2396,7 +2398,11 @@ hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
     f.inject_helper_failure = 0;
     hipLaunchKernelGGL(k_helper_inject, dim3(1), dim3(1), 0, s, f.flags);
   }
-  e = hipMemcpyAsync(f.h_flags, f.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s);
-  if (e != hipSuccess) return e;
+  if (f.defer_status) {
+    f.status_words |= 1;
+  } else {
+    e = hipMemcpyAsync(f.h_flags, f.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e != hipSuccess) return e;
+  }
   return hipGetLastError();
 }

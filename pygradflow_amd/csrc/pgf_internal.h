@@ -77,11 +77,21 @@ struct DenseLdlt {
   size_t vcap = 0, vdcap = 0;  // allocated doubles
   int inject_chain_failure = 0;  // test hook: the next chained solve reports a failure
   int inject_helper_failure = 0;  // test hook: the next factorisation reports failed helpers
+  // Status words of a dense Newton step (pgf_api.hip): flags_zeroed -- the caller's assembly
+  // launch has already cleared flags [0, 4 + LDLT_UPD_COUNTERS), so the next factorisation skips
+  // its memset (consumed by it); defer_status -- the factorisation's flags and the chained solve's
+  // status word are NOT copied to h_flags here: status_words records what is pending (bit 0: flags
+  // [0, 4), bit 1: the chained solve's word), and the caller's step-update launch gathers them
+  // into its status block, read with one copy.
+  bool flags_zeroed = false;
+  bool defer_status = false;
+  int status_words = 0;
 };
 
 hipError_t ldlt_alloc(DenseLdlt &f, int Nmax, hipStream_t stream);
 void ldlt_free(DenseLdlt &f);
 // enqueue the factorisation of the leading N x N lower triangle (+ rows up to nrows)
+void ldlt_chain_discard(DenseLdlt &f, int word);
 hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows);
 // wait and read flags: returns 0 ok / 1 singular / 2 the diagonal chain's helper workgroups
 // failed their checks (they are switched off, factorise again); sets f.n_neg.  (A chained solve that failed

@@ -9,18 +9,30 @@ void launch_scale_bounds(hipStream_t s, int n, double lamb, const double *lb, co
 void launch_active_set(hipStream_t s, int n, int use_tau, double lamb, double f_x, double f_x0,
                        double f_d, const double *xhat, const double *x, const double *g,
                        const double *slb, const double *sub, uint8_t *mask);
+// counts[0, 1] <- |I|, |A|; counts[3] <- (|I| != expect) for expect >= 0, else 0
 void launch_compact(hipStream_t s, int n, const uint8_t *mask, int *idxI, int *idxA, int *pos,
-                    int *counts);
+                    int *counts, int expect);
+// launch_active_set into `mask' and launch_compact of it in one single-workgroup launch
+void launch_mask_compact(hipStream_t s, int n, int use_tau, double lamb, double f_x, double f_x0,
+                         double f_d, const double *xhat, const double *x, const double *g,
+                         const double *slb, const double *sub, uint8_t *mask, int *idxI, int *idxA,
+                         int *pos, int *counts, int expect);
 void launch_residual(hipStream_t s, int n, int m, double lamb, double dt, const double *xhat,
                      const double *yhat, const double *x, const double *y, const double *g,
                      const double *c, const double *slb, const double *sub, const uint8_t *mask,
                      double *F, double *b0full);
+// launch_residual and, for |A| = 0, launch_reduced_rhs in one launch
+void launch_residual_rhs(hipStream_t s, int n, int m, int nI, double lamb, double dt, double fact,
+                         const double *xhat, const double *yhat, const double *x, const double *y,
+                         const double *g, const double *c, const double *slb, const double *sub,
+                         const uint8_t *mask, const int *idxI, double *F, double *b0full, double *rhs);
 void launch_reduced_rhs(hipStream_t s, int n, int m, int nI, int nA, double fact, const double *F,
                         const int *idxI, const int *idxA, const double *H, int64_t ldh, const double *J,
                         int64_t ldj, const double *b0full, double *partial, int nparts, double *rhs);
 void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H, int64_t ldh,
                          const double *J, int64_t ldj, const int *idxI, int nI, int m,
-                         double lamb, double delta);
+                         double lamb, double delta, int *zero = nullptr, int nzero = 0,
+                         const double *row_src = nullptr, double *row_dst = nullptr, int row_n = 0);
 void launch_copy(hipStream_t s, double *dst, const double *src, int n);
 void launch_copy_u8(hipStream_t s, uint8_t *dst, const uint8_t *src, int n);
 void launch_mask_diff(hipStream_t s, int n, const uint8_t *a, const uint8_t *b, int *out);
@@ -29,7 +41,10 @@ void launch_step_update(hipStream_t s, int n, int m, int nI, double fact, double
                         const double *x, const double *y, const double *lb, const double *ub,
                         const uint8_t *mask, const int *pos, const double *b0full,
                         const double *F, const double *sol, double *dx, double *dy, double *xn,
-                        double *yn, double *red, double *diff_out);
+                        double *yn, double *red, double *diff_out, unsigned *ticket, double lamb = 0.0,
+                        double *v = nullptr, double *lv = nullptr, double *zero3 = nullptr,
+                        const int *flags_src = nullptr, const int *chain_src = nullptr,
+                        int *status = nullptr);
 void launch_gemv_rows(hipStream_t s, int rows, int cols, const double *M, int64_t ld,
                       const double *v, const double *add, double sgn, double *out);
 void launch_gemvT(hipStream_t s, int rows, int cols, const double *M, int64_t ld,
@@ -39,7 +54,8 @@ void launch_mult_vec(hipStream_t s, int m, double rho, const double *c, const do
 void launch_unscaled_res_norm(hipStream_t s, int n, int m, double dt, const double *xhat,
                               const double *yhat, const double *x, const double *y,
                               const double *g, const double *c, const double *lb,
-                              const double *ub, double *red, double *out);
+                              const double *ub, double *red, double *out, double *out2,
+                              unsigned *ticket);
 void launch_final_reduce(hipStream_t s, const double *red, int cnt, double *out, int take_sqrt);
 void launch_measures(hipStream_t s, int n, int m, double active_tol, const double *x,
                      const double *y, const double *r, const double *c, const double *lb,
@@ -52,7 +68,8 @@ void launch_kkt_residual(hipStream_t s, int n, int m, int nI, double lamb, doubl
                          const double *H, int64_t ldh, const double *J, int64_t ldj,
                          const int *idxI, const int *pos, const uint8_t *mask, const double *rhs,
                          const double *sol, double *v, double *lv, double *u, double *wy,
-                         double *partial, int nparts, double *r, double *red3);
+                         double *partial, int nparts, double *r, double *red3,
+                         bool prepared = false);
 void launch_axpy1(hipStream_t s, int N, const double *d, double *x);
 void launch_symmetrize(hipStream_t s, double *A, int64_t ld, int N);
 // ||H||_inf, ||J||_inf, ||J||_1 -> norms3 (device), for the normwise backward error of the guard
@@ -75,4 +92,4 @@ void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, 
                               const uint8_t *mask, const double *rhs, const double *sol, double *v, double *lv,
                               double *u, double *wy, double *partial, int nparts, double *r, double *red3,
                               const double *xn, const double *yn, const double *b, const double *q, double rho,
-                              double *c, double *w, double *tmpn, double *g);
+                              double *c, double *w, double *tmpn, double *g, bool prepared = false);

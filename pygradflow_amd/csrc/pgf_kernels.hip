@@ -25,13 +25,13 @@ __device__ __forceinline__ void b_scale_bounds(int n, double lamb, const double 
 // ---------------------------------------------------------------- p and mask (a3, a4)
 // tau form: (f_x * x + f_x0 * x_hat) - f_d * g, evaluated left to right as numpy does
 // (implicit_func.py:237-244); plain form: lamb * x_hat - g (:246).
-__device__ __forceinline__ void b_active_set(int n, int use_tau, double lamb, double f_x,
-    double f_x0, double f_d,
-                             const double *__restrict__ xhat, const double *__restrict__ x,
-                             const double *__restrict__ g, const double *__restrict__ slb,
-                             const double *__restrict__ sub, uint8_t *__restrict__ mask) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ uint8_t active_flag(int i, int use_tau, double lamb, double f_x,
+                                               double f_x0, double f_d,
+                                               const double *__restrict__ xhat,
+                                               const double *__restrict__ x,
+                                               const double *__restrict__ g,
+                                               const double *__restrict__ slb,
+                                               const double *__restrict__ sub) {
   double p;
   if (use_tau) {
     const double a = f_x * x[i];
@@ -43,24 +43,52 @@ __device__ __forceinline__ void b_active_set(int n, int use_tau, double lamb, do
   }
   const double lo = slb[i] - ACTIVE_EPS;
   const double hi = sub[i] + ACTIVE_EPS;
-  mask[i] = (p < lo || p > hi) ? 1 : 0;
+  return (p < lo || p > hi) ? 1 : 0;
+}
+__device__ __forceinline__ void b_active_set(int n, int use_tau, double lamb, double f_x,
+    double f_x0, double f_d,
+                             const double *__restrict__ xhat, const double *__restrict__ x,
+                             const double *__restrict__ g, const double *__restrict__ slb,
+                             const double *__restrict__ sub, uint8_t *__restrict__ mask) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  mask[i] = active_flag(i, use_tau, lamb, f_x, f_x0, f_d, xhat, x, g, slb, sub);
 }
 
 // ---------------------------------------------------------------- compaction (k2)
 // One workgroup of 1024 lanes walks the mask in chunks; wavefront ballots + a scan of the
 // 16 wave totals give stable (ascending) index lists of the inactive and active sets.
-// pos[j] = rank of j inside its own list.
+// pos[j] = rank of j inside its own list.  counts[0, 1] <- |I|, |A|; counts[3] <- 1 when |I|
+// differs from `expect' (the count a speculatively enqueued step runs with; -1: none).
+// ActiveArgs::xhat != nullptr: the mask is evaluated here (b_active_set's predicate) and stored
+// to `mask' on the way -- the active set, its copy and the compaction in one launch.
+struct ActiveArgs {
+  int use_tau;
+  double lamb, f_x, f_x0, f_d;
+  const double *xhat, *x, *g, *slb, *sub;
+};
 __device__ __forceinline__ void b_compact(int n, const uint8_t *__restrict__ mask,
                                                   int *__restrict__ idxI, int *__restrict__ idxA,
-                                                  int *__restrict__ pos, int *__restrict__ counts) {
+                                                  int *__restrict__ pos, int *__restrict__ counts,
+                                                  int expect = -1, const ActiveArgs *eval = nullptr,
+                                                  uint8_t *__restrict__ mask_out = nullptr) {
   __shared__ int wtot[16];
-  __shared__ int base_s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int baseI = 0;
   for (int start = 0; start < n; start += 1024) {
     const int j = start + tid;
     const bool valid = j < n;
-    const bool inact = valid && (mask[j] == 0);
+    bool inact;
+    if (eval) {
+      const uint8_t mk = valid ? active_flag(j, eval->use_tau, eval->lamb, eval->f_x, eval->f_x0,
+                                             eval->f_d, eval->xhat, eval->x, eval->g, eval->slb,
+                                             eval->sub)
+                               : 1;
+      if (valid) mask_out[j] = mk;
+      inact = valid && mk == 0;
+    } else {
+      inact = valid && (mask[j] == 0);
+    }
     const unsigned long long bal = __ballot(inact);
     const int before = __popcll(bal & ((1ull << lane) - 1ull));
     if (lane == 0) wtot[wave] = __popcll(bal);
@@ -88,33 +116,40 @@ __device__ __forceinline__ void b_compact(int n, const uint8_t *__restrict__ mas
   if (tid == 0) {
     counts[0] = baseI;
     counts[1] = n - baseI;
-    base_s = baseI;
+    counts[3] = (expect >= 0 && baseI != expect) ? 1 : 0;
   }
-  (void)base_s;
 }
 
 // ---------------------------------------------------------------- residual (a5, a6)
 // F = [lamb x - P(p) ; -(lamb y - (lamb y_hat + c))], P clips only masked entries
 // (np.clip == min(max(p, lo), hi)).  Also emits b0full = mask ? dt * F_x : 0 (a8).
+__device__ __forceinline__ double residual_x(int i, double lamb, const double *__restrict__ xhat,
+                                            const double *__restrict__ x, const double *__restrict__ g,
+                                            const double *__restrict__ slb, const double *__restrict__ sub,
+                                            const uint8_t *__restrict__ mask) {
+  double p = lamb * xhat[i] - g[i];
+  if (mask[i] != 0) p = fmin(fmax(p, slb[i]), sub[i]);
+  return lamb * x[i] - p;
+}
+__device__ __forceinline__ double residual_y(int r, double lamb, const double *__restrict__ yhat,
+                                            const double *__restrict__ y, const double *__restrict__ c) {
+  const double t = lamb * yhat[r] + c[r];
+  return -(lamb * y[r] - t);
+}
 __device__ __forceinline__ void b_residual(int n, int m, double lamb, double dt,
     const double *__restrict__ xhat,
                            const double *__restrict__ yhat, const double *__restrict__ x,
                            const double *__restrict__ y, const double *__restrict__ g,
                            const double *__restrict__ c, const double *__restrict__ slb,
                            const double *__restrict__ sub, const uint8_t *__restrict__ mask,
-                           double *__restrict__ F, double *__restrict__ b0full) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+                           double *__restrict__ F, double *__restrict__ b0full,
+                           int i) {
   if (i < n) {
-    double p = lamb * xhat[i] - g[i];
-    const bool act = mask[i] != 0;
-    if (act) p = fmin(fmax(p, slb[i]), sub[i]);
-    const double f = lamb * x[i] - p;
+    const double f = residual_x(i, lamb, xhat, x, g, slb, sub, mask);
     F[i] = f;
-    if (b0full) b0full[i] = act ? dt * f : 0.0;
+    if (b0full) b0full[i] = mask[i] != 0 ? dt * f : 0.0;
   } else if (i < n + m) {
-    const int r = i - n;
-    const double t = lamb * yhat[r] + c[r];
-    F[i] = -(lamb * y[r] - t);
+    F[i] = residual_y(i - n, lamb, yhat, y, c);
   }
 }
 
@@ -507,8 +542,14 @@ __global__ void k_active_set(int n, int use_tau, double lamb, double f_x, double
 
 __global__ __launch_bounds__(1024) void k_compact(int n, const uint8_t *__restrict__ mask,
     int *__restrict__ idxI, int *__restrict__ idxA, int *__restrict__ pos,
-    int *__restrict__ counts) {
-  b_compact(n, mask, idxI, idxA, pos, counts);
+    int *__restrict__ counts, int expect) {
+  b_compact(n, mask, idxI, idxA, pos, counts, expect);
+}
+
+__global__ __launch_bounds__(1024) void k_mask_compact(int n, ActiveArgs a, uint8_t *__restrict__ mask,
+    int *__restrict__ idxI, int *__restrict__ idxA, int *__restrict__ pos,
+    int *__restrict__ counts, int expect) {
+  b_compact(n, nullptr, idxI, idxA, pos, counts, expect, &a, mask);
 }
 
 __global__ void k_residual(int n, int m, double lamb, double dt, const double *__restrict__ xhat,
@@ -516,7 +557,30 @@ __global__ void k_residual(int n, int m, double lamb, double dt, const double *_
     const double *__restrict__ g, const double *__restrict__ c, const double *__restrict__ slb,
     const double *__restrict__ sub, const uint8_t *__restrict__ mask, double *__restrict__ F,
     double *__restrict__ b0full) {
-  b_residual(n, m, lamb, dt, xhat, yhat, x, y, g, c, slb, sub, mask, F, b0full);
+  b_residual(n, m, lamb, dt, xhat, yhat, x, y, g, c, slb, sub, mask, F, b0full,
+             blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// k_residual and, for |A| = 0 (b0full = 0: no correction terms), k_reduced_rhs in one launch: the
+// rows of the reduced rhs take F at their index from the same per-element functions (bit-identical
+// to reading it back; F - 0.0 == F), so no workgroup waits for another.  256 lanes per workgroup
+// run the elementwise part, its 4 wavefronts one rhs row each.
+__global__ __launch_bounds__(256) void k_residual_rhs(int n, int m, int nI, double lamb, double dt,
+    double fact, const double *__restrict__ xhat, const double *__restrict__ yhat,
+    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ g,
+    const double *__restrict__ c, const double *__restrict__ slb, const double *__restrict__ sub,
+    const uint8_t *__restrict__ mask, const int *__restrict__ idxI, double *__restrict__ F,
+    double *__restrict__ b0full, double *__restrict__ rhs) {
+  b_residual(n, m, lamb, dt, xhat, yhat, x, y, g, c, slb, sub, mask, F, b0full,
+             blockIdx.x * 256 + threadIdx.x);
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if ((threadIdx.x & 63) != 0 || i >= nI + m) return;
+  if (i < nI) {
+    rhs[i] = residual_x(idxI[i], lamb, xhat, x, g, slb, sub, mask) - 0.0;
+  } else {
+    const int r = i - nI;
+    rhs[i] = fact * residual_y(r, lamb, yhat, y, c) - 0.0;
+  }
 }
 
 __global__ __launch_bounds__(256) void k_active_rows_partial(int n, int nA, const int *__restrict__ idxA,
@@ -531,9 +595,18 @@ __global__ __launch_bounds__(256) void k_reduced_rhs(int n, int m, int nI, int n
   b_reduced_rhs(n, m, nI, nA, fact, F, idxI, J, ldj, b0full, partial, nparts, rhs);
 }
 
+// (zero: words cleared by the first workgroup -- the factorisation's flags and tile counters;
+// row_src: copied to row_dst[0, row_n) by the workgroups of the first row group)
 __global__ __launch_bounds__(256) void k_assemble_kkt(double *__restrict__ K, int64_t ldk,
     const double *__restrict__ H, int64_t ldh, const double *__restrict__ J, int64_t ldj,
-    const int *__restrict__ idxI, int nI, int m, double lamb, double delta) {
+    const int *__restrict__ idxI, int nI, int m, double lamb, double delta, int *__restrict__ zero,
+    int nzero, const double *__restrict__ row_src, double *__restrict__ row_dst, int row_n) {
+  if (blockIdx.y == 0) {
+    if (zero && blockIdx.x == 0)
+      for (int t = threadIdx.x; t < nzero; t += 256) zero[t] = 0;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (row_src && j < row_n) row_dst[j] = row_src[j];
+  }
   b_assemble_kkt(K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta);
 }
 
@@ -550,14 +623,71 @@ __global__ void k_mask_diff(int n, const uint8_t *__restrict__ a, const uint8_t 
   b_mask_diff(n, a, b, out);
 }
 
+// The last workgroup to finish (atomic ticket) sums the per-block partials of red[0, nb) in
+// b_final_reduce's fixed order, every workgroup's partial having been published by a release
+// fence before its ticket; the ticket word is reset for the next launch.  Returns true in the
+// workgroup that did it.
+__device__ __forceinline__ bool last_block_reduce(const double *red, int nb, double *out,
+                                                  unsigned *ticket) {
+  __shared__ bool last;
+  __syncthreads();  // (red[blockIdx.x] is stored by lane 0 after the block's own barrier)
+  if (threadIdx.x == 0) {
+    __threadfence();
+    last = atomicAdd(ticket, 1u) == (unsigned)(nb - 1);
+  }
+  __syncthreads();
+  if (!last) return false;
+  __threadfence();
+  b_final_reduce(red, nb, out, 1);
+  if (threadIdx.x == 0) *ticket = 0u;
+  return true;
+}
+
+// Optional extras of the step-update launch (StepExtras, nullptr members are skipped):
+//   v, lv      the residual check's expansion of the solution (k_expand_sol)
+//   zero3      words cleared before the residual check's atomics (red3)
+//   flags_src  -> status[0, 4): the factorisation's flag words;  chain_src -> status[3]: the
+//              chained solve's status word (both copied by the last workgroup, so the host reads
+//              them with the rest of the step's status block)
+struct StepExtras {
+  double lamb;
+  double *v, *lv, *zero3;
+  const int *flags_src, *chain_src;
+  int *status;
+  unsigned *ticket;
+};
 __global__ __launch_bounds__(256) void k_step_update(int n, int m, int nI, double fact,
     double rho, const double *__restrict__ x, const double *__restrict__ y,
     const double *__restrict__ lb, const double *__restrict__ ub,
     const uint8_t *__restrict__ mask, const int *__restrict__ pos,
     const double *__restrict__ b0full, const double *__restrict__ F,
     const double *__restrict__ sol, double *__restrict__ dx, double *__restrict__ dy,
-    double *__restrict__ xn, double *__restrict__ yn, double *__restrict__ red) {
+    double *__restrict__ xn, double *__restrict__ yn, double *__restrict__ red,
+    double *__restrict__ diff_out, StepExtras ex) {
   b_step_update(n, m, nI, fact, rho, x, y, lb, ub, mask, pos, b0full, F, sol, dx, dy, xn, yn, red);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (ex.v && i < n) {
+    const double val = mask[i] ? 0.0 : sol[pos[i]];
+    ex.v[i] = val;
+    ex.lv[i] = ex.lamb * val;
+  }
+  if (ex.zero3 && blockIdx.x == 0 && threadIdx.x < 3) ex.zero3[threadIdx.x] = 0.0;
+  if (!last_block_reduce(red, gridDim.x, diff_out, ex.ticket)) return;
+  if (threadIdx.x < 4) {
+    int w = ex.flags_src ? ex.flags_src[threadIdx.x] : 0;
+    if (threadIdx.x == 3 && ex.chain_src) w = *ex.chain_src;
+    if (ex.flags_src || (threadIdx.x == 3 && ex.chain_src)) ex.status[threadIdx.x] = w;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_unscaled_res_norm(int n, int m, double dt,
+    const double *__restrict__ xhat, const double *__restrict__ yhat,
+    const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ g,
+    const double *__restrict__ c, const double *__restrict__ lb, const double *__restrict__ ub,
+    double *__restrict__ red, double *__restrict__ out, double *__restrict__ out2,
+    unsigned *__restrict__ ticket) {
+  b_unscaled_res_sq(n, m, dt, xhat, yhat, x, y, g, c, lb, ub, red);
+  if (last_block_reduce(red, gridDim.x, out, ticket) && out2 && threadIdx.x == 0) out2[0] = out[0];
 }
 
 __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__ red, int cnt,
@@ -612,8 +742,17 @@ void launch_active_set(hipStream_t s, int n, int use_tau, double lamb, double f_
 }
 
 void launch_compact(hipStream_t s, int n, const uint8_t *mask, int *idxI, int *idxA, int *pos,
-                    int *counts) {
-  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, n, mask, idxI, idxA, pos, counts);
+                    int *counts, int expect) {
+  hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, n, mask, idxI, idxA, pos, counts, expect);
+}
+
+void launch_mask_compact(hipStream_t s, int n, int use_tau, double lamb, double f_x, double f_x0,
+                         double f_d, const double *xhat, const double *x, const double *g,
+                         const double *slb, const double *sub, uint8_t *mask, int *idxI, int *idxA,
+                         int *pos, int *counts, int expect) {
+  const ActiveArgs a{use_tau, lamb, f_x, f_x0, f_d, xhat, x, g, slb, sub};
+  hipLaunchKernelGGL(k_mask_compact, dim3(1), dim3(1024), 0, s, n, a, mask, idxI, idxA, pos, counts,
+                     expect);
 }
 
 void launch_residual(hipStream_t s, int n, int m, double lamb, double dt, const double *xhat,
@@ -623,6 +762,16 @@ void launch_residual(hipStream_t s, int n, int m, double lamb, double dt, const 
   if (n + m)
     hipLaunchKernelGGL(k_residual, g1(n + m), dim3(256), 0, s, n, m, lamb, dt, xhat, yhat, x, y,
                        g, c, slb, sub, mask, F, b0full);
+}
+
+void launch_residual_rhs(hipStream_t s, int n, int m, int nI, double lamb, double dt, double fact,
+                         const double *xhat, const double *yhat, const double *x, const double *y,
+                         const double *g, const double *c, const double *slb, const double *sub,
+                         const uint8_t *mask, const int *idxI, double *F, double *b0full, double *rhs) {
+  const int nb = std::max((n + m + 255) / 256, (nI + m + 3) / 4);
+  if (nb)
+    hipLaunchKernelGGL(k_residual_rhs, dim3(nb), dim3(256), 0, s, n, m, nI, lamb, dt, fact, xhat, yhat, x, y,
+                       g, c, slb, sub, mask, idxI, F, b0full, rhs);
 }
 
 void launch_reduced_rhs(hipStream_t s, int n, int m, int nI, int nA, double fact, const double *F,
@@ -639,11 +788,13 @@ void launch_reduced_rhs(hipStream_t s, int n, int m, int nI, int nA, double fact
 
 void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H, int64_t ldh,
                          const double *J, int64_t ldj, const int *idxI, int nI, int m,
-                         double lamb, double delta) {
+                         double lamb, double delta, int *zero, int nzero, const double *row_src,
+                         double *row_dst, int row_n) {
   const int N = nI + m;
   if (N)
     hipLaunchKernelGGL(k_assemble_kkt, dim3((N + 255) / 256, (N + ASM_ROWS - 1) / ASM_ROWS),
-                       dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta);
+                       dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, zero, nzero,
+                       row_src, row_dst, std::min(row_n, N));
 }
 
 void launch_copy(hipStream_t s, double *dst, const double *src, int n) {
@@ -664,11 +815,16 @@ void launch_step_update(hipStream_t s, int n, int m, int nI, double fact, double
                         const double *x, const double *y, const double *lb, const double *ub,
                         const uint8_t *mask, const int *pos, const double *b0full,
                         const double *F, const double *sol, double *dx, double *dy, double *xn,
-                        double *yn, double *red, double *diff_out) {
+                        double *yn, double *red, double *diff_out, unsigned *ticket, double lamb,
+                        double *v, double *lv, double *zero3, const int *flags_src,
+                        const int *chain_src, int *status) {
   const int nb = step_update_blocks(n, m);
-  if (nb)
+  const StepExtras ex{lamb, v, lv, zero3, flags_src, chain_src, status, ticket};
+  if (nb) {
     hipLaunchKernelGGL(k_step_update, dim3(nb), dim3(256), 0, s, n, m, nI, fact, rho, x, y, lb, ub,
-                       mask, pos, b0full, F, sol, dx, dy, xn, yn, red);
+                       mask, pos, b0full, F, sol, dx, dy, xn, yn, red, diff_out, ex);
+    return;
+  }
   hipLaunchKernelGGL(k_final_reduce, dim3(1), dim3(256), 0, s, red, nb, diff_out, 1);
 }
 
@@ -702,12 +858,16 @@ void launch_mult_vec(hipStream_t s, int m, double rho, const double *c, const do
 void launch_unscaled_res_norm(hipStream_t s, int n, int m, double dt, const double *xhat,
                               const double *yhat, const double *x, const double *y,
                               const double *g, const double *c, const double *lb,
-                              const double *ub, double *red, double *out) {
+                              const double *ub, double *red, double *out, double *out2,
+                              unsigned *ticket) {
   const int nb = (n + m + 255) / 256;
-  if (nb)
-    hipLaunchKernelGGL(k_unscaled_res_sq, dim3(nb), dim3(256), 0, s, n, m, dt, xhat, yhat, x, y, g,
-                       c, lb, ub, red);
+  if (nb) {
+    hipLaunchKernelGGL(k_unscaled_res_norm, dim3(nb), dim3(256), 0, s, n, m, dt, xhat, yhat, x, y, g,
+                       c, lb, ub, red, out, out2, ticket);
+    return;
+  }
   hipLaunchKernelGGL(k_final_reduce, dim3(1), dim3(256), 0, s, red, nb, out, 1);
+  if (out2) (void)hipMemcpyAsync(out2, out, sizeof(double), hipMemcpyDeviceToDevice, s);
 }
 
 void launch_final_reduce(hipStream_t s, const double *red, int cnt, double *out, int take_sqrt) {
@@ -825,11 +985,11 @@ void launch_kkt_residual(hipStream_t s, int n, int m, int nI, double lamb, doubl
                          const double *H, int64_t ldh, const double *J, int64_t ldj,
                          const int *idxI, const int *pos, const uint8_t *mask, const double *rhs,
                          const double *sol, double *v, double *lv, double *u, double *wy,
-                         double *partial, int nparts, double *r, double *red3) {
+                         double *partial, int nparts, double *r, double *red3, bool prepared) {
   const int N = nI + m;
-  (void)hipMemsetAsync(red3, 0, 3 * sizeof(double), s);
+  if (!prepared) (void)hipMemsetAsync(red3, 0, 3 * sizeof(double), s);
   if (N == 0) return;
-  if (n) hipLaunchKernelGGL(k_expand_sol, g1(n), dim3(256), 0, s, n, nI, pos, mask, sol, lamb, v, lv);
+  if (n && !prepared) hipLaunchKernelGGL(k_expand_sol, g1(n), dim3(256), 0, s, n, nI, pos, mask, sol, lamb, v, lv);
   // u = H v + (lambda v + J' s_y)
   launch_gemvT(s, m, n, J, ldj, sol + nI, lv, partial, nparts, u);
   launch_gemv_rows(s, n, n, H, ldh, v, u, 1.0, lv);  // lv is free again: it receives H v + u
@@ -890,19 +1050,24 @@ __global__ __launch_bounds__(256) void k_gemv_rows2(int rows, int cols, const do
   }
 }
 // partial1[rb][j] = sum_{r in chunk rb} M[r][j] w1[r], partial2 likewise with w2
+// w1 = rho c + y1 (b_mult_vec's expression) is formed here, row by row, and stored by the first
+// column of workgroups
 __global__ __launch_bounds__(256) void k_gemvT_partial2(int rows, int cols, const double *__restrict__ M,
-                                                        int64_t ld, const double *__restrict__ w1,
+                                                        int64_t ld, double rho, const double *__restrict__ c,
+                                                        const double *__restrict__ y1, double *__restrict__ w1,
                                                         const double *__restrict__ w2, int chunk,
                                                         double *__restrict__ partial1,
                                                         double *__restrict__ partial2) {
   const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= cols) return;
   const int r0 = blockIdx.y * chunk;
   const int r1 = min(rows, r0 + chunk);
+  if (blockIdx.x == 0)
+    for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) w1[r] = rho * c[r] + y1[r];
+  if (j >= cols) return;
   double a1 = 0.0, a2 = 0.0;
   for (int r = r0; r < r1; ++r) {
     const double mv = M[(int64_t)r * ld + j];
-    a1 = fma(mv, w1[r], a1);
+    a1 = fma(mv, rho * c[r] + y1[r], a1);
     a2 = fma(mv, w2[r], a2);
   }
   partial1[(int64_t)blockIdx.y * cols + j] = a1;
@@ -931,16 +1096,16 @@ void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, 
                               const uint8_t *mask, const double *rhs, const double *sol, double *v, double *lv,
                               double *u, double *wy, double *partial, int nparts, double *r, double *red3,
                               const double *xn, const double *yn, const double *b, const double *q, double rho,
-                              double *c, double *w, double *tmpn, double *g) {
+                              double *c, double *w, double *tmpn, double *g, bool prepared) {
   const int N = nI + m;
-  (void)hipMemsetAsync(red3, 0, 3 * sizeof(double), s);
-  if (n) hipLaunchKernelGGL(k_expand_sol, g1(n), dim3(256), 0, s, n, nI, pos, mask, sol, lamb, v, lv);
+  if (!prepared) (void)hipMemsetAsync(red3, 0, 3 * sizeof(double), s);
+  if (n && !prepared) hipLaunchKernelGGL(k_expand_sol, g1(n), dim3(256), 0, s, n, nI, pos, mask, sol, lamb, v, lv);
   // one pass over J: c = J xn - b, wy = J v - delta s_y
   if (m)
     hipLaunchKernelGGL(k_gemv_rows2, dim3((m + 3) / 4), dim3(256), 0, s, m, n, J, ldj, xn, b, -1.0, c, v,
                        sol + nI, -delta, wy);
-  launch_mult_vec(s, m, rho, c, yn, w);
-  // one pass over J (transposed): tmpn = q + J' w, u = lambda v + J' s_y
+  // one pass over J (transposed): tmpn = q + J' w, u = lambda v + J' s_y (w = rho c + yn formed on the way)
+  if (n == 0) launch_mult_vec(s, m, rho, c, yn, w);
   if (n) {
     if (m == 0) {
       launch_copy(s, tmpn, q, n);
@@ -949,8 +1114,8 @@ void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, 
       const int chunk = (m + nparts - 1) / nparts;
       const int used = (m + chunk - 1) / chunk;
       double *p2 = partial + (size_t)nparts * n;
-      hipLaunchKernelGGL(k_gemvT_partial2, dim3((n + 255) / 256, used), dim3(256), 0, s, m, n, J, ldj, w,
-                         sol + nI, chunk, partial, p2);
+      hipLaunchKernelGGL(k_gemvT_partial2, dim3((n + 255) / 256, used), dim3(256), 0, s, m, n, J, ldj, rho, c,
+                         yn, w, sol + nI, chunk, partial, p2);
       hipLaunchKernelGGL(k_sum_partials2, g1(n), dim3(256), 0, s, n, used, partial, q, tmpn, p2, lv, u);
     }
     // one pass over H: g = H xn + tmpn, lv <- H v + u
@@ -1122,7 +1287,7 @@ __global__ void kb_residual(const BInst *__restrict__ tab, int n, int m) {
   if (I.ctl[3]) return;
   const double lamb = I.ps[BPS_LAMB], dt = I.ps[BPS_DT];
   b_residual(n, m, lamb, dt, I.xhat, I.yhat, I.x, I.y, I.g, I.c, I.slb, I.sub, I.mask, I.F,
-             I.b0full);
+             I.b0full, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 __global__ __launch_bounds__(256) void kb_active_rows_partial(const BInst *__restrict__ tab, int n,
@@ -1594,12 +1759,22 @@ void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchSc
 
 // V[i][r] = J[r][idxI[i]] (r < m), 0 for the padding columns: 32 x 32 tiles through LDS, reads
 // run along i (contiguous whenever I is), writes along r
+__device__ __forceinline__ void b_cond_tail(double *__restrict__ Vrow, double *__restrict__ vd, int r,
+                                            int mp, int m, const double *__restrict__ rhs_y, double delta) {
+  if (r >= mp) return;
+  Vrow[r] = (rhs_y && r < m) ? rhs_y[r] : 0.0;
+  vd[r] = -1.0 / delta;
+}
+// (the workgroups of the first column also write k_cond_tail's 32 entries of their row group)
 __global__ __launch_bounds__(256) void k_cond_panel(double *__restrict__ V, int64_t ldv, int mp,
                                                     const double *__restrict__ J, int64_t ldj,
-                                                    const int *__restrict__ idxI, int nI, int m) {
+                                                    const int *__restrict__ idxI, int nI, int m,
+                                                    double *__restrict__ vd, const double *__restrict__ rhs_y,
+                                                    double delta) {
   __shared__ double tile[32][33];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int i0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+  if (blockIdx.x == 0 && ty == 0) b_cond_tail(V + (int64_t)nI * ldv, vd, r0 + tx, mp, m, rhs_y, delta);
   const int i = i0 + tx;
   const int col = i < nI ? idxI[i] : 0;
 #pragma unroll
@@ -1618,10 +1793,7 @@ __global__ __launch_bounds__(256) void k_cond_panel(double *__restrict__ V, int6
 // row nI of V <- the constraint part of the right-hand side (or zeros), vd <- -1 / delta
 __global__ void k_cond_tail(double *__restrict__ Vrow, double *__restrict__ vd, int mp, int m,
                             const double *__restrict__ rhs_y, double delta) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= mp) return;
-  Vrow[r] = (rhs_y && r < m) ? rhs_y[r] : 0.0;
-  vd[r] = -1.0 / delta;
+  b_cond_tail(Vrow, vd, blockIdx.x * blockDim.x + threadIdx.x, mp, m, rhs_y, delta);
 }
 
 // out[i] = rhs[i] + dot(V[i][0:m], rhs[nI:nI+m]) / delta
@@ -1656,8 +1828,8 @@ void launch_cond_panel(hipStream_t s, double *V, int64_t ldv, int mp, double *vd
                        int64_t ldj, const int *idxI, int nI, int m, double delta, const double *rhs_y) {
   if (nI > 0 && mp > 0)
     hipLaunchKernelGGL(k_cond_panel, dim3((nI + 31) / 32, mp / 32), dim3(256), 0, s, V, ldv, mp, J, ldj,
-                       idxI, nI, m);
-  if (mp > 0)
+                       idxI, nI, m, vd, rhs_y, delta);
+  else if (mp > 0)
     hipLaunchKernelGGL(k_cond_tail, g1(mp), dim3(256), 0, s, V + (int64_t)nI * ldv, vd, mp, m, rhs_y, delta);
 }
 

@@ -1465,7 +1465,9 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
   f.N = N;
   f.factored = false;
   hipStream_t sA = f.stream;
-  hipError_t e = hipMemsetAsync(f.flags, 0, 4 * sizeof(int), sA);
+  hipError_t e = hipSuccess;
+  if (!f.flags_zeroed) e = hipMemsetAsync(f.flags, 0, 4 * sizeof(int), sA);
+  f.flags_zeroed = false;
   if (e != hipSuccess) return e;
   PgfProfile *p = (f.prof && f.prof->enabled) ? f.prof : nullptr;
   if (p) {
@@ -1490,8 +1492,12 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
     hipLaunchKernelGGL(k_inv_diag_blocks, dim3((N + 63) / 64), dim3(64), 0, sA, f.K, f.ldk, N,
                        f.Linv, f.LinvT);
   if (p) (void)hipEventRecord(p->factor_spans.back().second, sA);
-  e = hipMemcpyAsync(f.h_flags, f.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, sA);
-  if (e != hipSuccess) return e;
+  if (f.defer_status) {
+    f.status_words |= 1;
+  } else {
+    e = hipMemcpyAsync(f.h_flags, f.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, sA);
+    if (e != hipSuccess) return e;
+  }
   return hipGetLastError();
 }
 
@@ -1537,6 +1543,15 @@ int ldlt_chain_check(DenseLdlt &f) {
   return bad;
 }
 
+// a chained solve of a step that is discarded (pgf_api.hip, speculative index-set sizes) reported
+// a failure: the state it may have left half published is reset, but the chain stays on -- the
+// repeated step's own solve decides that
+void ldlt_chain_discard(DenseLdlt &f, int word) {
+  if (!f.chain || !word) return;
+  (void)hipMemsetAsync(f.chain + 2 * f.chain_stride + 1, 0, sizeof(int), f.stream);
+  (void)hipMemsetAsync(f.xpub, 0xff, 2 * (size_t)f.chain_stride * 64 * sizeof(double), f.stream);
+}
+
 // test hook (pgf_debug_fail_next_chain): make the chained solve just enqueued look like one that
 // failed its checks -- status word set, solution overwritten with NaN
 __global__ void k_chain_inject(double *__restrict__ sol, int N, int *__restrict__ ctl) {
@@ -1550,6 +1565,10 @@ static hipError_t chain_report(DenseLdlt &f, double *sol) {
     f.inject_chain_failure = 0;
     hipLaunchKernelGGL(k_chain_inject, dim3((f.N + 255) / 256), dim3(256), 0, f.stream, sol, f.N,
                        f.chain + 2 * f.chain_stride);
+  }
+  if (f.defer_status) {
+    f.status_words |= 2;
+    return hipSuccess;
   }
   return hipMemcpyAsync(f.h_flags + 3, f.chain + 2 * f.chain_stride + 1, sizeof(int),
                         hipMemcpyDeviceToHost, f.stream);
