@@ -606,7 +606,6 @@ static bool condensed_growth_ok(pgf_handle h) {
 static bool condensed_wanted(pgf_handle h) {
   const int mode = condensed_mode();
   if (!mode || h->condensed_veto || h->sparse || h->m == 0 || h->nI == 0 || h->m > h->n) return false;
-  if (!ldlt_use_lookahead()) return false;
   if (mode == 1 && (h->m < 64 || (h->N + 255) / 256 <= (h->nI + 255) / 256)) return false;
   if (residual_norms(h)) return false;
   return condensed_growth_ok(h);
@@ -1860,7 +1859,7 @@ int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev) {
 // ---------------------------------------------------------------- batched mode
 struct pgf_batch_s {
   std::vector<pgf_handle> hs;
-  int B = 0, n = 0, m = 0, device = 0, OB = 256;
+  int B = 0, n = 0, m = 0, device = 0;
   hipStream_t stream = nullptr;
   BInst *tab = nullptr;
   int *ctl = nullptr, *flags_out = nullptr, *h_flags = nullptr;
@@ -1926,7 +1925,6 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
   b->n = h0->n;
   b->m = h0->m;
   b->device = h0->device;
-  b->OB = h0->fac.OB;
   b->sc.n = b->n;
   b->sc.m = b->m;
   (void)hipSetDevice(b->device);
@@ -1954,9 +1952,8 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
   }
-  // the condensed order: dense handles, a constraint block worth a column block, the fused schedule
+  // the condensed order: dense handles, a constraint block worth a column block
   const bool cond_possible = condensed_mode() != 0 && !h0->sparse && h0->m > 0 && h0->m <= h0->n &&
-                             ldlt_use_lookahead() && ldlt_batch_condensed_schedule(b->OB) &&
                              (condensed_mode() == 2 ||
                               (h0->m >= 64 && (h0->n + h0->m + 255) / 256 > (h0->n + 255) / 256));
   b->cond_ok = cond_possible;
@@ -2197,8 +2194,8 @@ static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool ho
   // host knows that every instance refactorises (Full) or none does, skip the other half
   const bool none_factor = !recompute && host_knows_factored;
   if (!none_factor) {
-    ldlt_batch_factor_async(b->stream, b->tab, b->B, Nmax, mf, b->OB,
-                            b->prof.enabled ? &b->prof : nullptr, cond ? b->cond_mp : 0);
+    ldlt_batch_factor_async(b->stream, b->tab, b->B, Nmax, mf, b->prof.enabled ? &b->prof : nullptr,
+                            cond ? b->cond_mp : 0);
     if (b->inject_helper_failure) {
       b->inject_helper_failure = 0;
       ldlt_inject_helper_failure(b->stream, b->hs[0]->fac.flags);
@@ -2551,7 +2548,7 @@ int pgf_batch_profile_enable(pgf_batch b, int on) {
   return PGF_OK;
 }
 
-// Accumulated device time of the K = OB trailing-update launches since the last call and
+// Accumulated device time of the K = LDLT_OB trailing-update launches since the last call and
 // their algorithmic flops, from the reduced sizes of the last synchronised step.
 int pgf_batch_profile_read(pgf_batch b, double *update_ms, int64_t *update_launches,
                            double *update_flops) {
@@ -2565,13 +2562,13 @@ int pgf_batch_profile_read(pgf_batch b, double *update_ms, int64_t *update_launc
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, p.update_spans[i].first, p.update_spans[i].second) == hipSuccess)
       ms_sum += ms;
-    // update_flops[i] >= 0: first row of the launch's trailing region, K-depth OB; < 0: the rank-m
+    // update_flops[i] >= 0: first row of the launch's trailing region, K-depth LDLT_OB; < 0: the rank-m
     // launch of the condensed order over the whole lower triangle, K-depth = -value
     const double start = p.update_flops[i];
     for (int k = 0; k < b->B; ++k) {
       const double Nk = (double)(b->h_flags[3 * k + 2] + (b->cond_last ? 0 : b->m));
       const double T = start < 0 ? Nk : Nk - start;
-      const double depth = start < 0 ? -start : (double)b->OB;
+      const double depth = start < 0 ? -start : (double)LDLT_OB;
       if (T > 0) fl_sum += 2.0 * depth * (0.5 * T * (T + 1.0) + T);
     }
     p.pool.push_back(p.update_spans[i].first);

@@ -1,8 +1,8 @@
-// Look-ahead schedule of the dense LDL^T factorisation of the reduced KKT matrix (the default;
-// replaces SuperLU gstrf reached through scipy.sparse.linalg.splu at reference
-// pygradflow/linear_solver/lu_solver.py:14).  Same arithmetic as pgf_ldlt.hip (unpivoted
-// right-looking LDL^T in the natural order, inertia = number of negative pivots), different
-// division of labour.  Per outer block k of 256 columns:
+// Look-ahead schedule of the dense LDL^T factorisation of the reduced KKT matrix (replaces
+// SuperLU gstrf reached through scipy.sparse.linalg.splu at reference
+// pygradflow/linear_solver/lu_solver.py:14): unpivoted right-looking LDL^T in the natural order,
+// inertia = number of negative pivots; handle and solves in pgf_ldlt.hip.  Per outer block k of
+// LDLT_OB = 256 columns:
 //
 //   k_update_diag  (k-1 -> k)   the 256 x 256 DIAGONAL block of block k receives block k-1's
 //                               update first (36 tiles of 32 x 32, one workgroup each)
@@ -37,7 +37,6 @@
 
 #include "pgf_internal.h"
 #include "pgf_ldlt_dev.h"
-#include "pgf_chain3.h"
 
 #include <algorithm>
 #include <atomic>
@@ -49,6 +48,7 @@
 #define C_LD 66    // LDS row stride of 64-column tiles: conflict-free MFMA fragment reads
 #define C_WLD 18
 #define CH_ROWS 256
+#define CH_WAVES 16  // wavefronts of the chain workgroup (128 registers per lane, a few spilled)
 // M[256][66] | Wt[2][64][18] | D[64] | 1/D[64] | flag | 1/D of the previous sub-panel [64] |
 // Lt[2][16][16]: the factored 16 x 16 tile of a step, transposed (chain_b_own's multipliers)
 #define CH_LT_OFF (CH_ROWS * C_LD * 8 + 2 * 64 * C_WLD * 8 + 3 * 64 * 8 + 16)
@@ -537,9 +537,10 @@ __device__ __forceinline__ void chain_b_own(double (*M)[C_LD], int row, int sbp,
 }
 #else
 // wavefront 0: right-looking elimination of the 16 columns of sub-block sb of the 64 x 64
-// diagonal tile, lane <-> row (the scheme of panel_body's (a+), pgf_ldlt.hip): the tile's rows
-// and, in the same instruction stream, the tile rows below it; emits L into M, W = L D of the
-// rows below the 16 x 16 tile into Wt, D and 1/D.
+// diagonal tile, lane <-> row: every lane holds its row's 16 entries of the sub-block in VGPRs
+// and takes the pivot row's entries with v_readlane (lane_bcast), so the tile's rows and the
+// tile rows below it are eliminated in the same instruction stream; emits L into M, W = L D of
+// the rows below the 16 x 16 tile into Wt, D and 1/D.
 __device__ __forceinline__ void chain_a_plus(double (*M)[C_LD], double (*Wt)[C_WLD], double *dD,
                                              double *dI, int &s_bad, int lane, int sb, int ncol,
                                              double (*Lt)[16]) {
@@ -1012,11 +1013,10 @@ __device__ __forceinline__ void decode_subtile(int e, int &mi, int &mj) {
 // helper T (workgroup 8): for every sub-panel s with rows beyond the NEXT sub-panel, apply it to
 // the lower triangle of those rows / columns [cb + 128, bend): C -= (L D) L^T with L read back
 // from global memory (the chain wrote L = X D^-1; X itself stays in its LDS)
-template <int NW>
 __device__ __forceinline__ void helper_tiles(unsigned char *smem, double *K, int64_t ldk, int c0,
                                              int nb, const double *dvec, int *hc, int epoch,
                                              int *flags) {
-  constexpr int NT = 64 * NW;
+  constexpr int NT = 64 * CH_WAVES;
   double(*Mh)[C_LD] = reinterpret_cast<double(*)[C_LD]>(smem);
   double *dDs = reinterpret_cast<double *>(smem + 128 * C_LD * 8);
   // wave: uniform per wavefront -> scalar register, role tests and tile numbers on the SALU
@@ -1038,7 +1038,7 @@ __device__ __forceinline__ void helper_tiles(unsigned char *smem, double *K, int
     if (tid < 64) dDs[tid] = dvec[cb + tid];
     __syncthreads();
     const int total = nt * (nt + 1) / 2 * 16 - nt * 6;
-    for (int e = wave; e < total; e += NW) {
+    for (int e = wave; e < total; e += CH_WAVES) {
       int mi, mj;
       decode_subtile(e, mi, mj);
       const int gi = r0 + mi, gj = r0 + mj, j = gj + l15;
@@ -1067,7 +1067,6 @@ __device__ __forceinline__ void helper_tiles(unsigned char *smem, double *K, int
 }
 
 // helper I (workgroup 16): the inverse of every sub-panel's diagonal tile as soon as it is final
-template <int NW>
 __device__ __forceinline__ void helper_inverses(unsigned char *smem, const double *K, int64_t ldk,
                                                 int c0, int nb, int *hc, int epoch, int *flags,
                                                 double *__restrict__ Linv,
@@ -1083,7 +1082,7 @@ __device__ __forceinline__ void helper_inverses(unsigned char *smem, const doubl
   }
 }
 
-template <int NW, bool HELP>
+template <bool HELP>
 __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64_t ldk, int c0,
                                            int nb, double *__restrict__ dvec,
                                            double *__restrict__ dinv, int *__restrict__ flags,
@@ -1095,7 +1094,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
   double *dI = dD + 64;
   int &s_bad = *reinterpret_cast<int *>(dI + 64);
   double(*Lt)[16][16] = reinterpret_cast<double(*)[16][16]>(smem + CH_LT_OFF);
-  constexpr int NT = 64 * NW;  // NW = 16 or 8 wavefronts (8: 256 registers per lane)
+  constexpr int NT = 64 * CH_WAVES;
   // wave: uniform per wavefront -> scalar register, role tests and tile numbers on the SALU
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bend = c0 + nb;
@@ -1192,11 +1191,11 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
         // tj in [sb, 3], of step sb - 2
         const int ndd = sb >= 1 ? (3 - sb) * (4 - sb) / 2 : 0;
         const int ndo = sb >= 2 ? ot * (4 - sb) : 0;
-        // (wavefronts 4, 8, 12 share wavefront 0's SIMD: they stay out of its way)
+        // (wavefronts 4, 8, 12 share wavefront 0's SIMD: they stay out of its way; the other
+        // nine of 4..15 take the tiles in turn)
         const int w4 = wave - 4;
-        const int rk = (NW == 16) ? ((w4 & 3) ? w4 - (w4 >> 2) - 1 : -1) : w4;
-        const int nwk = (NW == 16) ? 9 : NW - 4;
-        for (int e0 = rk; rk >= 0 && e0 < ndd + ndo; e0 += nwk) {
+        const int rk = (w4 & 3) ? w4 - (w4 >> 2) - 1 : -1;
+        for (int e0 = rk; rk >= 0 && e0 < ndd + ndo; e0 += 9) {
           if (e0 < ndd) {
             int e = e0, tj = sb + 1;
             while (e >= 4 - tj) {
@@ -1220,7 +1219,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
       // step sb - 1
       const int nud = 3 - sb;
       const int nuo = sb >= 1 ? ot : 0;
-      for (int e0 = wave; e0 < nud + nuo; e0 += NW) {
+      for (int e0 = wave; e0 < nud + nuo; e0 += CH_WAVES) {
         if (e0 < nud) diag_tile(sb, sb + 1 + e0, sb + 1);
         else own_tile(sb - 1, 4 + (e0 - nud), sb);
       }
@@ -1235,7 +1234,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
     // phase is bound by the CU's matrix pipes, every wavefront should carry the same number.
     // With helpers only the tiles of the NEXT sub-panel's columns are this workgroup's: tile
     // column 0 of the region, 10 + 16 (nt - 1) sub-tiles; the rest is helper T's.
-    constexpr int MT = ((HELP ? 42 : 78) + NW - 1) / NW;  // sub-tiles per wavefront, at most
+    constexpr int MT = ((HELP ? 42 : 78) + CH_WAVES - 1) / CH_WAVES;  // sub-tiles per wavefront, at most
     const int nt = ownp / 64;
     const int total = HELP ? (nt ? 10 + 16 * (nt - 1) : 0) : nt * (nt + 1) / 2 * 16 - nt * 6;
     auto decode = [&](int e, int &gi, int &gj, int &mi, int &mj) {
@@ -1260,7 +1259,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
     const bool direct = own > 0 && (own & 63) == 0;
     double4_t ct[MT];
     early0 = false;
-    if (HELP && NW == 16 && direct) {
+    if (HELP && direct) {
       // ---- With helpers and whole tiles the sub-panel boundary is pipelined:
       //  A  wavefronts 1-3 finish the lagging rows (step 3); the others fetch their C sub-tiles
       //     and write the factored tile, D, 1/D and the flags back meanwhile
@@ -1271,7 +1270,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
       //  D  those go into M as the rest of the next stack
       auto eidx = [&](int q) {  // sub-tile of round q: round 0 one per wavefront, then 1..15 only
         if (q == 0) return wave;
-        return wave == 0 ? total : NW + (wave - 1) + (NW - 1) * (q - 1);
+        return wave == 0 ? total : CH_WAVES + (wave - 1) + (CH_WAVES - 1) * (q - 1);
       };
       // (the C loads of wavefronts 1-3 are in flight while they finish the lagging rows)
 #pragma unroll
@@ -1384,7 +1383,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
       CH_STAMP();  // panel factored
 #pragma unroll
       for (int q = 0; q < MT; ++q) {
-        const int e = wave + q * NW;
+        const int e = wave + q * CH_WAVES;
         ct[q] = (double4_t){0.0, 0.0, 0.0, 0.0};
         if (e < total) {
           int gi, gj, mi, mj;
@@ -1425,7 +1424,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
       if (s == 0) CH_STAMP();  // written back
 #pragma unroll
       for (int q = 0; q < MT; ++q) {
-        const int e = wave + q * NW;
+        const int e = wave + q * CH_WAVES;
         if (e < total) {
           int gi, gj, mi, mj;
           decode(e, gi, gj, mi, mj);
@@ -1459,7 +1458,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
         // accumulators straight into M: no round trip through global memory
 #pragma unroll
         for (int q = 0; q < MT; ++q) {
-          const int e = wave + q * NW;
+          const int e = wave + q * CH_WAVES;
           if (e < total) {
             int gi, gj, mi, mj;
             decode(e, gi, gj, mi, mj);
@@ -1488,7 +1487,7 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
   // ---- inverses of the block's unit-lower diagonal tiles (invert_tile), four wavefronts per
   // tile; with helpers this is helper I's work
   if (!HELP) {
-    for (int g0 = 0; g0 < ns; g0 += NW / 4) {
+    for (int g0 = 0; g0 < ns; g0 += CH_WAVES / 4) {
       const int g = g0 + (wave >> 2);
       const int b0 = c0 + 64 * g;
       invert_tile(smem, K, ldk, b0, min(64, bend - b0), g < ns, Linv, LinvT);
@@ -1500,22 +1499,22 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
 
 // workgroup 0: the chain; with HELP (grid of 17) workgroups 8 and 16 are its helpers, the
 // others leave at once
-template <int NW, bool HELP>
-__global__ __launch_bounds__(64 * NW) void k_diag_chain(double *K, int64_t ldk, int c0, int nb,
-                                                     double *__restrict__ dvec,
-                                                     double *__restrict__ dinv,
-                                                     int *__restrict__ flags,
-                                                     double *__restrict__ Linv,
-                                                     double *__restrict__ LinvT,
-                                                     long long *__restrict__ dbg, int *hc,
-                                                     int epoch) {
+template <bool HELP>
+__global__ __launch_bounds__(64 * CH_WAVES) void k_diag_chain(double *K, int64_t ldk, int c0, int nb,
+                                                           double *__restrict__ dvec,
+                                                           double *__restrict__ dinv,
+                                                           int *__restrict__ flags,
+                                                           double *__restrict__ Linv,
+                                                           double *__restrict__ LinvT,
+                                                           long long *__restrict__ dbg, int *hc,
+                                                           int epoch) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   if (blockIdx.x == 0) {
-    chain_body<NW, HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch);
+    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch);
   } else if (HELP && blockIdx.x == 8) {
-    helper_tiles<NW>(smem, K, ldk, c0, nb, dvec, hc, epoch, flags);
+    helper_tiles(smem, K, ldk, c0, nb, dvec, hc, epoch, flags);
   } else if (HELP && blockIdx.x == 16) {
-    helper_inverses<NW>(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
+    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
   }
 }
 
@@ -1613,15 +1612,15 @@ __global__ __launch_bounds__(1024) void k_chain_update(double *K, int64_t ldk, i
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   const int b = (int)blockIdx.x;
   if (b == 0) {
-    chain_body<16, HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, nullptr, hc, epoch);
+    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, nullptr, hc, epoch);
     return;
   }
   if (HELP && b == 8) {
-    helper_tiles<16>(smem, K, ldk, c0, nb, dvec, hc, epoch, flags);
+    helper_tiles(smem, K, ldk, c0, nb, dvec, hc, epoch, flags);
     return;
   }
   if (HELP && b == 16) {
-    helper_inverses<16>(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
+    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
     return;
   }
   update_worker(smem, K, ldk, dvec, N, nrows, jobs, uv, ctr);
@@ -1758,25 +1757,6 @@ __global__ __launch_bounds__(256) void kb_virtual_diag(const BInst *__restrict__
 // batch_decode (T); every instance has its own N on the device, workgroups beyond it return.
 // The chain runs WITHOUT helper workgroups here: with hundreds of instances there is one
 // chain per CU and a spinning helper could wait for a CU its own chain occupies.
-// ---- the register-resident chain (pgf_chain3.h; PGF_CHAIN=3): no helper workgroups
-static_assert(C3_SMEM <= CH_SMEM, "chain3 LDS footprint");
-// (ONE kernel for the chain alone -- an empty job table -- and beside update tiles: with two
-// kernels inlining chain3_body in one translation unit the compiler spills 58 registers in each,
-// with one 5)
-__global__ __launch_bounds__(1024) void k_chain3_update(double *K, int64_t ldk, int c0, int nb,
-                                                        double *__restrict__ dvec, double *__restrict__ dinv,
-                                                        int *__restrict__ flags, double *__restrict__ Linv,
-                                                        double *__restrict__ LinvT, int N, int nrows,
-                                                        const UpdJobs jobs, const UpdVirt uv, int *ctr) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
-  const int b = (int)blockIdx.x;
-  if (b == 0) {
-    chain3_body(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, nullptr);
-    return;
-  }
-  update_worker(smem, K, ldk, dvec, N, nrows, jobs, uv, ctr);
-}
-
 template <bool HELP>
 __global__ __launch_bounds__(1024) void kb_diag_chain(const BInst *__restrict__ tab, int B, int Bp, int m,
                                                       int c0, int epoch) {
@@ -1791,12 +1771,12 @@ __global__ __launch_bounds__(1024) void kb_diag_chain(const BInst *__restrict__ 
   if (c0 >= N) return;
   const int nb = min(256, N - c0);
   if (role == 0)
-    chain_body<16, HELP>(smem, I.K, I.ldk, c0, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
-                         I.hctl, epoch);
+    chain_body<HELP>(smem, I.K, I.ldk, c0, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
+                     I.hctl, epoch);
   else if (HELP && role == 1)
-    helper_tiles<16>(smem, I.K, I.ldk, c0, nb, I.dvec, I.hctl, epoch, I.flags);
+    helper_tiles(smem, I.K, I.ldk, c0, nb, I.dvec, I.hctl, epoch, I.flags);
   else if (HELP && role == 2)
-    helper_inverses<16>(smem, I.K, I.ldk, c0, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
+    helper_inverses(smem, I.K, I.ldk, c0, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
 }
 
 // chains of the outer block at c1 beside the previous block's trailing update (everything below
@@ -1820,12 +1800,12 @@ __global__ __launch_bounds__(1024) void kb_chain_update(const BInst *__restrict_
     if (c1 >= N) return;
     const int nb = min(256, N - c1);
     if (role == 0)
-      chain_body<16, HELP>(smem, I.K, I.ldk, c1, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
-                           I.hctl, epoch);
+      chain_body<HELP>(smem, I.K, I.ldk, c1, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
+                       I.hctl, epoch);
     else if (role == 1)
-      helper_tiles<16>(smem, I.K, I.ldk, c1, nb, I.dvec, I.hctl, epoch, I.flags);
+      helper_tiles(smem, I.K, I.ldk, c1, nb, I.dvec, I.hctl, epoch, I.flags);
     else
-      helper_inverses<16>(smem, I.K, I.ldk, c1, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
+      helper_inverses(smem, I.K, I.ldk, c1, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
     return;
   }
   int inst, t;
@@ -1922,24 +1902,6 @@ void ldlt_batch_launch_trsm(hipStream_t s, const BInst *tab, int B, int per, int
 }
 
 // ------------------------------------------------------------------ host schedule
-bool ldlt_use_lookahead() {
-  static const bool on = !(getenv("PGF_FACTOR") && atoi(getenv("PGF_FACTOR")) == 1);
-  return on;
-}
-
-// PGF_CHAIN=3: the register-resident chain of pgf_chain3.h instead of the LDS-panel chain
-static bool chain3_on() {
-  static const bool on = getenv("PGF_CHAIN") && atoi(getenv("PGF_CHAIN")) == 3;
-  return on;
-}
-
-// wavefronts of the chain workgroup: 16 (128 registers per lane, a few spilled) or 8
-static int chain_waves() {
-  static const int nw = (getenv("PGF_CHAIN_WAVES") && atoi(getenv("PGF_CHAIN_WAVES")) == 8) ? 8 : 16;
-  return nw;
-}
-
-
 // helper workgroups of the diagonal chain (PGF_CHAIN_HELP=0: the chain does everything itself);
 // switched off for the process after a failed placement check or a timed-out hand-over
 static bool g_help_off = false;
@@ -2159,7 +2121,7 @@ static void plan_updates(UpdPlan &pl, int N, int nrows, int OB, int budget, int 
   }
 }
 
-hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
+hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
   f.N = N;
   f.factored = false;
   hipStream_t s = f.stream;
@@ -2180,7 +2142,7 @@ hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
     p->factor_spans.emplace_back(prof_event(p), prof_event(p));
     (void)hipEventRecord(p->factor_spans.back().first, s);
   }
-  constexpr int OB = 256;
+  constexpr int OB = LDLT_OB;
   const int64_t ldw = OB;
   auto span_begin = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v) {
     if (!p) return;
@@ -2200,27 +2162,12 @@ hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
     long long *dbg = (c0 == 0) ? chain_dbg_buffer() : nullptr;
     const int nb = std::min(OB, N - c0);
     const int ep = next_help_epoch();
-    if (chain3_on()) {
-      UpdJobs none;
-      none.njobs = 0;
-      none.tile_begin[0] = 0;
-      hipLaunchKernelGGL(k_chain3_update, dim3(1), dim3(1024), 0, s, f.K, f.ldk, c0, nb, f.dvec, f.dinv,
-                         f.flags, f.Linv, f.LinvT, N, nrows, none, uv, f.flags + 4);
-    } else if (chain_waves() == 16) {
-      if (help)
-        hipLaunchKernelGGL((k_diag_chain<16, true>), dim3(17), dim3(1024), 0, s, f.K, f.ldk, c0, nb,
-                           f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
-      else
-        hipLaunchKernelGGL((k_diag_chain<16, false>), dim3(1), dim3(1024), 0, s, f.K, f.ldk, c0, nb,
-                           f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
-    } else {
-      if (help)
-        hipLaunchKernelGGL((k_diag_chain<8, true>), dim3(17), dim3(512), 0, s, f.K, f.ldk, c0, nb,
-                           f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
-      else
-        hipLaunchKernelGGL((k_diag_chain<8, false>), dim3(1), dim3(512), 0, s, f.K, f.ldk, c0, nb,
-                           f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
-    }
+    if (help)
+      hipLaunchKernelGGL(k_diag_chain<true>, dim3(17), dim3(1024), 0, s, f.K, f.ldk, c0, nb, f.dvec,
+                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
+    else
+      hipLaunchKernelGGL(k_diag_chain<false>, dim3(1), dim3(1024), 0, s, f.K, f.ldk, c0, nb, f.dvec,
+                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
     span_end(pr.chain_spans);
   };
   // T(c0) -- with the update of the next diagonal block in the same launch (k_trsm_ud) unless
@@ -2323,10 +2270,7 @@ hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows) {
       p->fused_bytes.push_back(by);
     }
     const int workers = std::min(ntiles, ncu - 3);  // one workgroup per CU: persistent tile loops
-    if (chain3_on())
-      hipLaunchKernelGGL(k_chain3_update, dim3(1 + workers), dim3(1024), 0, s, f.K, f.ldk, c1, nb1, f.dvec,
-                         f.dinv, f.flags, f.Linv, f.LinvT, N, nrows, js, uv, ctr);
-    else if (help)
+    if (help)
       hipLaunchKernelGGL(k_chain_update<true>, dim3(std::max(17, workers + 3)), dim3(1024), 0, s, f.K, f.ldk,
                          c1, nb1, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, f.hctl, ep, N, nrows, js, uv, ctr);
     else

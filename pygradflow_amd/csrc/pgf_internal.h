@@ -39,12 +39,14 @@ struct PgfProfile {
 // update launches of one factorisation that can have their own persistent-tile counter (behind
 // flags[0..3]; reused modulo this number: a launch is long finished 256 launches later)
 #define LDLT_UPD_COUNTERS 256
+// outer block width: the diagonal blocks of the chain, the K-depth of the bulk trailing update
+#define LDLT_OB 256
 
 struct DenseLdlt {
   int Nmax = 0;
   int64_t ldk = 0;
   double *K = nullptr;      // (Nmax + 1) x ldk
-  double *W = nullptr;      // (Nmax + 1) x panel-width workspace: W = L * D of the panel
+  double *W = nullptr;      // (Nmax + 1) x LDLT_OB workspace: W = L * D of the outer block
   double *dvec = nullptr;   // D
   double *dinv = nullptr;   // 1 / D
   double *zwork = nullptr;  // solve work vector (Nmax)
@@ -59,7 +61,6 @@ struct DenseLdlt {
   int *hctl = nullptr;      // stamps between the diagonal chain and its helper workgroups
   int *h_flags = nullptr;   // pinned host mirror ([3]: status word of the chained solves)
   hipStream_t stream = nullptr;
-  int OB = 256;             // outer block width (K-depth of the bulk trailing update)
   size_t wstride = 0;       // doubles per W buffer (two buffers)
   int N = 0;
   bool factored = false;
@@ -90,8 +91,9 @@ struct DenseLdlt {
 
 hipError_t ldlt_alloc(DenseLdlt &f, int Nmax, hipStream_t stream);
 void ldlt_free(DenseLdlt &f);
-// enqueue the factorisation of the leading N x N lower triangle (+ rows up to nrows)
 void ldlt_chain_discard(DenseLdlt &f, int word);
+// enqueue the factorisation of the leading N x N lower triangle (+ rows up to nrows): the
+// look-ahead schedule of pgf_factor2.hip
 hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows);
 // wait and read flags: returns 0 ok / 1 singular / 2 the diagonal chain's helper workgroups
 // failed their checks (they are switched off, factorise again); sets f.n_neg.  (A chained solve that failed
@@ -104,18 +106,13 @@ hipError_t ldlt_backsolve_async(DenseLdlt &f, const double *w, double *sol);
 // after a host sync: nonzero if a chained solve reported a timeout / placement problem
 int ldlt_chain_check(DenseLdlt &f);
 void ldlt_chain_set_enabled(bool on);  // test hook: undo the switch-off of a failed check
-// look-ahead schedule (pgf_factor2.hip): the default; PGF_FACTOR=1 selects the round-1 one
-bool ldlt_use_lookahead();
 void ldlt_chain_helpers_off();
 void ldlt_inject_helper_failure(hipStream_t s, int *flags);  // test hook: flags[2] |= 1
 bool ldlt_chain_helpers_enabled();     // helpers requested (PGF_CHAIN_HELP) and not switched off
 void ldlt_chain_helpers_set(bool on);  // test hook: undo / force the switch-off
-hipError_t ldlt_factor2_async(DenseLdlt &f, int N, int nrows);
 void ldlt_chain_timing_dump();  // PGF_CHAIN_TIMING diagnostic
-// shared launch helpers (pgf_ldlt.hip)
+// shared launch helper (pgf_ldlt.hip)
 hipEvent_t prof_event(PgfProfile *p);
-void launch_update(DenseLdlt &f, hipStream_t s, const double *Wp, int64_t ldw, int N, int nrows,
-                   int row0, int col0, int colEnd, int kc0, int KB, PgfProfile *p, int any_order);
 
 // ---- dense LU with partial pivoting (pgf_lu.hip): P A = L U, row-major, in place ----------
 struct DenseLu {
@@ -240,13 +237,9 @@ void ldlt_batch_launch_update_diag(hipStream_t s, const BInst *tab, int B, int m
 void ldlt_batch_launch_chain_update(hipStream_t s, const BInst *tab, int B, int Nmax, int m, int wbuf,
                                     int c1, bool helpers, int vdepth = 0);
 void ldlt_batch_launch_virtual_diag(hipStream_t s, const BInst *tab, int B, int vdepth);
-// the batched factorisation runs the fused look-ahead schedule for this batch size (the only one
-// that knows the condensed order)
-bool ldlt_batch_fused_schedule(int B, int OB, bool profiling);
-bool ldlt_batch_condensed_schedule(int OB);
 void ldlt_batch_launch_trsm(hipStream_t s, const BInst *tab, int B, int per, int m, int wbuf, int c0);
-void ldlt_batch_factor_async(hipStream_t s, const BInst *tab, int B, int Nmax, int m, int OB,
-                             PgfProfile *p, int vdepth = 0);
+void ldlt_batch_factor_async(hipStream_t s, const BInst *tab, int B, int Nmax, int m, PgfProfile *p,
+                             int vdepth = 0);
 bool ldlt_chain_enabled();  // chained solves requested (PGF_TRSV_CHAIN) and not switched off
 void ldlt_batch_solve_async(hipStream_t s, const BInst *tab, int B, int Nmax, int m,
                             bool any_unfactored_solve, bool cond_prep = false);

@@ -15,21 +15,17 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANTS = {
     "default": {},
     "no_helpers": {"PGF_CHAIN_HELP": "0"},
-    "chain_8_wavefronts": {"PGF_CHAIN_WAVES": "8"},
     "unfused_launches": {"PGF_FUSED": "0"},
     "separate_update_diag": {"PGF_FUSED_UD": "0"},
     "eager_update_plan": {"PGF_LAZY_BUDGET": "0"},
     "tight_update_budget": {"PGF_LAZY_BUDGET": "40", "PGF_LAZY_CAP": "1"},
-    "legacy_schedule": {"PGF_FACTOR": "1"},
     "solves_per_super_block": {"PGF_TRSV_CHAIN": "0"},
-    "register_resident_chain": {"PGF_CHAIN": "3"},  # csrc/pgf_chain3.h (experimental, not the default)
 }
 
 
 BATCH_VARIANTS = {
     "fused_lookahead": {},                          # default for small batches
     "chain_per_block": {"PGF_BATCH_FUSED_MAX": "0"},  # what larger batches run
-    "split_panel_steps": {"PGF_BATCH_CHAIN": "0"},    # the round-1 schedule
     "solves_per_super_block": {"PGF_TRSV_CHAIN": "0"},  # batched solves without the chained kernels
     "condensed_order": {"PGF_CONDENSED": "2"},        # constraint block first (what n=1024, m=256 runs by default)
     "natural_order": {"PGF_CONDENSED": "0"},

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""GPU check of the dense factorisation schedule selected by PGF_FACTOR / PGF_CHAIN_WAVES:
+"""GPU check of the dense factorisation schedule selected by the environment switches
+(PGF_CHAIN_HELP, PGF_FUSED, PGF_LAZY_*, ...):
 HipLinearSolver against numpy on quasi-definite matrices of awkward sizes, then the time of
 Full Newton steps of BASELINE config 2 (device-resident)."""
 import os
