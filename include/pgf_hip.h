@@ -370,6 +370,9 @@ int pgf_debug_chain_helpers(int on);
  * condensed system (constraint block eliminated first, pgf_api.hip condensed_wanted), 3 the
  * pivoted LU that took over after a failed residual check. */
 int pgf_debug_factor_kind(pgf_handle h);
+/* The pivot order of the factors a device batch's instances hold (tests): 0 none (no step yet),
+ * 1 the natural order, 2 the condensed system; the same for every instance of the batch. */
+int pgf_batch_debug_factor_kind(pgf_batch b);
 /* Counters of the dense qp steps (tests): host_syncs -- host synchronisations made for the
  * index-set sizes and the step's status (a Full step: one while |I| keeps its size, two with
  * PGF_STEP_SPEC=0; an ActiveSet step waits once more for the mask difference before it is

@@ -110,6 +110,7 @@ SIGNATURES = {
     "pgf_comm_destroy": (C.c_int, [C.c_void_p]),
     "pgf_batch_allgather_norms": (C.c_int, [_h, C.c_void_p, C.c_void_p]),
     "pgf_batch_debug_fail_next_helper": (C.c_int, [_h]),
+    "pgf_batch_debug_factor_kind": (C.c_int, [_h]),
 }
 
 _lib = None

@@ -291,6 +291,13 @@ class BatchedDeviceNewton:
             self._lib.check(self._lib.load().pgf_batch_refinement_stats(self._b, C.byref(k)), batch=self._b)
         return k.value
 
+    def factor_kind(self):
+        """Pivot order of the factors the batch's instances hold: 0 none yet, 1 the natural
+        order, 2 the condensed system (``pgf_batch_debug_factor_kind``).  Device batch only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        return int(self._lib.load().pgf_batch_debug_factor_kind(self._b))
+
     def profile(self, on=True):
         if self._b is not None:
             self._lib.check(self._lib.load().pgf_batch_profile_enable(self._b, int(on)),

@@ -1877,6 +1877,7 @@ struct pgf_batch_s {
   // cond_last = how the factors the instances hold were made; cond_free = the next step
   // refactorises every instance anyway and may choose
   bool cond_ok = false, cond_wanted = false, cond_last = false, cond_free = true;
+  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond_last
   int cond_mp = 0;
   int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
   int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
@@ -1903,6 +1904,21 @@ static int bfail(pgf_batch b, int code, const char *msg) {
   } while (0)
 
 const char *pgf_batch_last_error(pgf_batch b) { return b ? b->err.c_str() : k_no_handle; }
+
+// ||H||_inf, ||J||_1, ||J||_inf of every instance into the host copy of ps (residual_norms: one
+// pass over H and J per handle, cached until its derivatives change)
+static int batch_store_norms(pgf_batch b) {
+  for (int i = 0; i < b->B; ++i) {
+    pgf_handle h = b->hs[i];
+    int rc = residual_norms(h);
+    if (rc) return rc;
+    double *p = b->h_ps + (size_t)BPS_STRIDE * i;
+    p[BPS_NORM_H] = h->h_rs[4];
+    p[BPS_NORM_J1] = h->h_rs[6];
+    p[BPS_NORM_JINF] = h->h_rs[5];
+  }
+  return PGF_OK;
+}
 
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
@@ -2036,6 +2052,18 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
   }
+  // the matrix norms of every instance are on the device before any step (the device-resident
+  // controller writes only lambda and its kin into ps)
+  std::memset(b->h_ps, 0, (size_t)count * BPS_STRIDE * sizeof(double));
+  int rc = batch_store_norms(b);
+  if (rc == PGF_OK &&
+      (e = hipMemcpy(b->ps, b->h_ps, (size_t)count * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) !=
+          hipSuccess)
+    rc = PGF_HIP_ERROR + (int)e;
+  if (rc) {
+    pgf_batch_destroy(b);
+    return rc;
+  }
   *out = b;
   return PGF_OK;
 }
@@ -2122,6 +2150,7 @@ int pgf_batch_advance_outer_each(pgf_batch b, const double *dt, const double *rh
     b->cond_wanted = all;
   }
   b->cond_free = true;  // every instance refactorises in the next step (new lambda)
+  if (int rc = batch_store_norms(b)) return bfail(b, rc, "matrix norms of an instance");
   BHIPCHK(b, hipMemcpyAsync(b->ps, b->h_ps, (size_t)b->B * BPS_STRIDE * sizeof(double),
                             hipMemcpyHostToDevice, b->stream));
   BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
@@ -2187,6 +2216,7 @@ static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool ho
   const bool cond = (force || b->cond_free) ? b->cond_wanted : b->cond_last;
   b->cond_last = cond;
   b->cond_free = false;
+  b->stepped = true;
   batch_launch_rhs_assemble(b->stream, b->tab, b->B, b->sc, cond ? b->cond_mp : 0);
   // (condensed: the factor and solve kernels see nI rows -- their `m' is 0)
   const int Nmax = cond ? b->n : b->n + b->m, mf = cond ? 0 : b->m;
@@ -2400,7 +2430,10 @@ static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
     return hip_fail(h, e, "batched repair");
   if (ldlt_chain_check(f)) return fail(h, PGF_HIP_ERROR, k_chain_msg);
   *diff_out = h->h_scal[0];
-  invalidate_factor(h);  // host-side view only: the batch's own flag (ctl[1]) already says "refactorise"
+  // (host-side view only.  In the batch, kb_step_final left ctl[1] = 0 and pgf_batch_sync keeps
+  // all_factored false: the instance's next step assembles K again and launches the factorisation,
+  // a Simplified step included)
+  invalidate_factor(h);
   return PGF_OK;
 }
 
@@ -2410,7 +2443,7 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
   b->step_pending = false;
   (void)hipSetDevice(b->device);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
-  bool all_ok = true;
+  bool all_ok = true, any_repaired = false;
   for (int i = 0; i < b->B; ++i) {
     // bit 2 alone: the factorisation went through but the sampled residual of the solve is too
     // large (element growth): repaired on the instance's handle where the reference's pivoted LU
@@ -2423,6 +2456,7 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
         b->h_diff[i] = d;
         b->eval_fresh = false;  // the instance moved after the evaluation made ahead
         ++b->repaired;
+        any_repaired = true;
       }
     }
     const bool bad = b->h_flags[3 * i] != 0;
@@ -2443,7 +2477,9 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
     if (n_neg) n_neg[i] = b->h_flags[3 * i + 1] + (b->cond_last ? b->m : 0);  // (+ the m pivots -delta)
     if (diff) diff[i] = b->h_diff[i];
   }
-  b->all_factored = all_ok;
+  // a repaired instance holds no factor the batch can reuse (its ctl[1] is 0): a following
+  // Simplified step must not skip the factor launch, or it would solve with the bare matrix
+  b->all_factored = all_ok && !any_repaired;
   return PGF_OK;
 }
 
@@ -2540,6 +2576,11 @@ int pgf_batch_refinement_stats(pgf_batch b, int *repaired) {
   if (!b) return PGF_INVALID;
   if (repaired) *repaired = b->repaired;
   return PGF_OK;
+}
+
+int pgf_batch_debug_factor_kind(pgf_batch b) {
+  if (!b || !b->stepped) return 0;
+  return b->cond_last ? 2 : 1;
 }
 
 int pgf_batch_profile_enable(pgf_batch b, int on) {

@@ -177,6 +177,11 @@ struct BatchScalars {
 #define BPS_RHO 2
 #define BPS_FACT 3
 #define BPS_DELTA 4
+// ||H||_inf, ||J||_1, ||J||_inf of the instance (residual_norms): the normwise measure of
+// kb_sample_residual bounds ||K||_inf with them and the current lambda, delta
+#define BPS_NORM_H 5
+#define BPS_NORM_J1 6
+#define BPS_NORM_JINF 7
 #define BPS_STRIDE 8
 
 // device-resident step controller: per-instance state (cs) and constants (cp)

@@ -1345,28 +1345,47 @@ __global__ __launch_bounds__(256) void kb_step_update(const BInst *__restrict__ 
 // step); element growth in an unpivoted LDL^T spoils the whole solution vector, so a SAMPLE of
 // the rows of r = rhs - K s tells just as well: KB_NSAMPLE rows spread over the reduced system,
 // K applied from H, J, the index list and the instance's lambda / delta, one wavefront per row.
-// max |r_sampled| > KB_RES_TOL max |rhs| sets flags[3]: the step is reported as failed
-// (kb_step_final), which every controller answers with a rejected step and a doubled lambda --
-// the reference's own recovery path (step_control.py:80-107) and what makes the matrix
-// quasi-definite again.
+// The measure is the normwise backward error of the single-instance guard (residual_rel,
+// pgf_api.hip): max |r_sampled| > KB_RES_TOL (max |rhs| + ||K||_inf max |s|) sets flags[3], with
+// ||K||_inf <= max(||H||_inf + lambda + ||J||_1, ||J||_inf + delta) and KB_RES_TOL its default
+// refine_tol.  A tolerance of 1e-8 against max |rhs| passed solves spoilt by a pivot of 1e-9
+// (forward error 1.2e-9); at one tight enough for those, max |rhs| alone would flag backward-
+// stable solves of ill-conditioned systems (|r| ~ eps cond(K) |rhs|).  A flagged step is
+// repaired on the instance's handle by pgf_batch_sync; under the device-resident controller it
+// is reported as failed (kb_step_final), which the controller answers with a rejected step and
+// a doubled lambda -- the reference's own recovery path (step_control.py:80-107) and what makes
+// the matrix quasi-definite again.
 #define KB_NSAMPLE 32
-#define KB_RES_TOL 1e-8
+#define KB_RES_TOL 1e-11
 __global__ __launch_bounds__(256) void kb_sample_residual(const BInst *__restrict__ tab, int m) {
   // grid (KB_NSAMPLE / 4, 1, B): one sampled row per wavefront (a row is a chain of dependent
   // gathers: 32 rows one after the other in one workgroup cost 0.1 ms per batched step)
   const BInst &I = tab[blockIdx.z];
   if (I.ctl[3]) return;
-  __shared__ double bmax[4];
+  __shared__ double bmax[4], smax[4];
   const int nI = I.counts[0], N = nI + m;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double lamb = I.ps[BPS_LAMB], delta = I.ps[BPS_DELTA];
-  double rb = 0.0;
-  for (int j = tid; j < N; j += 256) rb = fmax(rb, fabs(I.rhs[j]));
+  double rb = 0.0, sb = 0.0;
+  for (int j = tid; j < N; j += 256) {
+    rb = fmax(rb, fabs(I.rhs[j]));
+    sb = fmax(sb, fabs(I.sol[j]));
+  }
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) rb = fmax(rb, __shfl_down(rb, off));
-  if (lane == 0) bmax[wave] = rb;
+  for (int off = 32; off > 0; off >>= 1) {
+    rb = fmax(rb, __shfl_down(rb, off));
+    sb = fmax(sb, __shfl_down(sb, off));
+  }
+  if (lane == 0) {
+    bmax[wave] = rb;
+    smax[wave] = sb;
+  }
   __syncthreads();
   const double b = fmax(fmax(bmax[0], bmax[1]), fmax(bmax[2], bmax[3]));
+  const double sn = fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]));
+  const double nK = fmax(I.ps[BPS_NORM_H] + lamb + I.ps[BPS_NORM_J1], I.ps[BPS_NORM_JINF] + delta);
+  double den = b;
+  if (sn <= 1.79e308) den += nK * sn;  // (a non-finite solution is measured against max |rhs|)
   const int ns = min(KB_NSAMPLE, N);
   const int k = blockIdx.x * 4 + wave;
   if (k >= ns) return;
@@ -1389,7 +1408,7 @@ __global__ __launch_bounds__(256) void kb_sample_residual(const BInst *__restric
     const double r = fabs(I.rhs[i] - acc);
     // (flags[3] was cleared by kb_solve_prep_bwd of this step; set only on failure: no
     // contention in the normal case)
-    if (!(r <= KB_RES_TOL * (b > 0.0 ? b : 1.0))) atomicOr(&I.flags[3], 1);
+    if (!(r <= KB_RES_TOL * (den > 0.0 ? den : 1.0))) atomicOr(&I.flags[3], 1);
   }
 }
 
