@@ -379,6 +379,12 @@ int pgf_batch_debug_factor_kind(pgf_batch b);
  * enqueued); redone_steps -- steps enqueued with the previous |I|, |A| that were discarded and
  * enqueued again by pgf_qp_sync because the sizes had changed.  Either pointer may be NULL. */
 int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
+/* Counters of the resident Gram matrix G = J^T J of the condensed dense factorisation (tests;
+ * DESIGN.md 4.0, PGF_CONDENSED_GRAM): builds -- how often G was formed for this handle (at most
+ * once per derivative upload); factorisations_with_gram -- condensed factorisations that took
+ * their rank-m term from G instead of the virtual column blocks (a factorisation that was
+ * discarded and enqueued again counts once).  Either pointer may be NULL. */
+int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,7 @@ SIGNATURES = {
     "pgf_debug_chain_helpers": (C.c_int, [C.c_int]),
     "pgf_debug_factor_kind": (C.c_int, [_h]),
     "pgf_debug_step_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_debug_gram_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pgf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

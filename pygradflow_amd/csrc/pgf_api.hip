@@ -99,6 +99,18 @@ struct pgf_solver {
   bool condensed = false;
   bool condensed_veto = false;  // it met a zero pivot: natural order until the matrix changes
   double *cd_t = nullptr;
+  // The condensed system's rank-m term from a resident Gram matrix (gram_prepare below): G = J^T J,
+  // n x n with row stride ldg, lower triangle; gram_aux: the identity index list of the build
+  // (n ints) and, behind it, the build's tile counter.  Valid until the next pgf_set_derivs_*
+  // (as norms_valid); gram_off: the allocation failed once, the handle keeps the virtual blocks.
+  double *G = nullptr;
+  int64_t ldg = 0;
+  int *gram_aux = nullptr;
+  bool gram_valid = false, gram_off = false;
+  int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
+  // what the factorisation in flight added to the counters (taken back when it is discarded)
+  bool fac_counted = false, fac_used_gram = false;
+  int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
 };
 
 struct pgf_linsolver {
@@ -247,7 +259,8 @@ int pgf_destroy(pgf_handle h) {
                   h->x,    h->y,    h->xn,  h->yn,   h->g,    h->c,        h->F,    h->b0full,
                   h->rhs,  h->sol,  h->dx,  h->dy,   h->q,    h->b,        h->w,    h->tmpn,
                   h->partial, h->red, h->stat, h->mask, h->mask_new, h->idxI, h->idxA, h->pos,
-                  h->meas, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->rs_r, h->rs_d, h->cd_t};
+                  h->meas, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->rs_r, h->rs_d, h->cd_t,
+                  h->G,    h->gram_aux};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (h->h_stat) (void)hipHostFree(h->h_stat);
@@ -290,6 +303,13 @@ static int down(pgf_handle h, void *dst, const void *src, size_t bytes) {
   if (!bytes) return PGF_OK;
   HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
   return PGF_OK;
+}
+
+// new derivatives: what was computed from the matrices in HBM goes (their norms, the Gram matrix)
+static void invalidate_derivs(pgf_handle h) {
+  h->norms_valid = false;
+  h->gram_valid = false;
+  h->cond_since_upload = 0;
 }
 
 static void invalidate_factor(pgf_handle h) {
@@ -367,7 +387,7 @@ int pgf_set_derivs_dense(pgf_handle h, const double *H, int64_t ldh, const doubl
   if ((rc = set_matrix(h, H, ldh, h->n, h->n, loc, &h->Hown, &h->H, &h->ldh, &h->ownH))) return rc;
   if ((rc = set_matrix(h, J, ldj, h->m, h->n, loc, &h->Jown, &h->J, &h->ldj, &h->ownJ))) return rc;
   h->derivs_set = true;
-  h->norms_valid = false;
+  invalidate_derivs(h);
   invalidate_factor(h);
   return PGF_OK;
 }
@@ -435,7 +455,7 @@ int pgf_set_derivs_csr(pgf_handle h, const int *Hptr, const int *Hidx, const dou
                                 &h->ownJ)))
     return rc;
   h->derivs_set = true;
-  h->norms_valid = false;
+  invalidate_derivs(h);
   invalidate_factor(h);
   return PGF_OK;
 }
@@ -639,6 +659,71 @@ static hipError_t condensed_reserve(pgf_handle h) {
   return e;
 }
 
+// The resident Gram matrix.  (J^T J)[I,I] = J_I^T J_I for every index set I: the rank-m term of S
+// depends on J alone -- not on the mask, lamb, delta, rho or the point -- and J only changes with
+// pgf_set_derivs_*.  With G = J^T J in HBM the assembly gathers S = H[I,I] + lamb I + G[I,I] / delta
+// in its one pass (k_assemble_kkt_gram) and the factorisation runs without virtual blocks
+// (vdepth = 0, no k_virtual_diag): n^2 m flops once per upload instead of nI^2 m in every
+// factorisation.  The build reuses the trailing update's tiles (ldlt_gram_async) on the panel
+// J^T of ALL n columns, which k_cond_panel writes for the identity index list.
+// PGF_CONDENSED_GRAM: 0 never (the virtual blocks, as before), 1 (default) G is built at the SECOND
+// condensed factorisation since the last upload -- a caller with fresh derivatives every step
+// never pays for it --, 2 at the first (tests).
+static int gram_mode() {
+  static const int v = []() {
+    const char *e = getenv("PGF_CONDENSED_GRAM");
+    return e ? atoi(e) : 1;
+  }();
+  return v;
+}
+// true: h->G holds J^T J for the matrices in HBM (built now if the rule says so); false: this
+// factorisation takes the virtual-block path.  Never an error: a failed allocation switches the
+// Gram path off for the handle.  (condensed_reserve has been called: f.V, f.vd hold n + 1 rows.)
+static bool gram_prepare(pgf_handle h) {
+  const int mode = gram_mode();
+  if (!mode || h->gram_off) return false;
+  if (h->gram_valid) return true;
+  if (mode == 1 && h->cond_since_upload < 1) return false;
+  DenseLdlt &f = h->fac;
+  const int n = h->n, mp = (h->m + 31) / 32 * 32;
+  if (!h->G) {
+    int64_t ld = ((int64_t)n + 15) / 16 * 16;  // (as pick_ldk: row starts off one HBM channel)
+    if (ld % 512 == 0) ld += 16;
+    std::vector<int> ident((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) ident[i] = i;
+    if (hipMalloc((void **)&h->G, (size_t)n * ld * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&h->gram_aux, ((size_t)n + 1) * sizeof(int)) != hipSuccess ||
+        hipMemcpy(h->gram_aux, ident.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      if (h->G) (void)hipFree(h->G);
+      if (h->gram_aux) (void)hipFree(h->gram_aux);
+      h->G = nullptr;
+      h->gram_aux = nullptr;
+      h->gram_off = true;
+      return false;
+    }
+    h->ldg = ld;
+  }
+  // V <- J^T (all columns), vd <- -1 (delta = 1); both are rewritten for this step right after
+  launch_cond_panel(h->stream, f.V, condensed_ldv(h->m), mp, f.vd, h->J, h->ldj, h->gram_aux, n, h->m, 1.0,
+                    nullptr);
+  if (ldlt_gram_async(h->stream, h->G, h->ldg, n, f.V, condensed_ldv(h->m), f.vd, mp, h->gram_aux + n) !=
+      hipSuccess) {
+    (void)hipGetLastError();
+    h->gram_off = true;
+    return false;
+  }
+  h->gram_valid = true;
+  ++h->stat_gram_builds;
+  return true;
+}
+// the factorisation that was counted last is discarded and will be enqueued again
+static void gram_uncount(pgf_handle h) {
+  if (h->fac_counted) --h->cond_since_upload;
+  if (h->fac_used_gram) --h->stat_gram_factors;
+  h->fac_counted = h->fac_used_gram = false;
+}
+
 // sol <- K^{-1} rhs with the current LDL^T factor (rhs, sol: N-vectors in the order
 // [inactive variables; constraints]; rhs != sol)
 static hipError_t kkt_solve_async(pgf_handle h, const double *rhs, double *sol) {
@@ -702,16 +787,37 @@ static int factor_async(pgf_handle h, bool with_rhs) {
   h->lu_active = false;
   h->condensed = condensed_wanted(h);
   h->fac.vdepth = 0;
+  h->fac.vneg = 0;
+  h->fac_counted = h->fac_used_gram = false;
   if (h->condensed) {
     DenseLdlt &f = h->fac;
     HIPCHK(h, condensed_reserve(h));
     const int nI = h->nI, mp = (h->m + 31) / 32 * 32;
     f.ldv = condensed_ldv(h->m);
-    f.vdepth = mp;
     f.vneg = h->m;  // the eliminated block is -delta I
+    const bool gram = gram_prepare(h);
+    ++h->cond_since_upload;
+    h->fac_counted = true;
+    f.flags_zeroed = nI > 0;
+    if (gram) {
+      // S = H[I,I] + lamb I + G[I,I] / delta in the assembly's one pass; V = J_I^T still serves the
+      // solves (launch_cond_rhs, launch_cond_y); row nI of K <- b_x + J_I^T b_y / delta, which the
+      // virtual blocks would have produced on the way (in place of k_virtual_diag: as many launches)
+      ++h->stat_gram_factors;
+      h->fac_used_gram = true;
+      launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
+                          f.flags, 4 + LDLT_UPD_COUNTERS, nullptr, nullptr, 0, h->G, h->ldg);
+      launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta,
+                        with_rhs ? h->rhs + nI : nullptr);
+      if (with_rhs)
+        launch_cond_rhs(h->stream, nI, h->m, f.V, f.ldv, h->rhs, h->delta, f.K + (int64_t)nI * f.ldk);
+      HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0)));
+      f.N = nI;
+      return PGF_OK;
+    }
+    f.vdepth = mp;
     // A = H[I,I] + lamb I (the assembly kernel with no constraint rows), V = J_I^T, b_y in row nI
     // (the assembly launch also clears the factorisation's flags and copies b_x into row nI)
-    f.flags_zeroed = nI > 0;
     launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
                         f.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
                         f.K + (int64_t)nI * f.ldk, nI);
@@ -740,8 +846,10 @@ static int finish_factor_state(pgf_handle h, hipError_t *e) {
   if (st == 1 && h->condensed && !h->condensed_veto) {
     h->condensed_veto = true;
     h->fac.factored = false;
+    gram_uncount(h);
     return 2;
   }
+  if (st == 2) gram_uncount(h);
   return st;
 }
 static const char *k_helper_msg =
@@ -1038,6 +1146,7 @@ int pgf_factor(pgf_handle h, int *n_neg) {
 static int newton_core_async(pgf_handle h, bool *did_factor) {
   hipStream_t s = h->stream;
   h->fused_eval_done = false;
+  h->fac_counted = h->fac_used_gram = false;  // (set by factor_async, if this step factorises)
   // dense, |A| = 0: the residual and the reduced right-hand side in one launch
   const bool rhs_fused = !h->sparse && h->nA == 0;
   if (rhs_fused)
@@ -1689,6 +1798,7 @@ static int settle_spec(pgf_handle h, bool *redone) {
   h->stat_bits = 0;  // (the discarded step's status words are not read)
   // a test hook's injected helper failure belongs to the step that is kept
   if (h->step_took_inject) h->fac.inject_helper_failure = 1;
+  gram_uncount(h);
   h->fac.factored = false;
   h->lu_active = false;
   std::swap(h->x, h->xn);
@@ -1808,6 +1918,13 @@ int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps) {
   if (!h) return PGF_INVALID;
   if (host_syncs) *host_syncs = h->stat_host_syncs;
   if (redone_steps) *redone_steps = h->stat_redone;
+  return PGF_OK;
+}
+
+int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram) {
+  if (!h) return PGF_INVALID;
+  if (builds) *builds = h->stat_gram_builds;
+  if (factorisations_with_gram) *factorisations_with_gram = h->stat_gram_factors;
   return PGF_OK;
 }
 
@@ -2414,7 +2531,7 @@ static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
   f.N = h->condensed ? nI : h->N;
   f.vdepth = h->condensed ? b->cond_mp : 0;
   f.ldv = condensed_ldv(h->m);
-  f.vneg = h->m;
+  f.vneg = h->condensed ? h->m : 0;
   f.factored = true;
   f.n_neg = b->h_flags[3 * i + 1] + (h->condensed ? h->m : 0);
   enqueue_residual(h);

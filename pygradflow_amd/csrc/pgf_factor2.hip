@@ -42,6 +42,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <unordered_map>
 #include <vector>
 
@@ -2348,5 +2349,42 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
     e = hipMemcpyAsync(f.h_flags, f.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return e;
   }
+  return hipGetLastError();
+}
+
+// G <- V V^T, lower triangle (declared in pgf_internal.h): the update role alone (k_update_jobs)
+// with one job over every 128-wide tile column, its K-range the panel V only (KB = 0: no column of
+// G itself is read as an operand).  With vd = -1 the tile's C -= V diag(vd) V^T adds V V^T to the
+// zeroed G.  n^2 depth flops once per derivative upload (pgf_api.hip, gram_prepare).
+hipError_t ldlt_gram_async(hipStream_t s, double *G, int64_t ldg, int n, const double *V, int64_t ldv,
+                           const double *vd, int depth, int *ctr) {
+  if (n <= 0 || depth <= 0 || depth % 32) return hipErrorInvalidValue;
+  hipError_t e;
+  if ((e = hipMemsetAsync(G, 0, (size_t)n * ldg * sizeof(double), s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(ctr, 0, sizeof(int), s)) != hipSuccess) return e;
+  static const int ncu = []() {
+    int dev = 0, c = 256;
+    hipDeviceProp_t pr;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+      c = pr.multiProcessorCount;
+    return c;
+  }();
+  UpdJobs js;
+  memset(&js, 0, sizeof js);
+  js.njobs = 1;
+  js.col0[0] = 0;
+  js.rowstart[0] = 0;
+  js.kc0[0] = 0;
+  js.KB[0] = 0;
+  js.kc0v[0] = 0;
+  js.KBv[0] = depth;
+  js.ntc[0] = (n + 127) / 128;
+  int ntiles = 0;  // as update_job_tile walks them: tile column c holds rows [128 c, n) in UPD_TM-row tiles
+  for (int c = 0; c < js.ntc[0]; ++c) ntiles += (n - 128 * c + UPD_TM - 1) / UPD_TM;
+  js.tile_begin[0] = 0;
+  js.tile_begin[1] = ntiles;
+  const UpdVirt uv{V, ldv, vd};
+  // (dvec belongs to the K-range's second segment, which is empty here: G stands in, never read)
+  hipLaunchKernelGGL(k_update_jobs, dim3(std::min(ntiles, ncu)), dim3(1024), 0, s, G, ldg, G, n, n, js, uv, ctr);
   return hipGetLastError();
 }

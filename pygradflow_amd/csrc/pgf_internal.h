@@ -69,7 +69,10 @@ struct DenseLdlt {
   // A pre-eliminated diagonal block (the condensed KKT system, pgf_api.hip): when vdepth > 0 the
   // matrix to factorise is K - V diag(vd) V^T, V = (N + 1) x vdepth row-major (row N rides along
   // like row N of K); the look-ahead schedule applies it as `virtual' column blocks that are
-  // already factorised, lazily, like any other pending block.  vneg = its negative pivots.
+  // already factorised, lazily, like any other pending block.  vneg = the negative pivots of the
+  // block eliminated beforehand; ldlt_finish adds them whatever vdepth is: a caller that has put
+  // the block's Schur term into K itself (the resident Gram matrix, pgf_api.hip) factorises with
+  // vdepth = 0 and still owes them to the inertia.  Whoever sets vdepth sets vneg with it.
   double *V = nullptr;
   int64_t ldv = 0;
   double *vd = nullptr;
@@ -95,6 +98,13 @@ void ldlt_chain_discard(DenseLdlt &f, int word);
 // enqueue the factorisation of the leading N x N lower triangle (+ rows up to nrows): the
 // look-ahead schedule of pgf_factor2.hip
 hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows);
+// G <- V V^T (lower triangle of n x n, row stride ldg) with the trailing update's own tiles: G is
+// zeroed, then C -= V diag(vd) V^T runs over the whole triangle as ONE virtual-only job (vd = -1
+// in all `depth' entries, depth a multiple of 32; V has row stride ldv).  ctr: a counter word of the
+// caller's for the persistent tile loop -- never one of a factorisation's (f.flags), which may be
+// in flight on the same stream's neighbours and is zeroed on another schedule.
+hipError_t ldlt_gram_async(hipStream_t s, double *G, int64_t ldg, int n, const double *V, int64_t ldv,
+                           const double *vd, int depth, int *ctr);
 // wait and read flags: returns 0 ok / 1 singular / 2 the diagonal chain's helper workgroups
 // failed their checks (they are switched off, factorise again); sets f.n_neg.  (A chained solve that failed
 // its own checks is reported by ldlt_chain_check after any host synchronisation.)

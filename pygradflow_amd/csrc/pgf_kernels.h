@@ -32,7 +32,8 @@ void launch_reduced_rhs(hipStream_t s, int n, int m, int nI, int nA, double fact
 void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H, int64_t ldh,
                          const double *J, int64_t ldj, const int *idxI, int nI, int m,
                          double lamb, double delta, int *zero = nullptr, int nzero = 0,
-                         const double *row_src = nullptr, double *row_dst = nullptr, int row_n = 0);
+                         const double *row_src = nullptr, double *row_dst = nullptr, int row_n = 0,
+                         const double *G = nullptr, int64_t ldg = 0);
 void launch_copy(hipStream_t s, double *dst, const double *src, int n);
 void launch_copy_u8(hipStream_t s, uint8_t *dst, const uint8_t *src, int n);
 void launch_mask_diff(hipStream_t s, int n, const uint8_t *a, const uint8_t *b, int *out);

@@ -236,13 +236,18 @@ __device__ __forceinline__ void b_reduced_rhs(int n, int m, int nI, int nA, doub
 // columns: coalesced stores, loads coalesced whenever I is contiguous); the column's index
 // in H / J is looked up once per lane.  One row per workgroup was dispatch-bound in the
 // batched step (1.6 M workgroups).
+// GRAM (the condensed system with the resident Gram matrix G = J^T J, pgf_api.hip): the H block
+// becomes H[I,I] + G[I,I] * ginv (ginv = 1 / delta), gathered in the same pass with the same
+// indices; the instantiations without it do not see the operand at all.
 #define ASM_ROWS 8
-template <int ROWS = ASM_ROWS>
+template <int ROWS = ASM_ROWS, bool GRAM = false>
 __device__ __forceinline__ void b_assemble_kkt(double *__restrict__ K, int64_t ldk,
                                                const double *__restrict__ H, int64_t ldh,
                                                const double *__restrict__ J, int64_t ldj,
                                                const int *__restrict__ idxI, int nI, int m,
-                                               double lamb, double delta) {
+                                               double lamb, double delta,
+                                               const double *__restrict__ G = nullptr, int64_t ldg = 0,
+                                               double ginv = 0.0) {
   const int N = nI + m;
   const int i0 = blockIdx.y * ROWS;
   const int j = blockIdx.x * 256 + threadIdx.x;
@@ -256,28 +261,32 @@ __device__ __forceinline__ void b_assemble_kkt(double *__restrict__ K, int64_t l
   static_assert(ROWS <= 64, "one lane per row of the workgroup");
   const int lane = threadIdx.x & 63;
   const int rowidx = (lane < ROWS && i0 + lane < nI) ? idxI[i0 + lane] : 0;
-  constexpr int G = ROWS < 8 ? ROWS : 8;
+  constexpr int GR = ROWS < 8 ? ROWS : 8;
 #pragma unroll
-  for (int r0 = 0; r0 < ROWS; r0 += G) {
-    double v[G];
+  for (int r0 = 0; r0 < ROWS; r0 += GR) {
+    double v[GR], vg[GR];
 #pragma unroll
-    for (int u = 0; u < G; ++u) {
+    for (int u = 0; u < GR; ++u) {
       const int i = i0 + r0 + u;
       const int gi = __builtin_amdgcn_readlane(rowidx, r0 + u);
       v[u] = 0.0;
+      if (GRAM) vg[u] = 0.0;
       if (i < N && j <= i && j < N) {
         if (i < nI) {
           v[u] = H[(int64_t)gi * ldh + gj];
+          // (only G's lower triangle is ever written: ldlt_gram_async)
+          if (GRAM) vg[u] = G[(int64_t)max(gi, gj) * ldg + min(gi, gj)];
         } else if (j < nI) {
           v[u] = J[(int64_t)(i - nI) * ldj + gj];
         }
       }
     }
 #pragma unroll
-    for (int u = 0; u < G; ++u) {
+    for (int u = 0; u < GR; ++u) {
       const int i = i0 + r0 + u;
       if (i < N && j <= i && j < N) {
         double w = v[u];
+        if (GRAM && i < nI) w += vg[u] * ginv;
         if (i == j) w = (i < nI) ? w + lamb : -delta;
         K[(int64_t)i * ldk + j] = w;
       }
@@ -609,6 +618,21 @@ __global__ __launch_bounds__(256) void k_assemble_kkt(double *__restrict__ K, in
   }
   b_assemble_kkt(K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta);
 }
+// the same with the Gram operand (a kernel of its own: k_assemble_kkt keeps its code and its
+// argument list)
+__global__ __launch_bounds__(256) void k_assemble_kkt_gram(double *__restrict__ K, int64_t ldk,
+    const double *__restrict__ H, int64_t ldh, const double *__restrict__ J, int64_t ldj,
+    const int *__restrict__ idxI, int nI, int m, double lamb, double delta, int *__restrict__ zero,
+    int nzero, const double *__restrict__ row_src, double *__restrict__ row_dst, int row_n,
+    const double *__restrict__ G, int64_t ldg, double ginv) {
+  if (blockIdx.y == 0) {
+    if (zero && blockIdx.x == 0)
+      for (int t = threadIdx.x; t < nzero; t += 256) zero[t] = 0;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (row_src && j < row_n) row_dst[j] = row_src[j];
+  }
+  b_assemble_kkt<ASM_ROWS, true>(K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, G, ldg, ginv);
+}
 
 __global__ void k_copy(double *__restrict__ dst, const double *__restrict__ src, int n) {
   b_copy(dst, src, n);
@@ -789,12 +813,16 @@ void launch_reduced_rhs(hipStream_t s, int n, int m, int nI, int nA, double fact
 void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H, int64_t ldh,
                          const double *J, int64_t ldj, const int *idxI, int nI, int m,
                          double lamb, double delta, int *zero, int nzero, const double *row_src,
-                         double *row_dst, int row_n) {
+                         double *row_dst, int row_n, const double *G, int64_t ldg) {
   const int N = nI + m;
-  if (N)
-    hipLaunchKernelGGL(k_assemble_kkt, dim3((N + 255) / 256, (N + ASM_ROWS - 1) / ASM_ROWS),
-                       dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, zero, nzero,
-                       row_src, row_dst, std::min(row_n, N));
+  if (!N) return;
+  const dim3 grid((N + 255) / 256, (N + ASM_ROWS - 1) / ASM_ROWS);
+  if (G)
+    hipLaunchKernelGGL(k_assemble_kkt_gram, grid, dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb,
+                       delta, zero, nzero, row_src, row_dst, std::min(row_n, N), G, ldg, 1.0 / delta);
+  else
+    hipLaunchKernelGGL(k_assemble_kkt, grid, dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta,
+                       zero, nzero, row_src, row_dst, std::min(row_n, N));
 }
 
 void launch_copy(hipStream_t s, double *dst, const double *src, int n) {

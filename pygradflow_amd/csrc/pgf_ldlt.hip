@@ -692,7 +692,7 @@ int ldlt_finish(DenseLdlt &f, hipError_t *err) {
     f.factored = false;
     return 2;
   }
-  f.n_neg = f.h_flags[1] + (f.vdepth > 0 ? f.vneg : 0);
+  f.n_neg = f.h_flags[1] + f.vneg;
   f.factored = (f.h_flags[0] == 0);
   return f.h_flags[0] ? 1 : 0;
 }
