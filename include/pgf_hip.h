@@ -213,6 +213,11 @@ int pgf_profile_read(pgf_handle h, double *update_ms, int64_t *update_launches,
 #define PGF_PROF_FUSED_BYTES 12
 #define PGF_PROF_TRSMUD_MS 13
 #define PGF_PROF_COUNT2 14
+/* the assembly launches of the unsymmetric formulations (pgf_set_formulation) while profiling is
+ * enabled (any mode): device ms and launches; read with count >= PGF_PROF_COUNT3 */
+#define PGF_PROF_UNSYM_ASM_MS 14
+#define PGF_PROF_UNSYM_ASM_LAUNCHES 15
+#define PGF_PROF_COUNT3 16
 int pgf_profile_read_ex(pgf_handle h, double *out, int count);
 
 /* ---- batched mode: many device-resident instances advanced by ONE launch sequence ---- */
@@ -328,6 +333,49 @@ int pgf_bench_update(int N, int KB, int variant, int reps, int device, double *m
  * These are the `mat @ x` / `mat.T @ x` products of the reference's ConditionEstimator
  * (step/cond_estimate.py:60-82); dense mode only. */
 int pgf_kkt_apply(pgf_handle h, const double *v, double *out);
+
+/* ---- the reference's unsymmetric step-solver formulations --------------------------------
+ * StandardStepSolver (step/solver/standard_step_solver.py:15-92), ExtendedStepSolver
+ * (extended_step_solver.py:13-112) and AsymmetricStepSolver (asymmetric_step_solver.py:15-173)
+ * take the same Newton step through an unsymmetric (n + m) x (n + m) matrix and a pivoted LU.
+ * pgf_set_formulation selects one on a DENSE handle (PGF_INVALID on a PGF_CREATE_SPARSE handle
+ * and for unknown values) and invalidates the factor; a handle that never calls it is Symmetric
+ * and behaves as described everywhere else in this header.  With another formulation the matrix
+ * is assembled in HBM from the resident H, J, mask and index lists and factorised in place by
+ * the LU of pgf_lu.hip; no (n + m)^2 matrix crosses PCIe.  The entry points keep their meaning
+ * over the (n + m) system:
+ *   pgf_factor          assemble + LU; *n_neg = -1 (LUSolver.num_neg_eigvals() is None)
+ *   pgf_newton_solve    residual, right-hand side in the formulation's row order, solve,
+ *                       dy = fact (s_y - rho b2) (Standard: s_y), clipping, diff;
+ *                       inertia_check != 0 -> PGF_INVALID
+ *   pgf_residual, pgf_active_set   Standard: the UNSCALED residual / mask (ImplicitFunc,
+ *                       implicit_func.py:102-199); Extended / Asymmetric: the scaled ones
+ *   pgf_linear_solve    rhs / sol have n + m entries, trans != 0 solves with the transpose
+ *   pgf_reduced_dims    |I|, n + m
+ *   pgf_qp_update_active_set, pgf_qp_step / _async / pgf_qp_sync   all policy bits; n_neg = -1;
+ *                       pgf_qp_step with inertia_check != 0 -> PGF_INVALID.  A step that
+ *                       factorises waits once inside pgf_qp_step_async (the LU reads its pivots).
+ * Standard needs H + rho J^T J (aug_lag_deriv_xx(rho), standard_step_solver.py:52): a caller of
+ * pgf_set_derivs_* uploads that matrix as H; after pgf_qp_set_problem (H = Q) the rho J^T J term
+ * comes from the resident Gram matrix (pgf_debug_gram_stats), built once per derivative upload.
+ * The LDL^T accuracy guard does not apply (the LU pivots).  Batched (pgf_batch_create refuses a
+ * handle whose formulation is not Symmetric) and banded unsymmetric formulations are out of scope. */
+#define PGF_FORM_SYMMETRIC 0 /* default */
+#define PGF_FORM_STANDARD 1
+#define PGF_FORM_EXTENDED 2
+#define PGF_FORM_ASYMMETRIC 3
+int pgf_set_formulation(pgf_handle h, int form);
+/* the assembled (pre-factor) Newton matrix of the current formulation, row-major (n + m) x
+ * (n + m) (debug / parity, like pgf_get_kkt; re-assembles, does not disturb the factor);
+ * PGF_INVALID on a Symmetric handle */
+int pgf_get_newton_matrix(pgf_handle h, double *M_out, int64_t ld);
+/* counters since pgf_create: device assemblies made for a factorisation, LU factorisations, and
+ * the bytes of (n + m)^2 matrices that crossed PCIe for this handle -- 0 on the device path; the
+ * host-assembly path of the Python classes (PGF_UNSYM_HOST=1) reports each matrix
+ * it sends to the stand-alone LU with pgf_debug_unsym_note_upload */
+int pgf_debug_unsym_stats(pgf_handle h, int *assemblies, int *lu_factorisations,
+                          int64_t *matrix_bytes_from_host);
+int pgf_debug_unsym_note_upload(pgf_handle h, int64_t bytes);
 
 /* ---- accuracy guard of the dense path ---------------------------------------------- */
 /* The reference factorises the reduced KKT matrix with a PIVOTED sparse LU (SuperLU through

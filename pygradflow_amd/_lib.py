@@ -24,6 +24,8 @@ PGF_OK, PGF_SINGULAR, PGF_INERTIA, PGF_INVALID, PGF_NOT_READY, PGF_HIP_ERROR = 0
 PGF_HOST, PGF_DEVICE = 0, 1
 STEP_RECOMPUTE_MASK, STEP_REFACTOR, STEP_REFACTOR_ON_CHANGE = 1, 2, 4
 CREATE_SPARSE = 1
+FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
+FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -112,6 +114,10 @@ SIGNATURES = {
     "pgf_batch_allgather_norms": (C.c_int, [_h, C.c_void_p, C.c_void_p]),
     "pgf_batch_debug_fail_next_helper": (C.c_int, [_h]),
     "pgf_batch_debug_factor_kind": (C.c_int, [_h]),
+    "pgf_set_formulation": (C.c_int, [_h, C.c_int]),
+    "pgf_get_newton_matrix": (C.c_int, [_h, _dp, C.c_int64]),
+    "pgf_debug_unsym_stats": (C.c_int, [_h, _ip, _ip, C.POINTER(C.c_int64)]),
+    "pgf_debug_unsym_note_upload": (C.c_int, [_h, C.c_int64]),
 }
 
 _lib = None

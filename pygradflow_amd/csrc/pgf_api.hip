@@ -10,6 +10,7 @@
 #include "pgf_internal.h"
 #include "pgf_kernels.h"
 #include "pgf_sparse.h"
+#include "pgf_unsym.h"
 
 #define PGF_GEMVT_PARTS 32
 
@@ -111,6 +112,23 @@ struct pgf_solver {
   // what the factorisation in flight added to the counters (taken back when it is discarded)
   bool fac_counted = false, fac_used_gram = false;
   int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
+  // The unsymmetric formulations (pgf_set_formulation; the section in front of pgf_factor): form --
+  // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
+  // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric
+  // path and is never touched here); ulu_ok -- it holds the factor of the current matrix;
+  // h_has_lag_only -- H in HBM is the plain Lagrangian Hessian (pgf_qp_set_problem), so Standard
+  // adds rho J^T J from the resident Gram matrix; a caller of pgf_set_derivs_* uploads
+  // aug_lag_deriv_xx(rho) itself.
+  int form = PGF_FORM_SYMMETRIC;
+  DenseLu ulu;
+  bool ulu_ok = false;
+  bool h_has_lag_only = false;
+  int stat_unsym_asm = 0, stat_unsym_lu = 0;  // pgf_debug_unsym_stats
+  int64_t stat_unsym_bytes = 0;
+  // while profiling is enabled: device time of the assembly launches of unsym_factor since the
+  // last pgf_profile_read_ex, and their count
+  double acc_unsym_asm_ms = 0;
+  int64_t acc_unsym_asm_launches = 0;
 };
 
 struct pgf_linsolver {
@@ -268,6 +286,7 @@ int pgf_destroy(pgf_handle h) {
   if (h->mask_ev) (void)hipEventDestroy(h->mask_ev);
   if (h->h_bred) (void)hipHostFree(h->h_bred);
   lu_free(h->lu);
+  lu_free(h->ulu);
   if (h->h_meas) (void)hipHostFree(h->h_meas);
   {
     SparseDev &sp = h->sp;
@@ -317,6 +336,7 @@ static void invalidate_factor(pgf_handle h) {
   h->condensed_veto = false;
   h->lu_active = false;
   h->factor_clean = false;
+  h->ulu_ok = false;
 }
 
 int pgf_set_bounds(pgf_handle h, const double *lb, const double *ub) {
@@ -387,6 +407,7 @@ int pgf_set_derivs_dense(pgf_handle h, const double *H, int64_t ldh, const doubl
   if ((rc = set_matrix(h, H, ldh, h->n, h->n, loc, &h->Hown, &h->H, &h->ldh, &h->ownH))) return rc;
   if ((rc = set_matrix(h, J, ldj, h->m, h->n, loc, &h->Jown, &h->J, &h->ldj, &h->ownJ))) return rc;
   h->derivs_set = true;
+  h->h_has_lag_only = false;
   invalidate_derivs(h);
   invalidate_factor(h);
   return PGF_OK;
@@ -455,6 +476,7 @@ int pgf_set_derivs_csr(pgf_handle h, const int *Hptr, const int *Hidx, const dou
                                 &h->ownJ)))
     return rc;
   h->derivs_set = true;
+  h->h_has_lag_only = false;
   invalidate_derivs(h);
   invalidate_factor(h);
   return PGF_OK;
@@ -481,8 +503,13 @@ int pgf_active_set(pgf_handle h, const double *x, const double *g, double tau, u
   int use_tau;
   double f_x, f_x0, f_d;
   tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
-  launch_active_set(h->stream, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->tmpn, h->g,
-                    h->slb, h->sub, h->mask_new);
+  if (h->form == PGF_FORM_STANDARD)  // the unscaled projection and thresholds
+    launch_unscaled_active_set(h->stream, h->n, use_tau, h->dt, use_tau ? 1.0 - tau * h->lamb : 0.0,
+                               use_tau ? tau * h->lamb : 0.0, use_tau ? tau : 0.0, h->xhat, h->tmpn, h->g,
+                               h->lb, h->ub, h->mask_new);
+  else
+    launch_active_set(h->stream, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->tmpn, h->g,
+                      h->slb, h->sub, h->mask_new);
   if ((rc = down(h, mask_out, h->mask_new, h->n))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->eval_fresh = false;
@@ -563,7 +590,7 @@ int pgf_reduced_dims(pgf_handle h, int *n_inactive, int *n_reduced) {
   if (!h) return PGF_INVALID;
   if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set");
   if (n_inactive) *n_inactive = h->nI;
-  if (n_reduced) *n_reduced = h->N;
+  if (n_reduced) *n_reduced = h->form ? h->n + h->m : h->N;
   return PGF_OK;
 }
 
@@ -679,11 +706,16 @@ static int gram_mode() {
 // true: h->G holds J^T J for the matrices in HBM (built now if the rule says so); false: this
 // factorisation takes the virtual-block path.  Never an error: a failed allocation switches the
 // Gram path off for the handle.  (condensed_reserve has been called: f.V, f.vd hold n + 1 rows.)
+static bool gram_build(pgf_handle h);
 static bool gram_prepare(pgf_handle h) {
   const int mode = gram_mode();
   if (!mode || h->gram_off) return false;
   if (h->gram_valid) return true;
   if (mode == 1 && h->cond_since_upload < 1) return false;
+  return gram_build(h);
+}
+// the build itself (also asked for by the device-resident Standard formulation, unsym_gram)
+static bool gram_build(pgf_handle h) {
   DenseLdlt &f = h->fac;
   const int n = h->n, mp = (h->m + 31) / 32 * 32;
   if (!h->G) {
@@ -1130,11 +1162,243 @@ static int chain_recover(pgf_handle h, bool swapped) {
   return PGF_OK;
 }
 
+static void qp_eval(pgf_handle h);
+// ---------------------------------------------------------------- unsymmetric formulations
+// Standard / Extended / Asymmetric (pgf_set_formulation): the same Newton step through the
+// (n + m) x (n + m) matrix of the reference's alternative step solvers, assembled in HBM from the
+// resident H, J, mask and index lists (pgf_unsym.hip) straight into the array the pivoted LU
+// factorises in place.  The system always has n + m rows: no size depends on |I|, the kernels read
+// |A| on the device, so a step needs no host synchronisation for the index sets -- the one wait
+// inside a factorising step is lu_factor's own (it reads its pivots).  No LDL^T, no inertia
+// (n_neg = -1, LUSolver.num_neg_eigvals() is None), no accuracy guard: the LU pivots.
+static const double *unsym_lo(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->lb : h->slb; }
+static const double *unsym_hi(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->ub : h->sub; }
+
+// Device-resident Standard linearises with aug_lag_deriv_xx(rho) = H + rho J^T J: the Gram matrix
+// the condensed LDL^T keeps per derivative upload (gram_build) -- never rebuilt per step.
+static int unsym_gram(pgf_handle h, const double **G) {
+  *G = nullptr;
+  if (h->form != PGF_FORM_STANDARD || !h->h_has_lag_only || h->m == 0 || h->n == 0) return PGF_OK;
+  if (!h->gram_valid) {
+    HIPCHK(h, condensed_reserve(h));
+    if (h->gram_off || !gram_build(h))
+      return fail(h, PGF_HIP_ERROR, "Standard formulation: the Gram matrix J^T J could not be built");
+  }
+  *G = h->G;
+  return PGF_OK;
+}
+
+static int unsym_assemble(pgf_handle h, double *M, int64_t ld) {
+  const double *G;
+  int rc;
+  if ((rc = unsym_gram(h, &G))) return rc;
+  launch_assemble_unsym(h->stream, h->form, M, ld, h->n, h->m, h->H, h->ldh, h->J, h->ldj, G, h->ldg,
+                        h->rho, h->mask, h->idxI, h->idxA, h->counts, h->dt, h->lamb, h->delta);
+  return PGF_OK;
+}
+
+// assemble + factorise (waits: lu_factor reads its pivots)
+static int unsym_factor(pgf_handle h) {
+  const int Nf = h->n + h->m;
+  if (!h->ulu.A) {
+    const hipError_t ea = lu_alloc(h->ulu, Nf, h->stream);
+    if (ea != hipSuccess) {
+      lu_free(h->ulu);  // (nothing half allocated stays behind)
+      return hip_fail(h, ea, "lu_alloc");
+    }
+  }
+  h->ulu_ok = false;
+  int rc;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (h->prof.enabled) {
+    e0 = prof_event(&h->prof);
+    e1 = prof_event(&h->prof);
+    (void)hipEventRecord(e0, h->stream);
+  }
+  rc = unsym_assemble(h, h->ulu.A, h->ulu.ld);
+  if (e0) (void)hipEventRecord(e1, h->stream);
+  hipError_t e = hipSuccess;
+  const int st = rc ? 0 : lu_factor(h->ulu, &e);  // (waits for the stream)
+  if (e0) {
+    float ms = 0.f;
+    if (!rc && st >= 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) {
+      h->acc_unsym_asm_ms += ms;
+      ++h->acc_unsym_asm_launches;
+    }
+    h->prof.pool.push_back(e0);
+    h->prof.pool.push_back(e1);
+  }
+  if (rc) return rc;
+  ++h->stat_unsym_asm;
+  if (st < 0) return hip_fail(h, e, "LU of the Newton matrix");
+  ++h->stat_unsym_lu;
+  if (st == 1) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the LU of the Newton matrix");
+  h->ulu_ok = true;
+  return PGF_OK;
+}
+
+// the mask at (x, g) into `out' (Standard: unscaled)
+static void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint8_t *out) {
+  int use_tau;
+  double f_x, f_x0, f_d;
+  tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
+  if (h->form == PGF_FORM_STANDARD)
+    launch_unscaled_active_set(h->stream, h->n, use_tau, h->dt, use_tau ? 1.0 - tau * h->lamb : 0.0,
+                               use_tau ? tau * h->lamb : 0.0, use_tau ? tau : 0.0, h->xhat, x, g, h->lb,
+                               h->ub, out);
+  else
+    launch_active_set(h->stream, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, x, g, h->slb, h->sub, out);
+}
+
+// residual, right-hand side, (factorisation,) solve and step update for the point in
+// (h->x, h->y, h->g, h->c); scal[0] <- the step length.  Enqueued, except for lu_factor's wait.
+static int unsym_step_core(pgf_handle h) {
+  hipStream_t s = h->stream;
+  h->fused_eval_done = false;
+  launch_unsym_residual_rhs(s, h->form, h->n, h->m, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y,
+                            h->g, h->c, unsym_lo(h), unsym_hi(h), h->mask, h->pos, h->counts, h->F, h->rhs);
+  int rc;
+  if (!h->ulu_ok && (rc = unsym_factor(h))) return rc;
+  HIPCHK(h, lu_solve_async(h->ulu, h->rhs, h->sol, 0));
+  launch_unsym_step_update(s, h->form, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F, h->sol,
+                           h->dx, h->dy, h->xn, h->yn, h->red);
+  launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
+  return PGF_OK;
+}
+
+// mask at the device point; adopted (index lists rebuilt, factor dropped) when forced, when there
+// is none yet, or when it differs.  The sizes of the index sets are not awaited (wait_counts: they
+// are, outside a step).
+static int unsym_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, bool wait_counts) {
+  hipStream_t s = h->stream;
+  unsym_mask(h, tau, h->x, h->g, h->mask_new);
+  int changed = 1;
+  int rc;
+  if (h->mask_set && !force) {
+    HIPCHK(h, hipMemsetAsync(h->counts + 2, 0, sizeof(int), s));
+    launch_mask_diff(s, h->n, h->mask, h->mask_new, h->counts + 2);
+    if ((rc = down(h, h->h_counts + 2, h->counts + 2, sizeof(int)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (!wait_counts) ++h->stat_host_syncs;
+    changed = h->h_counts[2] != 0;
+  }
+  if (changed_out) *changed_out = changed;
+  if (!changed) return PGF_OK;
+  launch_copy_u8(s, h->mask, h->mask_new, h->n);
+  launch_compact(s, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, -1);
+  h->mask_set = true;
+  invalidate_factor(h);
+  if (wait_counts) {
+    if ((rc = down(h, h->h_counts, h->counts, 2 * sizeof(int)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(s));
+    h->nI = h->h_counts[0];
+    h->nA = h->h_counts[1];
+    h->N = h->nI + h->m;
+    h->counts_known = true;
+  } else {
+    h->counts_known = false;  // (they arrive with the step's status block, pgf_qp_sync)
+  }
+  return PGF_OK;
+}
+
+static int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau) {
+  int rc;
+  qp_eval(h);
+  if (policy & PGF_STEP_RECOMPUTE_MASK) {
+    const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+    if ((rc = unsym_refresh_mask(h, tau, force, nullptr, false))) return rc;
+  }
+  if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first");
+  if (policy & PGF_STEP_REFACTOR) invalidate_factor(h);
+  if ((rc = unsym_step_core(h))) return rc;
+  std::swap(h->x, h->xn);
+  std::swap(h->y, h->yn);
+  h->eval_fresh = false;
+  if ((rc = down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double)))) return rc;
+  h->step_pending = true;
+  return PGF_OK;
+}
+
+static int unsym_qp_sync(pgf_handle h, int *n_neg, double *diff) {
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  ++h->stat_host_syncs;
+  h->nI = h->h_counts[0];
+  h->nA = h->h_counts[1];
+  h->N = h->nI + h->m;
+  h->counts_known = true;
+  if (n_neg) *n_neg = -1;
+  if (diff) *diff = h->h_scal[0];
+  return PGF_OK;
+}
+
+int pgf_set_formulation(pgf_handle h, int form) {
+  if (!h) return PGF_INVALID;
+  if (h->sparse) return fail(h, PGF_INVALID, "pgf_set_formulation: dense handles only");
+  if (form < PGF_FORM_SYMMETRIC || form > PGF_FORM_ASYMMETRIC)
+    return fail(h, PGF_INVALID, "pgf_set_formulation: unknown formulation");
+  if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the step in flight first");
+  h->form = form;
+  invalidate_factor(h);
+  // a handle that goes back to Symmetric gives the (n + m) x ld array of its LU back
+  if (form == PGF_FORM_SYMMETRIC && h->ulu.A) {
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    lu_free(h->ulu);
+  }
+  return PGF_OK;
+}
+
+int pgf_get_newton_matrix(pgf_handle h, double *M_out, int64_t ld) {
+  if (!h) return PGF_INVALID;
+  if (!h->form) return fail(h, PGF_INVALID, "pgf_get_newton_matrix: pgf_set_formulation first");
+  int rc;
+  if ((rc = check_ready(h))) return rc;
+  const int Nf = h->n + h->m;
+  if (Nf == 0) return PGF_OK;
+  if (!M_out || ld < Nf) return fail(h, PGF_INVALID, "bad output matrix");
+  (void)hipSetDevice(h->device);
+  double *tmp = nullptr;
+  HIPCHK(h, dalloc(&tmp, (size_t)Nf * Nf));
+  rc = unsym_assemble(h, tmp, Nf);
+  hipError_t e = hipSuccess;
+  if (!rc) {
+    e = hipMemcpy2DAsync(M_out, (size_t)ld * sizeof(double), tmp, (size_t)Nf * sizeof(double),
+                         (size_t)Nf * sizeof(double), Nf, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  } else {
+    (void)hipStreamSynchronize(h->stream);
+  }
+  (void)hipFree(tmp);
+  if (rc) return rc;
+  if (e != hipSuccess) return hip_fail(h, e, "pgf_get_newton_matrix");
+  return PGF_OK;
+}
+
+int pgf_debug_unsym_stats(pgf_handle h, int *assemblies, int *lu_factorisations,
+                          int64_t *matrix_bytes_from_host) {
+  if (!h) return PGF_INVALID;
+  if (assemblies) *assemblies = h->stat_unsym_asm;
+  if (lu_factorisations) *lu_factorisations = h->stat_unsym_lu;
+  if (matrix_bytes_from_host) *matrix_bytes_from_host = h->stat_unsym_bytes;
+  return PGF_OK;
+}
+
+int pgf_debug_unsym_note_upload(pgf_handle h, int64_t bytes) {
+  if (!h || bytes < 0) return PGF_INVALID;
+  h->stat_unsym_bytes += bytes;
+  return PGF_OK;
+}
+
 int pgf_factor(pgf_handle h, int *n_neg) {
   if (!h) return PGF_INVALID;
   int rc;
   if ((rc = check_ready(h))) return rc;
   (void)hipSetDevice(h->device);
+  if (h->form) {
+    if (!h->ulu_ok && (rc = unsym_factor(h))) return rc;  // (the factor of the current matrix stays)
+    if (n_neg) *n_neg = -1;
+    return PGF_OK;
+  }
   if ((rc = factor_sync(h))) return rc;
   if (n_neg) *n_neg = h->fac.n_neg;
   return PGF_OK;
@@ -1272,6 +1536,18 @@ int pgf_newton_solve(pgf_handle h, const double *x, const double *y, const doubl
   if ((rc = up(h, h->g, g, h->n * sizeof(double)))) return rc;
   if ((rc = up(h, h->c, c, h->m * sizeof(double)))) return rc;
   h->eval_fresh = false;
+  if (h->form) {
+    if (inertia_check) return fail(h, PGF_INVALID, "no inertia with an unsymmetric formulation (LU)");
+    if ((rc = unsym_step_core(h))) return rc;
+    if ((rc = down(h, h->h_scal, h->scal, sizeof(double)))) return rc;
+    if (dx && (rc = down(h, dx, h->dx, h->n * sizeof(double)))) return rc;
+    if (dy && (rc = down(h, dy, h->dy, h->m * sizeof(double)))) return rc;
+    if (xn && (rc = down(h, xn, h->xn, h->n * sizeof(double)))) return rc;
+    if (yn && (rc = down(h, yn, h->yn, h->m * sizeof(double)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (diff) *diff = h->h_scal[0];
+    return PGF_OK;
+  }
   bool did_factor;
   for (int attempt = 0;; ++attempt) {
     if ((rc = newton_core_async(h, &did_factor))) return rc;
@@ -1315,19 +1591,27 @@ int pgf_residual(pgf_handle h, const double *x, const double *y, const double *g
   if ((rc = up(h, h->w, c, h->m * sizeof(double)))) return rc;
   if (mask) {
     if ((rc = up(h, h->mask_new, mask, h->n))) return rc;
+  } else if (h->form == PGF_FORM_STANDARD) {
+    unsym_mask(h, NAN, h->xn, h->tmpn, h->mask_new);
   } else {
     launch_active_set(h->stream, h->n, 0, h->lamb, 0, 0, 0, h->xhat, h->xn, h->tmpn, h->slb,
                       h->sub, h->mask_new);
   }
-  launch_residual(h->stream, h->n, h->m, h->lamb, h->dt, h->xhat, h->yhat, h->xn, h->yn, h->tmpn,
-                  h->w, h->slb, h->sub, h->mask_new, h->sol, nullptr);
+  if (h->form == PGF_FORM_STANDARD) {  // the unscaled residual (ImplicitFunc.value_at)
+    launch_unsym_residual_rhs(h->stream, h->form, h->n, h->m, h->lamb, h->dt, h->fact, h->xhat, h->yhat,
+                              h->xn, h->yn, h->tmpn, h->w, h->lb, h->ub, h->mask_new, nullptr, nullptr,
+                              h->sol, nullptr);
+  } else {
+    launch_residual(h->stream, h->n, h->m, h->lamb, h->dt, h->xhat, h->yhat, h->xn, h->yn, h->tmpn,
+                    h->w, h->slb, h->sub, h->mask_new, h->sol, nullptr);
+  }
   if ((rc = down(h, F_out, h->sol, (size_t)(h->n + h->m) * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PGF_OK;
 }
 
 int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
-  (void)trans;  // K is symmetric
+  // (the Symmetric path ignores trans: K is symmetric; a formulation honours it)
   if (!h) return PGF_INVALID;
   int rc;
   if ((rc = check_ready(h))) return rc;
@@ -1374,6 +1658,18 @@ int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
     if (h->fac.h_flags[0]) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
     h->fac.n_neg = h->fac.h_flags[1];
     h->fac.factored = true;
+    return PGF_OK;
+  }
+  if (h->form) {  // the full system, A or A^T (cond_estimate.py:82)
+    const int Nf = h->n + h->m;
+    if (Nf && (!rhs || !sol)) return fail(h, PGF_INVALID, "null argument");
+    if (Nf == 0) return PGF_OK;
+    (void)hipSetDevice(h->device);
+    if (!h->ulu_ok && (rc = unsym_factor(h))) return rc;
+    if ((rc = up(h, h->rhs, rhs, (size_t)Nf * sizeof(double)))) return rc;
+    HIPCHK(h, lu_solve_async(h->ulu, h->rhs, h->sol, trans));
+    if ((rc = down(h, sol, h->sol, (size_t)Nf * sizeof(double)))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return PGF_OK;
   }
   if (h->N && (!rhs || !sol)) return fail(h, PGF_INVALID, "null argument");
@@ -1587,6 +1883,7 @@ int pgf_qp_set_vectors(pgf_handle h, const double *q, const double *b) {
   if ((rc = up(h, h->b, b, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
+  h->h_has_lag_only = true;
   return PGF_OK;
 }
 
@@ -1607,6 +1904,7 @@ int pgf_qp_set_problem(pgf_handle h, const double *Q, int64_t ldq, const double 
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
+  h->h_has_lag_only = true;
   return PGF_OK;
 }
 
@@ -1725,6 +2023,7 @@ int pgf_qp_update_active_set(pgf_handle h, double tau, int *changed) {
   if ((rc = qp_ready(h))) return rc;
   (void)hipSetDevice(h->device);
   qp_eval(h);
+  if (h->form) return unsym_refresh_mask(h, tau, false, changed, true);
   return qp_refresh_mask(h, tau, false, changed, false);
 }
 
@@ -1819,6 +2118,7 @@ int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
   if ((rc = qp_ready(h))) return rc;
   if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the previous step first");
   (void)hipSetDevice(h->device);
+  if (h->form) return unsym_qp_step_async(h, policy, tau);
   qp_eval(h);
   if (policy & PGF_STEP_RECOMPUTE_MASK) {
     // Full (newton.py:83-89): the mask is always re-set, which drops the factor;
@@ -1838,6 +2138,7 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   if (!h->step_pending) return fail(h, PGF_NOT_READY, "no step pending");
   h->step_pending = false;
   (void)hipSetDevice(h->device);
+  if (h->form) return unsym_qp_sync(h, n_neg, diff);
   hipError_t e;
   int rc;
   if ((rc = sparse_status_sync(h))) return rc;
@@ -1944,9 +2245,12 @@ int pgf_debug_chain_helpers(int on) {
 int pgf_qp_step(pgf_handle h, unsigned policy, double tau, int inertia_check, int *n_neg,
                 double *diff) {
   int rc;
+  if (h && h->form && inertia_check)
+    return fail(h, PGF_INVALID, "no inertia with an unsymmetric formulation (LU)");
   if ((rc = pgf_qp_step_async(h, policy, tau))) return rc;
   if ((rc = pgf_qp_sync(h, n_neg, diff))) return rc;
-  if (inertia_check && h->fac.n_neg != h->m) return fail(h, PGF_INERTIA, "Invalid matrix inertia");
+  if (!h->form && inertia_check && h->fac.n_neg != h->m)
+    return fail(h, PGF_INERTIA, "Invalid matrix inertia");
   return PGF_OK;
 }
 
@@ -2047,6 +2351,7 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
       return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
     if (h->sparse) return fail(h, PGF_INVALID, "batch: dense handles only");
+    if (h->form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
     if (!h->qp_mode || !h->bounds_set || !h->point_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_problem, pgf_qp_set_point first");
     if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
@@ -2934,6 +3239,12 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count) {
     out[PGF_PROF_FUSED_FLOPS] = p.acc_fused_flops;
     out[PGF_PROF_FUSED_BYTES] = p.acc_fused_bytes;
     out[PGF_PROF_TRSMUD_MS] = p.acc_trsmud_ms;
+  }
+  if (count >= PGF_PROF_COUNT3) {
+    out[PGF_PROF_UNSYM_ASM_MS] = h->acc_unsym_asm_ms;
+    out[PGF_PROF_UNSYM_ASM_LAUNCHES] = (double)h->acc_unsym_asm_launches;
+    h->acc_unsym_asm_ms = 0;
+    h->acc_unsym_asm_launches = 0;
   }
   profile_reset(p);
   return PGF_OK;

@@ -133,7 +133,8 @@ class GlobalizedNewtonMethod(NewtonMethod):
 def make_step_solver(problem, params, iterate, dt, rho):
     """Reference factory ``step_solver`` (step/solver/__init__.py:12-31): honours the
     ``params.step_solver`` hook, then ``params.step_solver_type``: Symmetric (default) is the
-    HIP hot path, Standard / Extended / Asymmetric go through the GPU LU."""
+    HIP hot path, Standard / Extended / Asymmetric assemble their matrix on the device and go
+    through the GPU LU."""
     from .unsym_step_solvers import step_solver
 
     return step_solver(problem, params, iterate, dt, rho)
@@ -183,7 +184,7 @@ class DeviceNewton:
     """
 
     def __init__(self, problem, newton_type, x_hat, y_hat, dt, rho, tau=None, device=0,
-                 start=None):
+                 start=None, step_solver_type="Symmetric"):
         _lib.require_gpu()
         self._lib = _lib.load()
         self.problem = problem
@@ -195,9 +196,21 @@ class DeviceNewton:
         self.tau = math.nan if tau is None else float(tau)
         self.sparse = (not problem.is_dense) and (
             bool(getattr(problem, "pgf_force_band", False)) or self.n + self.m > DENSE_LIMIT)
+        self.step_solver_type = (step_solver_type if isinstance(step_solver_type, str)
+                                 else enum_name(step_solver_type))
+        if self.step_solver_type not in _lib.FORMULATIONS:
+            raise ValueError(f"unknown step_solver_type {self.step_solver_type}")
+        self.formulation = _lib.FORMULATIONS[self.step_solver_type]
+        if self.formulation and self.sparse:
+            raise NotImplementedError(
+                f"step_solver_type={self.step_solver_type}: dense problems only (this one takes "
+                "the banded path)")
         self._hd = POOL.acquire(self.n, self.m, device, sparse=self.sparse)
         h = self._hd.h
         lib = self._lib
+        # on every dense handle, also to Symmetric: whatever its last user left does not matter
+        if not self.sparse:
+            _lib.check(lib.pgf_set_formulation(h, self.formulation), h, "pgf_set_formulation")
         lb, ub = _lib.as_f64(problem.var_lb), _lib.as_f64(problem.var_ub)
         _lib.check(lib.pgf_set_bounds(h, _lib.dptr(lb), _lib.dptr(ub)), h, "pgf_set_bounds")
         key = residency_key(problem)
@@ -260,6 +273,7 @@ class DeviceNewton:
                        "pgf_qp_update_active_set")
 
     def step(self, inertia_check=False):
+        """``(diff, n_neg)``; ``n_neg`` is -1 with an unsymmetric formulation (LU: no inertia)."""
         n_neg, diff = C.c_int(0), C.c_double(0.0)
         try:
             rc = self._lib.pgf_qp_step(self._hd.h, _POLICY_BITS[self.kind], self.tau,
@@ -310,6 +324,30 @@ class DeviceNewton:
                    self._hd.h, "pgf_qp_measures")
         return dict(stat_res=out[0], cons_violation=out[1], bound_violation=out[2], y_inf=out[3])
 
+    def newton_matrix(self):
+        """The assembled ``(n + m)^2`` Newton matrix of the formulation (``pgf_get_newton_matrix``;
+        debug / parity)."""
+        N = self.n + self.m
+        M = np.zeros((N, N))
+        if N:
+            _lib.check(self._lib.pgf_get_newton_matrix(self._hd.h, _lib.dptr(M), N), self._hd.h,
+                       "pgf_get_newton_matrix")
+        return M
+
+    def unsym_stats(self):
+        """(device assemblies, LU factorisations, bytes of (n + m)^2 matrices uploaded) of the
+        handle (``pgf_debug_unsym_stats``)."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int64(0)
+        _lib.check(self._lib.pgf_debug_unsym_stats(self._hd.h, C.byref(a), C.byref(b), C.byref(c)),
+                   self._hd.h)
+        return a.value, b.value, c.value
+
+    def gram_stats(self):
+        """(builds, factorisations with it) of the resident Gram matrix (``pgf_debug_gram_stats``)."""
+        a, b = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_gram_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
+        return a.value, b.value
+
     def factor_kind(self):
         """0 none, 1 LDL^T in the natural order, 2 LDL^T of the condensed system, 3 pivoted LU
         (``pgf_debug_factor_kind``)."""
@@ -342,6 +380,13 @@ class DeviceNewton:
 
     def close(self):
         if getattr(self, "_hd", None) is not None:
+            if getattr(self, "formulation", 0):
+                h = self._hd.h
+                if self._lib.pgf_set_formulation(h, _lib.FORM_SYMMETRIC) != _lib.PGF_OK:
+                    # a step is in flight (step_async without sync): settle it, then switch
+                    self._lib.pgf_qp_sync(h, None, None)
+                    _lib.check(self._lib.pgf_set_formulation(h, _lib.FORM_SYMMETRIC), h,
+                               "pgf_set_formulation")
             POOL.release(self._hd)
             self._hd = None
 

@@ -233,7 +233,12 @@ class HipStepFunc:
 
 # --------------------------------------------------------------------------- step solver
 class HipStepSolver:
-    def __init__(self, problem, params, orig_iterate, dt, rho, device: int = 0):
+    """``formulation``: 0 (default) the Symmetric reduced system; ``_lib.FORM_STANDARD`` /
+    ``_EXTENDED`` / ``_ASYMMETRIC`` make the handle assemble and factor the reference's
+    unsymmetric ``(n + m)`` system on the device instead (``pgf_set_formulation``; the product
+    classes of ``unsym_step_solvers.py`` drive it, dense handles only)."""
+
+    def __init__(self, problem, params, orig_iterate, dt, rho, device: int = 0, formulation: int = 0):
         if not (dt > 0.0 and rho > 0.0):
             raise ValueError("dt and rho must be positive")
         if np.dtype(params.dtype) != np.float64:
@@ -258,14 +263,23 @@ class HipStepSolver:
         self._mask_dirty = True
         self._outer_sent = False
         # sparse (banded) mode: problems too large for a dense KKT matrix, or on request
-        self.sparse = bool(getattr(problem, "pgf_force_band", False)) or (self.n + self.m > DENSE_LIMIT)
+        self.formulation = int(formulation)
+        self.sparse = not self.formulation and (
+            bool(getattr(problem, "pgf_force_band", False)) or (self.n + self.m > DENSE_LIMIT))
         self._hd = POOL.acquire(self.n, self.m, device, sparse=self.sparse)
+        self._set_formulation()
         self._func = HipStepFunc(self)
         self.last_n_neg = None
 
     # -- lifetime ----------------------------------------------------------
     def close(self):
         if getattr(self, "_hd", None) is not None:
+            if self.formulation:
+                # handles go back to the pool as Symmetric ones
+                _lib.check(self._lib.pgf_set_formulation(self._hd.h, _lib.FORM_SYMMETRIC), self._hd.h,
+                           "pgf_set_formulation")
+                if self.formulation == _lib.FORM_STANDARD:
+                    self._hd.derivs_key = None  # H in HBM carries the rho J'J term
             POOL.release(self._hd)
             self._hd = None
 
@@ -274,6 +288,13 @@ class HipStepSolver:
             self.close()
         except Exception:
             pass
+
+    def _set_formulation(self):
+        """On every dense handle taken from the pool, also to Symmetric: whatever the handle's
+        last user left does not matter (banded handles have no formulations)."""
+        if not self.sparse:
+            _lib.check(self._lib.pgf_set_formulation(self._hd.h, self.formulation), self._hd.h,
+                       "pgf_set_formulation")
 
     # -- StepSolver surface ------------------------------------------------
     @property
@@ -335,7 +356,9 @@ class HipStepSolver:
             # Newton steps and outer steps; the token pins the problem object so the
             # identity cannot be recycled
             key = None
-            if getattr(self.problem, "pgf_constant_derivs", False):
+            # (Standard uploads aug_lag_deriv_xx(rho), which changes with rho: never resident)
+            if (getattr(self.problem, "pgf_constant_derivs", False)
+                    and self.formulation != _lib.FORM_STANDARD):
                 key = residency_key(self.problem)
             if self.sparse and not same_key(key, hd.derivs_key):
                 if self._push_sparse_derivs():
@@ -403,6 +426,7 @@ class HipStepSolver:
         POOL.release(self._hd)
         self.sparse = False
         self._hd = POOL.acquire(self.n, self.m, device, sparse=False)
+        self._set_formulation()
         self._outer_sent = False
         self._mask_dirty = True
         self._derivs_dirty = True
@@ -507,14 +531,14 @@ class HipStepSolver:
             diff = C.c_double(0.0)
             rc = self._lib.pgf_newton_solve(
                 hd.h, _lib.dptr(x), _lib.dptr(y), _lib.dptr(g), _lib.dptr(c),
-                int(bool(getattr(params, "inertia_correction", False))),
+                0 if self.formulation else int(bool(getattr(params, "inertia_correction", False))),
                 _lib.dptr(dx), _lib.dptr(dy), _lib.dptr(xn), _lib.dptr(yn), C.byref(diff))
             _lib.check(rc, hd.h, "pgf_newton_solve")
         except LinearSolverError as e:
             raise StepSolverError(str(e)) from e
         self.solver = _DeviceFactorView(self)
         rcond = None
-        if getattr(params, "report_rcond", False):
+        if getattr(params, "report_rcond", False) and not self.formulation:
             from .cond_estimate import estimate_rcond
 
             # the estimator's products K x, K' x: on the device for the dense path (no N x N
@@ -570,6 +594,8 @@ class _DeviceFactorView:
             rc = o._lib.pgf_linear_solve(o._hd.h, _lib.dptr(full), int(bool(trans)), _lib.dptr(out))
             _lib.check(rc, o._hd.h, "pgf_linear_solve")
             return np.concatenate([out[: o.n][ina], out[o.n:]])
+        if o.formulation and rhs.shape != (o.n + o.m,):
+            raise ValueError("rhs shape mismatch")
         sol = np.empty_like(rhs)
         rc = o._lib.pgf_linear_solve(o._hd.h, _lib.dptr(rhs), int(bool(trans)), _lib.dptr(sol))
         _lib.check(rc, o._hd.h, "pgf_linear_solve")
@@ -577,6 +603,8 @@ class _DeviceFactorView:
 
     def num_neg_eigvals(self):
         o = self._o
+        if o.formulation:
+            return None  # (an LU has no inertia: LUSolver.num_neg_eigvals())
         out = C.c_int(0)
         _lib.check(o._lib.pgf_factor(o._hd.h, C.byref(out)), o._hd.h, "pgf_factor")
         return out.value

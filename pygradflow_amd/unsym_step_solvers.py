@@ -8,24 +8,34 @@ symmetric KKT matrix.  They exist in the reference as alternative linear-algebra
 its tests parametrise every Newton policy over all four (``tests/pygradflow/test_newton.py:142-214``,
 ``test_solver.py:191-215``); SURVEY.md section 8(f) ranks them "next" after the hot path.
 
-Division of labour here: the matrices are put together on the host with scipy, exactly as the
-reference does it (a handful of block operations per factorisation, never the hot path: the
-production formulation is ``HipStepSolver``); the factorisation and the solves -- the part that
-costs -- run on the GPU through ``HipLinearSolver(symmetric=False)``: dense LU with partial
-pivoting (``csrc/pgf_lu.hip``), which is what the reference's ``LUSolver`` does for every
-matrix (``linear_solver/lu_solver.py:9-21``).  The scaled residual / active set of the Extended
-and Asymmetric formulations come from the device kernels (``HipStepFunc``); the Standard
-formulation works with the UNSCALED residual (``implicit_func.py:102-199``), whose O(n)
-elementwise arithmetic is restated below in the reference's operation order (its active-set
-thresholds ``lb - 1e-8`` differ from the scaled ``lambda lb - 1e-8``, so it cannot borrow the
-scaled kernels bit for bit).
+Division of labour here: each class owns ONE device handle set to its formulation
+(``pgf_set_formulation``).  The matrix is assembled in HBM from the resident H, J, mask and
+index lists (``csrc/pgf_unsym.hip``) straight into the array the dense LU with partial pivoting
+(``csrc/pgf_lu.hip``; what the reference's ``LUSolver`` does for every matrix,
+``linear_solver/lu_solver.py:9-21``) factorises in place; residual, right-hand side in the
+formulation's row order, solve, ``dy`` and the clipping run on the device as well
+(``pgf_newton_solve``).  No ``(n + m)^2`` matrix crosses PCIe; ``.deriv`` downloads it on demand
+(``pgf_get_newton_matrix``) for ``report_rcond`` and for callers that look at it.  The Standard
+formulation works with the UNSCALED residual (``implicit_func.py:102-199``; its active-set
+thresholds ``lb - 1e-8`` differ from the scaled ``lambda lb - 1e-8``), which the handle computes
+in the reference's operation order when its formulation is Standard.
+
+The HOST path -- the matrices put together with scipy exactly as the reference does it and handed
+to ``linear_solver(mat)`` -- is kept for the reference's override points: a subclass that
+overrides ``linear_solver`` or ``_make_func`` gets it, and ``PGF_UNSYM_HOST=1`` forces it (with the
+default ``linear_solver`` the matrix then goes over PCIe to ``HipLinearSolver(symmetric=False)``;
+DESIGN.md 4d).
 """
 
 from __future__ import annotations
 
+import ctypes as C
+import os
+
 import numpy as np
 import scipy.sparse as sps
 
+from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .linear_solver import HipLinearSolver
 from .params import enum_name
@@ -93,9 +103,30 @@ class UnscaledStepFunc:
         return self.deriv(iterate.aug_lag_deriv_xy(), iterate.aug_lag_deriv_xx(rho), active_set)
 
 
+class _DeviceUnscaledFunc(UnscaledStepFunc):
+    """``UnscaledStepFunc`` with mask and residual from the device handle (formulation Standard:
+    ``pgf_active_set`` / ``pgf_residual`` are the unscaled ones); ``deriv`` stays the host one."""
+
+    def __init__(self, dev):
+        super().__init__(dev.problem, dev.orig_iterate, dev.dt)
+        self._f = dev.func
+
+    def compute_active_set(self, iterate, rho, tau=None):
+        return self._f.compute_active_set(iterate, rho, tau)
+
+    def value_at(self, iterate, rho, active_set=None):
+        return self._f.value_at(iterate, rho, active_set)
+
+
+def host_path_forced():
+    return os.environ.get("PGF_UNSYM_HOST", "") == "1"
+
+
 class _UnsymmetricStepSolver:
     """``StepSolver`` surface (step/solver/step_solver.py:66-130) shared by the three
     formulations: stash-and-invalidate setters, ``linear_solver(mat)`` override point."""
+
+    FORM = None  # _lib.FORM_* of the class
 
     def __init__(self, problem, params, orig_iterate, dt, rho, device=0):
         if not (dt > 0.0 and rho > 0.0):
@@ -110,6 +141,29 @@ class _UnsymmetricStepSolver:
         self._active_set = self._jac = self._hess = None
         self._deriv = None
         self.solver = None
+        self._dev = None
+        # the reference's override points keep today's host assembly (module docstring)
+        cls = type(self)
+        self._overridden = (cls.linear_solver is not _UnsymmetricStepSolver.linear_solver
+                            or cls._make_func is not _UnsymmetricStepSolver._make_func)
+        self._on_device = not (self._overridden or host_path_forced())
+
+    def _make_func(self):
+        """The residual function, and with it the device handle: set to the class's formulation
+        on the device path, a plain (Symmetric) one for the scaled residual / mask kernels and
+        the upload accounting on the host path."""
+        self._dev = HipStepSolver(self.problem, self.params, self.orig_iterate, self.dt, self.rho,
+                                  device=self.device,
+                                  formulation=self.FORM if self._on_device else 0)
+        return self._dev.func
+
+    def unsym_stats(self):
+        """(device assemblies, LU factorisations, bytes of (n + m)^2 matrices that went over PCIe)
+        of this solver's handle (``pgf_debug_unsym_stats``)."""
+        h = self._dev._hd.h
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int64(0)
+        _lib.check(self._dev._lib.pgf_debug_unsym_stats(h, C.byref(a), C.byref(b), C.byref(c)), h)
+        return a.value, b.value, c.value
 
     @property
     def active_set(self):
@@ -128,6 +182,15 @@ class _UnsymmetricStepSolver:
 
     @property
     def deriv(self):
+        if self._deriv is None and self._on_device:
+            dev = self._dev
+            dev._push_state()
+            N = self.n + self.m
+            M = np.zeros((N, N))
+            if N:
+                _lib.check(dev._lib.pgf_get_newton_matrix(dev._hd.h, _lib.dptr(M), N), dev._hd.h,
+                           "pgf_get_newton_matrix")
+            self._deriv = sps.csr_matrix(M)
         assert self._deriv is not None
         return self._deriv
 
@@ -146,11 +209,33 @@ class _UnsymmetricStepSolver:
     def update_active_set(self, active_set):
         self._active_set = np.array(active_set, dtype=np.bool_, copy=True)
         self.reset_deriv()
+        if self._on_device:
+            self._dev.update_active_set(self._active_set)
+
+    def _stash_derivs(self, jac, hess):
+        self._jac, self._hess = jac, hess
+        self.reset_deriv()
+        if self._on_device:
+            dev = self._dev
+            dev._jac, dev._hess = jac, hess
+            dev.reset_deriv()
+
+    def _solve_on_device(self, iterate):
+        """Assembly, LU, solve and step update on the handle (``pgf_newton_solve``)."""
+        res = self._dev.solve(iterate)
+        self.solver = self._dev.solver
+        res.active_set = self.active_set
+        res.rcond = self._rcond()
+        return res
 
     def _factor_and_solve(self, rhs, initial_sol=None):
         try:
             if self.solver is None:
                 self.solver = self.linear_solver(self.deriv)
+                if self._dev is not None and not self._overridden:
+                    # the dense matrix went over PCIe to the stand-alone LU
+                    N = self.n + self.m
+                    self._dev._lib.pgf_debug_unsym_note_upload(self._dev._hd.h, 8 * N * N)
             return self.solver.solve(rhs) if initial_sol is None else self.solver.solve(
                 rhs, initial_sol=initial_sol)
         except LinearSolverError as e:
@@ -165,7 +250,15 @@ class _UnsymmetricStepSolver:
             return None
 
     def close(self):
-        pass
+        if getattr(self, "_dev", None) is not None:
+            self._dev.close()
+            self._dev = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class StandardStepSolver(_UnsymmetricStepSolver):
@@ -173,20 +266,34 @@ class StandardStepSolver(_UnsymmetricStepSolver):
     ``ImplicitFunc.deriv`` (standard_step_solver.py:40-92); the Hessian carries the
     ``rho J'J`` term (``aug_lag_deriv_xx(rho)``, :52)."""
 
+    FORM = _lib.FORM_STANDARD
+
     def __init__(self, problem, params, orig_iterate, dt, rho, device=0):
         super().__init__(problem, params, orig_iterate, dt, rho, device)
-        self._func = UnscaledStepFunc(problem, orig_iterate, dt)
+        self._func = self._unscaled_func()
+
+    def _unscaled_func(self):
+        """Device path: the handle's unscaled mask / residual.  Host path: the host restatement
+        (as in the reference); when it is forced by PGF_UNSYM_HOST=1 the solver still owns a handle,
+        the one its matrix uploads are counted on (``unsym_stats``).  A subclass's ``_make_func``
+        only selects the host path and is not called: it is the override point of the SCALED
+        residual (``ScaledStepSolver``), which this formulation does not use."""
+        if not self._overridden:
+            _UnsymmetricStepSolver._make_func(self)  # (the handle)
+        if self._on_device:
+            return _DeviceUnscaledFunc(self._dev)
+        return UnscaledStepFunc(self.problem, self.orig_iterate, self.dt)
 
     @property
     def func(self):
         return self._func
 
     def update_derivs(self, iterate):
-        self._jac = iterate.aug_lag_deriv_xy()
-        self._hess = iterate.aug_lag_deriv_xx(self.rho)
-        self.reset_deriv()
+        self._stash_derivs(iterate.aug_lag_deriv_xy(), iterate.aug_lag_deriv_xx(self.rho))
 
     def solve(self, iterate):
+        if self._on_device:
+            return self._solve_on_device(iterate)
         if self._deriv is None:
             self._deriv = self.func.deriv(self.jac, self.hess, self.active_set)
         rhs = self.func.value_at(iterate, self.rho, self.active_set)
@@ -202,23 +309,14 @@ class _ScaledUnsymmetricStepSolver(_UnsymmetricStepSolver):
 
     def __init__(self, problem, params, orig_iterate, dt, rho, device=0):
         super().__init__(problem, params, orig_iterate, dt, rho, device)
-        self._dev = None
         self._func = self._make_func()
-
-    def _make_func(self):
-        # the device handle behind the scaled residual / active-set kernels
-        self._dev = HipStepSolver(self.problem, self.params, self.orig_iterate, self.dt, self.rho,
-                                  device=self.device)
-        return self._dev.func
 
     @property
     def func(self):
         return self._func
 
     def update_derivs(self, iterate):
-        self._jac = iterate.aug_lag_deriv_xy()
-        self._hess = iterate.aug_lag_deriv_xx(rho=0.0)
-        self.reset_deriv()
+        self._stash_derivs(iterate.aug_lag_deriv_xy(), iterate.aug_lag_deriv_xx(rho=0.0))
 
     def initial_rhs(self, iterate):
         rhs = self.func.value_at(iterate, self.rho, self.active_set)
@@ -231,21 +329,20 @@ class _ScaledUnsymmetricStepSolver(_UnsymmetricStepSolver):
         raise NotImplementedError
 
     def solve(self, iterate):
+        if self._on_device:
+            return self._solve_on_device(iterate)
         b0, b1, b2 = self.initial_rhs(iterate)
         lamb = 1.0 / self.dt
         fact = 1.0 / (1.0 + lamb * self.rho)
         sx, sy, rcond = self.solve_scaled(b0, b1, fact * b2)
         return StepResult(iterate, sx, fact * (sy - self.rho * b2), self.active_set, rcond)
 
-    def close(self):
-        if getattr(self, "_dev", None) is not None:
-            self._dev.close()
-            self._dev = None
-
 
 class ExtendedStepSolver(_ScaledUnsymmetricStepSolver):
     """Rows of the active variables replaced by unit rows, gathered on top
     (extended_step_solver.py:39-112): ``[[E_A, 0], [H_lambda[I, :], J[:, I]'], [J, -delta I]]``."""
+
+    FORM = _lib.FORM_EXTENDED
 
     def _compute_deriv(self):
         act = np.where(self.active_set)[0]
@@ -273,6 +370,8 @@ class ExtendedStepSolver(_ScaledUnsymmetricStepSolver):
 class AsymmetricStepSolver(_ScaledUnsymmetricStepSolver):
     """Full KKT matrix with the rows of the active variables overwritten in place by unit rows
     (asymmetric_step_solver.py:38-173)."""
+
+    FORM = _lib.FORM_ASYMMETRIC
 
     def _compute_deriv(self):
         n, m = self.n, self.m
