@@ -780,8 +780,9 @@ static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
 }
 
 // The banded system is solved by block cyclic reduction (B = 8: pgf_sparse.hip, B = 16, 32, 64:
-// pgf_band_wide.hip) or, for B = 0 (bw 9 .. 10) and under PGF_BAND_SEQ at B = 8, by the
-// sequential band walk (k_band_factor; supports bw <= 10 only)
+// pgf_band_wide.hip) or, under PGF_BAND_SEQ, by the sequential band walk (k_band_factor; supports
+// bw <= 10 only; unguarded, a diagnostic route): at B = 8, and at B = 0, which is what the automatic
+// choice then gives bw 9 .. 10 (auto_block_size)
 static bool sp_cyclic(const SparseDev &sp) {
   return sp.B > 8 || (sp.B == 8 && !getenv("PGF_BAND_SEQ"));
 }
@@ -1744,11 +1745,12 @@ int pgf_get_kkt(pgf_handle h, double *K_out, int64_t ldk_out) {
 }
 
 // ---------------------------------------------------------------- sparse (banded) mode
-// bw <= 8: 8 x 8 cyclic reduction; 9 .. 10: the sequential walk; 11 .. 64: the smallest of
-// 16, 32, 64 that holds the band
+// bw <= 8: 8 x 8 cyclic reduction; 9 .. 64: the smallest of 16, 32, 64 that holds the band.
+// Under PGF_BAND_SEQ bw 9 .. 10 gets 0, the sequential walk (bw <= 8 walks at B = 8: sp_cyclic);
+// sp_alloc_blocks sizes the work arrays for whichever this returns.
 static int auto_block_size(int bw) {
   if (bw <= 8) return 8;
-  if (bw <= 10) return 0;
+  if (bw <= 10 && getenv("PGF_BAND_SEQ")) return 0;
   return bw <= 16 ? 16 : bw <= 32 ? 32 : 64;
 }
 

@@ -8,7 +8,7 @@ struct SparseDev {
   bool active = false;
   int bw = 0, ldb = 0;
   // block size of the cyclic reduction: 8 (pgf_sparse.hip), 16 / 32 / 64 (pgf_band_wide.hip),
-  // 0: the sequential band walk (bw 9 .. 10 without a forced block size)
+  // 0: the sequential band walk (bw 9 .. 10 without a forced block size under PGF_BAND_SEQ)
   int B = 0;
   int nnzH = 0, nnzJ = 0;
   int *pos = nullptr;                       // permuted position of variable i / constraint n + r

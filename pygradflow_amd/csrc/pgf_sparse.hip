@@ -1012,6 +1012,8 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
   auto Lp = [&](int set) { return sp.bL + (size_t)set * sp.bstride * 64; };
   auto Up = [&](int set) { return sp.bU + (size_t)set * sp.bstride * 64; };
   auto Fp = [&](int set) { return sp.bF + (size_t)set * sp.bstride * 8; };
+  // (tests/band_util.py, bcr_launch_plan, restates this loop on the host so that the schedule tests
+  // can assert the plan each switch gives: keep the two in step)
   int st = 1;
   while (st < nb) {
     const int left = (nb + st - 1) / st;  // blocks still in play before this level

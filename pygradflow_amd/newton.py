@@ -217,7 +217,10 @@ class DeviceNewton:
         stale = not same_key(key, self._hd.derivs_key)
         block = getattr(problem, "pgf_band_block", None)
         replan = self._hd.plan is not None and self._hd.plan.block != (int(block) if block else None)
-        if self.sparse and (stale or replan or not getattr(self._hd, "qp_loaded", False)):
+        # q and b are resident for the problem THIS class uploaded last: a HipStepSolver that had the
+        # pooled handle in between makes derivs_key current for its problem without sending q, b
+        loaded = same_key(key, getattr(self._hd, "qp_key", None))
+        if self.sparse and (stale or replan or not loaded):
             plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m, block=block)
             if not plan.supported:
                 raise NotImplementedError(
@@ -231,8 +234,8 @@ class DeviceNewton:
             _lib.check(lib.pgf_qp_set_vectors(h, _lib.dptr(q), _lib.dptr(b)), h, "pgf_qp_set_vectors")
             self._hd.plan = plan
             self._hd.derivs_key = key
-            self._hd.qp_loaded = True
-        elif stale or not getattr(self._hd, "qp_loaded", False):
+            self._hd.qp_key = key
+        elif stale or not loaded:
             Q = np.ascontiguousarray(problem.hess_dense(), dtype=np.float64)
             A = np.ascontiguousarray(problem.jac_dense(), dtype=np.float64).reshape(self.m, self.n)
             q, b = _lib.as_f64(problem.q), _lib.as_f64(problem.b)
@@ -242,7 +245,7 @@ class DeviceNewton:
                 _lib.PGF_HOST)
             _lib.check(rc, h, "pgf_qp_set_problem")
             self._hd.derivs_key = key
-            self._hd.qp_loaded = True
+            self._hd.qp_key = key
         self.set_outer(x_hat, y_hat, dt, rho, start=start)
 
     def set_outer(self, x_hat, y_hat, dt, rho, start=None):

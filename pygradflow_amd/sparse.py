@@ -28,14 +28,14 @@ BLOCK_SIZES = (8, 16, 32, 64)
 
 def block_size_for(bw, forced=None):
     """Block size of the banded solve for half-bandwidth ``bw``: ``forced`` if given, else
-    8 for bw <= 8 (8 x 8 cyclic reduction), 0 for bw 9 .. 10 (the sequential band walk), the
-    smallest of 16, 32, 64 that is >= bw up to 64, and None beyond (no banded path)."""
+    8 for bw <= 8 (8 x 8 cyclic reduction), the smallest of 16, 32, 64 that is >= bw up to 64
+    (so 16 for bw 9 .. 10), and None beyond (no banded path).  Every one of these carries the
+    accuracy guard.  (With PGF_BAND_SEQ set in the environment the library runs the automatic
+    plans of bw <= 10 through the unguarded sequential band walk instead, whatever this says.)"""
     if forced:
         return int(forced)
     if bw <= 8:
         return 8
-    if bw <= 10:
-        return 0
     for B in BLOCK_SIZES[1:]:
         if bw <= B:
             return B
@@ -103,7 +103,7 @@ class BandPlan:
 
     @property
     def block_size(self):
-        """Block size the solve runs with (block_size_for; 0 = sequential band walk)."""
+        """Block size the solve runs with (block_size_for)."""
         return block_size_for(self.bw, self.block)
 
     def values(self, hess, jac):

@@ -10,54 +10,9 @@ import scipy.sparse as sps
 
 from oracle import newton_oracle as O
 from tests import golden_util as G
+from tests.band_util import TOL, _against_oracle, _as_sparse_lq
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-10
-
-
-def _as_sparse_lq(problem, block=None):
-    from pygradflow_amd import problems
-
-    sp = problems.LinearQuadraticProblem(
-        sps.csr_matrix(problem.hess_dense()), problem.q,
-        sps.csr_matrix(problem.jac_dense().reshape(problem.num_cons, problem.num_vars)),
-        problem.b, problem.var_lb, problem.var_ub)
-    sp.pgf_force_band = True
-    if block:
-        sp.pgf_band_block = block
-    return sp
-
-
-def _against_oracle(pgf, prob, policies, dt=1.0, rho=1.0, step_solver=True, n_neg=None):
-    """DeviceNewton (and, with step_solver, HipStepSolver through newton_steps) against the
-    oracle: masks identical, x and y within TOL; n_neg of every device step if given."""
-    n, m = prob.num_vars, prob.num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    churn = 0
-    for pol, steps in policies:
-        recs = O.NewtonOracle(prob, pol, x0, y0, dt, rho).run(x0, y0, steps)
-        dn = pgf.DeviceNewton(prob, pol, x0, y0, dt, rho)
-        assert dn.sparse
-        for k, rec in enumerate(recs):
-            _, nn = dn.step()
-            x, y = dn.point()
-            assert np.array_equal(dn.mask(), rec["mask"]), (pol, k)
-            assert G.rel_err(x, rec["xn"]) <= TOL, (pol, k)
-            assert G.rel_err(y, rec["yn"]) <= TOL, (pol, k)
-            if n_neg is not None:
-                assert nn == n_neg, (pol, k)
-            churn = max(churn, int(np.count_nonzero(rec["mask"])))
-        dn.close()
-        if step_solver:
-            params = pgf.Params(newton_type=pol, step_solver=pgf.HipStepSolver)
-            gen = pgf.newton_steps(prob, params, pgf.Iterate(prob, params, x0, y0), dt, rho)
-            for k, rec in enumerate(recs):
-                step = next(gen)
-                assert np.array_equal(step.active_set, rec["mask"]), (pol, k)
-                assert G.rel_err(step.iterate.x, rec["xn"]) <= TOL, (pol, k)
-                assert G.rel_err(step.iterate.y, rec["yn"]) <= TOL, (pol, k)
-    return churn
 
 
 # ------------------------------------------------------------------ A: the goldens

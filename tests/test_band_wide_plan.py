@@ -36,7 +36,7 @@ def test_supported_up_to_64():
     assert not _plan(problems.multistate_ocp(50, 24, 8)).supported
 
 
-@pytest.mark.parametrize("bw,B", [(0, 8), (8, 8), (9, 0), (10, 0), (11, 16), (16, 16), (17, 32),
+@pytest.mark.parametrize("bw,B", [(0, 8), (8, 8), (9, 16), (10, 16), (11, 16), (16, 16), (17, 32),
                                   (32, 32), (33, 64), (64, 64), (65, None)])
 def test_block_size_rule(bw, B):
     assert block_size_for(bw) == B

@@ -37,22 +37,87 @@ BAND_VARIANTS = {
     "paired_levels": {},                              # default: two levels per launch where launch-bound
     "one_level_per_launch": {"PGF_BCR_PAIRS": "0"},
     "separate_invert_reduce": {"PGF_BCR_FUSED": "0"},
+    "sequential_walk": {"PGF_BAND_SEQ": "1"},         # the diagnostic route: one wavefront walks the band
 }
+
+
+def _routes(stdout):
+    """{problem: route} from check_band.py's "route <name> bw <bw>: <route>" lines."""
+    return {ln.split()[1]: ln.split()[-1] for ln in stdout.splitlines() if ln.startswith("route ")}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(BAND_VARIANTS))
 def test_banded_schedule_variant_matches_oracle(gpu_available, name):
-    """tests/check_band.py: banded OCP and tridiagonal box QP (churning mask) against the CPU
-    oracle under each cyclic-reduction schedule."""
+    """tests/check_band.py: banded OCP (bw 6), tridiagonal box QP (churning mask) and two problems
+    of half-bandwidth 10 against the CPU oracle under each cyclic-reduction schedule (8 x 8
+    blocks up to bw 8, B = 16 for 9 .. 10) and through the sequential band walk, which then also
+    runs a four-panel problem of half-bandwidth 9 and sizes around its LDS panel."""
     if not gpu_available:
         pytest.skip("needs a GPU")
     env = dict(os.environ)
+    env.pop("PGF_BAND_SEQ", None)
     env.update(BAND_VARIANTS[name])
     out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "check_band.py")], env=env,
                          cwd=REPO, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "band ok" in out.stdout
+    routes = _routes(out.stdout)
+    if name == "sequential_walk":
+        assert len(routes) == 9 and set(routes.values()) == {"walk"}, routes
+    else:
+        assert routes == {"ocp": "bcr8", "box": "bcr8", "grid320": "bcr16", "mocp10": "bcr16"}, routes
+
+
+BAND_SWEEP_VARIANTS = {
+    "one_level_per_launch": {"PGF_BCR_PAIRS": "0"},
+    "separate_invert_reduce": {"PGF_BCR_FUSED": "0"},
+    # pairs only up to 128 blocks in play: 129 and 130 blocks run a single level, THEN a pair
+    # (k_bcr_level2 entered at stride 2, k_bcr_back2 before k_bcr_back).  (Up to 64 would pair
+    # nothing at all: a pair needs more than 32 blocks left after its first level.)
+    "mixed_paired_unpaired": {"PGF_BCR_PAIR_MAX": "128"},
+}
+
+
+def _plans(stdout):
+    """{problem: [levels before the tail]} from check_band.py's "plan <name> nb <nb>: ..." lines."""
+    out = {}
+    for ln in stdout.splitlines():
+        if ln.startswith("plan "):
+            f = ln.split()
+            out[f[1]] = [w for w in f[4:f.index("tail")] if w != "--"]
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(BAND_SWEEP_VARIANTS))
+def test_banded_block_count_sweep_under_schedule_variant(gpu_available, name):
+    """tests/check_band.py --sweep: the block counts of
+    test_band_narrow_gpu.py::test_block_counts_on_every_branch_of_the_launch_plan (1 .. 130 blocks,
+    both sides of 32, 64 and 128) through the 8 x 8 cyclic reduction with the launch plan each
+    switch forces."""
+    if not gpu_available:
+        pytest.skip("needs a GPU")
+    env = dict(os.environ)
+    env.pop("PGF_BAND_SEQ", None)
+    env.update(BAND_SWEEP_VARIANTS[name])
+    out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "check_band.py"), "--sweep"], env=env,
+                         cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "band sweep ok" in out.stdout
+    routes = _routes(out.stdout)
+    assert len(routes) == 28 and set(routes.values()) == {"bcr8"}, routes
+    plans = _plans(out.stdout)
+    assert len(plans) == 28
+    kinds = {w.split("@")[0] for p in plans.values() for w in p}
+    if name == "mixed_paired_unpaired":
+        # 65 .. 128 blocks still pair at once, 129 and 130 pair after a single level
+        assert plans["box1024"] == ["pair@1"] and plans["ocp171"] == ["pair@1"], plans
+        for case in ("box1025", "box1031", "box1033", "ocp342", "ocp343"):
+            assert plans[case] == ["single@1", "pair@2"], plans
+    else:
+        assert kinds == {"single"}, plans
+        assert plans["box1033"] == ["single@1", "single@2", "single@4"], plans
 
 
 @pytest.mark.gpu

@@ -2,7 +2,10 @@
 Simplified back-solve step of DeviceNewton, the dense path on the same problem where it fits
 (H and J handed over as dense arrays), and the CPU oracle's time per step beside each.
 
-    python tools/time_wide_band.py [--steps K] [--quick]
+    python tools/time_wide_band.py [--steps K] [--quick] [--narrow]
+
+--narrow: the bw 9 .. 10 problems instead (automatic block size: B = 16; with PGF_BAND_SEQ=1 in the
+environment the sequential band walk, the route these problems took before).
 """
 import argparse
 import json
@@ -47,8 +50,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--quick", action="store_true", help="skip the oracle and the dense comparison")
+    ap.add_argument("--narrow", action="store_true", help="the bw 9 .. 10 cases (implies --quick)")
     a = ap.parse_args()
     cases = [
+        ("grid_box_qp(9, 320)", problems.grid_box_qp(9, 320), False),
+        ("multistate_ocp(400, 4, 2)", problems.multistate_ocp(400, 4, 2), False),
+        ("grid_box_qp(9, 11000)", problems.grid_box_qp(9, 11000), False),
+        ("grid_box_qp(10, 10000)", problems.grid_box_qp(10, 10000), False),  # bw 11: B = 16 either way
+    ] if a.narrow else [
         ("multistate_ocp(1000, 12, 4)", problems.multistate_ocp(1000, 12, 4), True),
         ("multistate_ocp(5000, 8, 4)", problems.multistate_ocp(5000, 8, 4), False),
         ("multistate_ocp(7500, 8, 4)", problems.multistate_ocp(7500, 8, 4), False),
@@ -59,6 +68,10 @@ def main():
         n, m = prob.num_vars, prob.num_cons
         plan = BandPlan(prob.hess_sparse(), prob.jac_sparse(), n, m)
         row = {"case": name, "N": n + m, "bw": plan.bw, "B": plan.block_size}
+        if a.narrow:
+            a.quick = True
+            walk = os.environ.get("PGF_BAND_SEQ") and plan.bw <= 10
+            row["route"] = "walk" if walk else f"bcr{plan.block_size}"
         t = device_times(prob, a.steps)
         row["wide_full_ms"] = 1e3 * t["Full"]
         row["wide_full_steps_per_s"] = 1.0 / t["Full"]
