@@ -148,6 +148,18 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
  *   B = 8, 16, 32, 64: that block size (PGF_INVALID if B < bw).
  * Invalidates the factorisation; the work arrays are sized for the chosen B. */
 int pgf_sparse_set_block_size(pgf_handle h, int B);
+/* Bordered band, after pgf_sparse_set_pattern (which declares none): the last k positions of
+ * `pos` are border nodes -- dense rows / columns of the KKT pattern, variables or constraints --
+ * and bw, the band slots and the block size describe the remaining n + m - k rows only.  With
+ * kp = k rounded up to a multiple of 16, an entry between band row i and border node j has slot
+ * (n + m - k + 1) * ldb + i * kp + j, one between border nodes a >= b the slot behind those,
+ * + (n + m - k) * kp + a * kp + b (ldb = bw + 1 rounded up to even; pygradflow_amd/sparse.py).
+ * The band is eliminated first: Y = inv(B) C and the L D L' of S = D - C' Y are formed once per
+ * assembled matrix and kept while the factor is valid; a solve is one banded reduction plus the
+ * border kernels (csrc/pgf_border.hip).  k = 0 removes the border.  PGF_INVALID for k > 64 and
+ * for dense handles.  With PGF_BORDER_MULTI=0 in the environment Y is formed by k single
+ * banded solves also at block size 8 (the only route at 16, 32, 64). */
+int pgf_sparse_set_border(pgf_handle h, int k);
 /* values of H = lag_hess(x, y) and J = cons_jac(x) in pattern order (update_derivs) */
 int pgf_sparse_set_values(pgf_handle h, const double *Hval, const double *Jval);
 /* q and b of a linear-quadratic problem whose Q, A were given through the sparse pattern */
@@ -436,6 +448,9 @@ int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
  * their rank-m term from G instead of the virtual column blocks (a factorisation that was
  * discarded and enqueued again counts once).  Either pointer may be NULL. */
 int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram);
+/* the handle's border size and the factor / solve phases of the bordered route enqueued since
+ * pgf_sparse_set_border (tests: a step that keeps its factor runs the solve phase only) */
+int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,7 @@ SIGNATURES = {
     "pgf_sparse_set_pattern": (C.c_int, [_h, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int, _ip, _ip, _ip,
                                          _ip, _ip, _ip]),
     "pgf_sparse_set_block_size": (C.c_int, [_h, C.c_int]),
+    "pgf_sparse_set_border": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_values": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_vectors": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_problem": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
@@ -107,6 +108,7 @@ SIGNATURES = {
     "pgf_debug_factor_kind": (C.c_int, [_h]),
     "pgf_debug_step_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_gram_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_debug_border_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pgf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

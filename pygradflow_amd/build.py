@@ -18,6 +18,7 @@ SOURCES = [
     ("pgf_kernels.hip", ["-ffp-contract=off"]),
     ("pgf_sparse.hip", ["-ffp-contract=off"]),
     ("pgf_band_wide.hip", []),
+    ("pgf_border.hip", ["-ffp-contract=off"]),
     ("pgf_ldlt.hip", ["-DPGF_RECIP_ONE_STEP"] if os.environ.get("PGF_BUILD_RECIP1") else []),
     ("pgf_factor2.hip", []),
     ("pgf_lu.hip", []),

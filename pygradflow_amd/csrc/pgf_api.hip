@@ -293,7 +293,7 @@ int pgf_destroy(pgf_handle h) {
     void *sps[] = {sp.pos, sp.Hptr, sp.Hrow, sp.Hcol, sp.Hslot, sp.Jptr, sp.Jcol, sp.Jslot, sp.JTptr,
                    sp.JTrow, sp.JTmap, sp.Hval, sp.Jval, sp.band, sp.brhs, sp.Hb0, sp.Jb0,
                    sp.bD, sp.bL, sp.bU, sp.bDinv, sp.bF, sp.bneg, sp.brhs0, sp.bres, sp.bsol,
-                   sp.bred};
+                   sp.bred, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags};
     for (void *q : sps)
       if (q) (void)hipFree(q);
   }
@@ -784,19 +784,40 @@ static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
 // bw <= 10 only; unguarded, a diagnostic route): at B = 8, and at B = 0, which is what the automatic
 // choice then gives bw 9 .. 10 (auto_block_size)
 static bool sp_cyclic(const SparseDev &sp) {
-  return sp.B > 8 || (sp.B == 8 && !getenv("PGF_BAND_SEQ"));
+  return sp.bk > 0 || sp.B > 8 || (sp.B == 8 && !getenv("PGF_BAND_SEQ"));
 }
 static void sp_cyclic_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
-  if (sp.B > 8)
+  if (sp.bk)  // bordered band: the solve phase against the kept Y and factor of S (pgf_border.hip)
+    sp_border_solve(s, sp, flags, guard);
+  else if (sp.B > 8)
     sp_launch_bw_solve(s, sp, N, flags, guard);
   else
     sp_launch_bcr_solve(s, sp, N, flags, guard);
 }
 static void sp_cyclic_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
-  if (sp.B > 8)
+  if (sp.bk)
+    sp_border_residual(s, sp, flags);
+  else if (sp.B > 8)
     sp_launch_bw_residual(s, sp, N, flags);
   else
     sp_launch_band_residual(s, sp, N, flags);
+}
+
+// assemble the banded matrix for the current mask; with a border also its factor phase (Y = inv(B) C
+// and the factor of the Schur complement S, kept until the matrix is assembled again)
+static void sp_assemble(pgf_handle h) {
+  if (h->sp.bk) {
+    sp_border_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
+    PgfProfile *p = h->prof.enabled ? &h->prof : nullptr;  // the factor phase as factor_ms
+    if (p) {
+      p->factor_spans.emplace_back(prof_event(p), prof_event(p));
+      (void)hipEventRecord(p->factor_spans.back().first, h->stream);
+    }
+    sp_border_factor(h->stream, h->sp, h->fac.flags);
+    if (p) (void)hipEventRecord(p->factor_spans.back().second, h->stream);
+    return;
+  }
+  sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
 }
 
 // enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in row N
@@ -804,7 +825,7 @@ static int factor_async(pgf_handle h, bool with_rhs) {
   if (h->sparse) {
     // band assembly + banded LDL^T; the permuted rhs in sp.brhs is forward-substituted on
     // the way (harmless when the caller only wants the factor)
-    sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
+    sp_assemble(h);
     if (sp_cyclic(h->sp)) {
       // cyclic-reduction mode keeps the assembled band intact; run one reduction (on
       // whatever right-hand side is there) only to obtain the pivot flags / inertia
@@ -1428,7 +1449,7 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
       // block cyclic reduction: assemble (only when the mask / derivatives changed) and
       // solve in log2(N/B) parallel levels; the band itself is left untouched, so a
       // back-solve step just runs the reduction again on the same band (~1 ms)
-      if (!h->fac.factored) sp_launch_assemble(s, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
+      if (!h->fac.factored) sp_assemble(h);
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (h->prof.enabled) {
         for (hipEvent_t *e : {&e0, &e1}) {
@@ -1627,7 +1648,7 @@ int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
     sp_launch_permute(h->stream, h->sp, Nf, h->rhs, h->sp.brhs, 0);
     if (sp_cyclic(h->sp)) {
       // cyclic reduction keeps the assembled band intact: (re)assemble only when stale
-      if (!h->fac.factored) sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
+      if (!h->fac.factored) sp_assemble(h);
       sp_cyclic_solve(h->stream, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
       h->sp_guarded = h->refine_mode != 0;
       if (h->sp_guarded)
@@ -1782,6 +1803,21 @@ static int sp_alloc_blocks(pgf_handle h, int B) {
   return PGF_OK;
 }
 
+static void sp_border_free(SparseDev &sp) {
+  for (double **q : {&sp.bY, &sp.bS, &sp.bpart, &sp.bpartv, &sp.brb, &sp.bz})
+    if (*q) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+  if (sp.bsflags) {
+    (void)hipFree(sp.bsflags);
+    sp.bsflags = nullptr;
+  }
+  sp.bk = sp.bkp = sp.Nb = sp.bnchunk = 0;
+  sp.bC = sp.bDd = nullptr;
+  sp.stat_bfactor = sp.stat_bsolve = 0;
+}
+
 int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const int *Hptr,
                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
@@ -1836,11 +1872,79 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
   HIPCHK(h, dalloc(&sp.Hb0, (size_t)n + 1));
   HIPCHK(h, dalloc(&sp.Jb0, (size_t)m + 1));
   sp.B = 0;
+  sp_border_free(sp);  // (a border is declared after the pattern: pgf_sparse_set_border)
   if ((rc = sp_alloc_blocks(h, auto_block_size(bw)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   sp.active = true;
   sp.values_set = false;
   invalidate_factor(h);
+  return PGF_OK;
+}
+
+int pgf_sparse_set_border(pgf_handle h, int k) {
+  if (!h) return PGF_INVALID;
+  if (!h->sparse) return fail(h, PGF_INVALID, "pgf_sparse_set_border: banded handles only");
+  if (k < 0 || k > 64) return fail(h, PGF_INVALID, "border size must be 0..64");
+  if (!h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
+  const int N = h->n + h->m;
+  if (k > 0 && k >= N) return fail(h, PGF_INVALID, "the border must leave at least one band row");
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  SparseDev &sp = h->sp;
+  const bool had = sp.bk > 0;
+  sp_border_free(sp);
+  invalidate_factor(h);
+  if (k == 0 && !had) return PGF_OK;
+  const int Nb = N - k, kp = (k + 15) / 16 * 16;
+  const size_t band_doubles = (size_t)(Nb + 1) * sp.ldb;
+  // band, C and D in one array: the plan's slots index it as a whole
+  (void)hipFree(sp.band);
+  sp.band = nullptr;
+  if (k == 0) {
+    HIPCHK(h, dalloc(&sp.band, (size_t)(N + 1) * sp.ldb));
+    return PGF_OK;
+  }
+  if (band_doubles + (size_t)Nb * kp + (size_t)kp * kp > (size_t)INT32_MAX)
+    return fail(h, PGF_INVALID, "band and border store exceed 2^31 entries");
+  HIPCHK(h, dalloc(&sp.band, band_doubles + (size_t)Nb * kp + (size_t)kp * kp));
+  sp.bk = k;
+  sp.bkp = kp;
+  sp.Nb = Nb;
+  sp.bC = sp.band + band_doubles;
+  sp.bDd = sp.bC + (size_t)Nb * kp;
+  sp.bnchunk = (Nb + SP_BORDER_CHUNK - 1) / SP_BORDER_CHUNK;
+  HIPCHK(h, dalloc(&sp.bY, ((size_t)Nb + 64) * kp));
+  HIPCHK(h, dalloc(&sp.bS, (size_t)kp * kp));
+  HIPCHK(h, dalloc(&sp.bpart, (size_t)sp.bnchunk * kp * kp));
+  HIPCHK(h, dalloc(&sp.bpartv, (size_t)sp.bnchunk * 3 * kp));
+  HIPCHK(h, dalloc(&sp.brb, (size_t)kp));
+  HIPCHK(h, dalloc(&sp.bz, (size_t)kp));
+  HIPCHK(h, hipMalloc((void **)&sp.bsflags, 4 * sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(sp.brb, 0, (size_t)kp * sizeof(double), h->stream));  // padding stays zero
+  // the residual pairs: one per 256 band rows and one for the border rows
+  const int nred = std::max((N + 255) / 256, (Nb + 255) / 256 + 1);
+  (void)hipFree(sp.bred);
+  sp.bred = nullptr;
+  (void)hipHostFree(h->h_bred);
+  h->h_bred = nullptr;
+  sp.nred = nred;
+  HIPCHK(h, dalloc(&sp.bred, (size_t)3 * nred + 4));
+  HIPCHK(h, hipMemsetAsync(sp.bred, 0, ((size_t)3 * nred + 4) * sizeof(double), h->stream));
+  HIPCHK(h, hipHostMalloc((void **)&h->h_bred, ((size_t)3 * nred + 4) * sizeof(double)));
+  // a border always runs on a cyclic reduction (never the sequential walk)
+  if (sp.B == 0) {
+    int rc;
+    if ((rc = sp_alloc_blocks(h, sp.bw <= 8 ? 8 : 16))) return rc;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PGF_OK;
+}
+
+int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves) {
+  if (!h) return PGF_INVALID;
+  if (k) *k = h->sp.bk;
+  if (border_factorisations) *border_factorisations = h->sp.stat_bfactor;
+  if (border_solves) *border_solves = h->sp.stat_bsolve;
   return PGF_OK;
 }
 

@@ -33,7 +33,21 @@ struct SparseDev {
   // that does two cyclic-reduction levels at once reads one set and writes the other
   int64_t bstride = 0;
   bool values_set = false;
+  // Bordered band (pgf_border.hip): the last bk positions of `pos` are border nodes, the band
+  // holds the Nb = n + m - bk others.  K = [[B, C], [C', D]]: C (Nb x bkp, row-major) and the lower
+  // triangle of D (bkp x bkp; bkp = bk rounded up to 16, padding = identity) lie behind the band
+  // array, where the plan's slots point.  bk == 0: no border.
+  int bk = 0, bkp = 0, Nb = 0;
+  double *bC = nullptr, *bDd = nullptr;      // into `band`
+  double *bY = nullptr;                      // Y = inv(B) C, whole 8-row blocks x bkp
+  double *bS = nullptr;                      // L D L' of S = D - C' Y: L below, 1 / d on the diagonal
+  double *bpart = nullptr, *bpartv = nullptr;  // per-chunk sums of C' Y and of (C' v, |C|' |v|, tail of C' v)
+  double *brb = nullptr, *bz = nullptr;      // border part of the right-hand side / of the solution
+  int *bsflags = nullptr;                    // [0] bad pivot in S, [1] negative pivots of S
+  int bnchunk = 0;                           // chunks of SP_BORDER_CHUNK rows
+  mutable int stat_bfactor = 0, stat_bsolve = 0;  // factor / solve phases enqueued (pgf_debug_border_stats)
 };
+#define SP_BORDER_CHUNK 512
 
 void sp_launch_spmv(hipStream_t s, int rows, const int *ptr, const int *col, const double *val,
                     const double *x, const double *add, double sgn, double *y);
@@ -44,6 +58,7 @@ void sp_launch_eval(hipStream_t s, const SparseDev &sp, int n, int m, const doub
                     const double *b, const double *q, double rho, double *c, double *w, double *g);
 void sp_launch_assemble(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
                         double lamb, double delta);
+void sp_launch_scatter(hipStream_t s, const SparseDev &sp, const uint8_t *mask);
 void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
                    const double *F, const double *b0full, double fact, double *Hb0, double *Jb0);
 // out[pos[i]] = in[i] (gather == 0) or out[i] = in[pos[i]] (gather != 0)
@@ -63,3 +78,15 @@ void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, dou
                            double rho, const double *x, const double *y, const double *lb,
                            const double *ub, const double *F, double *dx, double *dy, double *xn,
                            double *yn, double *red);
+
+// ---- bordered band (pgf_border.hip) ----
+// assemble band, C and D for the mask
+void sp_border_assemble(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
+                        double lamb, double delta);
+// factor phase on the assembled matrix: Y = inv(B) C, S = D - C' Y, L D L' of S.  sp.brhs survives.
+void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags);
+// solve phase for the right-hand side in sp.brhs (Nb band entries, then bk border entries); the
+// solution replaces it.  flags[0] zero pivot, flags[1] negative pivots of B plus those of S.
+// guard: keep the right-hand side and finish with the residual over all Nb + bk rows.
+void sp_border_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard);
+void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags);

@@ -15,10 +15,40 @@
 //
 // Compiled with -ffp-contract=off like pgf_kernels.hip (explicit fma() only).
 #include "pgf_sparse.h"
+#include "pgf_bcr_dev.h"
 
 #define ACTIVE_EPS 1e-8
 
 // ---------------------------------------------------------------- CSR products
+// One row (or column) per lane: acc = step(k, acc) over the entries [k0, k1) of the lane's row.  Rows
+// are short -- except the dense rows and columns of a bordered band (a budget constraint over all
+// variables, a global parameter's column of J): one lane walking n dependent entries took 4 ms at
+// n = 16 384.  A row of more than SP_LONG_ROW entries is therefore summed by the whole wavefront, 64
+// entries at a time, and reduced in a fixed order; shorter rows are summed by their lane in entry
+// order, as ever.  EVERY lane of the wavefront must call this (lanes without a row: k0 == k1).
+#define SP_LONG_ROW 256
+template <class Step>
+__device__ __forceinline__ double sp_row_dot(int k0, int k1, Step step) {
+  const int lane = threadIdx.x & 63;
+  const bool longrow = k1 - k0 > SP_LONG_ROW;
+  double acc = 0.0;
+  if (!longrow)
+    for (int k = k0; k < k1; ++k) acc = step(k, acc);
+  unsigned long long pending = __ballot(longrow);
+  while (pending) {
+    const int src = __ffsll((long long)pending) - 1;
+    pending &= pending - 1;
+    const int a0 = __shfl(k0, src), a1 = __shfl(k1, src);
+    double part = 0.0;
+    for (int k = a0 + lane; k < a1; k += 64) part = step(k, part);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off);
+    part = __shfl(part, 0);
+    if (lane == src) acc = part;
+  }
+  return acc;
+}
+
 // y[r] = sum_k val[k] * x[col[k]]  (+ sgn * add[r]);  rows are short: one lane per row
 __global__ void k_csr_spmv(int rows, const int *__restrict__ ptr, const int *__restrict__ col,
                            const double *__restrict__ val, const double *__restrict__ x,
@@ -54,9 +84,10 @@ __global__ void k_sp_eval_c(int m, const int *__restrict__ ptr, const int *__res
                             const double *__restrict__ b, double rho, const double *__restrict__ y,
                             double *__restrict__ c, double *__restrict__ w) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= m) return;
-  double acc = 0.0;
-  for (int k = ptr[r]; k < ptr[r + 1]; ++k) acc = fma(val[k], x[col[k]], acc);
+  const bool in = r < m;
+  const double acc = sp_row_dot(in ? ptr[r] : 0, in ? ptr[r + 1] : 0,
+                                [&](int k, double a) { return fma(val[k], x[col[k]], a); });
+  if (!in) return;
   const double cr = acc + -1.0 * b[r];
   c[r] = cr;
   w[r] = rho * cr + y[r];
@@ -69,12 +100,13 @@ __global__ void k_sp_eval_g(int n, const int *__restrict__ hptr, const int *__re
                             const double *__restrict__ w, const double *__restrict__ q,
                             double *__restrict__ g) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  double at = 0.0;
-  for (int k = tptr[j]; k < tptr[j + 1]; ++k) at = fma(jval[tmap[k]], w[trow[k]], at);
+  const bool in = j < n;
+  const double at = sp_row_dot(in ? tptr[j] : 0, in ? tptr[j + 1] : 0,
+                               [&](int k, double a) { return fma(jval[tmap[k]], w[trow[k]], a); });
+  const double acc = sp_row_dot(in ? hptr[j] : 0, in ? hptr[j + 1] : 0,
+                                [&](int k, double a) { return fma(hval[k], x[hcol[k]], a); });
+  if (!in) return;
   const double base = q[j] + at;  // = tmpn[j] of the separate kernels
-  double acc = 0.0;
-  for (int k = hptr[j]; k < hptr[j + 1]; ++k) acc = fma(hval[k], x[hcol[k]], acc);
   g[j] = acc + 1.0 * base;
 }
 
@@ -87,18 +119,19 @@ __global__ void k_band_rhs_fused(int n, int m, const uint8_t *__restrict__ mask,
                                  const int *__restrict__ jcol, const double *__restrict__ jval,
                                  double fact, const int *__restrict__ pos, double *__restrict__ brhs) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  // (both products by every lane of the wavefront, sp_row_dot: a lane of the other kind has no entries)
+  const bool isvar = i < n, iscon = i >= n && i < n + m;
+  const int r = i - n;
+  const double hacc = sp_row_dot(isvar ? hptr[i] : 0, isvar ? hptr[i + 1] : 0,
+                                 [&](int k, double a) { return fma(hval[k], b0full[hcol[k]], a); });
+  const double jacc = sp_row_dot(iscon ? jptr[r] : 0, iscon ? jptr[r + 1] : 0,
+                                 [&](int k, double a) { return fma(jval[k], b0full[jcol[k]], a); });
   if (i >= n + m) return;
   double v;
-  if (i < n) {
-    double acc = 0.0;
-    for (int k = hptr[i]; k < hptr[i + 1]; ++k) acc = fma(hval[k], b0full[hcol[k]], acc);
-    v = mask[i] ? b0full[i] : F[i] - acc;
-  } else {
-    const int r = i - n;
-    double acc = 0.0;
-    for (int k = jptr[r]; k < jptr[r + 1]; ++k) acc = fma(jval[k], b0full[jcol[k]], acc);
-    v = fact * F[i] - acc;
-  }
+  if (isvar)
+    v = mask[i] ? b0full[i] : F[i] - hacc;
+  else
+    v = fact * F[i] - jacc;
   brhs[pos[i]] = v;
 }
 
@@ -156,14 +189,6 @@ __global__ void k_band_rhs(int n, int m, const uint8_t *__restrict__ mask,
 }
 
 // ---------------------------------------------------------------- banded LDL^T + forward solve
-__device__ __forceinline__ double recip2(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  double e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-d, r, 1.0);
-  return fma(r, e, r);
-}
-
 #define BAND_LDS_DOUBLES 15360  // 120 KB panel of band rows + right-hand side
 
 // One wavefront walks the band.  Panels of P rows are staged in LDS (coalesced loads),
@@ -388,6 +413,11 @@ void sp_launch_assemble(hipStream_t s, const SparseDev &sp, int n, int m, const 
   (void)hipMemsetAsync(sp.band, 0, (size_t)(N + 1) * sp.ldb * sizeof(double), s);
   hipLaunchKernelGGL(k_band_set_diag, g1(N), dim3(256), 0, s, n, m, sp.pos, mask, lamb, delta,
                      sp.band, sp.ldb);
+  sp_launch_scatter(s, sp, mask);
+}
+
+// the stored entries of H and J into their slots (band, or the border store behind it)
+void sp_launch_scatter(hipStream_t s, const SparseDev &sp, const uint8_t *mask) {
   if (sp.nnzH)
     hipLaunchKernelGGL(k_band_scatter_H, g1(sp.nnzH), dim3(256), 0, s, sp.nnzH, sp.Hrow, sp.Hcol,
                        sp.Hval, sp.Hslot, mask, sp.band);
@@ -490,37 +520,6 @@ __global__ __launch_bounds__(64) void k_bcr_extract(const double *__restrict__ b
   if (lane < 8) F[(int64_t)i * 8 + lane] = (i * 8 + lane < N) ? rhs[i * 8 + lane] : 0.0;
 }
 
-// in-place Gauss-Jordan inverse of the 8 x 8 block in LDS (one wavefront, lane = (r, c));
-// returns the number of negative pivots, sets *bad on a zero / non-finite pivot
-__device__ __forceinline__ int gj_inverse8(double *M, int lane, int *bad) {
-  const int r = lane >> 3, c = lane & 7;
-  int neg = 0;
-  double mrc = M[lane];  // own entry: stays in a register between the steps
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const double p = M[k * 8 + k];
-    const bool isbad = (p == 0.0) || !(fabs(p) <= 1.79e308);
-    *bad |= isbad ? 1 : 0;
-    neg += (p < 0.0) ? 1 : 0;
-    // v_rcp_f64 + two Newton steps (full precision) instead of the ~30-instruction IEEE
-    // division: eight of them sat on every block operation's dependent chain
-    const double d = isbad ? 0.0 : recip2(p);
-    const double mrk = M[r * 8 + k], mkc = M[k * 8 + c];
-    double v;
-    if (r == k && c == k)
-      v = d;
-    else if (r == k)
-      v = mkc * d;
-    else if (c == k)
-      v = -mrk * d;
-    else
-      v = fma(-mrk * d, mkc, mrc);
-    M[lane] = v;  // all lanes have read before any lane writes (one wavefront, lockstep)
-    mrc = v;
-  }
-  return neg;
-}
-
 // ---- per-block work of one wavefront (lane = threadIdx.x & 63); `sm` is the wavefront's own
 // LDS scratch of BCR_SCRATCH doubles.  Used by the one-block-per-workgroup kernels of the
 // large levels and by the fused tail kernel below.
@@ -542,14 +541,6 @@ __device__ __forceinline__ void bcr_invert_block(const double *__restrict__ D,
     if (bad) atomicOr(&flags[0], 1);
     negcnt[gi] = neg;
   }
-}
-
-// 8 x 8 product helper: out[r][c] = sum_k A[r][k] B[k][c], operands in LDS
-__device__ __forceinline__ double mm8(const double *A, const double *B, int r, int c) {
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) acc = fma(A[r * 8 + k], B[k * 8 + c], acc);
-  return acc;
 }
 
 // kept block i of the level with stride s (neighbours i - s, i + s are eliminated)

@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .params import enum_name
-from .sparse import MAX_BANDWIDTH, BandPlan
+from .sparse import MAX_BANDWIDTH, BandPlan, border_key
 from .step_solver import DENSE_LIMIT, POOL, HipStepSolver, residency_key, same_key
 
 
@@ -194,8 +194,10 @@ class DeviceNewton:
         self.n, self.m = problem.num_vars, problem.num_cons
         self.dt, self.rho = float(dt), float(rho)
         self.tau = math.nan if tau is None else float(tau)
+        border = getattr(problem, "pgf_border", None)  # a bordered band (sparse.BandPlan)
         self.sparse = (not problem.is_dense) and (
-            bool(getattr(problem, "pgf_force_band", False)) or self.n + self.m > DENSE_LIMIT)
+            bool(getattr(problem, "pgf_force_band", False)) or border is not None
+            or self.n + self.m > DENSE_LIMIT)
         self.step_solver_type = (step_solver_type if isinstance(step_solver_type, str)
                                  else enum_name(step_solver_type))
         if self.step_solver_type not in _lib.FORMULATIONS:
@@ -216,15 +218,19 @@ class DeviceNewton:
         key = residency_key(problem)
         stale = not same_key(key, self._hd.derivs_key)
         block = getattr(problem, "pgf_band_block", None)
-        replan = self._hd.plan is not None and self._hd.plan.block != (int(block) if block else None)
+        replan = self._hd.plan is not None and (
+            self._hd.plan.block != (int(block) if block else None)
+            or self._hd.plan.border_spec != border_key(border))
         # q and b are resident for the problem THIS class uploaded last: a HipStepSolver that had the
         # pooled handle in between makes derivs_key current for its problem without sending q, b
         loaded = same_key(key, getattr(self._hd, "qp_key", None))
         if self.sparse and (stale or replan or not loaded):
-            plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m, block=block)
+            plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m, block=block,
+                            border=border)
             if not plan.supported:
+                tried = "" if border is None else f" with a border of {plan.k} nodes"
                 raise NotImplementedError(
-                    f"banded path: half-bandwidth {plan.bw} > {MAX_BANDWIDTH}; use HipStepSolver "
+                    f"banded path: half-bandwidth {plan.bw} > {MAX_BANDWIDTH}{tried}; use HipStepSolver "
                     "(plugin path), which falls back to the dense factorisation")
             plan.upload(lib, h)
             hv, jv = plan.values(problem.hess_sparse(), problem.jac_sparse())
@@ -350,6 +356,14 @@ class DeviceNewton:
         a, b = C.c_int(0), C.c_int(0)
         _lib.check(self._lib.pgf_debug_gram_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
         return a.value, b.value
+
+    def border_stats(self):
+        """(border size, factor phases, solve phases) of the bordered band on this handle
+        (``pgf_debug_border_stats``; zeros without a border)."""
+        k, a, b = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_border_stats(self._hd.h, C.byref(k), C.byref(a), C.byref(b)),
+                   self._hd.h)
+        return k.value, a.value, b.value
 
     def factor_kind(self):
         """0 none, 1 LDL^T in the natural order, 2 LDL^T of the condensed system, 3 pivoted LU

@@ -307,6 +307,39 @@ def multistate_ocp(T, nx, nu, seed=0, ubound=0.3) -> LinearQuadraticProblem:
     return LinearQuadraticProblem(H.tocsr(), q, J, b, lb, ub)
 
 
+def budget_box_qp(n=16_384, seed=0, bw=1, bound=0.5) -> LinearQuadraticProblem:
+    """A banded H (diagonal uniform in [1, 2], the ``bw`` off-diagonals 0.2 / bw: diagonally
+    dominant), box |x_j| <= bound, and ONE dense constraint row a'x = 0 with a uniform in
+    [0.5, 1.5] (a budget): the constraint is a KKT node of degree n, which no band holds -- the
+    bordered band's simplest case (``pgf_border``)."""
+    rng = np.random.default_rng(seed)
+    d = rng.uniform(1.0, 2.0, n)
+    offs = [np.full(n - k, 0.2 / bw) for k in range(1, bw + 1)]
+    H = sps.diags([d] + offs + offs, [0] + list(range(1, bw + 1)) + list(range(-1, -bw - 1, -1)),
+                  shape=(n, n), format="csr")
+    a = rng.uniform(0.5, 1.5, n)
+    q = rng.standard_normal(n)
+    A = sps.csr_matrix(a.reshape(1, n))
+    return LinearQuadraticProblem(H, q, A, np.zeros(1), np.full(n, -bound), np.full(n, bound))
+
+
+def ocp_global_parameter(T, nx, nu, npar, seed=0, ubound=0.3, pbound=np.inf) -> LinearQuadraticProblem:
+    """``multistate_ocp(T, nx, nu, seed)`` with ``npar`` global parameters p appended to the
+    variables, x = [s, u, p]: c_t = s_t - A s_{t-1} - B u_t - E_t p with E_t dense, objective term
+    1/2 |p|^2 + q_p'p, |p| <= pbound.  Every parameter enters every dynamics row: ``npar`` KKT nodes
+    of degree T nx on top of the band of the OCP."""
+    base = multistate_ocp(T, nx, nu, seed=seed, ubound=ubound)
+    rng = np.random.default_rng([seed, 1])
+    n0, m = base.num_vars, base.num_cons
+    E = 0.2 * rng.standard_normal((m, npar))
+    H = sps.block_diag([base.hess_sparse(), sps.identity(npar)], format="csr")
+    J = sps.hstack([base.jac_sparse(), sps.csr_matrix(-E)], format="csr")
+    q = np.concatenate([base.q, rng.standard_normal(npar)])
+    lb = np.concatenate([base.var_lb, np.full(npar, -pbound)])
+    ub = np.concatenate([base.var_ub, np.full(npar, pbound)])
+    return LinearQuadraticProblem(H, q, J, base.b.copy(), lb, ub)
+
+
 def grid_box_qp(W, L, seed=0, bound=0.5) -> LinearQuadraticProblem:
     """Shifted 5-point Laplacian on a W x L grid (H = 4.5 I - adjacency, SPD), m = 0,
     q ~ N(0, 1), box |x| <= bound; bandwidth about W after RCM."""

@@ -23,6 +23,7 @@ from scipy.sparse.csgraph import reverse_cuthill_mckee
 from . import _lib
 
 MAX_BANDWIDTH = 64  # widest block of the cyclic reduction (csrc/pgf_band_wide.hip)
+MAX_BORDER = 64     # most border nodes of a bordered band (csrc/pgf_border.hip: S in 32 KB of LDS)
 BLOCK_SIZES = (8, 16, 32, 64)
 
 
@@ -42,8 +43,56 @@ def block_size_for(bw, forced=None):
     return None
 
 
+def _bandwidth(pat, pos):
+    coo = pat.tocoo()
+    return int(np.max(np.abs(pos[coo.row] - pos[coo.col]))) if coo.nnz else 0
+
+
+def _rcm_positions(pat):
+    """pos[old] = new under reverse Cuthill-McKee of the symmetric pattern."""
+    perm = reverse_cuthill_mckee(sps.csr_matrix(pat), symmetric_mode=True)  # perm[new] = old
+    pos = np.empty(pat.shape[0], dtype=np.int64)
+    pos[perm] = np.arange(pat.shape[0])
+    return pos
+
+
+def select_border(pat):
+    """The automatic border of a symmetric KKT pattern (diagonal present): every node whose degree
+    exceeds 2 * MAX_BANDWIDTH -- it fits no band of that half-width -- and then, while reverse
+    Cuthill-McKee of the remainder still gives a wider band, the remainder's node of highest
+    degree (the highest index among equals: where thousands of nodes tie, as in a uniform band,
+    the choice is arbitrary, and what RCM makes of the remainder can depend on it).  Returns (sorted border nodes, fits): fits is False
+    when MAX_BORDER nodes do not bring the remainder's bandwidth down to MAX_BANDWIDTH."""
+    N = pat.shape[0]
+    pat = sps.csr_matrix(pat)
+    deg = np.diff(pat.indptr) - 1
+    border = [int(i) for i in np.nonzero(deg > 2 * MAX_BANDWIDTH)[0]]
+    if len(border) > MAX_BORDER:
+        return sorted(border[:MAX_BORDER]), False
+    while True:
+        keep = np.ones(N, dtype=bool)
+        keep[border] = False
+        rem = np.nonzero(keep)[0]
+        sub = pat[rem, :][:, rem]
+        if rem.size == 0 or _bandwidth(sub, _rcm_positions(sub)) <= MAX_BANDWIDTH:
+            return sorted(border), True
+        if len(border) >= MAX_BORDER or rem.size <= 1:
+            return sorted(border), False
+        deg = np.diff(sub.indptr)
+        border.append(int(rem[np.nonzero(deg == deg.max())[0][-1]]))
+
+
 class BandPlan:
-    def __init__(self, hess, jac, n, m, block=None):
+    """``border``: None (a plain band, as ever), ``"auto"`` (select_border) or a sequence of KKT
+    node indices (``i < n``: variable ``i``; ``n + r``: constraint ``r``) that are kept out of the
+    band: K = [[B, C], [C', D]] with the band B of the ``Nb`` other nodes (reverse Cuthill-McKee
+    runs on those only) and the border nodes, in ascending order -- variables before constraints
+    -- at positions ``Nb .. Nb + k - 1``.  The entries that touch a border node get slots in a
+    border store directly behind the band array, which the scatter kernels write like any other
+    slot: C as ``Nb x kp`` row-major at ``base_C = (Nb + 1) ldb``, then the lower triangle of D as
+    ``kp x kp`` at ``base_D = base_C + Nb kp``; ``kp`` is ``k`` rounded up to a multiple of 16."""
+
+    def __init__(self, hess, jac, n, m, block=None, border=None):
         if block and int(block) not in BLOCK_SIZES:
             raise ValueError(f"band block size {block}: must be one of {BLOCK_SIZES}")
         self.block = int(block) if block else None  # forced block size (problem.pgf_band_block)
@@ -61,13 +110,58 @@ class BandPlan:
         Hp = sps.csr_matrix((np.ones(H.nnz), H.indices, H.indptr), shape=(n, n))
         Jp = sps.csr_matrix((np.ones(J.nnz), J.indices, J.indptr), shape=(m, n))
         pat = sps.bmat([[Hp + Hp.T + sps.identity(n), Jp.T], [Jp, sps.identity(m)]], format="csr")
-        perm = reverse_cuthill_mckee(pat, symmetric_mode=True)  # perm[new] = old
-        pos = np.empty(N, dtype=np.int64)
-        pos[perm] = np.arange(N)
-        coo = pat.tocoo()
-        self.bw = int(np.max(np.abs(pos[coo.row] - pos[coo.col]))) if coo.nnz else 0
+        self.border_spec = border_key(border)
+        self._border_fits = True
+        if border is None:
+            nodes = np.zeros(0, dtype=np.int64)
+        elif isinstance(border, str):
+            if border != "auto":
+                raise ValueError(f"pgf_border: {border!r} (\"auto\" or a sequence of KKT node indices)")
+            found, self._border_fits = select_border(pat)
+            nodes = np.asarray(found, dtype=np.int64)
+        else:
+            nodes = np.unique(np.asarray(list(border), dtype=np.int64))
+            if nodes.size != len(list(border)) or nodes.size == 0 or nodes[0] < 0 or nodes[-1] >= N:
+                raise ValueError("pgf_border: distinct KKT node indices in [0, n + m) expected")
+            if nodes.size > MAX_BORDER:
+                raise ValueError(f"pgf_border: {nodes.size} nodes, at most {MAX_BORDER}")
+            if nodes.size >= N:
+                raise ValueError("pgf_border: the border must leave a band")
+        self.border = nodes.astype(np.int32)
+        self.k = k = int(nodes.size)
+        self.kp = kp = (k + 15) // 16 * 16
+        self.Nb = Nb = N - k
+        if k == 0:
+            pos = _rcm_positions(pat)
+            self.bw = _bandwidth(pat, pos)
+        else:
+            keep = np.ones(N, dtype=bool)
+            keep[nodes] = False
+            rem = np.nonzero(keep)[0]
+            sub = pat[rem, :][:, rem]
+            sub_pos = _rcm_positions(sub)
+            pos = np.empty(N, dtype=np.int64)
+            pos[rem] = sub_pos
+            pos[nodes] = Nb + np.arange(k)
+            self.bw = _bandwidth(sub, sub_pos)
         self.ldb = (self.bw + 1 + 1) // 2 * 2
         self.pos = pos.astype(np.int32)
+        self.base_C = (Nb + 1) * self.ldb
+        self.base_D = self.base_C + Nb * kp
+        self.store_size = self.base_D + kp * kp if k else (N + 1) * self.ldb
+        if k and self.store_size >= 2 ** 31:
+            raise ValueError("bordered band: band and border store exceed 2^31 entries")
+
+        def slot(pa, pb):
+            """Slot of the entry between positions pa, pb: band, C or the lower triangle of D."""
+            a, lo = np.maximum(pa, pb), np.minimum(pa, pb)
+            band = a * self.ldb + (a - lo)
+            if k == 0:
+                return band
+            in_c = self.base_C + lo * kp + (a - Nb)
+            in_d = self.base_D + (a - Nb) * kp + (lo - Nb)
+            return np.where(a < Nb, band, np.where(lo < Nb, in_c, in_d))
+
         # H entries: lower part in permuted order gets a slot, the mirror is skipped.  An
         # unsymmetric *pattern* (entry (i, j) stored without (j, i)) keeps its only copy.
         hrow = np.repeat(np.arange(n), np.diff(H.indptr))
@@ -76,8 +170,7 @@ class BandPlan:
         lower = pi >= pj
         mirror_present = np.asarray(Hp[hcol, hrow]).ravel() > 0
         use = lower | ~mirror_present
-        a, b = np.maximum(pi, pj), np.abs(pi - pj)
-        self.Hslot = np.where(use, a * self.ldb + b, -1).astype(np.int32)
+        self.Hslot = np.where(use, slot(pi, pj), -1).astype(np.int32)
         self.Hptr = H.indptr.astype(np.int32)
         self.Hrow = hrow.astype(np.int32)
         self.Hcol = hcol.astype(np.int32)
@@ -85,7 +178,7 @@ class BandPlan:
         jrow = np.repeat(np.arange(m), np.diff(J.indptr))
         jcol = J.indices
         pa, pb = pos[n + jrow], pos[jcol]
-        self.Jslot = (np.maximum(pa, pb) * self.ldb + np.abs(pa - pb)).astype(np.int32)
+        self.Jslot = slot(pa, pb).astype(np.int32)
         self.Jptr = J.indptr.astype(np.int32)
         self.Jcol = jcol.astype(np.int32)
         # column-ordered copy of J's pattern for J' w without atomics
@@ -99,7 +192,7 @@ class BandPlan:
 
     @property
     def supported(self) -> bool:
-        return self.bw <= MAX_BANDWIDTH
+        return self.bw <= MAX_BANDWIDTH and self._border_fits
 
     @property
     def block_size(self):
@@ -146,8 +239,18 @@ class BandPlan:
             ip(self.Hslot), self.nnzJ, ip(self.Jptr), ip(self.Jcol), ip(self.Jslot), ip(self.JTptr),
             ip(self.JTrow), ip(self.JTmap))
         _lib.check(rc, handle, "pgf_sparse_set_pattern")
+        if self.k:
+            _lib.check(lib.pgf_sparse_set_border(handle, self.k), handle, "pgf_sparse_set_border")
         rc = lib.pgf_sparse_set_block_size(handle, self.block or 0)
         _lib.check(rc, handle, f"pgf_sparse_set_block_size (half-bandwidth {self.bw})")
+
+
+def border_key(border):
+    """Hashable form of a ``problem.pgf_border`` setting (None, "auto" or node indices): a handle's
+    plan is rebuilt when it differs."""
+    if border is None or isinstance(border, str):
+        return border
+    return tuple(int(i) for i in border)
 
 
 def wants_band(problem, hess, n, m, dense_limit=20000):

@@ -25,7 +25,7 @@ import scipy.sparse as sps
 from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .linear_solver import HipLinearSolver
-from .sparse import BandPlan, MAX_BANDWIDTH
+from .sparse import BandPlan, MAX_BANDWIDTH, border_key
 
 DENSE_LIMIT = 20000  # n + m above which sparse derivatives take the banded path
 DENSE_MAX = 60000    # largest n + m the dense path accepts (pgf_create; 28.8 GB of KKT matrix)
@@ -264,8 +264,12 @@ class HipStepSolver:
         self._outer_sent = False
         # sparse (banded) mode: problems too large for a dense KKT matrix, or on request
         self.formulation = int(formulation)
+        # ``problem.pgf_border`` ("auto" or KKT node indices): a bordered band (sparse.BandPlan)
+        self._border = getattr(problem, "pgf_border", None)
+        self._border_tried = None  # size of an automatic border that did not fit
         self.sparse = not self.formulation and (
-            bool(getattr(problem, "pgf_force_band", False)) or (self.n + self.m > DENSE_LIMIT))
+            bool(getattr(problem, "pgf_force_band", False)) or self._border is not None
+            or (self.n + self.m > DENSE_LIMIT))
         self._hd = POOL.acquire(self.n, self.m, device, sparse=self.sparse)
         self._set_formulation()
         self._func = HipStepFunc(self)
@@ -418,8 +422,15 @@ class HipStepSolver:
 
     def _switch_to_dense(self):
         if self.n + self.m > DENSE_MAX:
+            if self._border is None:
+                # too large for a dense KKT matrix: a few dense rows / columns may be all that
+                # keeps the pattern from a band -- try a bordered band before giving up
+                self._border = "auto"
+                return
+            tried = "" if self._border_tried is None else (
+                f" (a border of {self._border_tried} nodes does not bring the rest under it either)")
             raise NotImplementedError(
-                f"sparse problem with half-bandwidth > {MAX_BANDWIDTH} after RCM and "
+                f"sparse problem with half-bandwidth > {MAX_BANDWIDTH} after RCM{tried} and "
                 f"n + m = {self.n + self.m} > {DENSE_MAX}: neither the banded nor the dense path "
                 "can take it")
         device = self._hd.device
@@ -438,12 +449,14 @@ class HipStepSolver:
         hess = sps.csr_matrix(self._hess)
         jac = sps.csr_matrix(self._jac) if self.m else sps.csr_matrix((0, self.n))
         block = getattr(self.problem, "pgf_band_block", None)
-        if hd.plan is not None and hd.plan.block != (int(block) if block else None):
-            hd.plan = None  # a different block size was asked for: upload again
+        if hd.plan is not None and (hd.plan.block != (int(block) if block else None)
+                                    or hd.plan.border_spec != border_key(self._border)):
+            hd.plan = None  # a different block size or border was asked for: upload again
         for attempt in (0, 1):
             if hd.plan is None:
-                plan = BandPlan(hess, jac, self.n, self.m, block=block)
+                plan = BandPlan(hess, jac, self.n, self.m, block=block, border=self._border)
                 if not plan.supported:
+                    self._border_tried = plan.k if self._border is not None else None
                     return False
                 plan.upload(self._lib, hd.h)
                 hd.plan = plan
@@ -497,6 +510,14 @@ class HipStepSolver:
         _lib.check(self._lib.pgf_refinement_stats(self._hd.h, C.byref(a), C.byref(b), C.byref(r)),
                    self._hd.h)
         return a.value, b.value, r.value
+
+    def border_stats(self):
+        """(border size, factor phases, solve phases) of the bordered band on this solver's handle
+        (``pgf_debug_border_stats``; zeros without a border)."""
+        k, a, b = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_border_stats(self._hd.h, C.byref(k), C.byref(a), C.byref(b)),
+                   self._hd.h)
+        return k.value, a.value, b.value
 
     def solver_for_tests(self):
         """``LinearSolver`` view of the device factor without taking a step (parity tests:
