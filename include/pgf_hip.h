@@ -142,9 +142,7 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
 /* block size of the banded solve, after pgf_sparse_set_pattern (which selects B = 0):
  *   B = 0: automatic -- bw <= 8: 8 x 8 block cyclic reduction; bw 9 .. 64: block cyclic
  *          reduction with the smallest B in {16, 32, 64} >= bw (so 16 for bw 9 .. 10).  Every
- *          automatic route carries the accuracy guard.  With PGF_BAND_SEQ set in the
- *          environment the automatic choice for bw <= 10 is the sequential band walk instead
- *          (one wavefront, unguarded: a diagnostic route);
+ *          automatic route carries the accuracy guard;
  *   B = 8, 16, 32, 64: that block size (PGF_INVALID if B < bw).
  * Invalidates the factorisation; the work arrays are sized for the chosen B. */
 int pgf_sparse_set_block_size(pgf_handle h, int B);

@@ -24,6 +24,7 @@ SOURCES = [
     ("pgf_lu.hip", []),
     ("pgf_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api.hip", ["-ffp-contract=off"]),
+    ("pgf_api_band.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

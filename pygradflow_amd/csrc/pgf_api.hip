@@ -6,178 +6,21 @@
 #include <new>
 #include <utility>
 
-#include "../../include/pgf_hip.h"
-#include "pgf_internal.h"
+#include "pgf_api_internal.h"
 #include "pgf_kernels.h"
-#include "pgf_sparse.h"
 #include "pgf_unsym.h"
 
 #define PGF_GEMVT_PARTS 32
-
-// The status block of a dense step (doubles): every word the host reads after the step, read
-// with ONE device-to-host copy of STAT_COPY doubles into the pinned mirror h_stat.
-//   [0, 8)   rs_red: max |r|, max |rhs|, max |s| of the residual check; [4, 7) the matrix norms
-//   [8, 12)  scal:   [0] step diff, [1] residual norm
-//   [12, 14) counts (int): |I|, |A|, mask difference, size mismatch of a speculative step
-//   [14, 16) status (int): factor flags [0, 3), chained-solve status [3] (DenseLdlt::h_flags)
-//   [16, 17) two tickets of the last-workgroup reductions (never copied)
-#define STAT_COPY 16
-#define STAT_ALLOC 17
-
-struct pgf_solver {
-  int n = 0, m = 0, device = 0;
-  hipStream_t stream = nullptr;
-  std::string err = "";
-  // host-known state
-  double dt = 0, lamb = 0, rho = 0, fact = 0, delta = 0;
-  bool bounds_set = false, outer_set = false, derivs_set = false, mask_set = false;
-  bool qp_mode = false, point_set = false, eval_fresh = false;
-  int nI = 0, nA = 0, N = 0;
-  // device data
-  double *H = nullptr, *J = nullptr;
-  int64_t ldh = 0, ldj = 0;
-  bool ownH = false, ownJ = false;
-  double *Hown = nullptr, *Jown = nullptr;  // library-owned storage (reused across uploads)
-  // staging of pgf_set_derivs_csr (grown on demand): row pointers, column indices, values
-  int *csr_ptr = nullptr, *csr_idx = nullptr;
-  double *csr_val = nullptr;
-  size_t csr_ptr_cap = 0, csr_nnz_cap = 0;
-  double *lb = nullptr, *ub = nullptr, *slb = nullptr, *sub = nullptr;
-  double *xhat = nullptr, *yhat = nullptr;
-  double *x = nullptr, *y = nullptr, *xn = nullptr, *yn = nullptr;
-  double *g = nullptr, *c = nullptr, *F = nullptr, *b0full = nullptr;
-  double *rhs = nullptr, *sol = nullptr, *dx = nullptr, *dy = nullptr;
-  double *q = nullptr, *b = nullptr, *w = nullptr, *tmpn = nullptr, *partial = nullptr;
-  double *red = nullptr, *scal = nullptr;  // scal[0] diff, scal[1] residual norm
-  double *meas = nullptr;                  // termination measures: partial maxima + 4 results
-  double *h_meas = nullptr;
-  uint8_t *mask = nullptr, *mask_new = nullptr;
-  int *idxI = nullptr, *idxA = nullptr, *pos = nullptr, *counts = nullptr;
-  // pinned host mirrors
-  int *h_counts = nullptr;
-  double *h_scal = nullptr;
-  DenseLdlt fac;
-  SparseDev sp;
-  bool sparse = false;
-  PgfProfile prof;
-  bool step_pending = false;
-  int last_solve = 0;  // what newton_core_async enqueued: 1 back-solve of row N, 2 full solve
-  // residual check of the reduced system (dense mode): scratch vectors, r = rhs - K s, the
-  // correction, [max |r|, max |rhs|, max |s|] on device and pinned host; the pivoted LU that
-  // takes over when refinement does not converge (allocated on first use)
-  double *rs_v = nullptr, *rs_lv = nullptr, *rs_u = nullptr, *rs_wy = nullptr, *rs_r = nullptr,
-         *rs_d = nullptr, *rs_red = nullptr, *h_rs = nullptr;
-  DenseLu lu;
-  bool lu_active = false;       // the current factor is the LU (until the next factorisation)
-  int refine_mode = 1;          // 0 off, 1 check + refine on demand (default)
-  double refine_tol = 1e-11, refine_fail = 1e-7;
-  // ||H||_inf, ||J||_inf, ||J||_1 of the matrices in HBM (h_rs[4..6]); computed the first time a
-  // residual misses refine_tol against max |rhs| alone
-  bool norms_valid = false;
-  int stat_refined = 0, stat_lu = 0;
-  double stat_last_rel = 0.0;
-  // the factorisation step's own residual was far below the tolerance: the back-solve steps
-  // with the same factor (same backward error, other right-hand sides) skip the check
-  bool factor_clean = false;
-  bool rs_skipped = false;
-  bool sp_guarded = false;  // banded path: the last solve carried the residual check (k_band_residual)
-  double *h_bred = nullptr;  // pinned mirror of sp.bred
-  bool sp_stat_pending = false;  // a guarded banded step's status block is on its way to h_bred
-  // status block (STAT_COPY above) and its pinned mirror
-  double *stat = nullptr, *h_stat = nullptr;
-  unsigned *ticket = nullptr;
-  int stat_bits = 0;  // DenseLdlt::status_words gathered into the block by the step update
-  // speculative index-set sizes (pgf_qp_step_async): the step is enqueued with the last known
-  // |I|, |A|; the compaction flags a mismatch in counts[3], and pgf_qp_sync redoes the step
-  bool counts_known = false, spec_pending = false;
-  bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
-  int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
-  uint8_t *h_mask_stage = nullptr;  // pinned staging of pgf_set_active_set's mask
-  hipEvent_t mask_ev = nullptr;
-  // the current dense factor is that of the condensed system (constraint block eliminated
-  // first, condensed_wanted below); cd_t: its right-hand side
-  bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
-  bool condensed = false;
-  bool condensed_veto = false;  // it met a zero pivot: natural order until the matrix changes
-  double *cd_t = nullptr;
-  // The condensed system's rank-m term from a resident Gram matrix (gram_prepare below): G = J^T J,
-  // n x n with row stride ldg, lower triangle; gram_aux: the identity index list of the build
-  // (n ints) and, behind it, the build's tile counter.  Valid until the next pgf_set_derivs_*
-  // (as norms_valid); gram_off: the allocation failed once, the handle keeps the virtual blocks.
-  double *G = nullptr;
-  int64_t ldg = 0;
-  int *gram_aux = nullptr;
-  bool gram_valid = false, gram_off = false;
-  int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
-  // what the factorisation in flight added to the counters (taken back when it is discarded)
-  bool fac_counted = false, fac_used_gram = false;
-  int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
-  // The unsymmetric formulations (pgf_set_formulation; the section in front of pgf_factor): form --
-  // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
-  // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric
-  // path and is never touched here); ulu_ok -- it holds the factor of the current matrix;
-  // h_has_lag_only -- H in HBM is the plain Lagrangian Hessian (pgf_qp_set_problem), so Standard
-  // adds rho J^T J from the resident Gram matrix; a caller of pgf_set_derivs_* uploads
-  // aug_lag_deriv_xx(rho) itself.
-  int form = PGF_FORM_SYMMETRIC;
-  DenseLu ulu;
-  bool ulu_ok = false;
-  bool h_has_lag_only = false;
-  int stat_unsym_asm = 0, stat_unsym_lu = 0;  // pgf_debug_unsym_stats
-  int64_t stat_unsym_bytes = 0;
-  // while profiling is enabled: device time of the assembly launches of unsym_factor since the
-  // last pgf_profile_read_ex, and their count
-  double acc_unsym_asm_ms = 0;
-  int64_t acc_unsym_asm_launches = 0;
-};
-
-struct pgf_linsolver {
-  int N = 0, device = 0;
-  bool symmetric = true;  // LDL^T (fac) or LU with partial pivoting (lu)
-  hipStream_t stream = nullptr;
-  DenseLdlt fac;
-  DenseLu lu;
-  double *rhs = nullptr, *sol = nullptr;
-};
 
 static const char *k_no_handle = "null handle";
 static const char *k_chain_msg = "chained triangular solve failed its placement / timeout check "
                                  "and so did the per-block solve that replaced it";
 
-static int fail(pgf_handle h, int code, const char *msg) {
-  if (h) h->err = msg;
-  return code;
-}
-
-static int hip_fail(pgf_handle h, hipError_t e, const char *where) {
-  if (h) {
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", where, hipGetErrorString(e));
-    h->err = buf;
-  }
-  return PGF_HIP_ERROR + (int)e;
-}
-
-#define HIPCHK(h, call)                                  \
-  do {                                                   \
-    hipError_t e__ = (call);                             \
-    if (e__ != hipSuccess) return hip_fail(h, e__, #call); \
-  } while (0)
-
-template <typename T>
-static hipError_t dalloc(T **p, size_t count) {
-  return hipMalloc((void **)p, (count ? count : 1) * sizeof(T));
-}
-
-template <typename T>
-static int up_new(pgf_handle h, T **dst, const T *src, size_t count) {
-  if (*dst) {
-    (void)hipFree(*dst);
-    *dst = nullptr;
-  }
-  HIPCHK(h, dalloc(dst, count));
-  if (count) HIPCHK(h, hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
-  return PGF_OK;
+// PGF_EVAL_AHEAD=0: g and c at the new point are evaluated at the start of the next step, not
+// ahead of the host synchronisation of this one (newton_core_async, enqueue_qp_step, pgf_batch_step_async)
+static bool eval_ahead() {
+  static const bool ahead = !(getenv("PGF_EVAL_AHEAD") && atoi(getenv("PGF_EVAL_AHEAD")) == 0);
+  return ahead;
 }
 
 extern "C" {
@@ -284,19 +127,10 @@ int pgf_destroy(pgf_handle h) {
   if (h->h_stat) (void)hipHostFree(h->h_stat);
   if (h->h_mask_stage) (void)hipHostFree(h->h_mask_stage);
   if (h->mask_ev) (void)hipEventDestroy(h->mask_ev);
-  if (h->h_bred) (void)hipHostFree(h->h_bred);
   lu_free(h->lu);
   lu_free(h->ulu);
   if (h->h_meas) (void)hipHostFree(h->h_meas);
-  {
-    SparseDev &sp = h->sp;
-    void *sps[] = {sp.pos, sp.Hptr, sp.Hrow, sp.Hcol, sp.Hslot, sp.Jptr, sp.Jcol, sp.Jslot, sp.JTptr,
-                   sp.JTrow, sp.JTmap, sp.Hval, sp.Jval, sp.band, sp.brhs, sp.Hb0, sp.Jb0,
-                   sp.bD, sp.bL, sp.bU, sp.bDinv, sp.bF, sp.bneg, sp.brhs0, sp.bres, sp.bsol,
-                   sp.bred, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags};
-    for (void *q : sps)
-      if (q) (void)hipFree(q);
-  }
+  band_free(h);
   ldlt_free(h->fac);
   for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
   for (auto &sp : h->prof.update_spans) {
@@ -312,31 +146,11 @@ int pgf_destroy(pgf_handle h) {
   return PGF_OK;
 }
 
-static int up(pgf_handle h, void *dst, const void *src, size_t bytes) {
-  if (!bytes) return PGF_OK;
-  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-  return PGF_OK;
-}
-
-static int down(pgf_handle h, void *dst, const void *src, size_t bytes) {
-  if (!bytes) return PGF_OK;
-  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  return PGF_OK;
-}
-
 // new derivatives: what was computed from the matrices in HBM goes (their norms, the Gram matrix)
 static void invalidate_derivs(pgf_handle h) {
   h->norms_valid = false;
   h->gram_valid = false;
   h->cond_since_upload = 0;
-}
-
-static void invalidate_factor(pgf_handle h) {
-  h->fac.factored = false;
-  h->condensed_veto = false;
-  h->lu_active = false;
-  h->factor_clean = false;
-  h->ulu_ok = false;
 }
 
 int pgf_set_bounds(pgf_handle h, const double *lb, const double *ub) {
@@ -652,7 +466,7 @@ static bool condensed_growth_ok(pgf_handle h) {
 }
 static bool condensed_wanted(pgf_handle h) {
   const int mode = condensed_mode();
-  if (!mode || h->condensed_veto || h->sparse || h->m == 0 || h->nI == 0 || h->m > h->n) return false;
+  if (!mode || h->condensed_veto || h->m == 0 || h->nI == 0 || h->m > h->n) return false;
   if (mode == 1 && (h->m < 64 || (h->N + 255) / 256 <= (h->nI + 255) / 256)) return false;
   if (residual_norms(h)) return false;
   return condensed_growth_ok(h);
@@ -779,65 +593,9 @@ static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
   return hipGetLastError();
 }
 
-// The banded system is solved by block cyclic reduction (B = 8: pgf_sparse.hip, B = 16, 32, 64:
-// pgf_band_wide.hip) or, under PGF_BAND_SEQ, by the sequential band walk (k_band_factor; supports
-// bw <= 10 only; unguarded, a diagnostic route): at B = 8, and at B = 0, which is what the automatic
-// choice then gives bw 9 .. 10 (auto_block_size)
-static bool sp_cyclic(const SparseDev &sp) {
-  return sp.bk > 0 || sp.B > 8 || (sp.B == 8 && !getenv("PGF_BAND_SEQ"));
-}
-static void sp_cyclic_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
-  if (sp.bk)  // bordered band: the solve phase against the kept Y and factor of S (pgf_border.hip)
-    sp_border_solve(s, sp, flags, guard);
-  else if (sp.B > 8)
-    sp_launch_bw_solve(s, sp, N, flags, guard);
-  else
-    sp_launch_bcr_solve(s, sp, N, flags, guard);
-}
-static void sp_cyclic_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
-  if (sp.bk)
-    sp_border_residual(s, sp, flags);
-  else if (sp.B > 8)
-    sp_launch_bw_residual(s, sp, N, flags);
-  else
-    sp_launch_band_residual(s, sp, N, flags);
-}
-
-// assemble the banded matrix for the current mask; with a border also its factor phase (Y = inv(B) C
-// and the factor of the Schur complement S, kept until the matrix is assembled again)
-static void sp_assemble(pgf_handle h) {
-  if (h->sp.bk) {
-    sp_border_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
-    PgfProfile *p = h->prof.enabled ? &h->prof : nullptr;  // the factor phase as factor_ms
-    if (p) {
-      p->factor_spans.emplace_back(prof_event(p), prof_event(p));
-      (void)hipEventRecord(p->factor_spans.back().first, h->stream);
-    }
-    sp_border_factor(h->stream, h->sp, h->fac.flags);
-    if (p) (void)hipEventRecord(p->factor_spans.back().second, h->stream);
-    return;
-  }
-  sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
-}
-
 // enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in row N
 static int factor_async(pgf_handle h, bool with_rhs) {
-  if (h->sparse) {
-    // band assembly + banded LDL^T; the permuted rhs in sp.brhs is forward-substituted on
-    // the way (harmless when the caller only wants the factor)
-    sp_assemble(h);
-    if (sp_cyclic(h->sp)) {
-      // cyclic-reduction mode keeps the assembled band intact; run one reduction (on
-      // whatever right-hand side is there) only to obtain the pivot flags / inertia
-      sp_cyclic_solve(h->stream, h->sp, h->n + h->m, h->fac.flags, /*guard=*/false);
-    } else {
-      sp_launch_factor(h->stream, h->sp, h->n + h->m, h->fac.flags);
-    }
-    HIPCHK(h, hipMemcpyAsync(h->fac.h_flags, h->fac.flags, 4 * sizeof(int), hipMemcpyDeviceToHost,
-                             h->stream));
-    h->fac.factored = false;
-    return PGF_OK;
-  }
+  if (h->sparse) return band_factor_async(h);
   h->lu_active = false;
   h->condensed = condensed_wanted(h);
   h->fac.vdepth = 0;
@@ -909,23 +667,9 @@ static int finish_factor_state(pgf_handle h, hipError_t *e) {
 static const char *k_helper_msg =
     "the dense factorisation failed its hand-over checks with and without helper workgroups";
 
-// a guarded banded step's status block (newton_core_async): after the stream has drained, the
-// pivot flags and the step length take their usual places
-static int sparse_status_sync(pgf_handle h) {
-  if (!h->sparse || !h->sp_stat_pending) return PGF_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->sp_stat_pending = false;
-  const int nr = h->sp.nred;
-  double sum = 0.0;
-  for (int i = 0; i < nr; ++i) sum += h->h_bred[2 * nr + i];
-  h->h_scal[0] = sqrt(sum);
-  for (int k = 0; k < 4; ++k) h->fac.h_flags[k] = (int)h->h_bred[3 * nr + k];
-  return PGF_OK;
-}
-
 static int factor_finish(pgf_handle h) {
   int rcs;
-  if ((rcs = sparse_status_sync(h))) return rcs;
+  if ((rcs = band_status_sync(h))) return rcs;
   hipError_t e;
   const int st = finish_factor_state(h, &e);
   if (st < 0) return hip_fail(h, e, "factor");
@@ -972,7 +716,7 @@ static void absorb_status(pgf_handle h) {
 // r = rhs - K s of the solve just enqueued, with K applied from H, J and the mask (the factor
 // overwrote the assembled matrix); the three maxima reach the host with the next sync
 static void enqueue_residual(pgf_handle h, bool may_skip = false) {
-  if (h->sparse || !h->refine_mode) return;
+  if (!h->refine_mode) return;
   h->rs_skipped = may_skip && h->factor_clean;
   if (h->rs_skipped) return;
   launch_kkt_residual(h->stream, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj,
@@ -1019,9 +763,8 @@ static int residual_norms(pgf_handle h) {
 // partial pivoting of pgf_lu.hip (kept for the back-solve steps that follow).  Only when that
 // fails too does the call report PGF_SINGULAR -> LinearSolverError -> the step controller's
 // reject-and-halve path.
-static int sparse_refine(pgf_handle h, bool swapped, bool with_step);
 static int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true) {
-  if (h->sparse) return sparse_refine(h, swapped, with_step);
+  if (h->sparse) return band_refine(h, swapped, with_step);
   if (!h->refine_mode || h->N == 0 || h->rs_skipped) return PGF_OK;
   double rel = residual_rel(h);
   int rc;
@@ -1092,77 +835,13 @@ static int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true) {
   return PGF_OK;
 }
 
-// The same guard for the banded path (block cyclic reduction inverts its 8 x 8 pivot blocks
-// without pivoting, which is only safe while K is quasi-definite): after a host
-// synchronisation, max |rhs - K s| of the guarded solve (k_band_residual, K read from the intact
-// band) against refine_tol max |rhs|; beyond that up to two refinement steps -- one more
-// reduction on the residual each -- and PGF_SINGULAR when the residual stays above refine_fail:
-// the step controller then rejects the step and doubles lambda, which is what makes the
-// matrix quasi-definite again (the reference's own recovery path, step_control.py:80-107).
-static double sparse_residual_rel(pgf_handle h) {
-  double r = 0.0, b = 0.0;
-  for (int i = 0; i < h->sp.nred; ++i) {
-    const double ri = h->h_bred[2 * i];
-    if (!(ri == ri) || !(ri <= 1.79e308)) return HUGE_VAL;
-    r = std::max(r, ri);
-    b = std::max(b, h->h_bred[2 * i + 1]);
-  }
-  return r / (b > 0.0 ? b : 1.0);
-}
-
-static int sparse_refine(pgf_handle h, bool swapped, bool with_step) {
-  if (!h->refine_mode || !h->sp_guarded) return PGF_OK;
-  const int Nf = h->n + h->m;
-  if (Nf == 0) return PGF_OK;
-  double rel = sparse_residual_rel(h);
-  h->stat_last_rel = rel;
-  if (rel <= h->refine_tol) return PGF_OK;
-  hipStream_t s = h->stream;
-  SparseDev &sp = h->sp;
-  auto unswap = [&]() {
-    if (swapped) {
-      std::swap(h->x, h->xn);
-      std::swap(h->y, h->yn);
-    }
-  };
-  for (int it = 0; it < 2 && rel > h->refine_tol && rel < 1.0; ++it) {
-    HIPCHK(h, hipMemcpyAsync(sp.bsol, sp.brhs, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(sp.brhs, sp.bres, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
-    sp_cyclic_solve(s, sp, Nf, h->fac.flags, /*guard=*/false);
-    sp_launch_band_axpy(s, Nf, sp.bsol, sp.brhs);
-    sp_cyclic_residual(s, sp, Nf, h->fac.flags);
-    HIPCHK(h, hipMemcpyAsync(h->h_bred, sp.bred, (size_t)2 * sp.nred * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (with_step) {
-      unswap();
-      sp_launch_step_update(s, sp, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F, h->dx,
-                            h->dy, h->xn, h->yn, h->red);
-      launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
-      unswap();
-      HIPCHK(h, hipMemcpyAsync(h->h_scal, h->scal, sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(h, hipStreamSynchronize(s));
-    ++h->stat_refined;
-    const double now = sparse_residual_rel(h);
-    if (!(now < rel)) {
-      rel = now;
-      break;
-    }
-    rel = now;
-  }
-  h->stat_last_rel = rel;
-  if (!(rel <= h->refine_fail))
-    return fail(h, PGF_SINGULAR,
-                "banded KKT system could not be solved to a small residual (unpivoted block cyclic reduction)");
-  return PGF_OK;
-}
-
 // After a host synchronisation: a chained triangular solve that failed its own checks
 // (placement, timeout) has left garbage in h->sol and whatever was derived from it.  The
 // chain is off from now on (ldlt_chain_check); the solve and the step update are enqueued
 // again with the per-super-block kernels and awaited, so that the caller never sees the
 // failure.  swapped: the caller has already exchanged (x, y) with (xn, yn) (pgf_qp_step_async).
 static int chain_recover(pgf_handle h, bool swapped) {
-  if (h->sparse || !ldlt_chain_check(h->fac)) return PGF_OK;
+  if (!ldlt_chain_check(h->fac)) return PGF_OK;  // (0 on a banded handle: it has no chain)
   h->eval_fresh = false;  // the point is computed again
   if (swapped) {
     std::swap(h->x, h->xn);
@@ -1433,79 +1112,16 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   hipStream_t s = h->stream;
   h->fused_eval_done = false;
   h->fac_counted = h->fac_used_gram = false;  // (set by factor_async, if this step factorises)
-  // dense, |A| = 0: the residual and the reduced right-hand side in one launch
-  const bool rhs_fused = !h->sparse && h->nA == 0;
-  if (rhs_fused)
+  if (h->sparse) return band_step_async(h, did_factor);
+  if (h->nA == 0) {  // the residual and the reduced right-hand side in one launch
     launch_residual_rhs(s, h->n, h->m, h->nI, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y, h->g,
                         h->c, h->slb, h->sub, h->mask, h->idxI, h->F, h->b0full, h->rhs);
-  else
+  } else {
     launch_residual(s, h->n, h->m, h->lamb, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c, h->slb,
                     h->sub, h->mask, h->F, h->b0full);
-  if (h->sparse) {
-    const int Nf = h->n + h->m;
-    sp_launch_rhs(s, h->sp, h->n, h->m, h->mask, h->F, h->b0full, h->fact, h->sp.Hb0, h->sp.Jb0);
-    *did_factor = false;
-    if (sp_cyclic(h->sp)) {
-      // block cyclic reduction: assemble (only when the mask / derivatives changed) and
-      // solve in log2(N/B) parallel levels; the band itself is left untouched, so a
-      // back-solve step just runs the reduction again on the same band (~1 ms)
-      if (!h->fac.factored) sp_assemble(h);
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (h->prof.enabled) {
-        for (hipEvent_t *e : {&e0, &e1}) {
-          if (!h->prof.pool.empty()) {
-            *e = h->prof.pool.back();
-            h->prof.pool.pop_back();
-          } else {
-            (void)hipEventCreate(e);
-          }
-        }
-        (void)hipEventRecord(e0, s);
-      }
-      sp_cyclic_solve(s, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
-      h->sp_guarded = h->refine_mode != 0;
-      if (e0) {
-        (void)hipEventRecord(e1, s);
-        h->prof.update_spans.emplace_back(e0, e1);
-        // algorithmic bytes of one cyclic-reduction solve: every block (D, L, U, inv D:
-        // 4 x 8 B^2, rhs + solution 16 B) is written once and read about twice
-        const double Bk = (double)h->sp.B;
-        h->prof.update_flops.push_back(3.0 * (double)((Nf + h->sp.B - 1) / h->sp.B) *
-                                       (4 * 8 * Bk * Bk + 16 * Bk));
-      }
-      if (!h->sp_guarded)
-        HIPCHK(h, hipMemcpyAsync(h->fac.h_flags, h->fac.flags, 4 * sizeof(int),
-                                 hipMemcpyDeviceToHost, s));
-      *did_factor = true;  // flags need checking at the sync
-    } else {
-      h->sp_guarded = false;
-      if (!h->fac.factored) {
-        int rc;
-        if ((rc = factor_async(h, true))) return rc;
-        *did_factor = true;
-      } else {
-        sp_launch_fwdsolve(s, h->sp, Nf);
-      }
-      sp_launch_backsolve(s, h->sp, Nf);
-    }
-    if (h->sp_guarded) {
-      // ONE status block for the host: residual pairs, the step update's partial sums (summed
-      // on the host: no reduction kernel) and the pivot flags -- one copy instead of three
-      sp_launch_step_update(s, h->sp, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F,
-                            h->dx, h->dy, h->xn, h->yn, h->sp.bred + 2 * h->sp.nred);
-      HIPCHK(h, hipMemcpyAsync(h->h_bred, h->sp.bred, ((size_t)3 * h->sp.nred + 4) * sizeof(double),
-                               hipMemcpyDeviceToHost, s));
-      h->sp_stat_pending = true;
-      return PGF_OK;
-    }
-    sp_launch_step_update(s, h->sp, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F,
-                          h->dx, h->dy, h->xn, h->yn, h->red);
-    launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
-    return PGF_OK;
-  }
-  if (!rhs_fused)
     launch_reduced_rhs(s, h->n, h->m, h->nI, h->nA, h->fact, h->F, h->idxI, h->idxA, h->H, h->ldh, h->J,
                        h->ldj, h->b0full, h->partial, PGF_GEMVT_PARTS, h->rhs);
+  }
   *did_factor = false;
   if (!h->fac.factored) {
     int rc;
@@ -1525,10 +1141,9 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   // produces read the same matrices -- one pass over H and two over J for both
   // (launch_residual_and_eval) instead of two and four.  (PGF_EVAL_AHEAD=0: separately, the
   // evaluation at the start of the next step.)
-  static const bool ahead = !(getenv("PGF_EVAL_AHEAD") && atoi(getenv("PGF_EVAL_AHEAD")) == 0);
   h->fused_eval_done = false;
   h->rs_skipped = !*did_factor && h->factor_clean;
-  if (ahead && h->qp_mode && h->refine_mode && !h->rs_skipped) {
+  if (eval_ahead() && h->qp_mode && h->refine_mode && !h->rs_skipped) {
     enqueue_step_update(h, /*expand=*/true);
     launch_residual_and_eval(s, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj, h->idxI,
                              h->pos, h->mask, h->rhs, h->sol, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->partial,
@@ -1573,7 +1188,8 @@ int pgf_newton_solve(pgf_handle h, const double *x, const double *y, const doubl
   bool did_factor;
   for (int attempt = 0;; ++attempt) {
     if ((rc = newton_core_async(h, &did_factor))) return rc;
-    if (!h->sp_stat_pending && (rc = down(h, h->h_scal, h->scal, sizeof(double)))) return rc;
+    // (a banded step has enqueued the copy of its own status: band_step_async)
+    if (!h->sparse && (rc = down(h, h->h_scal, h->scal, sizeof(double)))) return rc;
     if (did_factor) {
       rc = factor_finish(h);
       if (rc == PGF_RETRY_FACTOR) {  // once more, without the chain's helper workgroups
@@ -1637,51 +1253,7 @@ int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
   if (!h) return PGF_INVALID;
   int rc;
   if ((rc = check_ready(h))) return rc;
-  if (h->sparse) {
-    // banded mode: the system keeps its full size n + m (an active variable is an identity
-    // row), so rhs / sol have n + m entries in the order [variables; constraints]; entries of
-    // active variables pass through (sol = rhs there)
-    const int Nf = h->n + h->m;
-    if (Nf && (!rhs || !sol)) return fail(h, PGF_INVALID, "null argument");
-    (void)hipSetDevice(h->device);
-    if ((rc = up(h, h->rhs, rhs, (size_t)Nf * sizeof(double)))) return rc;
-    sp_launch_permute(h->stream, h->sp, Nf, h->rhs, h->sp.brhs, 0);
-    if (sp_cyclic(h->sp)) {
-      // cyclic reduction keeps the assembled band intact: (re)assemble only when stale
-      if (!h->fac.factored) sp_assemble(h);
-      sp_cyclic_solve(h->stream, h->sp, Nf, h->fac.flags, h->refine_mode != 0);
-      h->sp_guarded = h->refine_mode != 0;
-      if (h->sp_guarded)
-        HIPCHK(h, hipMemcpyAsync(h->h_bred, h->sp.bred, (size_t)2 * h->sp.nred * sizeof(double),
-                                 hipMemcpyDeviceToHost, h->stream));
-    } else {
-      h->sp_guarded = false;
-      if (!h->fac.factored) {
-        sp_launch_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
-        sp_launch_factor(h->stream, h->sp, Nf, h->fac.flags);  // forward-substitutes brhs on the way
-      } else {
-        sp_launch_fwdsolve(h->stream, h->sp, Nf);
-      }
-      sp_launch_backsolve(h->stream, h->sp, Nf);
-    }
-    HIPCHK(h, hipMemcpyAsync(h->fac.h_flags, h->fac.flags, 4 * sizeof(int), hipMemcpyDeviceToHost,
-                             h->stream));
-    if (h->sp_guarded) {  // residual check (and refinement) before the solution leaves
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if (h->fac.h_flags[0]) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
-      const int nneg = h->fac.h_flags[1];
-      if ((rc = sparse_refine(h, false, false))) return rc;
-      h->fac.h_flags[0] = 0;
-      h->fac.h_flags[1] = nneg;
-    }
-    sp_launch_permute(h->stream, h->sp, Nf, h->sp.brhs, h->sol, 1);
-    if ((rc = down(h, sol, h->sol, (size_t)Nf * sizeof(double)))) return rc;
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->fac.h_flags[0]) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
-    h->fac.n_neg = h->fac.h_flags[1];
-    h->fac.factored = true;
-    return PGF_OK;
-  }
+  if (h->sparse) return band_linear_solve(h, rhs, sol);
   if (h->form) {  // the full system, A or A^T (cond_estimate.py:82)
     const int Nf = h->n + h->m;
     if (Nf && (!rhs || !sol)) return fail(h, PGF_INVALID, "null argument");
@@ -1765,221 +1337,6 @@ int pgf_get_kkt(pgf_handle h, double *K_out, int64_t ldk_out) {
   return PGF_OK;
 }
 
-// ---------------------------------------------------------------- sparse (banded) mode
-// bw <= 8: 8 x 8 cyclic reduction; 9 .. 64: the smallest of 16, 32, 64 that holds the band.
-// Under PGF_BAND_SEQ bw 9 .. 10 gets 0, the sequential walk (bw <= 8 walks at B = 8: sp_cyclic);
-// sp_alloc_blocks sizes the work arrays for whichever this returns.
-static int auto_block_size(int bw) {
-  if (bw <= 8) return 8;
-  if (bw <= 10 && getenv("PGF_BAND_SEQ")) return 0;
-  return bw <= 16 ? 16 : bw <= 32 ? 32 : 64;
-}
-
-// work arrays of the cyclic reduction for block size B (none for the walk, B = 0).  B = 8 keeps
-// two block sets (k_bcr_level2 reads one and writes the other); the wide kernels use one.
-static int sp_alloc_blocks(pgf_handle h, int B) {
-  SparseDev &sp = h->sp;
-  for (double **q : {&sp.bD, &sp.bL, &sp.bU, &sp.bDinv, &sp.bF})
-    if (*q) {
-      (void)hipFree(*q);
-      *q = nullptr;
-    }
-  if (sp.bneg) {
-    (void)hipFree(sp.bneg);
-    sp.bneg = nullptr;
-  }
-  sp.B = B;
-  sp.bX = sp.brhs;  // the back-substitution writes the solution where the step update reads it
-  const int N = h->n + h->m;
-  const size_t nsets = (B == 8) ? 2 : 1, Bk = (size_t)(B ? B : 8);
-  const size_t nbk = ((size_t)N + Bk - 1) / Bk + 1;
-  HIPCHK(h, dalloc(&sp.bD, nsets * nbk * Bk * Bk));
-  HIPCHK(h, dalloc(&sp.bL, nsets * nbk * Bk * Bk));
-  HIPCHK(h, dalloc(&sp.bU, nsets * nbk * Bk * Bk));
-  HIPCHK(h, dalloc(&sp.bDinv, nbk * Bk * Bk));
-  HIPCHK(h, dalloc(&sp.bF, nsets * nbk * Bk));
-  sp.bstride = (int64_t)nbk;
-  HIPCHK(h, dalloc(&sp.bneg, nbk));
-  return PGF_OK;
-}
-
-static void sp_border_free(SparseDev &sp) {
-  for (double **q : {&sp.bY, &sp.bS, &sp.bpart, &sp.bpartv, &sp.brb, &sp.bz})
-    if (*q) {
-      (void)hipFree(*q);
-      *q = nullptr;
-    }
-  if (sp.bsflags) {
-    (void)hipFree(sp.bsflags);
-    sp.bsflags = nullptr;
-  }
-  sp.bk = sp.bkp = sp.Nb = sp.bnchunk = 0;
-  sp.bC = sp.bDd = nullptr;
-  sp.stat_bfactor = sp.stat_bsolve = 0;
-}
-
-int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const int *Hptr,
-                           const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
-                           const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
-                           const int *JTrow, const int *JTmap) {
-  if (!h) return PGF_INVALID;
-  if (!h->sparse) return fail(h, PGF_NOT_READY, "handle was not created with PGF_CREATE_SPARSE");
-  if (bw < 0 || bw > 64) return fail(h, PGF_INVALID, "bandwidth must be 0..64 in this version");
-  if (nnzH < 0 || nnzJ < 0 || !pos || !Hptr || !Jptr || !JTptr)
-    return fail(h, PGF_INVALID, "null pattern");
-  (void)hipSetDevice(h->device);
-  SparseDev &sp = h->sp;
-  const int n = h->n, m = h->m, N = n + m;
-  sp.bw = bw;
-  sp.ldb = ((bw + 1) + 1) / 2 * 2;
-  sp.nnzH = nnzH;
-  sp.nnzJ = nnzJ;
-  int rc;
-  if ((rc = up_new(h, &sp.pos, pos, (size_t)N))) return rc;
-  if ((rc = up_new(h, &sp.Hptr, Hptr, (size_t)n + 1))) return rc;
-  if ((rc = up_new(h, &sp.Hrow, Hrow, (size_t)nnzH))) return rc;
-  if ((rc = up_new(h, &sp.Hcol, Hcol, (size_t)nnzH))) return rc;
-  if ((rc = up_new(h, &sp.Hslot, Hslot, (size_t)nnzH))) return rc;
-  if ((rc = up_new(h, &sp.Jptr, Jptr, (size_t)m + 1))) return rc;
-  if ((rc = up_new(h, &sp.Jcol, Jcol, (size_t)nnzJ))) return rc;
-  if ((rc = up_new(h, &sp.Jslot, Jslot, (size_t)nnzJ))) return rc;
-  if ((rc = up_new(h, &sp.JTptr, JTptr, (size_t)n + 1))) return rc;
-  if ((rc = up_new(h, &sp.JTrow, JTrow, (size_t)nnzJ))) return rc;
-  if ((rc = up_new(h, &sp.JTmap, JTmap, (size_t)nnzJ))) return rc;
-  for (double **q : {&sp.Hval, &sp.Jval, &sp.band, &sp.brhs, &sp.Hb0, &sp.Jb0, &sp.brhs0, &sp.bres, &sp.bsol})
-    if (*q) {
-      (void)hipFree(*q);
-      *q = nullptr;
-    }
-  HIPCHK(h, dalloc(&sp.Hval, (size_t)nnzH));
-  HIPCHK(h, dalloc(&sp.Jval, (size_t)nnzJ));
-  HIPCHK(h, dalloc(&sp.band, (size_t)(N + 1) * sp.ldb));
-  HIPCHK(h, dalloc(&sp.brhs, (size_t)N + 64));  // whole B-row blocks: the cyclic reduction's X
-  HIPCHK(h, dalloc(&sp.brhs0, (size_t)N + 1));
-  HIPCHK(h, dalloc(&sp.bres, (size_t)N + 1));
-  HIPCHK(h, dalloc(&sp.bsol, (size_t)N + 1));
-  if (sp.bred) {
-    (void)hipFree(sp.bred);
-    sp.bred = nullptr;
-  }
-  if (h->h_bred) {
-    (void)hipHostFree(h->h_bred);
-    h->h_bred = nullptr;
-  }
-  sp.nred = (N + 255) / 256;
-  HIPCHK(h, dalloc(&sp.bred, (size_t)3 * sp.nred + 4));
-  HIPCHK(h, hipHostMalloc((void **)&h->h_bred, ((size_t)3 * sp.nred + 4) * sizeof(double)));
-  HIPCHK(h, dalloc(&sp.Hb0, (size_t)n + 1));
-  HIPCHK(h, dalloc(&sp.Jb0, (size_t)m + 1));
-  sp.B = 0;
-  sp_border_free(sp);  // (a border is declared after the pattern: pgf_sparse_set_border)
-  if ((rc = sp_alloc_blocks(h, auto_block_size(bw)))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  sp.active = true;
-  sp.values_set = false;
-  invalidate_factor(h);
-  return PGF_OK;
-}
-
-int pgf_sparse_set_border(pgf_handle h, int k) {
-  if (!h) return PGF_INVALID;
-  if (!h->sparse) return fail(h, PGF_INVALID, "pgf_sparse_set_border: banded handles only");
-  if (k < 0 || k > 64) return fail(h, PGF_INVALID, "border size must be 0..64");
-  if (!h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
-  const int N = h->n + h->m;
-  if (k > 0 && k >= N) return fail(h, PGF_INVALID, "the border must leave at least one band row");
-  (void)hipSetDevice(h->device);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  SparseDev &sp = h->sp;
-  const bool had = sp.bk > 0;
-  sp_border_free(sp);
-  invalidate_factor(h);
-  if (k == 0 && !had) return PGF_OK;
-  const int Nb = N - k, kp = (k + 15) / 16 * 16;
-  const size_t band_doubles = (size_t)(Nb + 1) * sp.ldb;
-  // band, C and D in one array: the plan's slots index it as a whole
-  (void)hipFree(sp.band);
-  sp.band = nullptr;
-  if (k == 0) {
-    HIPCHK(h, dalloc(&sp.band, (size_t)(N + 1) * sp.ldb));
-    return PGF_OK;
-  }
-  if (band_doubles + (size_t)Nb * kp + (size_t)kp * kp > (size_t)INT32_MAX)
-    return fail(h, PGF_INVALID, "band and border store exceed 2^31 entries");
-  HIPCHK(h, dalloc(&sp.band, band_doubles + (size_t)Nb * kp + (size_t)kp * kp));
-  sp.bk = k;
-  sp.bkp = kp;
-  sp.Nb = Nb;
-  sp.bC = sp.band + band_doubles;
-  sp.bDd = sp.bC + (size_t)Nb * kp;
-  sp.bnchunk = (Nb + SP_BORDER_CHUNK - 1) / SP_BORDER_CHUNK;
-  HIPCHK(h, dalloc(&sp.bY, ((size_t)Nb + 64) * kp));
-  HIPCHK(h, dalloc(&sp.bS, (size_t)kp * kp));
-  HIPCHK(h, dalloc(&sp.bpart, (size_t)sp.bnchunk * kp * kp));
-  HIPCHK(h, dalloc(&sp.bpartv, (size_t)sp.bnchunk * 3 * kp));
-  HIPCHK(h, dalloc(&sp.brb, (size_t)kp));
-  HIPCHK(h, dalloc(&sp.bz, (size_t)kp));
-  HIPCHK(h, hipMalloc((void **)&sp.bsflags, 4 * sizeof(int)));
-  HIPCHK(h, hipMemsetAsync(sp.brb, 0, (size_t)kp * sizeof(double), h->stream));  // padding stays zero
-  // the residual pairs: one per 256 band rows and one for the border rows
-  const int nred = std::max((N + 255) / 256, (Nb + 255) / 256 + 1);
-  (void)hipFree(sp.bred);
-  sp.bred = nullptr;
-  (void)hipHostFree(h->h_bred);
-  h->h_bred = nullptr;
-  sp.nred = nred;
-  HIPCHK(h, dalloc(&sp.bred, (size_t)3 * nred + 4));
-  HIPCHK(h, hipMemsetAsync(sp.bred, 0, ((size_t)3 * nred + 4) * sizeof(double), h->stream));
-  HIPCHK(h, hipHostMalloc((void **)&h->h_bred, ((size_t)3 * nred + 4) * sizeof(double)));
-  // a border always runs on a cyclic reduction (never the sequential walk)
-  if (sp.B == 0) {
-    int rc;
-    if ((rc = sp_alloc_blocks(h, sp.bw <= 8 ? 8 : 16))) return rc;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return PGF_OK;
-}
-
-int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves) {
-  if (!h) return PGF_INVALID;
-  if (k) *k = h->sp.bk;
-  if (border_factorisations) *border_factorisations = h->sp.stat_bfactor;
-  if (border_solves) *border_solves = h->sp.stat_bsolve;
-  return PGF_OK;
-}
-
-int pgf_sparse_set_block_size(pgf_handle h, int B) {
-  if (!h) return PGF_INVALID;
-  if (!h->sparse || !h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
-  if (B != 0 && B != 8 && B != 16 && B != 32 && B != 64)
-    return fail(h, PGF_INVALID, "block size must be 0 (automatic), 8, 16, 32 or 64");
-  if (B != 0 && B < h->sp.bw)
-    return fail(h, PGF_INVALID, "block size is smaller than the half-bandwidth");
-  (void)hipSetDevice(h->device);
-  const int want = B ? B : auto_block_size(h->sp.bw);
-  if (want == h->sp.B) return PGF_OK;
-  int rc;
-  if ((rc = sp_alloc_blocks(h, want))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  invalidate_factor(h);
-  return PGF_OK;
-}
-
-int pgf_sparse_set_values(pgf_handle h, const double *Hval, const double *Jval) {
-  if (!h) return PGF_INVALID;
-  if (!h->sparse || !h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
-  if ((h->sp.nnzH && !Hval) || (h->sp.nnzJ && !Jval)) return fail(h, PGF_INVALID, "null values");
-  (void)hipSetDevice(h->device);
-  int rc;
-  if ((rc = up(h, h->sp.Hval, Hval, (size_t)h->sp.nnzH * sizeof(double)))) return rc;
-  if ((rc = up(h, h->sp.Jval, Jval, (size_t)h->sp.nnzJ * sizeof(double)))) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->sp.values_set = true;
-  h->derivs_set = true;
-  invalidate_factor(h);
-  return PGF_OK;
-}
-
 int pgf_qp_set_vectors(pgf_handle h, const double *q, const double *b) {
   if (!h) return PGF_INVALID;
   if ((h->n && !q) || (h->m && !b)) return fail(h, PGF_INVALID, "null argument");
@@ -2031,7 +1388,7 @@ int pgf_qp_set_point(pgf_handle h, const double *x, const double *y) {
 // off the production path), so that the point read is never that of a discarded step
 static int settle_spec(pgf_handle h, bool *redone);
 static int settle_before_read(pgf_handle h) {
-  if (h->sparse || !h->step_pending || !h->spec_pending) return PGF_OK;
+  if (!h->step_pending || !h->spec_pending) return PGF_OK;  // (never speculative on a banded handle)
   HIPCHK(h, hipStreamSynchronize(h->stream));
   bool redone;
   return settle_spec(h, &redone);
@@ -2062,18 +1419,13 @@ int pgf_qp_get_mask(pgf_handle h, uint8_t *mask) {
 // c = A x - b ; w = rho c + y ; g = Q x + (q + A' w)   at the device point
 static void qp_eval(pgf_handle h) {
   if (h->eval_fresh) return;
+  h->eval_fresh = true;
+  if (h->sparse) return band_eval(h);
   hipStream_t s = h->stream;
-  if (h->sparse) {
-    const SparseDev &sp = h->sp;
-    sp_launch_eval(s, sp, h->n, h->m, h->x, h->y, h->b, h->q, h->rho, h->c, h->w, h->g);
-    h->eval_fresh = true;
-    return;
-  }
   launch_gemv_rows(s, h->m, h->n, h->J, h->ldj, h->x, h->b, -1.0, h->c);
   launch_mult_vec(s, h->m, h->rho, h->c, h->y, h->w);
   launch_gemvT(s, h->m, h->n, h->J, h->ldj, h->w, h->q, h->partial, PGF_GEMVT_PARTS, h->tmpn);
   launch_gemv_rows(s, h->n, h->n, h->H, h->ldh, h->x, h->tmpn, 1.0, h->g);
-  h->eval_fresh = true;
 }
 
 static int qp_ready(pgf_handle h) {
@@ -2160,7 +1512,7 @@ static int enqueue_qp_step(pgf_handle h) {
   qp_eval(h);
   bool did_factor;
   const bool armed = h->fac.inject_helper_failure != 0;
-  h->fac.defer_status = !h->sparse;
+  h->fac.defer_status = true;  // (read by the dense factorisation and solves only)
   int rc = newton_core_async(h, &did_factor);
   h->fac.defer_status = false;
   h->step_took_inject = armed && !h->fac.inject_helper_failure;
@@ -2173,16 +1525,14 @@ static int enqueue_qp_step(pgf_handle h) {
   // step's host synchronisation the four small launches would wait for the host one by one
   // (~35 us of gaps at config 2).  Whatever moves the point afterwards (refinement, a repeated
   // step, pgf_qp_set_point, a new rho) clears eval_fresh again.
-  static const bool ahead = !(getenv("PGF_EVAL_AHEAD") && atoi(getenv("PGF_EVAL_AHEAD")) == 0);
+  if (h->sparse) return PGF_OK;  // (nothing ahead; band_step_async has enqueued the copy of its status)
   if (h->fused_eval_done) {  // (newton_core_async did it beside the residual check)
     h->eval_fresh = true;
     h->fused_eval_done = false;
-  } else if (ahead && !h->sparse) {
+  } else if (eval_ahead()) {
     qp_eval(h);
   }
-  if (!h->sparse) return down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double));
-  if (!h->sp_stat_pending) return down(h, h->h_scal, h->scal, sizeof(double));
-  return PGF_OK;
+  return down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double));
 }
 
 // A step in flight that was enqueued with speculative index-set sizes, after a host
@@ -2194,7 +1544,7 @@ static int enqueue_qp_step(pgf_handle h) {
 // point it started at, with the true sizes.  *redone: it was.
 static int settle_spec(pgf_handle h, bool *redone) {
   *redone = false;
-  if (h->sparse || !h->step_pending || !h->spec_pending) return PGF_OK;
+  if (!h->step_pending || !h->spec_pending) return PGF_OK;  // (never speculative on a banded handle)
   h->spec_pending = false;
   if (!h->h_counts[3]) return PGF_OK;
   ++h->stat_redone;
@@ -2247,7 +1597,7 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   if (h->form) return unsym_qp_sync(h, n_neg, diff);
   hipError_t e;
   int rc;
-  if ((rc = sparse_status_sync(h))) return rc;
+  if ((rc = band_status_sync(h))) return rc;
   if (!h->sparse) {
     // the step's one wait: its status block
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2786,8 +2136,7 @@ int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   batch_enqueue_step(b, policy, tau, b->all_factored);
   // g and c at the new points, enqueued ahead of the host synchronisation (as pgf_qp_step_async):
   // behind it the five small launches would wait for the host one by one
-  static const bool ahead = !(getenv("PGF_EVAL_AHEAD") && atoi(getenv("PGF_EVAL_AHEAD")) == 0);
-  if (ahead) batch_eval(b);
+  if (eval_ahead()) batch_eval(b);
   BHIPCHK(b, hipMemcpyAsync(b->h_diff, b->diff_out, b->B * sizeof(double), hipMemcpyDeviceToHost,
                             b->stream));
   BHIPCHK(b, hipMemcpyAsync(b->h_flags, b->flags_out, (size_t)b->B * 3 * sizeof(int),
@@ -3225,10 +2574,7 @@ int pgf_qp_measures(pgf_handle h, double active_tol, double *out) {
   // c = A x - b and r = Q x + q + A'y (no rho term: iterate.py:141, 176)
   launch_copy(s, h->w, h->y, m);
   if (h->sparse) {
-    const SparseDev &sp = h->sp;
-    sp_launch_spmv(s, m, sp.Jptr, sp.Jcol, sp.Jval, h->x, h->b, -1.0, h->c);
-    sp_launch_spmvT(s, n, sp.JTptr, sp.JTrow, sp.JTmap, sp.Jval, h->w, h->q, h->tmpn);
-    sp_launch_spmv(s, n, sp.Hptr, sp.Hcol, sp.Hval, h->x, h->tmpn, 1.0, h->F);
+    band_measures_eval(h);
   } else {
     launch_gemv_rows(s, m, n, h->J, h->ldj, h->x, h->b, -1.0, h->c);
     launch_gemvT(s, m, n, h->J, h->ldj, h->w, h->q, h->partial, PGF_GEMVT_PARTS, h->tmpn);

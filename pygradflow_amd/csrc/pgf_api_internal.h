@@ -1,0 +1,201 @@
+// What the translation units behind the C ABI share (pgf_api.hip: dense, batch, unsymmetric and
+// profile sections; pgf_api_band.hip: the banded driver): the handles, the error helpers and the
+// small interface through which the dense functions hand a banded handle over.
+#pragma once
+
+#include <cstdio>
+#include <string>
+
+#include "../../include/pgf_hip.h"
+#include "pgf_internal.h"
+#include "pgf_sparse.h"
+
+// The status block of a dense step (doubles): every word the host reads after the step, read
+// with ONE device-to-host copy of STAT_COPY doubles into the pinned mirror h_stat.
+//   [0, 8)   rs_red: max |r|, max |rhs|, max |s| of the residual check; [4, 7) the matrix norms
+//   [8, 12)  scal:   [0] step diff, [1] residual norm
+//   [12, 14) counts (int): |I|, |A|, mask difference, size mismatch of a speculative step
+//   [14, 16) status (int): factor flags [0, 3), chained-solve status [3] (DenseLdlt::h_flags)
+//   [16, 17) two tickets of the last-workgroup reductions (never copied)
+#define STAT_COPY 16
+#define STAT_ALLOC 17
+
+struct pgf_solver {
+  int n = 0, m = 0, device = 0;
+  hipStream_t stream = nullptr;
+  std::string err = "";
+  // host-known state
+  double dt = 0, lamb = 0, rho = 0, fact = 0, delta = 0;
+  bool bounds_set = false, outer_set = false, derivs_set = false, mask_set = false;
+  bool qp_mode = false, point_set = false, eval_fresh = false;
+  int nI = 0, nA = 0, N = 0;
+  // device data
+  double *H = nullptr, *J = nullptr;
+  int64_t ldh = 0, ldj = 0;
+  bool ownH = false, ownJ = false;
+  double *Hown = nullptr, *Jown = nullptr;  // library-owned storage (reused across uploads)
+  // staging of pgf_set_derivs_csr (grown on demand): row pointers, column indices, values
+  int *csr_ptr = nullptr, *csr_idx = nullptr;
+  double *csr_val = nullptr;
+  size_t csr_ptr_cap = 0, csr_nnz_cap = 0;
+  double *lb = nullptr, *ub = nullptr, *slb = nullptr, *sub = nullptr;
+  double *xhat = nullptr, *yhat = nullptr;
+  double *x = nullptr, *y = nullptr, *xn = nullptr, *yn = nullptr;
+  double *g = nullptr, *c = nullptr, *F = nullptr, *b0full = nullptr;
+  double *rhs = nullptr, *sol = nullptr, *dx = nullptr, *dy = nullptr;
+  double *q = nullptr, *b = nullptr, *w = nullptr, *tmpn = nullptr, *partial = nullptr;
+  double *red = nullptr, *scal = nullptr;  // scal[0] diff, scal[1] residual norm
+  double *meas = nullptr;                  // termination measures: partial maxima + 4 results
+  double *h_meas = nullptr;
+  uint8_t *mask = nullptr, *mask_new = nullptr;
+  int *idxI = nullptr, *idxA = nullptr, *pos = nullptr, *counts = nullptr;
+  // pinned host mirrors
+  int *h_counts = nullptr;
+  double *h_scal = nullptr;
+  DenseLdlt fac;
+  SparseDev sp;
+  bool sparse = false;
+  PgfProfile prof;
+  bool step_pending = false;
+  int last_solve = 0;  // what newton_core_async enqueued: 1 back-solve of row N, 2 full solve
+  // residual check of the reduced system (dense mode): scratch vectors, r = rhs - K s, the
+  // correction, [max |r|, max |rhs|, max |s|] on device and pinned host; the pivoted LU that
+  // takes over when refinement does not converge (allocated on first use)
+  double *rs_v = nullptr, *rs_lv = nullptr, *rs_u = nullptr, *rs_wy = nullptr, *rs_r = nullptr,
+         *rs_d = nullptr, *rs_red = nullptr, *h_rs = nullptr;
+  DenseLu lu;
+  bool lu_active = false;       // the current factor is the LU (until the next factorisation)
+  int refine_mode = 1;          // 0 off, 1 check + refine on demand (default)
+  double refine_tol = 1e-11, refine_fail = 1e-7;
+  // ||H||_inf, ||J||_inf, ||J||_1 of the matrices in HBM (h_rs[4..6]); computed the first time a
+  // residual misses refine_tol against max |rhs| alone
+  bool norms_valid = false;
+  int stat_refined = 0, stat_lu = 0;
+  double stat_last_rel = 0.0;
+  // the factorisation step's own residual was far below the tolerance: the back-solve steps
+  // with the same factor (same backward error, other right-hand sides) skip the check
+  bool factor_clean = false;
+  bool rs_skipped = false;
+  // status block (STAT_COPY above) and its pinned mirror
+  double *stat = nullptr, *h_stat = nullptr;
+  unsigned *ticket = nullptr;
+  int stat_bits = 0;  // DenseLdlt::status_words gathered into the block by the step update
+  // speculative index-set sizes (pgf_qp_step_async): the step is enqueued with the last known
+  // |I|, |A|; the compaction flags a mismatch in counts[3], and pgf_qp_sync redoes the step
+  bool counts_known = false, spec_pending = false;
+  bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
+  int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
+  uint8_t *h_mask_stage = nullptr;  // pinned staging of pgf_set_active_set's mask
+  hipEvent_t mask_ev = nullptr;
+  // the current dense factor is that of the condensed system (constraint block eliminated
+  // first, condensed_wanted below); cd_t: its right-hand side
+  bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
+  bool condensed = false;
+  bool condensed_veto = false;  // it met a zero pivot: natural order until the matrix changes
+  double *cd_t = nullptr;
+  // The condensed system's rank-m term from a resident Gram matrix (gram_prepare below): G = J^T J,
+  // n x n with row stride ldg, lower triangle; gram_aux: the identity index list of the build
+  // (n ints) and, behind it, the build's tile counter.  Valid until the next pgf_set_derivs_*
+  // (as norms_valid); gram_off: the allocation failed once, the handle keeps the virtual blocks.
+  double *G = nullptr;
+  int64_t ldg = 0;
+  int *gram_aux = nullptr;
+  bool gram_valid = false, gram_off = false;
+  int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
+  // what the factorisation in flight added to the counters (taken back when it is discarded)
+  bool fac_counted = false, fac_used_gram = false;
+  int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
+  // The unsymmetric formulations (pgf_set_formulation; the section in front of pgf_factor): form --
+  // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
+  // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric
+  // path and is never touched here); ulu_ok -- it holds the factor of the current matrix;
+  // h_has_lag_only -- H in HBM is the plain Lagrangian Hessian (pgf_qp_set_problem), so Standard
+  // adds rho J^T J from the resident Gram matrix; a caller of pgf_set_derivs_* uploads
+  // aug_lag_deriv_xx(rho) itself.
+  int form = PGF_FORM_SYMMETRIC;
+  DenseLu ulu;
+  bool ulu_ok = false;
+  bool h_has_lag_only = false;
+  int stat_unsym_asm = 0, stat_unsym_lu = 0;  // pgf_debug_unsym_stats
+  int64_t stat_unsym_bytes = 0;
+  // while profiling is enabled: device time of the assembly launches of unsym_factor since the
+  // last pgf_profile_read_ex, and their count
+  double acc_unsym_asm_ms = 0;
+  int64_t acc_unsym_asm_launches = 0;
+};
+
+struct pgf_linsolver {
+  int N = 0, device = 0;
+  bool symmetric = true;  // LDL^T (fac) or LU with partial pivoting (lu)
+  hipStream_t stream = nullptr;
+  DenseLdlt fac;
+  DenseLu lu;
+  double *rhs = nullptr, *sol = nullptr;
+};
+
+static inline int fail(pgf_handle h, int code, const char *msg) {
+  if (h) h->err = msg;
+  return code;
+}
+
+static inline int hip_fail(pgf_handle h, hipError_t e, const char *where) {
+  if (h) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", where, hipGetErrorString(e));
+    h->err = buf;
+  }
+  return PGF_HIP_ERROR + (int)e;
+}
+
+#define HIPCHK(h, call)                                  \
+  do {                                                   \
+    hipError_t e__ = (call);                             \
+    if (e__ != hipSuccess) return hip_fail(h, e__, #call); \
+  } while (0)
+
+template <typename T>
+static inline hipError_t dalloc(T **p, size_t count) {
+  return hipMalloc((void **)p, (count ? count : 1) * sizeof(T));
+}
+
+template <typename T>
+static inline int up_new(pgf_handle h, T **dst, const T *src, size_t count) {
+  if (*dst) {
+    (void)hipFree(*dst);
+    *dst = nullptr;
+  }
+  HIPCHK(h, dalloc(dst, count));
+  if (count) HIPCHK(h, hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
+  return PGF_OK;
+}
+
+static inline int up(pgf_handle h, void *dst, const void *src, size_t bytes) {
+  if (!bytes) return PGF_OK;
+  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
+  return PGF_OK;
+}
+
+static inline int down(pgf_handle h, void *dst, const void *src, size_t bytes) {
+  if (!bytes) return PGF_OK;
+  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+  return PGF_OK;
+}
+
+static inline void invalidate_factor(pgf_handle h) {
+  h->fac.factored = false;
+  h->condensed_veto = false;
+  h->lu_active = false;
+  h->factor_clean = false;
+  h->ulu_ok = false;
+}
+
+// ---- the banded driver (pgf_api_band.hip), for handles created with PGF_CREATE_SPARSE ----------
+// Each is the banded half of the dense function named beside it, which hands over in one line.
+void band_free(pgf_handle h);                                  // pgf_destroy
+int band_factor_async(pgf_handle h);                           // factor_async
+int band_step_async(pgf_handle h, bool *did_factor);           // newton_core_async
+int band_status_sync(pgf_handle h);                            // factor_finish, pgf_qp_sync (no-op on dense handles)
+int band_refine(pgf_handle h, bool swapped, bool with_step);   // refine_if_needed
+int band_linear_solve(pgf_handle h, const double *rhs, double *sol);  // pgf_linear_solve
+void band_eval(pgf_handle h);                                  // qp_eval
+void band_measures_eval(pgf_handle h);                         // pgf_qp_measures

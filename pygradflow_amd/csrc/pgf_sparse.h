@@ -7,8 +7,8 @@
 struct SparseDev {
   bool active = false;
   int bw = 0, ldb = 0;
-  // block size of the cyclic reduction: 8 (pgf_sparse.hip), 16 / 32 / 64 (pgf_band_wide.hip),
-  // 0: the sequential band walk (bw 9 .. 10 without a forced block size under PGF_BAND_SEQ)
+  // block size of the cyclic reduction: 8 (pgf_sparse.hip), 16 / 32 / 64 (pgf_band_wide.hip);
+  // never 0 once a pattern is set
   int B = 0;
   int nnzH = 0, nnzJ = 0;
   int *pos = nullptr;                       // permuted position of variable i / constraint n + r
@@ -25,6 +25,9 @@ struct SparseDev {
   // steps), [3 nred, 3 nred + 4) the solve's pivot flags
   double *bred = nullptr;
   int nred = 0;
+  double *h_bred = nullptr;   // pinned mirror of bred
+  bool guarded = false;       // the last solve carried the residual check
+  bool stat_pending = false;  // a guarded step's status block is on its way to h_bred
   double *Hb0 = nullptr, *Jb0 = nullptr;
   // block cyclic reduction work arrays: (N/B) blocks of B x B (D, L, U, inv D), rhs, solution
   double *bD = nullptr, *bL = nullptr, *bU = nullptr, *bDinv = nullptr, *bF = nullptr, *bX = nullptr;
@@ -64,7 +67,6 @@ void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8
 // out[pos[i]] = in[i] (gather == 0) or out[i] = in[pos[i]] (gather != 0)
 void sp_launch_permute(hipStream_t s, const SparseDev &sp, int N, const double *in, double *out,
                        int gather);
-void sp_launch_factor(hipStream_t s, const SparseDev &sp, int N, int *flags);
 void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard = true);
 void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 // B = 16, 32, 64 (pgf_band_wide.hip): the same contract as sp_launch_bcr_solve /
@@ -72,8 +74,6 @@ void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const in
 void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard);
 void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 void sp_launch_band_axpy(hipStream_t s, int N, const double *a, double *x);
-void sp_launch_fwdsolve(hipStream_t s, const SparseDev &sp, int N);
-void sp_launch_backsolve(hipStream_t s, const SparseDev &sp, int N);
 void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, double fact,
                            double rho, const double *x, const double *y, const double *lb,
                            const double *ub, const double *F, double *dx, double *dy, double *xn,

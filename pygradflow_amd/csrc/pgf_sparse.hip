@@ -188,153 +188,6 @@ __global__ void k_band_rhs(int n, int m, const uint8_t *__restrict__ mask,
   brhs[pos[i]] = v;
 }
 
-// ---------------------------------------------------------------- banded LDL^T + forward solve
-#define BAND_LDS_DOUBLES 15360  // 120 KB panel of band rows + right-hand side
-
-// One wavefront walks the band.  Panels of P rows are staged in LDS (coalesced loads),
-// columns are eliminated one after the other inside the panel (lane <-> pair (r, k) of
-// the (bw+1)^2 / 2 window update), consecutive panels overlap by bw rows through global
-// memory.  The right-hand side rides along (forward substitution for free).  The chain
-// pivot -> reciprocal -> update -> next pivot is inherently serial: this kernel is
-// latency-bound by design; the planned successor partitions the band into independent
-// segments with a small dense Schur complement.
-__global__ __launch_bounds__(64) void k_band_factor(double *__restrict__ band, int ldb, int bw,
-                                                    double *__restrict__ rhs, int N,
-                                                    int *__restrict__ flags) {
-  __shared__ double sm[BAND_LDS_DOUBLES];
-  const int lane = threadIdx.x;
-  const int P = BAND_LDS_DOUBLES / (ldb + 1);
-  double *Bp = sm;            // [P][ldb]
-  double *rp = sm + P * ldb;  // [P]
-  // lane -> pair (r, k), 1 <= k <= r <= bw
-  const int npairs = bw * (bw + 1) / 2;
-  int r = 0, k = 0;
-  if (lane < npairs) {
-    int t = lane;
-    r = 1;
-    while (t >= r) {
-      t -= r;
-      ++r;
-    }
-    k = t + 1;
-  }
-  const bool act = lane < npairs;
-  int neg = 0, bad = 0;
-  const int stepP = P - bw;
-  for (int s0 = 0; s0 < N; s0 += stepP) {
-    const int rows = min(P, N - s0);
-    // stage rows [s0, s0 + rows) (+ zero padding up to P)
-    for (int idx = lane; idx < P * ldb; idx += 64) {
-      const int rr = idx / ldb;
-      Bp[idx] = (rr < rows) ? band[(int64_t)s0 * ldb + idx] : 0.0;
-    }
-    for (int idx = lane; idx < P; idx += 64) rp[idx] = (idx < rows) ? rhs[s0 + idx] : 0.0;
-    __syncthreads();
-    // columns whose whole window lies in the panel (all remaining ones in the last panel)
-    const bool last = (s0 + P >= N);
-    const int ncols = last ? rows : stepP;
-    for (int j = 0; j < ncols; ++j) {
-      const double d = Bp[j * ldb];
-      const bool isbad = (d == 0.0) || !(fabs(d) <= 1.79e308);
-      const double di = isbad ? 0.0 : recip2(d);
-      bad |= isbad ? 1 : 0;
-      neg += (d < 0.0) ? 1 : 0;
-      if (act && j + r < P) {
-        const double cr = Bp[(j + r) * ldb + r];
-        const double ck = Bp[(j + k) * ldb + k];
-        const double l = cr * di;
-        double t = Bp[(j + r) * ldb + (r - k)];
-        t = fma(-l, ck, t);
-        double rr = 0.0;
-        if (k == r) rr = fma(-l, rp[j], rp[j + r]);
-        Bp[(j + r) * ldb + (r - k)] = t;
-        if (k == r) rp[j + r] = rr;
-        if (k == 1) Bp[(j + r) * ldb + r] = l;  // L entry (column read by all lanes above)
-      }
-    }
-    __syncthreads();
-    for (int idx = lane; idx < rows * ldb; idx += 64) band[(int64_t)s0 * ldb + idx] = Bp[idx];
-    for (int idx = lane; idx < rows; idx += 64) rhs[s0 + idx] = rp[idx];
-    __threadfence();  // the next panel re-reads the bw overlapping rows from memory
-    __syncthreads();
-    if (last) break;
-  }
-  if (lane == 0) {
-    if (bad) atomicOr(&flags[0], 1);
-    if (neg) atomicAdd(&flags[1], neg);
-  }
-}
-
-// y <- L^-1 z with the stored factor (back-solve steps that reuse a factorisation):
-// mirror image of k_band_backsolve, walking forward.
-__global__ __launch_bounds__(64) void k_band_fwdsolve(const double *__restrict__ band, int ldb,
-                                                      int bw, double *__restrict__ z, int N) {
-  __shared__ double sm[BAND_LDS_DOUBLES];
-  const int lane = threadIdx.x;
-  const int P = BAND_LDS_DOUBLES / (ldb + 1);
-  double *Bp = sm;
-  double *zp = sm + P * ldb;
-  const int rr = lane + 1;
-  const int stepP = P - bw;
-  for (int s0 = 0; s0 < N; s0 += stepP) {
-    const int rows = min(P, N - s0);
-    for (int idx = lane; idx < rows * ldb; idx += 64) Bp[idx] = band[(int64_t)s0 * ldb + idx];
-    for (int idx = lane; idx < rows; idx += 64) zp[idx] = z[s0 + idx];
-    __syncthreads();
-    const bool last = (s0 + P >= N);
-    const int ncols = last ? rows : stepP;
-    for (int j = 0; j < ncols; ++j) {
-      const double yj = zp[j];
-      if (rr <= bw && j + rr < rows) zp[j + rr] = fma(-Bp[(j + rr) * ldb + rr], yj, zp[j + rr]);
-    }
-    __syncthreads();
-    for (int idx = lane; idx < rows; idx += 64) z[s0 + idx] = zp[idx];
-    __threadfence();
-    __syncthreads();
-    if (last) break;
-  }
-}
-
-// z <- D^-1 z
-__global__ void k_band_scale(double *__restrict__ z, const double *__restrict__ band, int ldb,
-                             int N) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) z[i] = z[i] / band[(int64_t)i * ldb];
-}
-
-// x <- L^-T z, sequential from the last row (right-looking: once x_i is final it is folded
-// into the bw entries above it, lane <-> distance r).  Panels of P rows in LDS, walked from
-// the end; a panel finalises and propagates its rows [bw, P) and hands its top bw rows
-// (complete, but not yet propagated upwards) to the next panel through global memory.
-__global__ __launch_bounds__(64) void k_band_backsolve(const double *__restrict__ band, int ldb,
-                                                       int bw, double *__restrict__ z, int N) {
-  __shared__ double sm[BAND_LDS_DOUBLES];
-  const int lane = threadIdx.x;
-  const int P = BAND_LDS_DOUBLES / (ldb + 1);
-  double *Bp = sm;
-  double *zp = sm + P * ldb;
-  const int rr = lane + 1;
-  int e0 = N;
-  while (e0 > 0) {
-    const int s0 = max(0, e0 - P);
-    const int rows = e0 - s0;
-    for (int idx = lane; idx < rows * ldb; idx += 64) Bp[idx] = band[(int64_t)s0 * ldb + idx];
-    for (int idx = lane; idx < rows; idx += 64) zp[idx] = z[s0 + idx];
-    __syncthreads();
-    const int lo = (s0 == 0) ? 0 : bw;
-    for (int i = rows - 1; i >= lo; --i) {
-      const double xi = zp[i];
-      if (rr <= bw && i - rr >= 0) zp[i - rr] = fma(-Bp[i * ldb + rr], xi, zp[i - rr]);
-    }
-    __syncthreads();
-    for (int idx = lane; idx < rows; idx += 64) z[s0 + idx] = zp[idx];
-    __threadfence();
-    __syncthreads();
-    if (s0 == 0) break;
-    e0 = s0 + bw;
-  }
-}
-
 // full-length vector <-> permuted band order (LinearSolver.solve against the banded factor)
 __global__ void k_band_permute(int N, const int *__restrict__ pos, const double *__restrict__ in,
                                double *__restrict__ out, int gather) {
@@ -438,22 +291,6 @@ void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8
 void sp_launch_permute(hipStream_t s, const SparseDev &sp, int N, const double *in, double *out,
                        int gather) {
   if (N) hipLaunchKernelGGL(k_band_permute, g1(N), dim3(256), 0, s, N, sp.pos, in, out, gather);
-}
-
-void sp_launch_factor(hipStream_t s, const SparseDev &sp, int N, int *flags) {
-  (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
-  hipLaunchKernelGGL(k_band_factor, dim3(1), dim3(64), 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N, flags);
-}
-
-void sp_launch_fwdsolve(hipStream_t s, const SparseDev &sp, int N) {
-  if (N == 0) return;
-  hipLaunchKernelGGL(k_band_fwdsolve, dim3(1), dim3(64), 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N);
-}
-
-void sp_launch_backsolve(hipStream_t s, const SparseDev &sp, int N) {
-  if (N == 0) return;
-  hipLaunchKernelGGL(k_band_scale, g1(N), dim3(256), 0, s, sp.brhs, sp.band, sp.ldb, N);
-  hipLaunchKernelGGL(k_band_backsolve, dim3(1), dim3(64), 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N);
 }
 
 void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, double fact,

@@ -31,8 +31,7 @@ def block_size_for(bw, forced=None):
     """Block size of the banded solve for half-bandwidth ``bw``: ``forced`` if given, else
     8 for bw <= 8 (8 x 8 cyclic reduction), the smallest of 16, 32, 64 that is >= bw up to 64
     (so 16 for bw 9 .. 10), and None beyond (no banded path).  Every one of these carries the
-    accuracy guard.  (With PGF_BAND_SEQ set in the environment the library runs the automatic
-    plans of bw <= 10 through the unguarded sequential band walk instead, whatever this says.)"""
+    accuracy guard."""
     if forced:
         return int(forced)
     if bw <= 8:

@@ -3,12 +3,9 @@
 by tests/test_gpu_schedules.py (the switches are read once per process).
 
 Default: a sparse optimal-control problem (bw 6, N = 9000), a tridiagonal box QP with a churning
-mask (bw 1, N = 4099) and two problems from the bw 9 .. 10 range spanning several LDS panels of the
-sequential walk (grid_box_qp(9, 320), N = 2880, and multistate_ocp(400, 4, 2), N = 4000: both bw 10
-after RCM, three and four panels).  Under PGF_BAND_SEQ=1 all four take the sequential band walk
-(k_band_factor, k_band_fwdsolve, k_band_backsolve), followed by a bw-9 problem of four panels
-(grid_box_qp(9, 500), N = 4500) and four sizes on both sides of one walk panel (1396 rows at bw 9,
-1181 at bw 10); otherwise the first two take the 8 x 8 cyclic reduction and the last two B = 16.
+mask (bw 1, N = 4099), both on the 8 x 8 cyclic reduction, and three problems from the bw 9 .. 10
+range on B = 16 (grid_box_qp(9, 320), N = 2880, and multistate_ocp(400, 4, 2), N = 4000: both bw 10
+after RCM; grid_box_qp(9, 500), N = 4500, bw 9).
 
 --sweep: the block-count sweep of tests/test_band_narrow_gpu.py (band_util.SWEEP_BOX, SWEEP_OCP)
 through the 8 x 8 reduction, Full x 2 + Simplified x 1 (PGF_BCR_PAIRS, PGF_BCR_FUSED,
@@ -17,9 +14,9 @@ plan the switches in the environment give that block count (band_util.bcr_launch
 arithmetic of sp_launch_bcr_solve restated on the host), which the parent test checks, so that a
 variant cannot quietly run the same plan as another.
 
-Prints "route <name> bw <bw>: <route>" per problem, the route read from the plan's block size
-and the environment, and (default mode) checked against the library: only the guarded cyclic
-reductions leave a residual in pgf_refinement_stats."""
+Prints "route <name> bw <bw>: <route>" per problem, the route read from the plan's block size,
+and (default mode) checked against the library: the guarded cyclic reductions leave a residual in
+pgf_refinement_stats."""
 import os
 import sys
 
@@ -31,19 +28,14 @@ from pygradflow_amd import problems  # noqa: E402
 from oracle import newton_oracle as O  # noqa: E402  (test infrastructure: the checker)
 from tests.band_util import SWEEP_BOX, SWEEP_OCP, bcr_launch_plan_from_env, plan_of  # noqa: E402
 
-SEQ = bool(os.environ.get("PGF_BAND_SEQ"))
-
 
 def rel(a, b):
     return float(np.max(np.abs(a - b)) / max(1.0, np.max(np.abs(b)))) if a.size else 0.0
 
 
 def route_of(prob):
-    """Which solve the library runs for the problem: the walk takes every automatic plan of
-    bw <= 10 under PGF_BAND_SEQ."""
+    """Which solve the library runs for the problem: the cyclic reduction of the plan's block size."""
     plan = plan_of(prob)
-    if SEQ and plan.block is None and plan.bw <= 10:
-        return plan.bw, "walk"
     return plan.bw, f"bcr{plan.block_size}"
 
 
@@ -67,11 +59,10 @@ def check(name, prob, policies, want_bw=None, residual_tells=False):
             assert e <= 1e-10, (name, pol, k, e)
             assert n_neg == m, (name, pol, k, n_neg)
         if residual_tells:
-            # what the library itself says about the route: the walk overwrites the band and forms
-            # no residual (the handle's last relative residual stays at its initial 0), every
-            # cyclic reduction records one per step (never exactly 0 at these sizes)
+            # what the library itself says about the route: every cyclic reduction records a
+            # residual per step (never exactly 0 at these sizes; the handle's initial value is 0)
             last_rel = dn.refinement_stats()[2]
-            assert (last_rel == 0.0) == (route == "walk"), (name, route, last_rel)
+            assert last_rel != 0.0, (name, route, last_rel)
         dn.close()
     print(f"route {name} bw {bw}: {route}", flush=True)
     print(f"{name}: ok", flush=True)
@@ -94,9 +85,5 @@ else:
     worst = max(worst, check("box", problems.box_qp(4099, seed=2), long, want_bw=(1,), residual_tells=True))
     worst = max(worst, check("grid320", problems.grid_box_qp(9, 320), long, want_bw=(9, 10), residual_tells=True))
     worst = max(worst, check("mocp10", problems.multistate_ocp(400, 4, 2), long, want_bw=(9, 10), residual_tells=True))
-    if SEQ:
-        worst = max(worst, check("grid9x500", problems.grid_box_qp(9, 500, seed=3), long, want_bw=(9,), residual_tells=True))
-        for W, L in ((9, 155), (9, 156), (10, 118), (10, 119)):
-            worst = max(worst, check(f"grid{W}x{L}", problems.grid_box_qp(W, L, seed=L),
-                                     (("Full", 2), ("Simplified", 1)), want_bw=(9, 10)))
+    worst = max(worst, check("grid9x500", problems.grid_box_qp(9, 500, seed=3), long, want_bw=(9,), residual_tells=True))
     print("band ok, worst", worst, flush=True)

@@ -2,8 +2,8 @@
 bw 9 .. 10) against the CPU oracle, on every route a problem can take into it.
 
 Bars as in test_gpu_parity.py: masks bit-identical, x and y within 1e-10 relative, n_neg = m.
-The sequential band walk (PGF_BAND_SEQ=1, read once per process) and the launch-plan switches of
-the 8 x 8 reduction run in child processes: tests/test_gpu_schedules.py, tests/check_band.py.
+The launch-plan switches of the 8 x 8 reduction (read once per process) run in child processes:
+tests/test_gpu_schedules.py, tests/check_band.py.
 
 The banded path exposes no factorisation counter.  That the second Simplified step is a back-solve
 step is checked through its result where the test says so (section A, two Simplified steps, with
@@ -65,9 +65,9 @@ def test_auto_route_constrained_indefinite(pgf, shape):
 
 @pytest.mark.parametrize("W,L", [(9, 155), (9, 156), (9, 320), (10, 118), (10, 119), (10, 300)])
 def test_auto_route_around_the_walk_panel(pgf, W, L):
-    """N just below, just above and well above one LDS panel of the sequential walk (1396 rows
-    at ldb 10, 1181 at ldb 12): 1395, 1404, 2880 and 1180, 1190, 3000.  (The walk itself runs
-    these sizes in tests/check_band.py under PGF_BAND_SEQ=1.)"""
+    """N = 1395, 1404, 2880 and 1180, 1190, 3000 on the B = 16 reduction: just below, just above
+    and well above what was one LDS panel of the retired sequential band walk (1396 rows at ldb 10,
+    1181 at ldb 12), the route these bandwidths once took."""
     from pygradflow_amd import problems
 
     prob = _forced(problems.grid_box_qp(W, L, seed=L))
@@ -131,10 +131,8 @@ def _block_in_use(prob):
 
 def _badly_placed(prob):
     """Variable whose diagonal entry the route in use takes as a pivot as it stands: the head of
-    block 1 of a cyclic reduction (inverted unpivoted by level one), the first row of the
-    sequential walk (block size 0)."""
-    B = _block_in_use(prob)
-    return head_of_first_eliminated(prob, B) if B else int(np.nonzero(plan_of(prob).pos == 0)[0][0])
+    block 1 of the cyclic reduction (inverted unpivoted by level one)."""
+    return head_of_first_eliminated(prob, _block_in_use(prob))
 
 
 @pytest.mark.parametrize("bw", [9, 10])

@@ -42,6 +42,12 @@ def test_block_size_rule(bw, B):
     assert block_size_for(bw) == B
 
 
+def test_every_supported_bandwidth_gets_a_cyclic_reduction():
+    """No bandwidth of the banded path is left without a block size (there is no other route)."""
+    for bw in range(MAX_BANDWIDTH + 1):
+        assert block_size_for(bw) in (8, 16, 32, 64), bw
+
+
 def test_block_size_of_plans():
     assert _plan(problems.multistate_ocp(100, 8, 4)).block_size == 32
     assert _plan(problems.multistate_ocp(100, 16, 8)).block_size == 64

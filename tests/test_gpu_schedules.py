@@ -37,7 +37,6 @@ BAND_VARIANTS = {
     "paired_levels": {},                              # default: two levels per launch where launch-bound
     "one_level_per_launch": {"PGF_BCR_PAIRS": "0"},
     "separate_invert_reduce": {"PGF_BCR_FUSED": "0"},
-    "sequential_walk": {"PGF_BAND_SEQ": "1"},         # the diagnostic route: one wavefront walks the band
 }
 
 
@@ -49,24 +48,20 @@ def _routes(stdout):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", sorted(BAND_VARIANTS))
 def test_banded_schedule_variant_matches_oracle(gpu_available, name):
-    """tests/check_band.py: banded OCP (bw 6), tridiagonal box QP (churning mask) and two problems
-    of half-bandwidth 10 against the CPU oracle under each cyclic-reduction schedule (8 x 8
-    blocks up to bw 8, B = 16 for 9 .. 10) and through the sequential band walk, which then also
-    runs a four-panel problem of half-bandwidth 9 and sizes around its LDS panel."""
+    """tests/check_band.py: banded OCP (bw 6), tridiagonal box QP (churning mask), two problems
+    of half-bandwidth 10 and one of half-bandwidth 9 against the CPU oracle under each
+    cyclic-reduction schedule (8 x 8 blocks up to bw 8, B = 16 for 9 .. 10)."""
     if not gpu_available:
         pytest.skip("needs a GPU")
     env = dict(os.environ)
-    env.pop("PGF_BAND_SEQ", None)
     env.update(BAND_VARIANTS[name])
     out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "check_band.py")], env=env,
                          cwd=REPO, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "band ok" in out.stdout
     routes = _routes(out.stdout)
-    if name == "sequential_walk":
-        assert len(routes) == 9 and set(routes.values()) == {"walk"}, routes
-    else:
-        assert routes == {"ocp": "bcr8", "box": "bcr8", "grid320": "bcr16", "mocp10": "bcr16"}, routes
+    assert routes == {"ocp": "bcr8", "box": "bcr8", "grid320": "bcr16", "mocp10": "bcr16",
+                      "grid9x500": "bcr16"}, routes
 
 
 BAND_SWEEP_VARIANTS = {
@@ -99,7 +94,6 @@ def test_banded_block_count_sweep_under_schedule_variant(gpu_available, name):
     if not gpu_available:
         pytest.skip("needs a GPU")
     env = dict(os.environ)
-    env.pop("PGF_BAND_SEQ", None)
     env.update(BAND_SWEEP_VARIANTS[name])
     out = subprocess.run([sys.executable, os.path.join(REPO, "tests", "check_band.py"), "--sweep"], env=env,
                          cwd=REPO, capture_output=True, text=True, timeout=600)

@@ -4,8 +4,7 @@ Simplified back-solve step of DeviceNewton, the dense path on the same problem w
 
     python tools/time_wide_band.py [--steps K] [--quick] [--narrow]
 
---narrow: the bw 9 .. 10 problems instead (automatic block size: B = 16; with PGF_BAND_SEQ=1 in the
-environment the sequential band walk, the route these problems took before).
+--narrow: the bw 9 .. 10 problems instead (automatic block size: B = 16).
 """
 import argparse
 import json
@@ -70,8 +69,7 @@ def main():
         row = {"case": name, "N": n + m, "bw": plan.bw, "B": plan.block_size}
         if a.narrow:
             a.quick = True
-            walk = os.environ.get("PGF_BAND_SEQ") and plan.bw <= 10
-            row["route"] = "walk" if walk else f"bcr{plan.block_size}"
+            row["route"] = f"bcr{plan.block_size}"
         t = device_times(prob, a.steps)
         row["wide_full_ms"] = 1e3 * t["Full"]
         row["wide_full_steps_per_s"] = 1.0 / t["Full"]
