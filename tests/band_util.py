@@ -1,4 +1,5 @@
-"""Helpers shared by the banded-path GPU tests (test_band_wide_gpu.py, test_band_narrow_gpu.py).
+"""Helpers shared by the banded-path GPU tests (test_band_wide_gpu.py, test_band_narrow_gpu.py,
+test_border_gpu.py, test_border_edges_gpu.py).
 
 Bars as in test_gpu_parity.py: masks bit-identical, x and y within 1e-10 relative."""
 
@@ -124,12 +125,53 @@ def band_problem(n, d, seed, bw, lb=None, ub=None):
                                            lb, ub)
 
 
-def plan_of(prob):
-    """The band plan the solvers build for the problem (automatic or forced block size)."""
+def bordered_lq(n0, bw, mloc, kv, kc, seed, block=None, bound=0.5):
+    """A band plus an explicit border of k = kv + kc nodes, every size exact (host only):
+
+      n0    band variables: H banded with half-width bw, diagonal in [1, 2], off-diagonals
+            0.04 U(0.5, 1) (band_problem);
+      mloc  local constraints x[a] - c x[a + 1] = b, c in U(0.5, 1), a spread evenly: B gets
+            negative pivots of its own (mloc <= n0 - 1);
+      kv    global variables behind the band ones, coupled to every band variable through H with
+            U(-1, 1) 0.3 / sqrt(n0), diagonal in [1, 2];
+      kc    dense constraint rows over all n = n0 + kv variables, N(0, 1) / sqrt(n);
+      box   [-bound, bound] on every variable, q ~ N(0, 1), b ~ 0.1 N(0, 1).
+
+    prob.pgf_border lists the kv variables and the kc dense rows, so k = kv + kc and
+    Nb = n0 + mloc whatever select_border would find; block: a forced pgf_band_block."""
+    from pygradflow_amd import problems
+
+    assert n0 >= 1 and 0 <= mloc <= max(n0 - 1, 0) and kv >= 0 and kc >= 0 and kv + kc >= 1
+    rng = np.random.default_rng(seed)
+    n, m = n0 + kv, mloc + kc
+    wb = min(bw, n0 - 1)
+    offs = [k for k in range(-wb, wb + 1) if k != 0]
+    vals = {k: 0.04 * rng.uniform(0.5, 1.0, n0 - k) for k in range(1, wb + 1)}
+    Hb = sps.diags(rng.uniform(1.0, 2.0, n0))
+    if offs:
+        Hb = Hb + sps.diags([vals[abs(k)] for k in offs], offs, shape=(n0, n0))
+    G = sps.csr_matrix(rng.uniform(-1.0, 1.0, (n0, kv)) * 0.3 / np.sqrt(n0))
+    H = sps.bmat([[Hb, G], [G.T, sps.diags(rng.uniform(1.0, 2.0, kv))]], format="csr")
+    a = (np.arange(mloc) * (n0 - 1)) // max(mloc, 1)
+    loc = sps.csr_matrix((np.concatenate([np.ones(mloc), -rng.uniform(0.5, 1.0, mloc)]),
+                          (np.concatenate([np.arange(mloc)] * 2), np.concatenate([a, a + 1]))), shape=(mloc, n))
+    A = sps.vstack([loc, sps.csr_matrix(rng.standard_normal((kc, n)) / np.sqrt(n))], format="csr")
+    prob = problems.LinearQuadraticProblem(H, rng.standard_normal(n), A, 0.1 * rng.standard_normal(m),
+                                           np.full(n, -bound), np.full(n, bound))
+    prob.pgf_border = [n0 + j for j in range(kv)] + [n + mloc + r for r in range(kc)]
+    if block:
+        prob.pgf_band_block = block
+    return prob
+
+
+def plan_of(prob, border=None):
+    """The band plan the solvers build for the problem (automatic or forced block size; border:
+    the problem's own pgf_border unless given)."""
     from pygradflow_amd.sparse import BandPlan
 
     return BandPlan(prob.hess_sparse(), prob.jac_sparse(), prob.num_vars, prob.num_cons,
-                    block=getattr(prob, "pgf_band_block", None))
+                    block=getattr(prob, "pgf_band_block", None),
+                    border=getattr(prob, "pgf_border", None) if border is None else border)
 
 
 def head_of_first_eliminated(prob, block):
@@ -142,7 +184,8 @@ def head_of_first_eliminated(prob, block):
 
 def refined_solve(K, rhs):
     """float64 solve followed by two refinement steps whose residual is accumulated in
-    np.longdouble; returns (refined, plain float64) solutions."""
+    np.longdouble; returns (refined, plain float64) solutions.  rhs: a vector, or right-hand sides
+    in columns."""
     plain = np.linalg.solve(K, rhs)
     Kl, bl = K.astype(np.longdouble), rhs.astype(np.longdouble)
     x = plain.astype(np.longdouble)

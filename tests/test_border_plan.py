@@ -11,6 +11,7 @@ from scipy.sparse.csgraph import reverse_cuthill_mckee
 from oracle import newton_oracle as O
 from pygradflow_amd import problems
 from pygradflow_amd.sparse import MAX_BANDWIDTH, BandPlan
+from tests.band_util import bordered_lq
 
 
 def _plan(prob, border):
@@ -127,6 +128,26 @@ def test_explicit_border_is_honoured():
         _plan(prob, [n + 1])
     with pytest.raises(ValueError):
         _plan(prob, "widest")
+
+
+@pytest.mark.parametrize("k", [33, 48, 49])
+def test_layout_at_padded_widths_48_and_64(k):
+    """k = 33, 48 (kp = 48: the first and the last width of that padding) and 49 (kp = 64), border
+    variables and constraints mixed, one border variable active and one not: C, the lower triangle
+    of D and the padding land where the device reads them."""
+    kv = k // 3
+    prob = bordered_lq(45, 2, 12, kv, k - kv, seed=k)
+    n, m = prob.num_vars, prob.num_cons
+    plan = _plan(prob, prob.pgf_border)
+    assert plan.k == k and plan.kp == (48 if k <= 48 else 64) and plan.Nb == 57 and plan.supported
+    assert list(plan.border) == list(range(45, n)) + list(range(n + 12, n + m))
+    assert np.array_equal(plan.pos[plan.border], 57 + np.arange(k))
+    hv, jv = plan.values(prob.hess_sparse(), prob.jac_sparse())
+    mask = np.random.default_rng(k).uniform(size=n) < 0.4
+    mask[45], mask[46] = True, False
+    lamb, rho = 0.8, 1.7
+    assert np.array_equal(restate(plan, hv, jv, mask, lamb, lamb / (1.0 + lamb * rho)),
+                          oracle_full(prob, mask, lamb, rho, plan.pos))
 
 
 def test_more_than_64_border_nodes_is_unsupported():
