@@ -446,6 +446,19 @@ int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
  * their rank-m term from G instead of the virtual column blocks (a factorisation that was
  * discarded and enqueued again counts once).  Either pointer may be NULL. */
 int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram);
+/* Counters of the dense factorisations by how the step's head -- K's assembly and the condensed
+ * system's panel -- was enqueued (tests; DESIGN.md 4.1b, PGF_HEAD_FUSED): fused -- beside the
+ * first diagonal chain, in its launch; plain -- as launches of their own in front of it (a
+ * factorisation that was discarded and enqueued again counts once).  Either pointer may be NULL. */
+int pgf_debug_head_stats(pgf_handle h, int *fused, int *plain);
+/* The unit list of the fused head, walked on the host (no GPU) for a reduced size: nI inactive
+ * variables, m constraints, condensed != 0: N = nI and a panel V of m columns padded to mp = a
+ * multiple of 32; else N = nI + m and no panel.  Counts are ADDED per entry: k_units (N x N) --
+ * units of the chain's launch that write the entry of K; k_head (N x N) -- the same for the head
+ * launch in front; v_units ((nI + 1) x mp, the tail row last) -- units that write the entry of V;
+ * n_units -- the length of the list (for N <= 256 the panel's tiles alone; no head is fused for
+ * such a size).  Any pointer may be NULL. */
+int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head, int *v_units, int *n_units);
 /* the handle's border size and the factor / solve phases of the bordered route enqueued since
  * pgf_sparse_set_border (tests: a step that keeps its factor runs the solve phase only) */
 int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves);

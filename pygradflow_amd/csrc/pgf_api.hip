@@ -567,7 +567,10 @@ static bool gram_build(pgf_handle h) {
 static void gram_uncount(pgf_handle h) {
   if (h->fac_counted) --h->cond_since_upload;
   if (h->fac_used_gram) --h->stat_gram_factors;
+  if (h->fac_head == 1) --h->stat_head_fused;
+  if (h->fac_head == 2) --h->stat_head_plain;
   h->fac_counted = h->fac_used_gram = false;
+  h->fac_head = 0;
 }
 
 // sol <- K^{-1} rhs with the current LDL^T factor (rhs, sol: N-vectors in the order
@@ -593,6 +596,26 @@ static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
   return hipGetLastError();
 }
 
+// the assembly operands of a head descriptor (m: the constraint rows that go into K)
+static LdltHead head_assembly(pgf_handle h, int nI, int m) {
+  LdltHead hw;
+  hw.H = h->H;
+  hw.ldh = h->ldh;
+  hw.J = h->J;
+  hw.ldj = h->ldj;
+  hw.idxI = h->idxI;
+  hw.nI = nI;
+  hw.m = m;
+  hw.lamb = h->lamb;
+  hw.delta = h->delta;
+  return hw;
+}
+// pgf_debug_head_stats: the factorisation being enqueued, by kind (undone by gram_uncount)
+static void count_head(pgf_handle h, bool fused) {
+  ++(fused ? h->stat_head_fused : h->stat_head_plain);
+  h->fac_head = fused ? 1 : 2;
+}
+
 // enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in row N
 static int factor_async(pgf_handle h, bool with_rhs) {
   if (h->sparse) return band_factor_async(h);
@@ -601,6 +624,7 @@ static int factor_async(pgf_handle h, bool with_rhs) {
   h->fac.vdepth = 0;
   h->fac.vneg = 0;
   h->fac_counted = h->fac_used_gram = false;
+  h->fac_head = 0;
   if (h->condensed) {
     DenseLdlt &f = h->fac;
     HIPCHK(h, condensed_reserve(h));
@@ -617,6 +641,27 @@ static int factor_async(pgf_handle h, bool with_rhs) {
       // virtual blocks would have produced on the way (in place of k_virtual_diag: as many launches)
       ++h->stat_gram_factors;
       h->fac_used_gram = true;
+      if (ldlt_head_wanted(f, nI)) {
+        // all of it beside the first diagonal chain, which reads the first 256 rows only
+        LdltHead hw = head_assembly(h, nI, 0);
+        hw.G = h->G;
+        hw.ldg = h->ldg;
+        hw.V = f.V;
+        hw.ldv = f.ldv;
+        hw.mp = mp;
+        hw.pm = h->m;
+        hw.vd = f.vd;
+        hw.rhs_y = with_rhs ? h->rhs + nI : nullptr;
+        if (with_rhs) {
+          hw.crhs = h->rhs;
+          hw.crhs_out = f.K + (int64_t)nI * f.ldk;
+        }
+        count_head(h, true);
+        HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0), &hw));
+        f.N = nI;
+        return PGF_OK;
+      }
+      count_head(h, false);
       launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
                           f.flags, 4 + LDLT_UPD_COUNTERS, nullptr, nullptr, 0, h->G, h->ldg);
       launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta,
@@ -628,6 +673,7 @@ static int factor_async(pgf_handle h, bool with_rhs) {
       return PGF_OK;
     }
     f.vdepth = mp;
+    count_head(h, false);
     // A = H[I,I] + lamb I (the assembly kernel with no constraint rows), V = J_I^T, b_y in row nI
     // (the assembly launch also clears the factorisation's flags and copies b_x into row nI)
     launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
@@ -641,6 +687,18 @@ static int factor_async(pgf_handle h, bool with_rhs) {
   }
   // (the assembly launch also clears the factorisation's flags and copies the rhs into row N)
   h->fac.flags_zeroed = h->N > 0;
+  if (ldlt_head_wanted(h->fac, h->N)) {
+    LdltHead hw = head_assembly(h, h->nI, h->m);
+    if (with_rhs) {
+      hw.row_src = h->rhs;
+      hw.row_dst = h->fac.K + (int64_t)h->N * h->fac.ldk;
+      hw.row_n = h->N;
+    }
+    count_head(h, true);
+    HIPCHK(h, ldlt_factor_async(h->fac, h->N, h->N + (with_rhs ? 1 : 0), &hw));
+    return PGF_OK;
+  }
+  count_head(h, false);
   launch_assemble_kkt(h->stream, h->fac.K, h->fac.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, h->nI, h->m,
                       h->lamb, h->delta, h->fac.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
                       h->fac.K + (int64_t)h->N * h->fac.ldk, h->N);
@@ -1112,6 +1170,7 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   hipStream_t s = h->stream;
   h->fused_eval_done = false;
   h->fac_counted = h->fac_used_gram = false;  // (set by factor_async, if this step factorises)
+  h->fac_head = 0;
   if (h->sparse) return band_step_async(h, did_factor);
   if (h->nA == 0) {  // the residual and the reduced right-hand side in one launch
     launch_residual_rhs(s, h->n, h->m, h->nI, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y, h->g,
@@ -1682,6 +1741,49 @@ int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gra
   if (!h) return PGF_INVALID;
   if (builds) *builds = h->stat_gram_builds;
   if (factorisations_with_gram) *factorisations_with_gram = h->stat_gram_factors;
+  return PGF_OK;
+}
+
+int pgf_debug_head_stats(pgf_handle h, int *fused, int *plain) {
+  if (!h) return PGF_INVALID;
+  if (fused) *fused = h->stat_head_fused;
+  if (plain) *plain = h->stat_head_plain;
+  return PGF_OK;
+}
+
+// The head workers' unit list, walked on the host (no GPU): k_units[i * N + j] counts the units
+// that write entry (i, j) of K, k_head the same for the head launch's row groups, v_units the
+// units per entry of V ((nI + 1) x mp: the tail row last) -- N = nI in the condensed layout
+// (V: m columns padded to mp = a multiple of 32), nI + m in the natural one (no V).  The entry
+// tests are those of b_assemble_kkt and the panel's tile body.
+int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head, int *v_units, int *n_units) {
+  if (nI < 0 || m < 0) return PGF_INVALID;
+  const int N = condensed ? nI : nI + m, mp = condensed ? (m + 31) / 32 * 32 : 0;
+  // (the list as head_unit defines it; ldlt_head_wanted fuses nothing for N <= 256, whose list is
+  // the panel's tiles alone)
+  const int total = head_asm_units(N) + head_panel_units(nI, mp);
+  if (n_units) *n_units = total;
+  auto rows = [&](int *cnt, int cb, int rg) {
+    if (cb * 256 >= N || cb * 256 > rg * HEAD_ASM_ROWS + HEAD_ASM_ROWS - 1) return;
+    for (int i = rg * HEAD_ASM_ROWS; i < (rg + 1) * HEAD_ASM_ROWS; ++i)
+      for (int j = cb * 256; j < cb * 256 + 256; ++j)
+        if (i < N && j <= i && j < N) ++cnt[(size_t)i * N + j];
+  };
+  if (k_head)
+    for (int rg = 0; rg < (std::min(N, LDLT_OB) + HEAD_ASM_ROWS - 1) / HEAD_ASM_ROWS; ++rg) rows(k_head, 0, rg);
+  for (int u = 0; u < total; ++u) {
+    const HeadUnit hu = head_unit(u, N, nI, mp);
+    if (hu.kind == 0 && k_units) rows(k_units, hu.a, hu.b);
+    if (hu.kind == 1 && v_units) {
+      for (int i = hu.a * 32; i < hu.a * 32 + 32; ++i)
+        for (int r = hu.b * 32; r < hu.b * 32 + 32; ++r)
+          if (i < nI && r < mp) ++v_units[(size_t)i * mp + r];
+      if (hu.a == 0)
+        for (int r = hu.b * 32; r < hu.b * 32 + 32; ++r)
+          if (r < mp) ++v_units[(size_t)nI * mp + r];
+    }
+    if (hu.kind < 0) return PGF_INVALID;
+  }
   return PGF_OK;
 }
 

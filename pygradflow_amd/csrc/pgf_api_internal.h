@@ -105,6 +105,10 @@ struct pgf_solver {
   // what the factorisation in flight added to the counters (taken back when it is discarded)
   bool fac_counted = false, fac_used_gram = false;
   int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
+  // the factorisation in flight took the step's head beside its first chain (1) or not (2);
+  // pgf_debug_head_stats counts both kinds
+  int fac_head = 0;
+  int stat_head_fused = 0, stat_head_plain = 0;
   // The unsymmetric formulations (pgf_set_formulation; the section in front of pgf_factor): form --
   // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
   // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric

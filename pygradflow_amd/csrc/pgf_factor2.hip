@@ -22,6 +22,9 @@
 //                               plan (plan_updates): column blocks are kept complete only when
 //                               the chain is about to need them, the rest on a budget that
 //                               hides behind the chain; W = L D formed from L and D on the fly
+//   k_chain_head                the FIRST chain's launch of a dense Newton step: the same roles, the
+//                               other workgroups write the part of K and of the panel V that D(0)
+//                               does not read (LdltHead) instead of update tiles
 //   k_trsm_block   T(k)         all rows below the block: X = T inv(L_kk)^T blocked by 64
 //                               (MFMA, B operands straight from L2 into registers); writes
 //                               W = X = L D (operand of k_update_diag) and L = X D^-1.
@@ -35,7 +38,9 @@
 // Batched mode (kb_*): the same chain / T(k) / update-diag device code with a batch dimension.
 #include <hip/hip_ext.h>
 
+#include "pgf_head_dev.h"
 #include "pgf_internal.h"
+#include "pgf_kernels.h"
 #include "pgf_ldlt_dev.h"
 
 #include <algorithm>
@@ -1627,6 +1632,76 @@ __global__ __launch_bounds__(1024) void k_chain_update(double *K, int64_t ldk, i
   update_worker(smem, K, ldk, dvec, N, nrows, jobs, uv, ctr);
 }
 
+// ------------------------------------------------------------------ D(0) beside the step's head
+// The first chain's launch of a step (LdltHead, pgf_internal.h): the same grid and roles as
+// k_chain_update, but the workgroups beside the chain and its helpers write what the step has
+// not assembled yet -- K's rows below the first diagonal block and the panel V -- instead of
+// update tiles: D(0) reads K[0:256, 0:256] alone, which the launch in front (k_assemble_kkt_head)
+// has written.  Nobody waits for anybody: the roles write disjoint cache lines, and the first
+// reader of the workers' entries is a later launch.  A kernel of its own: k_diag_chain and
+// k_chain_update keep their code.
+static_assert(ASM_ROWS == HEAD_ASM_ROWS, "head_unit's row groups are b_assemble_kkt's");
+// Worker w of W: the four 256-lane quarters of the workgroup take units 4 w + q, 4 (w + W) + q, ...
+// of head_unit's list, one each per round.  The panel's tiles go through the kernel's LDS buffer
+// (two sets of four tiles, by the round's parity: ONE barrier per round keeps a tile's readers
+// ahead of its next writers); every quarter runs every round, so all reach the barriers together.
+__device__ __forceinline__ void head_worker(unsigned char *smem, double *K, int64_t ldk, const LdltHead &hw,
+                                            int w, int W) {
+  CondTile *tiles = reinterpret_cast<CondTile *>(smem);
+  static_assert(8 * sizeof(CondTile) <= CH_SMEM, "two sets of four tiles");
+  const int q = threadIdx.x >> 8, t = threadIdx.x & 255;
+  const int N = hw.nI + hw.m, mp = hw.V ? hw.mp : 0;
+  const int nasm = head_asm_units(N), total = nasm + head_panel_units(hw.nI, mp);
+  const double ginv = 1.0 / hw.delta;
+  int par = 0;
+  for (int base = 4 * w; base < total; base += 4 * W, par ^= 4) {
+    const HeadUnit hu = head_unit(base + q < total ? base + q : -1, N, hw.nI, mp);
+    if (hu.kind == 0) {
+      if (hw.G)
+        b_assemble_kkt<ASM_ROWS, true>(hu.a, hu.b, t, K, ldk, hw.H, hw.ldh, hw.J, hw.ldj, hw.idxI, hw.nI, hw.m,
+                                       hw.lamb, hw.delta, hw.G, hw.ldg, ginv);
+      else
+        b_assemble_kkt<ASM_ROWS, false>(hu.a, hu.b, t, K, ldk, hw.H, hw.ldh, hw.J, hw.ldj, hw.idxI, hw.nI, hw.m,
+                                        hw.lamb, hw.delta);
+    }
+    if (base + 3 < nasm) continue;  // (the whole workgroup: a round without a tile needs no barrier)
+    if (hu.kind == 1)
+      b_cond_panel_load(tiles[par + q], hu.a, hu.b, t, hw.V, hw.ldv, mp, hw.J, hw.ldj, hw.idxI, hw.nI, hw.pm,
+                        hw.vd, hw.rhs_y, hw.delta);
+    __syncthreads();
+    if (hu.kind == 1) b_cond_panel_store(tiles[par + q], hu.a, hu.b, t, hw.V, hw.ldv, mp, hw.nI);
+  }
+}
+
+template <bool HELP>
+__global__ __launch_bounds__(1024) void k_chain_head(double *K, int64_t ldk, int nb,
+                                                     double *__restrict__ dvec,
+                                                     double *__restrict__ dinv,
+                                                     int *__restrict__ flags,
+                                                     double *__restrict__ Linv,
+                                                     double *__restrict__ LinvT,
+                                                     long long *__restrict__ dbg, int *hc, int epoch,
+                                                     const LdltHead hw) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
+  const int b = (int)blockIdx.x;
+  if (b == 0) {
+    chain_body<HELP>(smem, K, ldk, 0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch);
+    return;
+  }
+  if (HELP && b == 8) {
+    helper_tiles(smem, K, ldk, 0, nb, dvec, hc, epoch, flags);
+    return;
+  }
+  if (HELP && b == 16) {
+    helper_inverses(smem, K, ldk, 0, nb, hc, epoch, flags, Linv, LinvT);
+    return;
+  }
+  if (HELP)
+    head_worker(smem, K, ldk, hw, b - 1 - (b > 8) - (b > 16), (int)gridDim.x - 3);
+  else
+    head_worker(smem, K, ldk, hw, b - 1, (int)gridDim.x - 1);
+}
+
 // the update role alone (per-kernel profiling, PGF_FUSED=0): same tiles, same job table
 __global__ __launch_bounds__(1024) void k_update_jobs(double *K, int64_t ldk,
                                                       const double *__restrict__ dvec, int N,
@@ -1956,6 +2031,17 @@ static bool fused() {
   return on;
 }
 
+// the step's head beside the first chain (k_chain_head); PGF_HEAD_FUSED=0: the assembly and the
+// panel as launches of their own in front of a plain first chain
+static bool head_fused() {
+  static const bool on = !(getenv("PGF_HEAD_FUSED") && atoi(getenv("PGF_HEAD_FUSED")) == 0);
+  return on;
+}
+bool ldlt_head_wanted(const DenseLdlt &f, int N) {
+  const bool per_kernel = f.prof && f.prof->enabled && f.prof->mode != 2;
+  return head_fused() && fused() && !per_kernel && N > LDLT_OB && f.vdepth == 0;
+}
+
 // PGF_CHAIN_TIMING=1 (diagnostic): the chain kernel of the FIRST block of every factorisation
 // stamps its phases into this buffer; ldlt_chain_timing_dump prints the last set
 static long long *g_chain_dbg = nullptr;
@@ -2122,13 +2208,15 @@ static void plan_updates(UpdPlan &pl, int N, int nrows, int OB, int budget, int 
   }
 }
 
-hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
+hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *head) {
+  if (head && (!ldlt_head_wanted(f, N) || head->nI + head->m != N)) return hipErrorInvalidValue;
   f.N = N;
   f.factored = false;
   hipStream_t s = f.stream;
   // flags [0, 4) and the update launches' tile counters behind them
   hipError_t e = hipSuccess;
-  if (!f.flags_zeroed) e = hipMemsetAsync(f.flags, 0, (4 + LDLT_UPD_COUNTERS) * sizeof(int), s);
+  // (with a head its first launch zeroes them, flags_zeroed or not)
+  if (!f.flags_zeroed && !head) e = hipMemsetAsync(f.flags, 0, (4 + LDLT_UPD_COUNTERS) * sizeof(int), s);
   f.flags_zeroed = false;
   if (e != hipSuccess) return e;
   static const int ncu = []() {
@@ -2309,7 +2397,24 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows) {
       hipLaunchKernelGGL(k_virtual_diag, dim3(nt * (nt + 1) / 2), dim3(256), 0, s, f.K, f.ldk, 0, nb0, f.V,
                          f.ldv, f.vd, vdepth, nrows);
     }
-    if (vdepth > 0 && lazy && plan.first.njobs > 0) {
+    if (head) {
+      // the first diagonal block's rows and the zeroing, then D(0) with the rest of the head's
+      // units on the other CUs; row nI of K needs the whole of V: a launch of its own behind them
+      launch_assemble_kkt_head(s, f.K, f.ldk, *head, f.flags, 4 + LDLT_UPD_COUNTERS);
+      const int units = head_asm_units(N) + head_panel_units(head->nI, head->V ? head->mp : 0);
+      const int workers = std::min((units + 3) / 4, ncu - 3);
+      const int ep = next_help_epoch();
+      span_begin(pr.chain_spans);
+      if (help)
+        hipLaunchKernelGGL(k_chain_head<true>, dim3(std::max(17, workers + 3)), dim3(1024), 0, s, f.K, f.ldk,
+                           OB, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, chain_dbg_buffer(), f.hctl, ep, *head);
+      else
+        hipLaunchKernelGGL(k_chain_head<false>, dim3(1 + workers), dim3(1024), 0, s, f.K, f.ldk, OB, f.dvec,
+                           f.dinv, f.flags, f.Linv, f.LinvT, chain_dbg_buffer(), f.hctl, ep, *head);
+      span_end(pr.chain_spans);
+      if (head->crhs)
+        launch_cond_rhs(s, head->nI, head->pm, head->V, head->ldv, head->crhs, head->delta, head->crhs_out);
+    } else if (vdepth > 0 && lazy && plan.first.njobs > 0) {
       launch_fused(0, std::min(OB, N), plan.first, f.flags + 4);
     } else {
       launch_d(0);

@@ -92,12 +92,78 @@ struct DenseLdlt {
   int status_words = 0;
 };
 
+// Head work of a dense Newton step (pgf_api.hip, factor_async): what the step writes in front of
+// a factorisation whose first diagonal chain reads nothing but K[0:256, 0:256].  Given to
+// ldlt_factor_async, the rows below 256 of the assembly and the panel V = J_I^T are written by
+// the idle workgroups of the first chain's launch (k_chain_head, pgf_factor2.hip) instead of by
+// launches of their own in front of it.  The operands are those of launch_assemble_kkt,
+// launch_cond_panel and launch_cond_rhs.
+struct LdltHead {
+  const double *H = nullptr, *J = nullptr;
+  int64_t ldh = 0, ldj = 0;
+  const int *idxI = nullptr;
+  int nI = 0, m = 0;  // m: constraint rows assembled into K (0 in the condensed order)
+  double lamb = 0, delta = 0;
+  const double *G = nullptr;  // the resident Gram matrix (condensed order) or null
+  int64_t ldg = 0;
+  const double *row_src = nullptr;  // natural order: copied to row_dst[0, row_n) (the rhs row)
+  double *row_dst = nullptr;
+  int row_n = 0;
+  double *V = nullptr;  // the panel (condensed order) or null: pm constraint columns padded to mp
+  int64_t ldv = 0;
+  int mp = 0, pm = 0;
+  double *vd = nullptr;
+  const double *rhs_y = nullptr;
+  // row nI of K <- crhs[0:nI] + V crhs[nI:] / delta behind the first chain's launch
+  // (launch_cond_rhs reads V); null: none
+  const double *crhs = nullptr;
+  double *crhs_out = nullptr;
+};
+#define HEAD_ASM_ROWS 8  // rows of an assembly unit (ASM_ROWS of pgf_head_dev.h), 256 columns
+// One unit of the head workers' list.  kind 0: assembly rows [8 b, 8 b + 8) x columns
+// [256 a, 256 a + 256) of K (what lies on or below the diagonal and inside N); kind 1: the
+// 32 x 32 tile of V at rows [32 a, 32 a + 32), columns [32 b, 32 b + 32), and for a == 0 the same
+// columns of the tail row nI and of vd; kind -1: past the end.
+struct HeadUnit {
+  int kind, a, b;
+};
+// assembly units: the row groups of rows >= 256, one unit per column block up to the diagonal's
+__host__ __device__ inline int head_asm_units(int N) {
+  const int nrg = (N + HEAD_ASM_ROWS - 1) / HEAD_ASM_ROWS, per = LDLT_OB / HEAD_ASM_ROWS;
+  int cnt = 0;
+  for (int B = 1; B * per < nrg; ++B) cnt += ((nrg < (B + 1) * per ? nrg : (B + 1) * per) - B * per) * (B + 1);
+  return cnt;
+}
+__host__ __device__ inline int head_panel_units(int nI, int mp) {
+  return (nI > 0 && mp > 0) ? ((nI + 31) / 32) * (mp / 32) : 0;
+}
+// THE unit -> (rows, columns) mapping, on the device (k_chain_head) and on the host
+// (pgf_debug_head_plan): assembly units first, band of 256 rows by band, a row group's column
+// blocks side by side; then the panel's tiles, a row of tiles side by side.
+__host__ __device__ inline HeadUnit head_unit(int u, int N, int nI, int mp) {
+  const int nrg = (N + HEAD_ASM_ROWS - 1) / HEAD_ASM_ROWS, per = LDLT_OB / HEAD_ASM_ROWS;
+  if (u < 0) return HeadUnit{-1, 0, 0};
+  for (int B = 1; B * per < nrg; ++B) {
+    const int cnt = ((nrg < (B + 1) * per ? nrg : (B + 1) * per) - B * per) * (B + 1);
+    if (u < cnt) return HeadUnit{0, u % (B + 1), B * per + u / (B + 1)};
+    u -= cnt;
+  }
+  if (u < head_panel_units(nI, mp)) return HeadUnit{1, u / (mp / 32), u % (mp / 32)};
+  return HeadUnit{-1, 0, 0};
+}
+
 hipError_t ldlt_alloc(DenseLdlt &f, int Nmax, hipStream_t stream);
 void ldlt_free(DenseLdlt &f);
 void ldlt_chain_discard(DenseLdlt &f, int word);
+// true: a factorisation of size N enqueued now takes an LdltHead (PGF_HEAD_FUSED, the production
+// launches, more than one outer block, no pre-eliminated panel: the virtual blocks' first launch
+// already carries update jobs that read the assembled K and V)
+bool ldlt_head_wanted(const DenseLdlt &f, int N);
 // enqueue the factorisation of the leading N x N lower triangle (+ rows up to nrows): the
-// look-ahead schedule of pgf_factor2.hip
-hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows);
+// look-ahead schedule of pgf_factor2.hip.  head (only where ldlt_head_wanted): K's assembly, the
+// panel and the zeroing of the flags are enqueued here, around the first chain -- the caller has
+// issued none of them.
+hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *head = nullptr);
 // G <- V V^T (lower triangle of n x n, row stride ldg) with the trailing update's own tiles: G is
 // zeroed, then C -= V diag(vd) V^T runs over the whole triangle as ONE virtual-only job (vd = -1
 // in all `depth' entries, depth a multiple of 32; V has row stride ldv).  ctr: a counter word of the

@@ -34,6 +34,10 @@ void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H,
                          double lamb, double delta, int *zero = nullptr, int nzero = 0,
                          const double *row_src = nullptr, double *row_dst = nullptr, int row_n = 0,
                          const double *G = nullptr, int64_t ldg = 0);
+// the first diagonal block's rows of the assembly described by hw (pgf_internal.h), the zeroing of
+// `zero' and the rhs row: the launch in front of a first chain that carries the rest (k_chain_head)
+struct LdltHead;
+void launch_assemble_kkt_head(hipStream_t s, double *K, int64_t ldk, const LdltHead &hw, int *zero, int nzero);
 void launch_copy(hipStream_t s, double *dst, const double *src, int n);
 void launch_copy_u8(hipStream_t s, uint8_t *dst, const uint8_t *src, int n);
 void launch_mask_diff(hipStream_t s, int n, const uint8_t *a, const uint8_t *b, int *out);

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "pgf_head_dev.h"
 #include "pgf_internal.h"
 
 #define ACTIVE_EPS 1e-8  // reference implicit_func.py:44
@@ -231,68 +232,7 @@ __device__ __forceinline__ void b_reduced_rhs(int n, int m, int nI, int nA, doub
 }
 
 // ---------------------------------------------------------------- K assembly (a10, a12)
-// Lower triangle of K = [[H[I,I] + lamb I, .],[J[:,I], -delta I]] gathered from the
-// device-resident H, J.  A workgroup covers ASM_ROWS rows x 256 columns (lanes run along
-// columns: coalesced stores, loads coalesced whenever I is contiguous); the column's index
-// in H / J is looked up once per lane.  One row per workgroup was dispatch-bound in the
-// batched step (1.6 M workgroups).
-// GRAM (the condensed system with the resident Gram matrix G = J^T J, pgf_api.hip): the H block
-// becomes H[I,I] + G[I,I] * ginv (ginv = 1 / delta), gathered in the same pass with the same
-// indices; the instantiations without it do not see the operand at all.
-#define ASM_ROWS 8
-template <int ROWS = ASM_ROWS, bool GRAM = false>
-__device__ __forceinline__ void b_assemble_kkt(double *__restrict__ K, int64_t ldk,
-                                               const double *__restrict__ H, int64_t ldh,
-                                               const double *__restrict__ J, int64_t ldj,
-                                               const int *__restrict__ idxI, int nI, int m,
-                                               double lamb, double delta,
-                                               const double *__restrict__ G = nullptr, int64_t ldg = 0,
-                                               double ginv = 0.0) {
-  const int N = nI + m;
-  const int i0 = blockIdx.y * ROWS;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if ((int)blockIdx.x * 256 >= N || (int)blockIdx.x * 256 > i0 + ROWS - 1) return;  // (whole workgroups only:
-                                                             // every lane may be asked for its row index)
-  const int gj = (j < nI) ? idxI[j] : 0;
-  // The rows' indices in H come from ONE vector load (lane u holds row i0 + u's) and reach the
-  // scalar unit through v_readlane: looked up row by row (`idxI[i]', a scalar load and its wait in
-  // front of every row's global load) the rows ran one after the other -- 0.9 ms for a batch of
-  // 256 x 1024^2, 2.4 TB/s.  Eight rows at a time: all loads of the group, then the stores.
-  static_assert(ROWS <= 64, "one lane per row of the workgroup");
-  const int lane = threadIdx.x & 63;
-  const int rowidx = (lane < ROWS && i0 + lane < nI) ? idxI[i0 + lane] : 0;
-  constexpr int GR = ROWS < 8 ? ROWS : 8;
-#pragma unroll
-  for (int r0 = 0; r0 < ROWS; r0 += GR) {
-    double v[GR], vg[GR];
-#pragma unroll
-    for (int u = 0; u < GR; ++u) {
-      const int i = i0 + r0 + u;
-      const int gi = __builtin_amdgcn_readlane(rowidx, r0 + u);
-      v[u] = 0.0;
-      if (GRAM) vg[u] = 0.0;
-      if (i < N && j <= i && j < N) {
-        if (i < nI) {
-          v[u] = H[(int64_t)gi * ldh + gj];
-          // (only G's lower triangle is ever written: ldlt_gram_async)
-          if (GRAM) vg[u] = G[(int64_t)max(gi, gj) * ldg + min(gi, gj)];
-        } else if (j < nI) {
-          v[u] = J[(int64_t)(i - nI) * ldj + gj];
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < GR; ++u) {
-      const int i = i0 + r0 + u;
-      if (i < N && j <= i && j < N) {
-        double w = v[u];
-        if (GRAM && i < nI) w += vg[u] * ginv;
-        if (i == j) w = (i < nI) ? w + lamb : -delta;
-        K[(int64_t)i * ldk + j] = w;
-      }
-    }
-  }
-}
+// (b_assemble_kkt: pgf_head_dev.h)
 
 __device__ __forceinline__ void b_copy(double *__restrict__ dst, const double *__restrict__ src,
     int n) {
@@ -616,7 +556,7 @@ __global__ __launch_bounds__(256) void k_assemble_kkt(double *__restrict__ K, in
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (row_src && j < row_n) row_dst[j] = row_src[j];
   }
-  b_assemble_kkt(K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta);
+  b_assemble_kkt(blockIdx.x, blockIdx.y, threadIdx.x, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta);
 }
 // the same with the Gram operand (a kernel of its own: k_assemble_kkt keeps its code and its
 // argument list)
@@ -631,7 +571,25 @@ __global__ __launch_bounds__(256) void k_assemble_kkt_gram(double *__restrict__ 
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (row_src && j < row_n) row_dst[j] = row_src[j];
   }
-  b_assemble_kkt<ASM_ROWS, true>(K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, G, ldg, ginv);
+  b_assemble_kkt<ASM_ROWS, true>(blockIdx.x, blockIdx.y, threadIdx.x, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, G, ldg, ginv);
+}
+
+// The head of a step whose assembly runs beside the first diagonal chain (LdltHead,
+// pgf_internal.h): only the row groups of the first diagonal block, rows [0, min(256, N)) -- one
+// column block --, the zeroing of the factorisation's words, which the chain's own launch cannot
+// do for itself, and the rhs row, copied by all workgroups together.  Grid (1, row groups).
+template <bool GRAM>
+__global__ __launch_bounds__(256) void k_assemble_kkt_head(double *__restrict__ K, int64_t ldk,
+    const double *__restrict__ H, int64_t ldh, const double *__restrict__ J, int64_t ldj,
+    const int *__restrict__ idxI, int nI, int m, double lamb, double delta, int *__restrict__ zero,
+    int nzero, const double *__restrict__ row_src, double *__restrict__ row_dst, int row_n,
+    const double *__restrict__ G, int64_t ldg, double ginv) {
+  if (zero && blockIdx.y == 0)
+    for (int t = threadIdx.x; t < nzero; t += 256) zero[t] = 0;
+  if (row_src)
+    for (int j = blockIdx.y * 256 + threadIdx.x; j < row_n; j += gridDim.y * 256) row_dst[j] = row_src[j];
+  b_assemble_kkt<ASM_ROWS, GRAM>(0, blockIdx.y, threadIdx.x, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta, G,
+                                 ldg, ginv);
 }
 
 __global__ void k_copy(double *__restrict__ dst, const double *__restrict__ src, int n) {
@@ -823,6 +781,20 @@ void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H,
   else
     hipLaunchKernelGGL(k_assemble_kkt, grid, dim3(256), 0, s, K, ldk, H, ldh, J, ldj, idxI, nI, m, lamb, delta,
                        zero, nzero, row_src, row_dst, std::min(row_n, N));
+}
+
+void launch_assemble_kkt_head(hipStream_t s, double *K, int64_t ldk, const LdltHead &hw, int *zero, int nzero) {
+  const int N = hw.nI + hw.m;
+  if (!N) return;
+  const dim3 grid(1, (std::min(N, LDLT_OB) + ASM_ROWS - 1) / ASM_ROWS);
+  if (hw.G)
+    hipLaunchKernelGGL(k_assemble_kkt_head<true>, grid, dim3(256), 0, s, K, ldk, hw.H, hw.ldh, hw.J, hw.ldj,
+                       hw.idxI, hw.nI, hw.m, hw.lamb, hw.delta, zero, nzero, hw.row_src, hw.row_dst,
+                       std::min(hw.row_n, N), hw.G, hw.ldg, 1.0 / hw.delta);
+  else
+    hipLaunchKernelGGL(k_assemble_kkt_head<false>, grid, dim3(256), 0, s, K, ldk, hw.H, hw.ldh, hw.J, hw.ldj,
+                       hw.idxI, hw.nI, hw.m, hw.lamb, hw.delta, zero, nzero, hw.row_src, hw.row_dst,
+                       std::min(hw.row_n, N), (const double *)nullptr, (int64_t)0, 0.0);
 }
 
 void launch_copy(hipStream_t s, double *dst, const double *src, int n) {
@@ -1348,7 +1320,7 @@ __global__ __launch_bounds__(256) void kb_assemble(const BInst *__restrict__ tab
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j < N) I.K[(int64_t)N * I.ldk + j] = I.rhs[j];
   }
-  b_assemble_kkt<KB_ASM_ROWS>(I.K, I.ldk, I.H, I.ldh, I.J, I.ldj, I.idxI, nI, m, lamb, delta);
+  b_assemble_kkt<KB_ASM_ROWS>(blockIdx.x, blockIdx.y, threadIdx.x, I.K, I.ldk, I.H, I.ldh, I.J, I.ldj, I.idxI, nI, m, lamb, delta);
 }
 
 __global__ __launch_bounds__(256) void kb_step_update(const BInst *__restrict__ tab, int n,
@@ -1804,37 +1776,16 @@ void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchSc
 // row nI of K (b_x) into b_x + J_I^T b_y / delta on the way.
 //   S s_x = b_x + J_I^T b_y / delta,      s_y = (J_I s_x - b_y) / delta.
 
-// V[i][r] = J[r][idxI[i]] (r < m), 0 for the padding columns: 32 x 32 tiles through LDS, reads
-// run along i (contiguous whenever I is), writes along r
-__device__ __forceinline__ void b_cond_tail(double *__restrict__ Vrow, double *__restrict__ vd, int r,
-                                            int mp, int m, const double *__restrict__ rhs_y, double delta) {
-  if (r >= mp) return;
-  Vrow[r] = (rhs_y && r < m) ? rhs_y[r] : 0.0;
-  vd[r] = -1.0 / delta;
-}
-// (the workgroups of the first column also write k_cond_tail's 32 entries of their row group)
+// (b_cond_tail and the tile body: pgf_head_dev.h)
 __global__ __launch_bounds__(256) void k_cond_panel(double *__restrict__ V, int64_t ldv, int mp,
                                                     const double *__restrict__ J, int64_t ldj,
                                                     const int *__restrict__ idxI, int nI, int m,
                                                     double *__restrict__ vd, const double *__restrict__ rhs_y,
                                                     double delta) {
-  __shared__ double tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int i0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-  if (blockIdx.x == 0 && ty == 0) b_cond_tail(V + (int64_t)nI * ldv, vd, r0 + tx, mp, m, rhs_y, delta);
-  const int i = i0 + tx;
-  const int col = i < nI ? idxI[i] : 0;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int r = r0 + ty + 8 * p;
-    tile[ty + 8 * p][tx] = (r < m && i < nI) ? J[(int64_t)r * ldj + col] : 0.0;
-  }
+  __shared__ CondTile tile;
+  b_cond_panel_load(tile, blockIdx.x, blockIdx.y, threadIdx.x, V, ldv, mp, J, ldj, idxI, nI, m, vd, rhs_y, delta);
   __syncthreads();
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const int ii = i0 + ty + 8 * p, r = r0 + tx;
-    if (ii < nI && r < mp) V[(int64_t)ii * ldv + r] = tile[tx][ty + 8 * p];
-  }
+  b_cond_panel_store(tile, blockIdx.x, blockIdx.y, threadIdx.x, V, ldv, mp, nI);
 }
 
 // row nI of V <- the constraint part of the right-hand side (or zeros), vd <- -1 / delta
