@@ -451,6 +451,11 @@ int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gra
  * first diagonal chain, in its launch; plain -- as launches of their own in front of it (a
  * factorisation that was discarded and enqueued again counts once).  Either pointer may be NULL. */
 int pgf_debug_head_stats(pgf_handle h, int *fused, int *plain);
+/* Counters of the qp steps enqueued with the residual check and the evaluation ahead, by their
+ * launch sequence behind the back-solve (tests; DESIGN.md 4d, PGF_STEP_FUSED): fused_steps -- s_y in
+ * the step update, one row launch over J and H, one combine launch; plain_steps -- the separate
+ * launches (a step that was discarded and enqueued again counts twice).  Either pointer may be NULL. */
+int pgf_debug_tail_stats(pgf_handle h, int *fused_steps, int *plain_steps);
 /* The unit list of the fused head, walked on the host (no GPU) for a reduced size: nI inactive
  * variables, m constraints, condensed != 0: N = nI and a panel V of m columns padded to mp = a
  * multiple of 32; else N = nI + m and no panel.  Counts are ADDED per entry: k_units (N x N) --

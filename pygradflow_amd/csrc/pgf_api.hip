@@ -23,6 +23,14 @@ static bool eval_ahead() {
   return ahead;
 }
 
+// PGF_STEP_FUSED=0: the launches in front of and behind the factorisation of a qp step as before --
+// k_mask_compact + k_residual_rhs; k_cond_y, k_step_update, the J and H row passes, k_sum_partials2,
+// k_kkt_residual; three launches in pgf_qp_advance_outer -- instead of the fused ones (same values)
+static bool step_fused() {
+  static const bool on = !(getenv("PGF_STEP_FUSED") && atoi(getenv("PGF_STEP_FUSED")) == 0);
+  return on;
+}
+
 extern "C" {
 
 int pgf_version(void) { return 1; }
@@ -586,13 +594,24 @@ static hipError_t kkt_solve_async(pgf_handle h, const double *rhs, double *sol) 
   return hipGetLastError();
 }
 // the backward half for the right-hand side h->rhs that rode through the factorisation
-static hipError_t kkt_backsolve_async(pgf_handle h, double *sol) {
+// (cy: a condensed step leaves s_y to the step update that follows directly -- only the partial
+// products are enqueued here, *cy describes them)
+static hipError_t kkt_backsolve_async(pgf_handle h, double *sol, StepCondY *cy = nullptr) {
   DenseLdlt &f = h->fac;
+  if (cy) cy->partial = nullptr;
   if (!h->condensed) return ldlt_backsolve_async(f, f.K + (int64_t)h->N * f.ldk, sol);
   hipError_t e = ldlt_backsolve_async(f, f.K + (int64_t)h->nI * f.ldk, sol);
   if (e != hipSuccess) return e;
-  launch_cond_y(h->stream, h->nI, h->m, f.V, f.ldv, sol, h->rhs + h->nI, h->delta, h->partial,
-                (size_t)PGF_GEMVT_PARTS * (h->n ? h->n : 1), sol + h->nI);
+  const size_t cap = (size_t)PGF_GEMVT_PARTS * (h->n ? h->n : 1);
+  if (cy && h->m) {
+    cy->nparts = launch_cond_y_partial(h->stream, h->nI, h->m, f.V, f.ldv, sol, h->partial, cap);
+    cy->partial = h->partial;
+    cy->rhs_y = h->rhs + h->nI;
+    cy->sol_y = sol + h->nI;
+    cy->delta = h->delta;
+    return hipGetLastError();
+  }
+  launch_cond_y(h->stream, h->nI, h->m, f.V, f.ldv, sol, h->rhs + h->nI, h->delta, h->partial, cap, sol + h->nI);
   return hipGetLastError();
 }
 
@@ -748,7 +767,7 @@ static int factor_sync(pgf_handle h) {
 
 // (expand: also the residual check's expansion of the solution into rs_v, rs_lv and the zeroing of
 // its maxima, launch_residual_and_eval(..., prepared = true))
-static void enqueue_step_update(pgf_handle h, bool expand = false) {
+static void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr) {
   DenseLdlt &f = h->fac;
   const int bits = f.status_words;  // deferred status words go to the status block
   f.status_words = 0;
@@ -758,7 +777,7 @@ static void enqueue_step_update(pgf_handle h, bool expand = false) {
                      h->scal, h->ticket, h->lamb, expand ? h->rs_v : nullptr, expand ? h->rs_lv : nullptr,
                      expand ? h->rs_red : nullptr, (bits & 1) ? f.flags : nullptr,
                      (bits & 2) ? f.chain + 2 * f.chain_stride + 1 : nullptr,
-                     reinterpret_cast<int *>(h->stat + 14));
+                     reinterpret_cast<int *>(h->stat + 14), cy && cy->partial ? cy : nullptr);
 }
 // after the host synchronisation of a step with deferred status words: to DenseLdlt::h_flags,
 // in the order the two separate copies would have left them
@@ -1172,7 +1191,11 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   h->fac_counted = h->fac_used_gram = false;  // (set by factor_async, if this step factorises)
   h->fac_head = 0;
   if (h->sparse) return band_step_async(h, did_factor);
-  if (h->nA == 0) {  // the residual and the reduced right-hand side in one launch
+  const bool front_done = h->front_done;
+  h->front_done = false;
+  if (front_done) {
+    // (qp_refresh_mask: F, b0full and rhs came with the compaction's launch)
+  } else if (h->nA == 0) {  // the residual and the reduced right-hand side in one launch
     launch_residual_rhs(s, h->n, h->m, h->nI, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y, h->g,
                         h->c, h->slb, h->sub, h->mask, h->idxI, h->F, h->b0full, h->rhs);
   } else {
@@ -1182,13 +1205,19 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
                        h->ldj, h->b0full, h->partial, PGF_GEMVT_PARTS, h->rhs);
   }
   *did_factor = false;
+  h->rs_skipped = h->fac.factored && h->factor_clean;  // (a step that factorises is always checked)
+  // the tail of a qp step in fewer launches (same values): s_y in the step update, the row passes
+  // over J and H in one launch, the sums, the H pass's epilogue and the residual in another
+  const bool ahead = eval_ahead() && h->qp_mode && h->refine_mode && !h->rs_skipped;
+  const bool fused_tail = ahead && step_fused();
+  StepCondY cy{nullptr, nullptr, nullptr, 0.0, 0};
   if (!h->fac.factored) {
     int rc;
     if ((rc = factor_async(h, true))) return rc;
     *did_factor = true;
     h->last_solve = 1;
     h->lu_active = false;
-    HIPCHK(h, kkt_backsolve_async(h, h->sol));
+    HIPCHK(h, kkt_backsolve_async(h, h->sol, fused_tail ? &cy : nullptr));
   } else {
     h->last_solve = 2;
     if (h->lu_active)
@@ -1201,13 +1230,19 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   // (launch_residual_and_eval) instead of two and four.  (PGF_EVAL_AHEAD=0: separately, the
   // evaluation at the start of the next step.)
   h->fused_eval_done = false;
-  h->rs_skipped = !*did_factor && h->factor_clean;
-  if (eval_ahead() && h->qp_mode && h->refine_mode && !h->rs_skipped) {
-    enqueue_step_update(h, /*expand=*/true);
-    launch_residual_and_eval(s, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj, h->idxI,
-                             h->pos, h->mask, h->rhs, h->sol, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->partial,
-                             PGF_GEMVT_PARTS, h->rs_r, h->rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c, h->w,
-                             h->tmpn, h->g, /*prepared=*/true);
+  if (ahead) {
+    enqueue_step_update(h, /*expand=*/true, &cy);
+    ++(fused_tail ? h->stat_tail_fused : h->stat_tail_plain);
+    if (fused_tail)
+      launch_residual_and_eval_fused(s, h->n, h->m, h->nI, h->delta, h->H, h->ldh, h->J, h->ldj, h->pos, h->mask,
+                                     h->rhs, h->sol, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->partial,
+                                     PGF_GEMVT_PARTS, h->rs_r, h->rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c,
+                                     h->w, h->tmpn, h->g);
+    else
+      launch_residual_and_eval(s, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj, h->idxI,
+                               h->pos, h->mask, h->rhs, h->sol, h->rs_v, h->rs_lv, h->rs_u, h->rs_wy, h->partial,
+                               PGF_GEMVT_PARTS, h->rs_r, h->rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c, h->w,
+                               h->tmpn, h->g, /*prepared=*/true);
     // (a qp step reads the maxima with its whole status block)
     if (!h->fac.defer_status)
       (void)hipMemcpyAsync(h->h_rs, h->rs_red, 3 * sizeof(double), hipMemcpyDeviceToHost, s);
@@ -1505,8 +1540,16 @@ static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_ou
     // the mask, straight into h->mask, and its compaction in one launch
     const bool spec = in_step && h->counts_known && step_spec();
     if (changed_out) *changed_out = 1;
-    launch_mask_compact(s, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->x, h->g, h->slb, h->sub,
-                        h->mask, h->idxI, h->idxA, h->pos, h->counts, spec ? h->nI : -1);
+    // a step enqueued with |A| = 0: its residual and reduced rhs in the same launch (newton_core_async
+    // then enqueues neither; a step that is discarded and redone takes the launches of its own)
+    h->front_done = spec && h->nA == 0 && step_fused();
+    if (h->front_done)
+      launch_mask_compact_rhs(s, h->n, h->m, h->nI, use_tau, h->lamb, f_x, f_x0, f_d, h->dt, h->fact, h->xhat,
+                              h->yhat, h->x, h->y, h->g, h->c, h->slb, h->sub, h->mask, h->idxI, h->idxA, h->pos,
+                              h->counts, h->nI, h->F, h->b0full, h->rhs);
+    else
+      launch_mask_compact(s, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->x, h->g, h->slb, h->sub,
+                          h->mask, h->idxI, h->idxA, h->pos, h->counts, spec ? h->nI : -1);
     return adopt_index_sets(h, spec);
   }
   launch_active_set(s, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, h->x, h->g, h->slb, h->sub,
@@ -1550,15 +1593,22 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
   if ((rc = qp_ready(h))) return rc;
   if (!(dt > 0.0) || !(rho > 0.0)) return fail(h, PGF_INVALID, "dt and rho must be positive");
   (void)hipSetDevice(h->device);
-  launch_copy(h->stream, h->xhat, h->x, h->n);
-  launch_copy(h->stream, h->yhat, h->y, h->m);
+  const bool one = step_fused() && !h->sparse;  // the copies and the scaling in one launch
+  if (!one) {
+    launch_copy(h->stream, h->xhat, h->x, h->n);
+    launch_copy(h->stream, h->yhat, h->y, h->m);
+  }
   if (rho != h->rho) h->eval_fresh = false;  // g depends on rho
   h->dt = dt;
   h->lamb = 1.0 / dt;
   h->rho = rho;
   h->fact = 1.0 / (1.0 + h->lamb * rho);
   h->delta = h->lamb / (1.0 + h->lamb * rho);
-  launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
+  if (one)
+    launch_advance_outer(h->stream, h->n, h->m, h->lamb, h->x, h->y, h->lb, h->ub, h->xhat, h->yhat, h->slb,
+                         h->sub);
+  else
+    launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   h->mask_set = false;
   invalidate_factor(h);
   return PGF_OK;
@@ -1634,6 +1684,7 @@ int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
   if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the previous step first");
   (void)hipSetDevice(h->device);
   if (h->form) return unsym_qp_step_async(h, policy, tau);
+  h->front_done = false;
   qp_eval(h);
   if (policy & PGF_STEP_RECOMPUTE_MASK) {
     // Full (newton.py:83-89): the mask is always re-set, which drops the factor;
@@ -1741,6 +1792,13 @@ int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gra
   if (!h) return PGF_INVALID;
   if (builds) *builds = h->stat_gram_builds;
   if (factorisations_with_gram) *factorisations_with_gram = h->stat_gram_factors;
+  return PGF_OK;
+}
+
+int pgf_debug_tail_stats(pgf_handle h, int *fused_steps, int *plain_steps) {
+  if (!h) return PGF_INVALID;
+  if (fused_steps) *fused_steps = h->stat_tail_fused;
+  if (plain_steps) *plain_steps = h->stat_tail_plain;
   return PGF_OK;
 }
 

@@ -85,6 +85,11 @@ struct pgf_solver {
   bool counts_known = false, spec_pending = false;
   bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
   int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
+  // PGF_STEP_FUSED: the forced mask refresh of the step being enqueued has also written F, b0full
+  // and the reduced rhs (consumed by newton_core_async); steps enqueued with the residual check and
+  // the evaluation ahead in the fused / the separate launches (pgf_debug_tail_stats)
+  bool front_done = false;
+  int stat_tail_fused = 0, stat_tail_plain = 0;
   uint8_t *h_mask_stage = nullptr;  // pinned staging of pgf_set_active_set's mask
   hipEvent_t mask_ev = nullptr;
   // the current dense factor is that of the condensed system (constraint block eliminated

@@ -17,6 +17,17 @@ void launch_mask_compact(hipStream_t s, int n, int use_tau, double lamb, double 
                          double f_d, const double *xhat, const double *x, const double *g,
                          const double *slb, const double *sub, uint8_t *mask, int *idxI, int *idxA,
                          int *pos, int *counts, int expect);
+// launch_mask_compact and launch_residual_rhs (nI: the count the step is enqueued with) in the one launch
+void launch_mask_compact_rhs(hipStream_t s, int n, int m, int nI, int use_tau, double lamb, double f_x,
+                             double f_x0, double f_d, double dt, double fact, const double *xhat,
+                             const double *yhat, const double *x, const double *y, const double *g,
+                             const double *c, const double *slb, const double *sub, uint8_t *mask, int *idxI,
+                             int *idxA, int *pos, int *counts, int expect, double *F, double *b0full,
+                             double *rhs);
+// xhat <- x, yhat <- y, (slb, sub) <- lamb (lb, ub) in one launch
+void launch_advance_outer(hipStream_t s, int n, int m, double lamb, const double *x, const double *y,
+                          const double *lb, const double *ub, double *xhat, double *yhat, double *slb,
+                          double *sub);
 void launch_residual(hipStream_t s, int n, int m, double lamb, double dt, const double *xhat,
                      const double *yhat, const double *x, const double *y, const double *g,
                      const double *c, const double *slb, const double *sub, const uint8_t *mask,
@@ -42,6 +53,14 @@ void launch_copy(hipStream_t s, double *dst, const double *src, int n);
 void launch_copy_u8(hipStream_t s, uint8_t *dst, const uint8_t *src, int n);
 void launch_mask_diff(hipStream_t s, int n, const uint8_t *a, const uint8_t *b, int *out);
 int step_update_blocks(int n, int m);
+// cy: the y rows form the condensed step's s_y = (sum_p partial[p][r] - rhs_y[r]) / delta themselves
+// (k_cond_y's order; partial as launch_cond_y_partial left it) and store it to sol_y
+struct StepCondY {
+  const double *partial, *rhs_y;
+  double *sol_y;
+  double delta;
+  int nparts;
+};
 void launch_step_update(hipStream_t s, int n, int m, int nI, double fact, double rho,
                         const double *x, const double *y, const double *lb, const double *ub,
                         const uint8_t *mask, const int *pos, const double *b0full,
@@ -49,7 +68,7 @@ void launch_step_update(hipStream_t s, int n, int m, int nI, double fact, double
                         double *yn, double *red, double *diff_out, unsigned *ticket, double lamb = 0.0,
                         double *v = nullptr, double *lv = nullptr, double *zero3 = nullptr,
                         const int *flags_src = nullptr, const int *chain_src = nullptr,
-                        int *status = nullptr);
+                        int *status = nullptr, const StepCondY *cy = nullptr);
 void launch_gemv_rows(hipStream_t s, int rows, int cols, const double *M, int64_t ld,
                       const double *v, const double *add, double sgn, double *out);
 void launch_gemvT(hipStream_t s, int rows, int cols, const double *M, int64_t ld,
@@ -90,6 +109,18 @@ void launch_cond_rhs(hipStream_t s, int nI, int m, const double *V, int64_t ldv,
 // sol_y <- (V^T sol_x - rhs_y) / delta
 void launch_cond_y(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
                    const double *rhs_y, double delta, double *partial, size_t partial_cap, double *sol_y);
+// launch_cond_y's first launch alone (the partial products); returns the number of chunks written,
+// for StepCondY::nparts
+int launch_cond_y_partial(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
+                          double *partial, size_t partial_cap);
+// launch_residual_and_eval(..., prepared = true) with the row passes over J and H in one launch and
+// the sums, the H pass's epilogue and the residual in another: at most three launches, same values
+void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double delta, const double *H, int64_t ldh,
+                                    const double *J, int64_t ldj, const int *pos, const uint8_t *mask,
+                                    const double *rhs, const double *sol, const double *v, double *lv, double *u,
+                                    double *wy, double *partial, int nparts, double *r, double *red3,
+                                    const double *xn, const double *yn, const double *b, const double *q,
+                                    double rho, double *c, double *w, double *tmpn, double *g);
 // launch_kkt_residual of the solve just made AND the evaluation of g, c at the new point (xn, yn)
 // in one pass over H and two over J (the separate kernels: two and four); partial: 2 * nparts * n
 void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, double delta, const double *H,

@@ -68,11 +68,24 @@ struct ActiveArgs {
   double lamb, f_x, f_x0, f_d;
   const double *xhat, *x, *g, *slb, *sub;
 };
+// FrontArgs (with ActiveArgs): the variable rows of k_residual_rhs on the way, for a step enqueued
+// with |A| = 0 -- every lane has its entry's mask flag and rank in hand: F, b0full (b_residual's
+// expressions) and rhs[rank] = F - 0.0 for the inactive entries (what the row idxI[rank] = j of
+// k_residual_rhs computes; a step whose enqueued sizes turn out stale is discarded, as ever).
+struct FrontArgs {
+  double dt;
+  double *F, *b0full, *rhs;
+};
+__device__ __forceinline__ double residual_x_m(int i, double lamb, const double *__restrict__ xhat,
+                                              const double *__restrict__ x, const double *__restrict__ g,
+                                              const double *__restrict__ slb, const double *__restrict__ sub,
+                                              bool active);
 __device__ __forceinline__ void b_compact(int n, const uint8_t *__restrict__ mask,
                                                   int *__restrict__ idxI, int *__restrict__ idxA,
                                                   int *__restrict__ pos, int *__restrict__ counts,
                                                   int expect = -1, const ActiveArgs *eval = nullptr,
-                                                  uint8_t *__restrict__ mask_out = nullptr) {
+                                                  uint8_t *__restrict__ mask_out = nullptr,
+                                                  const FrontArgs *front = nullptr) {
   __shared__ int wtot[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int baseI = 0;
@@ -110,6 +123,12 @@ __device__ __forceinline__ void b_compact(int n, const uint8_t *__restrict__ mas
         idxA[r] = j;
         pos[j] = r;
       }
+      if (front) {
+        const double f = residual_x_m(j, eval->lamb, eval->xhat, eval->x, eval->g, eval->slb, eval->sub, !inact);
+        front->F[j] = f;
+        front->b0full[j] = !inact ? front->dt * f : 0.0;
+        if (inact) front->rhs[baseI + woff + before] = f - 0.0;
+      }
     }
     baseI += tot;
     __syncthreads();
@@ -128,8 +147,14 @@ __device__ __forceinline__ double residual_x(int i, double lamb, const double *_
                                             const double *__restrict__ x, const double *__restrict__ g,
                                             const double *__restrict__ slb, const double *__restrict__ sub,
                                             const uint8_t *__restrict__ mask) {
+  return residual_x_m(i, lamb, xhat, x, g, slb, sub, mask[i] != 0);
+}
+__device__ __forceinline__ double residual_x_m(int i, double lamb, const double *__restrict__ xhat,
+                                              const double *__restrict__ x, const double *__restrict__ g,
+                                              const double *__restrict__ slb, const double *__restrict__ sub,
+                                              bool active) {
   double p = lamb * xhat[i] - g[i];
-  if (mask[i] != 0) p = fmin(fmax(p, slb[i]), sub[i]);
+  if (active) p = fmin(fmax(p, slb[i]), sub[i]);
   return lamb * x[i] - p;
 }
 __device__ __forceinline__ double residual_y(int r, double lamb, const double *__restrict__ yhat,
@@ -266,7 +291,8 @@ __device__ __forceinline__ void b_step_update(
     const uint8_t *__restrict__ mask, const int *__restrict__ pos,
     const double *__restrict__ b0full, const double *__restrict__ F,
     const double *__restrict__ sol, double *__restrict__ dx, double *__restrict__ dy,
-    double *__restrict__ xn, double *__restrict__ yn, double *__restrict__ red) {
+    double *__restrict__ xn, double *__restrict__ yn, double *__restrict__ red,
+    bool own_sy = false, double sy = 0.0) {  // (own_sy: this row's sol[nI + r] is sy, formed by the caller)
   __shared__ double part[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double sq = 0.0;
@@ -289,7 +315,7 @@ __device__ __forceinline__ void b_step_update(
   } else if (i < n + m) {
     const int r = i - n;
     const double t = rho * F[n + r];
-    const double d = fact * (sol[nI + r] - t);
+    const double d = fact * ((own_sy ? sy : sol[nI + r]) - t);
     dy[r] = d;
     yn[r] = y[r] - d;
     sq = d * d;
@@ -532,6 +558,33 @@ __global__ __launch_bounds__(256) void k_residual_rhs(int n, int m, int nI, doub
   }
 }
 
+// k_mask_compact and, for a step enqueued with |A| = 0, k_residual_rhs's work in the one workgroup:
+// the constraint rows first (nI: the count the step is enqueued with), the variable rows in the
+// compaction's own pass (FrontArgs), by the same per-element functions.
+__global__ __launch_bounds__(1024) void k_mask_compact_rhs(int n, ActiveArgs a, uint8_t *__restrict__ mask,
+    int *__restrict__ idxI, int *__restrict__ idxA, int *__restrict__ pos, int *__restrict__ counts,
+    int expect, int m, int nI, double dt, double fact, const double *__restrict__ yhat,
+    const double *__restrict__ y, const double *__restrict__ c, double *__restrict__ F,
+    double *__restrict__ b0full, double *__restrict__ rhs) {
+  for (int r = threadIdx.x; r < m; r += 1024) {
+    F[n + r] = residual_y(r, a.lamb, yhat, y, c);
+    rhs[nI + r] = fact * residual_y(r, a.lamb, yhat, y, c) - 0.0;
+  }
+  const FrontArgs front{dt, F, b0full, rhs};
+  b_compact(n, nullptr, idxI, idxA, pos, counts, expect, &a, mask, &front);
+}
+
+// pgf_qp_advance_outer's two copies and the scaling of the bounds in one launch
+__global__ void k_advance_outer(int n, int m, double lamb, const double *__restrict__ x,
+    const double *__restrict__ y, const double *__restrict__ lb, const double *__restrict__ ub,
+    double *__restrict__ xhat, double *__restrict__ yhat, double *__restrict__ slb,
+    double *__restrict__ sub) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) xhat[i] = x[i];
+  if (i < m) yhat[i] = y[i];
+  b_scale_bounds(n, lamb, lb, ub, slb, sub);
+}
+
 __global__ __launch_bounds__(256) void k_active_rows_partial(int n, int nA, const int *__restrict__ idxA,
     const double *__restrict__ H, int64_t ldh, const double *__restrict__ b0full, int nparts,
     double *__restrict__ partial) {
@@ -631,13 +684,38 @@ __device__ __forceinline__ bool last_block_reduce(const double *red, int nb, dou
 //   flags_src  -> status[0, 4): the factorisation's flag words;  chain_src -> status[3]: the
 //              chained solve's status word (both copied by the last workgroup, so the host reads
 //              them with the rest of the step's status block)
+//   cy_partial the condensed step's s_y formed by the y rows themselves (StepCondY, in place of
+//              k_cond_y in front of this launch) and stored to cy_sol = sol + nI
 struct StepExtras {
   double lamb;
   double *v, *lv, *zero3;
   const int *flags_src, *chain_src;
   int *status;
   unsigned *ticket;
+  const double *cy_partial, *cy_rhs;
+  double *cy_sol;
+  double cy_delta;
+  int cy_parts;
 };
+// k_cond_y's value for row r in one lane: the chunks p = g, g + 4, ... summed in four sequential
+// groups, combined as ((g0 + g1) + (g2 + g3)), the same expression after that
+__device__ __forceinline__ double cond_y_row(int m, int nparts, const double *__restrict__ partial,
+                                             const double *__restrict__ rhs_y, double delta, int r) {
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  const double *col = partial + r;
+  int p = 0;
+#pragma unroll 8
+  for (; p + 3 < nparts; p += 4) {
+    s0 += col[(int64_t)p * m];
+    s1 += col[(int64_t)(p + 1) * m];
+    s2 += col[(int64_t)(p + 2) * m];
+    s3 += col[(int64_t)(p + 3) * m];
+  }
+  if (p < nparts) s0 += col[(int64_t)p * m];
+  if (p + 1 < nparts) s1 += col[(int64_t)(p + 1) * m];
+  if (p + 2 < nparts) s2 += col[(int64_t)(p + 2) * m];
+  return (((s0 + s1) + (s2 + s3)) - rhs_y[r]) / delta;
+}
 __global__ __launch_bounds__(256) void k_step_update(int n, int m, int nI, double fact,
     double rho, const double *__restrict__ x, const double *__restrict__ y,
     const double *__restrict__ lb, const double *__restrict__ ub,
@@ -646,8 +724,14 @@ __global__ __launch_bounds__(256) void k_step_update(int n, int m, int nI, doubl
     const double *__restrict__ sol, double *__restrict__ dx, double *__restrict__ dy,
     double *__restrict__ xn, double *__restrict__ yn, double *__restrict__ red,
     double *__restrict__ diff_out, StepExtras ex) {
-  b_step_update(n, m, nI, fact, rho, x, y, lb, ub, mask, pos, b0full, F, sol, dx, dy, xn, yn, red);
   const int i = blockIdx.x * 256 + threadIdx.x;
+  double sy = 0.0;
+  if (ex.cy_partial && i >= n && i < n + m) {
+    sy = cond_y_row(m, ex.cy_parts, ex.cy_partial, ex.cy_rhs, ex.cy_delta, i - n);
+    ex.cy_sol[i - n] = sy;  // (the residual check reads it)
+  }
+  b_step_update(n, m, nI, fact, rho, x, y, lb, ub, mask, pos, b0full, F, sol, dx, dy, xn, yn, red,
+                ex.cy_partial != nullptr, sy);
   if (ex.v && i < n) {
     const double val = mask[i] ? 0.0 : sol[pos[i]];
     ex.v[i] = val;
@@ -737,6 +821,24 @@ void launch_mask_compact(hipStream_t s, int n, int use_tau, double lamb, double 
                      expect);
 }
 
+void launch_mask_compact_rhs(hipStream_t s, int n, int m, int nI, int use_tau, double lamb, double f_x,
+                             double f_x0, double f_d, double dt, double fact, const double *xhat,
+                             const double *yhat, const double *x, const double *y, const double *g,
+                             const double *c, const double *slb, const double *sub, uint8_t *mask, int *idxI,
+                             int *idxA, int *pos, int *counts, int expect, double *F, double *b0full,
+                             double *rhs) {
+  const ActiveArgs a{use_tau, lamb, f_x, f_x0, f_d, xhat, x, g, slb, sub};
+  hipLaunchKernelGGL(k_mask_compact_rhs, dim3(1), dim3(1024), 0, s, n, a, mask, idxI, idxA, pos, counts, expect,
+                     m, nI, dt, fact, yhat, y, c, F, b0full, rhs);
+}
+
+void launch_advance_outer(hipStream_t s, int n, int m, double lamb, const double *x, const double *y,
+                          const double *lb, const double *ub, double *xhat, double *yhat, double *slb,
+                          double *sub) {
+  const int k = std::max(n, m);
+  if (k) hipLaunchKernelGGL(k_advance_outer, g1(k), dim3(256), 0, s, n, m, lamb, x, y, lb, ub, xhat, yhat, slb, sub);
+}
+
 void launch_residual(hipStream_t s, int n, int m, double lamb, double dt, const double *xhat,
                      const double *yhat, const double *x, const double *y, const double *g,
                      const double *c, const double *slb, const double *sub, const uint8_t *mask,
@@ -817,9 +919,16 @@ void launch_step_update(hipStream_t s, int n, int m, int nI, double fact, double
                         const double *F, const double *sol, double *dx, double *dy, double *xn,
                         double *yn, double *red, double *diff_out, unsigned *ticket, double lamb,
                         double *v, double *lv, double *zero3, const int *flags_src,
-                        const int *chain_src, int *status) {
+                        const int *chain_src, int *status, const StepCondY *cy) {
   const int nb = step_update_blocks(n, m);
-  const StepExtras ex{lamb, v, lv, zero3, flags_src, chain_src, status, ticket};
+  StepExtras ex{lamb, v, lv, zero3, flags_src, chain_src, status, ticket, nullptr, nullptr, nullptr, 0.0, 0};
+  if (cy && m) {
+    ex.cy_partial = cy->partial;
+    ex.cy_rhs = cy->rhs_y;
+    ex.cy_sol = cy->sol_y;
+    ex.cy_delta = cy->delta;
+    ex.cy_parts = cy->nparts;
+  }
   if (nb) {
     hipLaunchKernelGGL(k_step_update, dim3(nb), dim3(256), 0, s, n, m, nI, fact, rho, x, y, lb, ub,
                        mask, pos, b0full, F, sol, dx, dy, xn, yn, red, diff_out, ex);
@@ -1125,6 +1234,128 @@ void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, 
   if (N)
     hipLaunchKernelGGL(k_kkt_residual, g1(N), dim3(256), 0, s, N, nI, idxI, rhs, sol, lv, wy, r,
                        reinterpret_cast<unsigned long long *>(red3));
+}
+
+// ---- the same in three launches (PGF_STEP_FUSED, pgf_api.hip): every value is computed by the
+// expressions above in the same order, only the launch it is computed in changes.
+// The row passes over J and H in one launch: the first jb workgroups are k_gemv_rows2 over J
+// (c = J xn - b, wy = J v - delta s_y, complete), the others row_dot2 of H with (xn, v), stored raw
+// to dot1, dot2 -- they need nothing from the J passes, the combine launch adds tmpn and u.
+__global__ __launch_bounds__(256) void k_rows_jh(int m, int n, int jb, const double *__restrict__ J, int64_t ldj,
+                                                 const double *__restrict__ H, int64_t ldh,
+                                                 const double *__restrict__ xn, const double *__restrict__ v,
+                                                 const double *__restrict__ b, double *__restrict__ c,
+                                                 const double *__restrict__ sy, double delta,
+                                                 double *__restrict__ wy, double *__restrict__ dot1,
+                                                 double *__restrict__ dot2) {
+  const int lane = threadIdx.x & 63;
+  double d1, d2;
+  if ((int)blockIdx.x < jb) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= m) return;
+    row_dot2(J + (int64_t)r * ldj, xn, v, n, lane, d1, d2);
+    if (lane == 0) {
+      c[r] = d1 + -1.0 * b[r];
+      wy[r] = d2 + -delta * sy[r];
+    }
+    return;
+  }
+  const int r = ((int)blockIdx.x - jb) * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  row_dot2(H + (int64_t)r * ldh, xn, v, n, lane, d1, d2);
+  if (lane == 0) {
+    dot1[r] = d1;
+    dot2[r] = d2;
+  }
+}
+
+// k_sum_partials2, the epilogue of the H pass and k_kkt_residual in one launch of 64-lane
+// workgroups.  Lane t < n takes column t: its own chunks summed sequentially over p,
+//   tmpn = q + sum_p partial1, u = lv + sum_p partial2, g = dot1 + 1.0 tmpn, lv <- dot2 + 1.0 u
+// (dot1 arrives in g, dot2 in u; nparts == 0: the plain copies of the m == 0 branch), and
+// r[pos[t]] = rhs[pos[t]] - lv[t] where the variable is inactive; lane n + k takes the constraint row
+// k from wy.  The maxima: atomicMax on bit patterns (red zeroed by k_step_update).
+__global__ __launch_bounds__(64) void k_tail_combine(int n, int m, int nI, int nparts,
+                                                     const double *__restrict__ partial1,
+                                                     const double *__restrict__ partial2,
+                                                     const double *__restrict__ q, double *__restrict__ tmpn,
+                                                     double *__restrict__ g, double *__restrict__ u,
+                                                     double *__restrict__ lv, const uint8_t *__restrict__ mask,
+                                                     const int *__restrict__ pos, const double *rhs,  // may alias r
+                                                     const double *__restrict__ sol,
+                                                     const double *__restrict__ wy, double *r,
+                                                     unsigned long long *__restrict__ red) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  double ar = 0.0, ab = 0.0, as = 0.0;
+  int i = -1;
+  double ks = 0.0;
+  if (t < n) {
+    double s1 = 0.0, s2 = 0.0;
+#pragma unroll 8
+    for (int p = 0; p < nparts; ++p) {
+      s1 += partial1[(int64_t)p * n + t];
+      s2 += partial2[(int64_t)p * n + t];
+    }
+    const double sgn = 1.0;
+    const double tv = nparts ? q[t] + s1 : q[t];
+    const double uv = nparts ? lv[t] + s2 : lv[t];
+    const double d1 = g[t], d2 = u[t];
+    tmpn[t] = tv;
+    u[t] = uv;
+    g[t] = d1 + sgn * tv;
+    ks = d2 + sgn * uv;
+    lv[t] = ks;
+    if (!mask[t]) i = pos[t];
+  } else if (t < n + m) {
+    i = nI + (t - n);
+    ks = wy[t - n];
+  }
+  if (i >= 0) {
+    const double bi = rhs[i];
+    const double ri = bi - ks;
+    r[i] = ri;
+    ar = fabs(ri);
+    ab = fabs(bi);
+    as = fabs(sol[i]);
+    if (ar != ar) ar = __builtin_inf();  // a NaN must not vanish in the max
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    ar = fmax(ar, __shfl_down(ar, off));
+    ab = fmax(ab, __shfl_down(ab, off));
+    as = fmax(as, __shfl_down(as, off));
+  }
+  if (threadIdx.x == 0) {
+    atomicMax(&red[0], (unsigned long long)__double_as_longlong(ar));
+    atomicMax(&red[1], (unsigned long long)__double_as_longlong(ab));
+    atomicMax(&red[2], (unsigned long long)__double_as_longlong(as));
+  }
+}
+
+// launch_residual_and_eval(..., prepared = true) in at most three launches
+void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double delta, const double *H, int64_t ldh,
+                                    const double *J, int64_t ldj, const int *pos, const uint8_t *mask,
+                                    const double *rhs, const double *sol, const double *v, double *lv, double *u,
+                                    double *wy, double *partial, int nparts, double *r, double *red3,
+                                    const double *xn, const double *yn, const double *b, const double *q,
+                                    double rho, double *c, double *w, double *tmpn, double *g) {
+  const int N = nI + m;
+  const int jb = (m + 3) / 4, hb = (n + 3) / 4;
+  if (jb + hb)
+    hipLaunchKernelGGL(k_rows_jh, dim3(jb + hb), dim3(256), 0, s, m, n, jb, J, ldj, H, ldh, xn, v, b, c, sol + nI,
+                       delta, wy, g, u);
+  if (n == 0) launch_mult_vec(s, m, rho, c, yn, w);
+  int used = 0;
+  double *p2 = partial + (size_t)nparts * n;
+  if (n && m) {
+    const int chunk = (m + nparts - 1) / nparts;
+    used = (m + chunk - 1) / chunk;
+    hipLaunchKernelGGL(k_gemvT_partial2, dim3((n + 255) / 256, used), dim3(256), 0, s, m, n, J, ldj, rho, c, yn, w,
+                       sol + nI, chunk, partial, p2);
+  }
+  if (n || N)
+    hipLaunchKernelGGL(k_tail_combine, dim3((n + m + 63) / 64), dim3(64), 0, s, n, m, nI, used, partial, p2, q, tmpn,
+                       g, u, lv, mask, pos, rhs, sol, wy, r, reinterpret_cast<unsigned long long *>(red3));
 }
 
 // ---- matrix norms for the normwise backward error of the residual guard (pgf_api.hip)
@@ -1836,9 +2067,9 @@ void launch_cond_rhs(hipStream_t s, int nI, int m, const double *V, int64_t ldv,
   if (nI) hipLaunchKernelGGL(k_cond_rhs, dim3((nI + 3) / 4), dim3(256), 0, s, nI, m, V, ldv, rhs, delta, out);
 }
 
-void launch_cond_y(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
-                   const double *rhs_y, double delta, double *partial, size_t partial_cap, double *sol_y) {
-  if (!m) return;
+int launch_cond_y_partial(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
+                          double *partial, size_t partial_cap) {
+  if (!m) return 0;
   // as many row chunks as the scratch holds (up to 128): the product reads V once, 8 m nI bytes
   const int nparts = (int)std::max<size_t>(1, std::min<size_t>(128, partial_cap / (size_t)m));
   const int chunk = (std::max(nI, 1) + nparts - 1) / nparts;
@@ -1846,5 +2077,12 @@ void launch_cond_y(hipStream_t s, int nI, int m, const double *V, int64_t ldv, c
   if (used)
     hipLaunchKernelGGL(k_gemvT_partial, dim3((m + 255) / 256, used), dim3(256), 0, s, nI, m, V, ldv, solx,
                        chunk, partial);
+  return used;
+}
+
+void launch_cond_y(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
+                   const double *rhs_y, double delta, double *partial, size_t partial_cap, double *sol_y) {
+  if (!m) return;
+  const int used = launch_cond_y_partial(s, nI, m, V, ldv, solx, partial, partial_cap);
   hipLaunchKernelGGL(k_cond_y, dim3((m + 63) / 64), dim3(256), 0, s, m, used, partial, rhs_y, delta, sol_y);
 }

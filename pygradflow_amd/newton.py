@@ -364,6 +364,13 @@ class DeviceNewton:
         _lib.check(self._lib.pgf_debug_head_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
         return a.value, b.value
 
+    def tail_stats(self):
+        """(fused, plain): steps whose residual check and evaluation ahead were enqueued in the fused /
+        the separate launches (``pgf_debug_tail_stats``)."""
+        a, b = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_tail_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
+        return a.value, b.value
+
     def border_stats(self):
         """(border size, factor phases, solve phases) of the bordered band on this handle
         (``pgf_debug_border_stats``; zeros without a border)."""
