@@ -120,6 +120,14 @@ int pgf_residual(pgf_handle h, const double *x, const double *y, const double *g
 /* LinearSolver.solve(rhs, trans) (linear_solver/linear_solver.py:23-25) against the
  * current reduced KKT factor; rhs/sol have |I| + m entries */
 int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol);
+/* nrhs right-hand sides against the same factor: column j at rhs + j * ld, its solution at
+ * sol + j * ld (ld >= the system's size).  A wide band (B = 16, 32, 64) without a border and with the
+ * factor / solve split on solves them as panels of at most 64 columns against the kept factors
+ * (one factor-only reduction when there are none), checks every column's residual and solves a
+ * column above the refinement tolerance again through pgf_linear_solve; every other handle loops
+ * over pgf_linear_solve.  (LUSolver.solve with a 2-D right-hand side.) */
+int pgf_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t ld, int trans,
+                           double *sol);
 
 /* size of the reduced system of the current mask: |I|, |I| + m */
 int pgf_reduced_dims(pgf_handle h, int *n_inactive, int *n_reduced);
@@ -146,6 +154,14 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
  *   B = 8, 16, 32, 64: that block size (PGF_INVALID if B < bw).
  * Invalidates the factorisation; the work arrays are sized for the chosen B. */
 int pgf_sparse_set_block_size(pgf_handle h, int B);
+/* Factor / solve split of the wide block cyclic reduction (B = 16, 32, 64, no border): on (the
+ * default; PGF_BW_SPLIT=0 in the environment makes off the default of new handles), the first
+ * solve on a matrix runs the fused reduction and keeps its forward multipliers (2 B^2 doubles per
+ * block more), and every further solve on the same matrix -- a back-solve step, a refinement
+ * correction, pgf_linear_solve -- runs the solve phase against them without any inversion; off,
+ * every solve runs the whole reduction and the multiplier store is not allocated.  The results
+ * are the same bit for bit.  Drops the kept factors. */
+int pgf_sparse_set_factor_split(pgf_handle h, int on);
 /* Bordered band, after pgf_sparse_set_pattern (which declares none): the last k positions of
  * `pos` are border nodes -- dense rows / columns of the KKT pattern, variables or constraints --
  * and bw, the band slots and the block size describe the remaining n + m - k rows only.  With
@@ -467,6 +483,10 @@ int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head,
 /* the handle's border size and the factor / solve phases of the bordered route enqueued since
  * pgf_sparse_set_border (tests: a step that keeps its factor runs the solve phase only) */
 int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves);
+/* phases of the wide band (B = 16, 32, 64) enqueued on the handle since its creation: reductions
+ * (fused or factor-only), solve phases for one right-hand side against kept factors, panel
+ * solves.  Any pointer may be NULL. */
+int pgf_debug_band_stats(pgf_handle h, int *reductions, int *solve_phases, int *panel_solves);
 
 #ifdef __cplusplus
 }

@@ -49,11 +49,13 @@ SIGNATURES = {
     "pgf_newton_solve": (C.c_int, [_h, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "pgf_residual": (C.c_int, [_h, _dp, _dp, _dp, _dp, _u8p, _dp]),
     "pgf_linear_solve": (C.c_int, [_h, _dp, C.c_int, _dp]),
+    "pgf_linear_solve_multi": (C.c_int, [_h, _dp, C.c_int, C.c_int64, C.c_int, _dp]),
     "pgf_reduced_dims": (C.c_int, [_h, _ip, _ip]),
     "pgf_get_kkt": (C.c_int, [_h, _dp, C.c_int64]),
     "pgf_sparse_set_pattern": (C.c_int, [_h, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int, _ip, _ip, _ip,
                                          _ip, _ip, _ip]),
     "pgf_sparse_set_block_size": (C.c_int, [_h, C.c_int]),
+    "pgf_sparse_set_factor_split": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_border": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_values": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_vectors": (C.c_int, [_h, _dp, _dp]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "pgf_debug_tail_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_head_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
     "pgf_debug_border_stats": (C.c_int, [_h, _ip, _ip, _ip]),
+    "pgf_debug_band_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pgf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

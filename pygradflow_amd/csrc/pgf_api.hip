@@ -101,6 +101,7 @@ int pgf_create(int n, int m, int device, unsigned flags, pgf_handle *out) {
   h->h_scal = h->h_stat + 8;
   h->h_counts = reinterpret_cast<int *>(h->h_stat + 12);
   h->sparse = sparse;
+  h->sp.split = band_split_default();
   if (sparse) {
     // banded mode: no dense N x N storage; only the factor's flag words are shared
     h->fac.stream = h->stream;
@@ -732,6 +733,7 @@ static int factor_async(pgf_handle h, bool with_rhs) {
 #define PGF_RETRY_FACTOR (-2)
 static int finish_factor_state(pgf_handle h, hipError_t *e) {
   const int st = ldlt_finish(h->fac, e);
+  if (h->sparse && st >= 0) band_kept_resolve(h);
   if (st == 1 && h->condensed && !h->condensed_veto) {
     h->condensed_veto = true;
     h->fac.factored = false;
@@ -1384,6 +1386,22 @@ int pgf_linear_solve(pgf_handle h, const double *rhs, int trans, double *sol) {
   if ((rc = refine_if_needed(h, false, false))) return rc;
   if ((rc = down(h, sol, h->sol, h->N * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PGF_OK;
+}
+
+int pgf_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t ld, int trans, double *sol) {
+  if (!h) return PGF_INVALID;
+  int rc;
+  if ((rc = check_ready(h))) return rc;
+  if (nrhs < 0) return fail(h, PGF_INVALID, "negative number of right-hand sides");
+  if (nrhs == 0) return PGF_OK;
+  const int rows = h->sparse || h->form ? h->n + h->m : h->N;
+  if (!rhs || !sol) return fail(h, PGF_INVALID, "null argument");
+  if (nrhs > 1 && ld < rows) return fail(h, PGF_INVALID, "column stride is smaller than the system");
+  // a wide band without a border: panels on the matrix pipes; everything else column by column
+  if (band_multi_panel(h)) return band_linear_solve_multi(h, rhs, nrhs, ld, sol);
+  for (int j = 0; j < nrhs; ++j)
+    if ((rc = pgf_linear_solve(h, rhs + (int64_t)j * ld, trans, sol + (int64_t)j * ld))) return rc;
   return PGF_OK;
 }
 

@@ -3,21 +3,46 @@
 // them).  The system keeps its full size n + m (an active variable is an identity row) and is
 // solved by block cyclic reduction: B = 8 (pgf_sparse.hip), B = 16, 32, 64 (pgf_band_wide.hip),
 // or the bordered band on top of either (pgf_border.hip).  The reduction leaves the assembled band
-// intact, so every solve can be followed by its residual (the accuracy guard).
+// intact, so every solve can be followed by its residual (the accuracy guard).  A wide reduction
+// also keeps its factors (SparseDev::kept): further solves on the same matrix run its solve phase.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <utility>
 
 #include "pgf_api_internal.h"
 #include "pgf_kernels.h"
 
-static void sp_cyclic_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+// PGF_BW_SPLIT=0: new handles start with the wide band's factor / solve split off
+bool band_split_default() {
+  static const bool on = !(getenv("PGF_BW_SPLIT") && atoi(getenv("PGF_BW_SPLIT")) == 0);
+  return on;
+}
+
+// Wide band without a border: against the kept factors when there are some (sp.kept == 2),
+// otherwise the fused KEEP reduction, which solves as ever and leaves the factors.  Its pivot
+// flags reach the host with the caller's next synchronisation; band_kept_resolve then decides.
+static void sp_cyclic_solve(hipStream_t s, SparseDev &sp, int N, int *flags, bool guard) {
   if (sp.bk)  // bordered band: the solve phase against the kept Y and factor of S (pgf_border.hip)
     sp_border_solve(s, sp, flags, guard);
-  else if (sp.B > 8)
+  else if (sp.B > 8 && sp.split && sp.bMr && N > 0) {
+    if (sp.kept == 2) {
+      sp_launch_bw_backsolve(s, sp, N, flags, guard);
+    } else {
+      sp_launch_bw_solve(s, sp, N, flags, guard, /*keep=*/true);
+      sp.kept = 1;
+    }
+  } else if (sp.B > 8)
     sp_launch_bw_solve(s, sp, N, flags, guard);
   else
     sp_launch_bcr_solve(s, sp, N, flags, guard);
+}
+
+// after a host synchronisation that brought the pivot flags of every reduction enqueued so far to
+// fac.h_flags: a KEEP reduction with clean flags leaves a kept factor, a bad pivot never does
+void band_kept_resolve(pgf_handle h) {
+  SparseDev &sp = h->sp;
+  if (sp.kept == 1) sp.kept = h->fac.h_flags[0] ? 0 : 2;
 }
 static void sp_cyclic_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
   if (sp.bk)
@@ -31,6 +56,7 @@ static void sp_cyclic_residual(hipStream_t s, const SparseDev &sp, int N, const 
 // assemble the banded matrix for the current mask; with a border also its factor phase (Y = inv(B) C
 // and the factor of the Schur complement S, kept until the matrix is assembled again)
 static void sp_assemble(pgf_handle h) {
+  h->sp.kept = 0;  // new matrix: the wide band's kept factors are stale
   if (h->sp.bk) {
     sp_border_assemble(h->stream, h->sp, h->n, h->m, h->mask, h->lamb, h->delta);
     PgfProfile *p = h->prof.enabled ? &h->prof : nullptr;  // the factor phase as factor_ms
@@ -78,16 +104,17 @@ int band_status_sync(pgf_handle h) {
 // reduction on the residual each -- and PGF_SINGULAR when the residual stays above refine_fail:
 // the step controller then rejects the step and doubles lambda, which is what makes the
 // matrix quasi-definite again (the reference's own recovery path, step_control.py:80-107).
-static double sparse_residual_rel(pgf_handle h) {
+static double residual_rel_of(const double *pairs, int nred) {
   double r = 0.0, b = 0.0;
-  for (int i = 0; i < h->sp.nred; ++i) {
-    const double ri = h->sp.h_bred[2 * i];
+  for (int i = 0; i < nred; ++i) {
+    const double ri = pairs[2 * i];
     if (!(ri == ri) || !(ri <= 1.79e308)) return HUGE_VAL;
     r = std::max(r, ri);
-    b = std::max(b, h->sp.h_bred[2 * i + 1]);
+    b = std::max(b, pairs[2 * i + 1]);
   }
   return r / (b > 0.0 ? b : 1.0);
 }
+static double sparse_residual_rel(pgf_handle h) { return residual_rel_of(h->sp.h_bred, h->sp.nred); }
 
 int band_refine(pgf_handle h, bool swapped, bool with_step) {
   if (!h->refine_mode || !h->sp.guarded) return PGF_OK;
@@ -146,8 +173,8 @@ int band_step_async(pgf_handle h, bool *did_factor) {
                   h->sub, h->mask, h->F, h->b0full);
   sp_launch_rhs(s, sp, h->n, h->m, h->mask, h->F, h->b0full, h->fact, sp.Hb0, sp.Jb0);
   // assemble (only when the mask / derivatives changed) and solve in log2(N/B) parallel levels;
-  // the band itself is left untouched, so a back-solve step just runs the reduction again on the
-  // same band (~1 ms)
+  // the band itself is left untouched, so a back-solve step runs the reduction again on the same
+  // band (B = 8, borders at B = 8) or the solve phase against the factors a wide reduction kept
   if (!h->fac.factored) sp_assemble(h);
   PgfProfile *p = h->prof.enabled ? &h->prof : nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -156,15 +183,22 @@ int band_step_async(pgf_handle h, bool *did_factor) {
     e1 = prof_event(p);
     (void)hipEventRecord(e0, s);
   }
+  const bool solve_phase = !sp.bk && sp.kept == 2;
   sp_cyclic_solve(s, sp, Nf, h->fac.flags, h->refine_mode != 0);
+  const bool keep_red = sp.kept == 1;
   sp.guarded = h->refine_mode != 0;
   if (p) {
     (void)hipEventRecord(e1, s);
     p->update_spans.emplace_back(e0, e1);
     // algorithmic bytes of one cyclic-reduction solve: every block (D, L, U, inv D:
-    // 4 x 8 B^2, rhs + solution 16 B) is written once and read about twice
-    const double Bk = (double)sp.B;
-    p->update_flops.push_back(3.0 * (double)((Nf + sp.B - 1) / sp.B) * (4 * 8 * Bk * Bk + 16 * Bk));
+    // 4 x 8 B^2, rhs + solution 16 B) is written once and read about twice; a KEEP reduction
+    // writes two more blocks (the multipliers); a solve phase against kept factors reads five
+    // blocks (Mr, Ml, L, U, inv D) once and f twice, and writes f and x
+    const double Bk = (double)sp.B, nblk = (double)((Nf + sp.B - 1) / sp.B);
+    if (solve_phase)
+      p->update_flops.push_back(nblk * (5 * 8 * Bk * Bk + 32 * Bk));
+    else
+      p->update_flops.push_back(3.0 * nblk * (4 * 8 * Bk * Bk + 16 * Bk) + (keep_red ? nblk * 16 * Bk * Bk : 0.0));
   }
   *did_factor = true;
   if (sp.guarded) {
@@ -205,6 +239,7 @@ int band_linear_solve(pgf_handle h, const double *rhs, double *sol) {
                            h->stream));
   if (sp.guarded) {  // residual check (and refinement) before the solution leaves
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    band_kept_resolve(h);
     if (h->fac.h_flags[0]) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
     const int nneg = h->fac.h_flags[1];
     if ((rc = band_refine(h, false, false))) return rc;
@@ -214,9 +249,84 @@ int band_linear_solve(pgf_handle h, const double *rhs, double *sol) {
   sp_launch_permute(h->stream, sp, Nf, sp.brhs, h->sol, 1);
   if ((rc = down(h, sol, h->sol, (size_t)Nf * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  band_kept_resolve(h);
   if (h->fac.h_flags[0]) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
   h->fac.n_neg = h->fac.h_flags[1];
   h->fac.factored = true;
+  return PGF_OK;
+}
+
+// Several right-hand sides at once on a wide band without a border (split on): the factors of one
+// factor-only KEEP reduction (or those a step left), then per chunk of at most 64 columns one
+// panel solve on the matrix pipes.  Every column's residual is checked by k_bw_residual; one
+// above refine_tol is solved again through the guarded single right-hand side path.
+bool band_multi_panel(pgf_handle h) {
+  const SparseDev &sp = h->sp;
+  return h->sparse && sp.active && !sp.bk && sp.B > 8 && sp.split && sp.bMr && h->n + h->m > 0;
+}
+
+int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t ld, double *sol) {
+  const int Nf = h->n + h->m;
+  (void)hipSetDevice(h->device);
+  hipStream_t s = h->stream;
+  SparseDev &sp = h->sp;
+  const size_t Bk = (size_t)sp.B, nbk = (size_t)sp.bstride, prows = nbk * Bk;
+  const size_t pairs = (size_t)3 * sp.nred + 4;
+  if (!sp.bP) {  // the panel and, behind it, the right-hand sides as they came (natural order)
+    HIPCHK(h, dalloc(&sp.bP, prows * 64 + (size_t)64 * Nf));
+    HIPCHK(h, dalloc(&sp.bredm, 64 * pairs));
+    HIPCHK(h, hipHostMalloc((void **)&sp.h_bredm, 64 * pairs * sizeof(double)));
+  }
+  double *R = sp.bP + prows * 64;
+  if (!h->fac.factored) sp_assemble(h);
+  if (sp.kept != 2) {
+    sp_launch_bw_factor(s, sp, Nf, h->fac.flags);
+    sp.kept = 1;
+    HIPCHK(h, hipMemcpyAsync(h->fac.h_flags, h->fac.flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    band_kept_resolve(h);
+    if (h->fac.h_flags[0])
+      return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the banded KKT factorisation");
+    h->fac.n_neg = h->fac.h_flags[1];
+    h->fac.factored = true;
+  }
+  const bool guard = h->refine_mode != 0;
+  const int nb = (Nf + sp.B - 1) / sp.B;
+  int rc;
+  double worst = 0.0;
+  for (int c0 = 0; c0 < nrhs; c0 += 64) {
+    const int nc = std::min(64, nrhs - c0), kp = (nc + 15) / 16 * 16;
+    HIPCHK(h, hipMemsetAsync(sp.bP, 0, (size_t)nb * Bk * kp * sizeof(double), s));
+    for (int j = 0; j < nc; ++j) {
+      double *Rj = R + (size_t)j * Nf;
+      if ((rc = up(h, Rj, rhs + (int64_t)(c0 + j) * ld, (size_t)Nf * sizeof(double)))) return rc;
+      sp_launch_bw_panel_put(s, sp, Nf, Rj, sp.bP, kp, j);
+    }
+    sp_launch_bw_panel_solve(s, sp, Nf, sp.bP, kp);
+    for (int j = 0; j < nc; ++j) {
+      sp_launch_bw_panel_get(s, Nf, sp.bP, kp, j, sp.brhs);
+      if (guard) {
+        sp_launch_permute(s, sp, Nf, R + (size_t)j * Nf, sp.brhs0, 0);
+        sp_launch_bw_residual_to(s, sp, Nf, h->fac.flags, sp.bredm + (size_t)j * pairs);
+      }
+      sp_launch_permute(s, sp, Nf, sp.brhs, h->sol, 1);
+      if ((rc = down(h, sol + (int64_t)(c0 + j) * ld, h->sol, (size_t)Nf * sizeof(double)))) return rc;
+    }
+    if (guard)
+      HIPCHK(h, hipMemcpyAsync(sp.h_bredm, sp.bredm, (size_t)nc * pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    if (!guard) continue;
+    for (int j = 0; j < nc; ++j) {
+      const double rel = residual_rel_of(sp.h_bredm + (size_t)j * pairs, sp.nred);
+      if (rel > h->refine_tol) {  // this column once more, guarded and refined
+        if ((rc = band_linear_solve(h, rhs + (int64_t)(c0 + j) * ld, sol + (int64_t)(c0 + j) * ld))) return rc;
+        worst = std::max(worst, h->stat_last_rel);
+      } else {
+        worst = std::max(worst, rel);
+      }
+    }
+  }
+  if (guard) h->stat_last_rel = worst;
   return PGF_OK;
 }
 
@@ -242,7 +352,7 @@ static int auto_block_size(int bw) { return bw <= 8 ? 8 : bw <= 16 ? 16 : bw <= 
 // (k_bcr_level2 reads one and writes the other); the wide kernels use one.
 static int sp_alloc_blocks(pgf_handle h, int B) {
   SparseDev &sp = h->sp;
-  for (double **q : {&sp.bD, &sp.bL, &sp.bU, &sp.bDinv, &sp.bF})
+  for (double **q : {&sp.bD, &sp.bL, &sp.bU, &sp.bDinv, &sp.bF, &sp.bMr, &sp.bMl, &sp.bP, &sp.bredm})
     if (*q) {
       (void)hipFree(*q);
       *q = nullptr;
@@ -251,6 +361,11 @@ static int sp_alloc_blocks(pgf_handle h, int B) {
     (void)hipFree(sp.bneg);
     sp.bneg = nullptr;
   }
+  if (sp.h_bredm) {
+    (void)hipHostFree(sp.h_bredm);
+    sp.h_bredm = nullptr;
+  }
+  sp.kept = 0;
   sp.B = B;
   sp.bX = sp.brhs;  // the back-substitution writes the solution where the step update reads it
   const int N = h->n + h->m;
@@ -263,6 +378,10 @@ static int sp_alloc_blocks(pgf_handle h, int B) {
   HIPCHK(h, dalloc(&sp.bF, nsets * nbk * Bk));
   sp.bstride = (int64_t)nbk;
   HIPCHK(h, dalloc(&sp.bneg, nbk));
+  if (B > 8 && sp.split) {  // the kept forward multipliers of the wide reduction
+    HIPCHK(h, dalloc(&sp.bMr, nbk * Bk * Bk));
+    HIPCHK(h, dalloc(&sp.bMl, nbk * Bk * Bk));
+  }
   return PGF_OK;
 }
 
@@ -302,10 +421,11 @@ static int sp_alloc_bred(pgf_handle h, int nred) {
 void band_free(pgf_handle h) {
   SparseDev &sp = h->sp;
   if (sp.h_bred) (void)hipHostFree(sp.h_bred);
+  if (sp.h_bredm) (void)hipHostFree(sp.h_bredm);
   void *sps[] = {sp.pos, sp.Hptr, sp.Hrow, sp.Hcol, sp.Hslot, sp.Jptr, sp.Jcol, sp.Jslot, sp.JTptr,
                  sp.JTrow, sp.JTmap, sp.Hval, sp.Jval, sp.band, sp.brhs, sp.Hb0, sp.Jb0,
                  sp.bD, sp.bL, sp.bU, sp.bDinv, sp.bF, sp.bneg, sp.brhs0, sp.bres, sp.bsol,
-                 sp.bred, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags};
+                 sp.bred, sp.bMr, sp.bMl, sp.bP, sp.bredm, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags};
   for (void *q : sps)
     if (q) (void)hipFree(q);
 }
@@ -417,6 +537,38 @@ int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int
   if (k) *k = h->sp.bk;
   if (border_factorisations) *border_factorisations = h->sp.stat_bfactor;
   if (border_solves) *border_solves = h->sp.stat_bsolve;
+  return PGF_OK;
+}
+
+int pgf_sparse_set_factor_split(pgf_handle h, int on) {
+  if (!h) return PGF_INVALID;
+  if (!h->sparse) return fail(h, PGF_INVALID, "pgf_sparse_set_factor_split: banded handles only");
+  SparseDev &sp = h->sp;
+  const bool want = on != 0;
+  if (want == sp.split) return PGF_OK;
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  sp.split = want;
+  sp.kept = 0;
+  invalidate_factor(h);  // (a bordered band's factor phase depends on the route too)
+  for (double **q : {&sp.bMr, &sp.bMl})
+    if (*q) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+  if (want && sp.active && sp.B > 8) {
+    const size_t Bk = (size_t)sp.B, nbk = (size_t)sp.bstride;
+    HIPCHK(h, dalloc(&sp.bMr, nbk * Bk * Bk));
+    HIPCHK(h, dalloc(&sp.bMl, nbk * Bk * Bk));
+  }
+  return PGF_OK;
+}
+
+int pgf_debug_band_stats(pgf_handle h, int *reductions, int *solve_phases, int *panel_solves) {
+  if (!h) return PGF_INVALID;
+  if (reductions) *reductions = h->sp.stat_bw_reduce;
+  if (solve_phases) *solve_phases = h->sp.stat_bw_solve;
+  if (panel_solves) *panel_solves = h->sp.stat_bw_panel;
   return PGF_OK;
 }
 

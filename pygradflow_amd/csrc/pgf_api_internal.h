@@ -206,5 +206,11 @@ int band_step_async(pgf_handle h, bool *did_factor);           // newton_core_as
 int band_status_sync(pgf_handle h);                            // factor_finish, pgf_qp_sync (no-op on dense handles)
 int band_refine(pgf_handle h, bool swapped, bool with_step);   // refine_if_needed
 int band_linear_solve(pgf_handle h, const double *rhs, double *sol);  // pgf_linear_solve
+// pgf_linear_solve_multi: whether the handle takes the panel route, and that route
+bool band_multi_panel(pgf_handle h);
+int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t ld, double *sol);
+// after a sync that brought the pivot flags to fac.h_flags: settle the wide band's kept factors
+void band_kept_resolve(pgf_handle h);                          // finish_factor_state
+bool band_split_default();                                     // pgf_create (PGF_BW_SPLIT)
 void band_eval(pgf_handle h);                                  // qp_eval
 void band_measures_eval(pgf_handle h);                         // pgf_qp_measures

@@ -22,9 +22,22 @@
 //   * one level per launch pair (invert, then reduce): at B >= 16 the block count, and with it
 //     the number of levels, is 2 .. 8 x smaller than at B = 8, and the levels do real
 //     arithmetic rather than being bound by their launch.
-// Every solve re-runs the reduction on the intact band, as the 8 x 8 code does.
 //
-// Block storage (one set): D, L, U, inv D row-major B x B at block * B * B; F at block * B.
+// Factor / solve split.  A block e != 0 is eliminated at exactly one level s; from then on
+// inv(D_e), L_e, U_e (its couplings to e -+ s at that level) are final, and so are the two forward
+// multipliers that the kept neighbours formed from it:
+//   Mr[e] = L_{e+s} inv(D_e)   (used by the kept block e + s)
+//   Ml[e] = U_{e-s} inv(D_e)   (used by the kept block e - s)
+// The KEEP variant of k_bw_reduce stores them (2 B^2 doubles per block; the arithmetic of D, L, U, F
+// is untouched), and a solve against the kept factors (sp_launch_bw_backsolve, one right-hand side;
+// sp_launch_bw_panel_solve, a panel of them on the matrix pipes) runs no inversion:
+//   forward, per level: f_i -= Mr[i-s] f_{i-s} + Ml[i+s] f_{i+s} for the kept blocks i;
+//   x_0 = inv(D_0) f_0;  backward, per level: k_bw_back as in the fused solve.
+// The single right-hand side forward step shares bw_f_dot with k_bw_reduce, so it returns the bits
+// of the fused reduction.  Without kept factors every solve re-runs the reduction on the intact
+// band, as the 8 x 8 code does.
+//
+// Block storage (one set): D, L, U, inv D, Mr, Ml row-major B x B at block * B * B; F at block * B.
 #include "pgf_sparse.h"
 
 typedef double bw_double4 __attribute__((ext_vector_type(4)));
@@ -186,13 +199,26 @@ __device__ __forceinline__ bw_double4 bw_tile(const double *A, int lda, const do
   return acc;
 }
 
+// (T f_e)[row] for the row of T (LDS) at Trow: the forward update f_i -= T f_e of k_bw_reduce and
+// of k_bw_fwd -- one function, one operation order, the same bits
+template <int B>
+__device__ __forceinline__ double bw_f_dot(const double *Trow, const double *__restrict__ fe) {
+  double acc = 0.0;
+#pragma unroll 8
+  for (int k = 0; k < B; ++k) acc = fma(Trow[k], fe[k], acc);
+  return acc;
+}
+
 // Reduce the kept blocks of this level: i = 0, 2s, 4s, ...  The eliminated neighbours are not
 // written at this level, every kept block only writes its own D, L, U, F: no races.
-template <int B>
+// KEEP: also store the multipliers T (Mr[i - s], Ml[i + s]: each belongs to one eliminated block and
+// one kept block, so nobody else writes them).  RHS false: no right-hand side is carried (F unused).
+template <int B, bool KEEP, bool RHS>
 __global__ __launch_bounds__(BW_THREADS) void k_bw_reduce(double *__restrict__ D, double *__restrict__ L,
                                                           double *__restrict__ U, double *__restrict__ F,
-                                                          const double *__restrict__ Dinv, int nb,
-                                                          int s) {
+                                                          const double *__restrict__ Dinv,
+                                                          double *__restrict__ Mr, double *__restrict__ Ml,
+                                                          int nb, int s) {
   constexpr int LD = B + 1, NT = (B / 16) * (B / 16);  // 16 x 16 tiles of a block
   constexpr int TPW = NT >= 4 ? NT / 4 : 1;            // tiles per wavefront
   constexpr int BB = B * B;
@@ -219,7 +245,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_reduce(double *__restrict__ D
     for (int g = 0; g < 4; ++g)
       dacc[t][g] = busy ? D[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] : 0.0;
   }
-  double fv = (tid < B) ? F[(int64_t)i * B + tid] : 0.0;
+  double fv = (RHS && tid < B) ? F[(int64_t)i * B + tid] : 0.0;
   // two sides: (coupling of i, eliminated neighbour, its coupling further out, output)
   for (int side = 0; side < 2; ++side) {
     const int e = side == 0 ? le : ri;
@@ -259,12 +285,10 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_reduce(double *__restrict__ D
         for (int g = 0; g < 4; ++g) Ci[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] = acc[g];
       }
     }
-    if (tid < B) {  // f_i -= T f_e
-      const double *fe = F + (int64_t)e * B;
-      double acc = 0.0;
-#pragma unroll 8
-      for (int k = 0; k < B; ++k) acc = fma(T[tid * LD + k], fe[k], acc);
-      fv -= acc;
+    if (RHS && tid < B) fv -= bw_f_dot<B>(T + tid * LD, F + (int64_t)e * B);  // f_i -= T f_e
+    if (KEEP) {
+      double *M = (side == 0 ? Mr : Ml) + be;
+      for (int p = tid; p < BB; p += BW_THREADS) M[p] = T[(p / B) * LD + p % B];
     }
     __syncthreads();  // T is read by everyone before the other side overwrites it
   }
@@ -277,7 +301,7 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_reduce(double *__restrict__ D
       for (int g = 0; g < 4; ++g) D[bi + (int64_t)(r0 + l4 + 4 * g) * B + c0 + l15] = dacc[t][g];
     }
   }
-  if (tid < B) F[(int64_t)i * B + tid] = fv;
+  if (RHS && tid < B) F[(int64_t)i * B + tid] = fv;
 }
 
 // y = M v (B x B row-major in global memory, v in LDS), the rows split over 256 / B threads
@@ -372,6 +396,140 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_last(const double *__restrict
   }
 }
 
+// ---- solve phase against the kept factors, one right-hand side ----
+// F <- the right-hand side in whole blocks (zero padding), rhs0 <- its copy for the guard
+__global__ __launch_bounds__(256) void k_bw_load(const double *__restrict__ rhs, int N, int nrows,
+                                                 double *__restrict__ F, double *__restrict__ rhs0) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= nrows) return;
+  const double v = (g < N) ? rhs[g] : 0.0;
+  F[g] = v;
+  if (rhs0 && g < N) rhs0[g] = v;
+}
+
+// forward step of one level for the kept blocks i = 0, 2s, ...: f_i -= Mr[i-s] f_{i-s} + Ml[i+s] f_{i+s}
+// (a neighbour that does not exist contributes nothing).  The multiplier is staged in LDS with the
+// row stride of k_bw_reduce's T and applied by the same bw_f_dot, left side first.  A kept block
+// writes its own f only and reads those of blocks eliminated at this level: no races.
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_fwd(const double *__restrict__ Mr,
+                                                       const double *__restrict__ Ml,
+                                                       double *__restrict__ F, int nb, int s) {
+  constexpr int LD = B + 1, BB = B * B;
+  __shared__ double T[B * LD];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * 2 * s;
+  if (i >= nb) return;
+  double fv = (tid < B) ? F[(int64_t)i * B + tid] : 0.0;
+  for (int side = 0; side < 2; ++side) {
+    const int e = side == 0 ? i - s : i + s;
+    if (e < 0 || e >= nb) continue;
+    const double *M = (side == 0 ? Mr : Ml) + (int64_t)e * BB;
+    for (int p = tid; p < BB; p += BW_THREADS) T[(p / B) * LD + p % B] = M[p];
+    __syncthreads();
+    if (tid < B) fv -= bw_f_dot<B>(T + tid * LD, F + (int64_t)e * B);
+    __syncthreads();  // T is read by everyone before the other side overwrites it
+  }
+  if (tid < B) F[(int64_t)i * B + tid] = fv;
+}
+
+// x_0 = inv(D_0) f_0 (the operation order of k_bw_last's product)
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_x0(const double *__restrict__ Dinv,
+                                                      const double *__restrict__ F,
+                                                      double *__restrict__ X) {
+  constexpr int P = BW_THREADS / B;
+  __shared__ double t[B];
+  const int tid = threadIdx.x;
+  if (tid < B) t[tid] = F[tid];
+  __syncthreads();
+  const double x = bw_matvec<B>(Dinv, t, tid);
+  if (tid % P == 0) X[tid / P] = x;
+}
+
+// ---- solve phase against the kept factors, a panel of kp right-hand sides (row-major, row stride
+// kp, a block's B x kp rows contiguous; kp a multiple of 16, at most 64), in place, on
+// v_mfma_f64_16x16x4_f64: (B / 16) (kp / 16) <= 16 output tiles, at most four per wavefront.
+//
+// In place without races (the argument of k_mbcr_level, pgf_sparse.hip): forward, a kept block
+// writes only its own rows and reads rows of blocks eliminated at its level, which no block of
+// that launch writes; backward, an eliminated block writes only its own rows and reads rows of
+// blocks solved at earlier launches.
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_fwd_panel(const double *__restrict__ Mr,
+                                                             const double *__restrict__ Ml,
+                                                             double *__restrict__ P, int kp, int nb,
+                                                             int s) {
+  constexpr int BB = B * B;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l4 = lane >> 4, l15 = lane & 15;
+  const int i = blockIdx.x * 2 * s;
+  if (i >= nb) return;
+  const int le = i - s, ri = i + s;
+  const int tc = kp / 16, nt = (B / 16) * tc;
+  double *Pi = P + (int64_t)i * B * kp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;  // (uniform over the wavefront)
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
+    if (le >= 0)
+      acc = bw_tile<B>(Mr + (int64_t)le * BB, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
+    if (ri < nb)
+      acc = bw_tile<B>(Ml + (int64_t)ri * BB, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+  }
+}
+
+// X_e = inv(D_e) (F_e - L_e X_{e-s} - U_e X_{e+s}) for e = first, first + stride, ...; s == 0: the
+// last block, no neighbours.  T = F_e - ... in LDS (row stride kp + 1), then the product.
+template <int B>
+__global__ __launch_bounds__(BW_THREADS) void k_bw_back_panel(const double *__restrict__ Dinv,
+                                                              const double *__restrict__ L,
+                                                              const double *__restrict__ U,
+                                                              double *__restrict__ P, int kp, int nb,
+                                                              int s, int first, int stride) {
+  constexpr int BB = B * B;
+  __shared__ double T[B * 65];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l4 = lane >> 4, l15 = lane & 15;
+  const int e = first + blockIdx.x * stride;
+  if (e >= nb) return;
+  const int le = e - s, ri = e + s, ldt = kp + 1;
+  const bool hl = s > 0 && le >= 0, hr = s > 0 && ri < nb;
+  const int tc = kp / 16, nt = (B / 16) * tc;
+  const int64_t be = (int64_t)e * BB;
+  double *Pe = P + (int64_t)e * B * kp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
+    if (hl) acc = bw_tile<B>(L + be, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
+    if (hr) acc = bw_tile<B>(U + be, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) T[(r0 + l4 + 4 * g) * ldt + c0 + l15] = acc[g];
+  }
+  __syncthreads();  // T complete (every tile of X_e reads all its rows)
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc = {0.0, 0.0, 0.0, 0.0};
+    acc = bw_tile<B>(Dinv + be, B, T, ldt, r0, c0, acc, lane, false);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+  }
+}
+
 // Accuracy guard for bw <= 64: the same (max |r|, max (|K| |x| + |rhs0|)) pair per 256 rows as
 // k_band_residual (pgf_sparse.hip), which stages its rows in LDS for bw <= 10; here a row reads
 // its band entries straight from memory (up to 2 x 65 of them, L2-resident neighbours).
@@ -424,10 +582,14 @@ void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int 
                      sp.brhs, sp.brhs0, sp.bres, sp.bred, flags, sp.nred);
 }
 
+// the fused reduction (+ solve when with_rhs); keep: the KEEP variant, which leaves the factors
 template <int B>
-static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard, bool keep,
+                     bool with_rhs) {
   const int nb = (N + B - 1) / B;
   const dim3 blk(BW_THREADS);
+  ++sp.stat_bw_reduce;
+  // (the extraction always fills F; a factor-only reduction just does not carry it along)
   hipLaunchKernelGGL(k_bw_extract<B>, dim3(nb), blk, 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N, nb, sp.bD,
                      sp.bL, sp.bU, sp.bF, guard ? sp.brhs0 : nullptr, flags);
   int levels[32], nlev = 0;
@@ -435,11 +597,21 @@ static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool
     const int ne = (nb - st + 2 * st - 1) / (2 * st);  // eliminated: st, 3st, ...
     const int nk = (nb + 2 * st - 1) / (2 * st);       // kept: 0, 2st, ...
     hipLaunchKernelGGL(k_bw_invert<B>, dim3(ne), blk, 0, s, sp.bD, sp.bDinv, nb, st, 2 * st, flags, sp.bneg);
-    hipLaunchKernelGGL(k_bw_reduce<B>, dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF, sp.bDinv, nb, st);
+    if (!with_rhs)
+      hipLaunchKernelGGL((k_bw_reduce<B, true, false>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
+                         sp.bDinv, sp.bMr, sp.bMl, nb, st);
+    else if (keep)
+      hipLaunchKernelGGL((k_bw_reduce<B, true, true>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
+                         sp.bDinv, sp.bMr, sp.bMl, nb, st);
+    else
+      hipLaunchKernelGGL((k_bw_reduce<B, false, true>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
+                         sp.bDinv, nullptr, nullptr, nb, st);
     levels[nlev++] = st;
   }
-  hipLaunchKernelGGL(k_bw_last<B>, dim3(1), blk, 0, s, sp.bD, sp.bDinv, sp.bF, sp.bX, nb, flags,
-                     sp.bneg);
+  // (factor-only: the last block's product goes to the spare block behind F and is not used)
+  hipLaunchKernelGGL(k_bw_last<B>, dim3(1), blk, 0, s, sp.bD, sp.bDinv, sp.bF,
+                     with_rhs ? sp.bX : sp.bF + (int64_t)nb * B, nb, flags, sp.bneg);
+  if (!with_rhs) return;
   for (int q = nlev - 1; q >= 0; --q) {
     const int st = levels[q];
     const int ne = (nb - st + 2 * st - 1) / (2 * st);
@@ -448,17 +620,123 @@ static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool
   if (guard) sp_launch_bw_residual(s, sp, N, flags);
 }
 
+template <int B>
+static void bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard) {
+  const int nb = (N + B - 1) / B;
+  const dim3 blk(BW_THREADS);
+  ++sp.stat_bw_solve;
+  hipLaunchKernelGGL(k_bw_load, dim3((nb * B + 255) / 256), dim3(256), 0, s, sp.brhs, N, nb * B, sp.bF,
+                     guard ? sp.brhs0 : nullptr);
+  int levels[32], nlev = 0;
+  for (int st = 1; st < nb; st *= 2) {
+    const int nk = (nb + 2 * st - 1) / (2 * st);
+    hipLaunchKernelGGL(k_bw_fwd<B>, dim3(nk), blk, 0, s, sp.bMr, sp.bMl, sp.bF, nb, st);
+    levels[nlev++] = st;
+  }
+  hipLaunchKernelGGL(k_bw_x0<B>, dim3(1), blk, 0, s, sp.bDinv, sp.bF, sp.bX);
+  for (int q = nlev - 1; q >= 0; --q) {
+    const int st = levels[q];
+    const int ne = (nb - st + 2 * st - 1) / (2 * st);
+    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, sp.bF, sp.bX, nb, st);
+  }
+  if (guard) sp_launch_bw_residual(s, sp, N, flags);
+}
+
+template <int B>
+static void bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp) {
+  const int nb = (N + B - 1) / B;
+  const dim3 blk(BW_THREADS);
+  ++sp.stat_bw_panel;
+  int levels[32], nlev = 0;
+  for (int st = 1; st < nb; st *= 2) {
+    const int nk = (nb + 2 * st - 1) / (2 * st);
+    hipLaunchKernelGGL(k_bw_fwd_panel<B>, dim3(nk), blk, 0, s, sp.bMr, sp.bMl, P, kp, nb, st);
+    levels[nlev++] = st;
+  }
+  hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(1), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, kp, nb, 0, 0, 1);
+  for (int q = nlev - 1; q >= 0; --q) {
+    const int st = levels[q];
+    const int ne = (nb - st + 2 * st - 1) / (2 * st);
+    hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, kp, nb, st, st,
+                       2 * st);
+  }
+}
+
 // Solve the banded system in sp.band / sp.brhs with B = sp.B x sp.B blocks (16, 32, 64); the
 // solution replaces sp.brhs (which holds whole blocks: sp.bX).  flags[0] zero pivot, flags[1]
 // negative pivots; guard: keep the right-hand side and finish with the residual (bres, bred).
-void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
+// keep: also leave the forward multipliers in sp.bMr / sp.bMl (the same solution, bit for bit).
+void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard, bool keep) {
   if (N == 0) {
     (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
     return;
   }
   switch (sp.B) {
-    case 16: bw_solve<16>(s, sp, N, flags, guard); break;
-    case 32: bw_solve<32>(s, sp, N, flags, guard); break;
-    default: bw_solve<64>(s, sp, N, flags, guard); break;
+    case 16: bw_solve<16>(s, sp, N, flags, guard, keep, true); break;
+    case 32: bw_solve<32>(s, sp, N, flags, guard, keep, true); break;
+    default: bw_solve<64>(s, sp, N, flags, guard, keep, true); break;
+  }
+}
+
+// The KEEP reduction without a right-hand side: factors and pivot flags only; sp.brhs survives.
+void sp_launch_bw_factor(hipStream_t s, const SparseDev &sp, int N, int *flags) {
+  if (N == 0) {
+    (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
+    return;
+  }
+  switch (sp.B) {
+    case 16: bw_solve<16>(s, sp, N, flags, false, true, false); break;
+    case 32: bw_solve<32>(s, sp, N, flags, false, true, false); break;
+    default: bw_solve<64>(s, sp, N, flags, false, true, false); break;
+  }
+}
+
+// Solve phase against the factors a KEEP reduction left, for the right-hand side in sp.brhs: load,
+// one forward launch per level, x_0, one backward launch per level (2 levels + 3 launches with the
+// guard's residual; no inversion, no MFMA).  The pivot flags stay what the reduction reported.
+void sp_launch_bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard) {
+  if (N == 0) return;
+  switch (sp.B) {
+    case 16: bw_backsolve<16>(s, sp, N, flags, guard); break;
+    case 32: bw_backsolve<32>(s, sp, N, flags, guard); break;
+    default: bw_backsolve<64>(s, sp, N, flags, guard); break;
+  }
+}
+
+// column j of the panel <-> a vector: P[pos[i]][j] = in[i] (natural order in, put), and
+// out[g] = P[g][j] (permuted order out, get)
+__global__ __launch_bounds__(256) void k_bw_panel_put(int N, const int *__restrict__ pos,
+                                                      const double *__restrict__ in,
+                                                      double *__restrict__ P, int kp, int j) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < N) P[(int64_t)pos[i] * kp + j] = in[i];
+}
+__global__ __launch_bounds__(256) void k_bw_panel_get(int N, const double *__restrict__ P, int kp, int j,
+                                                      double *__restrict__ out) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g < N) out[g] = P[(int64_t)g * kp + j];
+}
+void sp_launch_bw_panel_put(hipStream_t s, const SparseDev &sp, int N, const double *in, double *P, int kp,
+                            int j) {
+  if (N) hipLaunchKernelGGL(k_bw_panel_put, dim3((N + 255) / 256), dim3(256), 0, s, N, sp.pos, in, P, kp, j);
+}
+void sp_launch_bw_panel_get(hipStream_t s, int N, const double *P, int kp, int j, double *out) {
+  if (N) hipLaunchKernelGGL(k_bw_panel_get, dim3((N + 255) / 256), dim3(256), 0, s, N, P, kp, j, out);
+}
+// the guard's residual of sp.brhs against sp.brhs0 with the pairs written to `pairs`
+void sp_launch_bw_residual_to(hipStream_t s, const SparseDev &sp, int N, const int *flags, double *pairs) {
+  if (N == 0) return;
+  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, N,
+                     sp.brhs, sp.brhs0, sp.bres, pairs, flags, sp.nred);
+}
+
+// Solve phase for a panel: P is (nb B) x kp row-major, kp a multiple of 16 and at most 64, rows >= N
+// zero on entry; the solutions replace the right-hand sides.
+void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp) {
+  if (N == 0) return;
+  switch (sp.B) {
+    case 16: bw_panel_solve<16>(s, sp, N, P, kp); break;
+    case 32: bw_panel_solve<32>(s, sp, N, P, kp); break;
+    default: bw_panel_solve<64>(s, sp, N, P, kp); break;
   }
 }

@@ -517,14 +517,54 @@ __global__ __launch_bounds__(256) void k_border_residual(
 }
 
 // ---------------------------------------------------------------- phases
+// Wide remainder (B = 16, 32, 64) with the factor / solve split on: B is factorised ONCE per
+// assembled matrix (the factor-only KEEP reduction of pgf_band_wide.hip), and every solve with B --
+// the kp columns of Y as one panel, v of each solve phase -- runs against the kept factors.
+static bool wide_kept(const SparseDev &sp) { return sp.B > 8 && sp.split && sp.bMr; }
+
+// The solve phase of the wide band leaves the pivot flags alone, and k_border_small_solve ADDS
+// those of S to them: the flags of B are parked in bsflags[2, 4) by the factor phase (save) and
+// put back in front of every solve phase (flags[2], flags[3] cleared as the extraction does).
+__global__ void k_border_bflags(int *__restrict__ flags, int *__restrict__ sflags, int save) {
+  if (threadIdx.x != 0) return;
+  if (save) {
+    sflags[2] = flags[0];
+    sflags[3] = flags[1];
+  } else {
+    flags[0] = sflags[2];
+    flags[1] = sflags[3];
+    flags[2] = 0;
+    flags[3] = 0;
+  }
+}
+
 void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
   const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
   ++sp.stat_bfactor;
-  // PGF_BORDER_MULTI=0: Y column by column through the single-right-hand-side reduction also at
-  // B = 8 (the only route at B = 16, 32, 64): slower, and an independent check of the panel kernels
+  // PGF_BORDER_MULTI=0: Y column by column through the single-right-hand-side solves at every B:
+  // slower, and an independent check of the panel kernels
   static const bool multi = !(getenv("PGF_BORDER_MULTI") && atoi(getenv("PGF_BORDER_MULTI")) == 0);
   if (sp.B == 8 && multi) {
     mbcr_solve(s, sp);
+  } else if (wide_kept(sp)) {
+    sp_launch_bw_factor(s, sp, Nb, flags);  // (reads sp.brhs, writes none of it)
+    hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 1);
+    const int nbB = (Nb + sp.B - 1) / sp.B * sp.B;  // Y in whole B-row blocks, the padding rows zero
+    if (multi) {
+      (void)hipMemcpyAsync(sp.bY, sp.bC, (size_t)Nb * kp * sizeof(double), hipMemcpyDeviceToDevice, s);
+      if (nbB > Nb)
+        (void)hipMemsetAsync(sp.bY + (size_t)Nb * kp, 0, (size_t)(nbB - Nb) * kp * sizeof(double), s);
+      sp_launch_bw_panel_solve(s, sp, Nb, sp.bY, kp);
+    } else {
+      (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+      (void)hipMemsetAsync(sp.bY, 0, (size_t)nbB * kp * sizeof(double), s);
+      for (int j = 0; j < k; ++j) {
+        hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bC, sp.brhs, 0);
+        sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
+        hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.brhs, sp.bY, 1);
+      }
+      (void)hipMemcpyAsync(sp.brhs, sp.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    }
   } else {
     // the band solves work in sp.brhs: whatever right-hand side waits there moves out of the way
     (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
@@ -555,7 +595,12 @@ void sp_border_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard)
   (void)hipMemcpyAsync(sp.brb, sp.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (guard)
     (void)hipMemcpyAsync(sp.brhs0, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-  band_solve(s, sp, Nb, flags);  // v = inv(B) ra; flags <- pivots of B
+  if (wide_kept(sp)) {  // v = inv(B) ra against the kept factors; flags <- pivots of B as kept
+    hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 0);
+    sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
+  } else {
+    band_solve(s, sp, Nb, flags);  // v = inv(B) ra; flags <- pivots of B
+  }
   hipLaunchKernelGGL(k_border_ctv, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.brhs, Nb, kp, sp.bpartv);
   hipLaunchKernelGGL(k_border_small_solve, dim3(1), dim3(64), 0, s, sp.bS, k, kp, sp.brb, sp.bpartv, sp.bnchunk,
                      sp.bsflags, sp.bz, sp.brhs + Nb, flags);

@@ -32,6 +32,18 @@ struct SparseDev {
   // block cyclic reduction work arrays: (N/B) blocks of B x B (D, L, U, inv D), rhs, solution
   double *bD = nullptr, *bL = nullptr, *bU = nullptr, *bDinv = nullptr, *bF = nullptr, *bX = nullptr;
   int *bneg = nullptr;                      // negative pivots met while inverting block i
+  // Factor / solve split of the wide reduction (B > 8, pgf_band_wide.hip): the forward multipliers
+  // of the eliminated block e, Mr[e] = L_{e+s} inv(D_e) and Ml[e] = U_{e-s} inv(D_e); allocated only
+  // while `split` is on.  kept: 0 no factors, 1 a KEEP reduction is enqueued whose pivot flags the
+  // host has not seen yet, 2 its flags were clean: solves run the solve phase.
+  double *bMr = nullptr, *bMl = nullptr;
+  bool split = true;
+  int kept = 0;
+  // pgf_linear_solve_multi on a wide band: the panel (whole blocks x 64) and, per column, the
+  // residual pairs + flags of k_bw_residual (device and pinned mirror); allocated on first use
+  double *bP = nullptr, *bredm = nullptr, *h_bredm = nullptr;
+  // wide-band phases enqueued (pgf_debug_band_stats)
+  mutable int stat_bw_reduce = 0, stat_bw_solve = 0, stat_bw_panel = 0;
   // bD, bL, bU, bF hold TWO sets of blocks, the second bstride blocks behind the first: a launch
   // that does two cyclic-reduction levels at once reads one set and writes the other
   int64_t bstride = 0;
@@ -71,7 +83,22 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
 void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 // B = 16, 32, 64 (pgf_band_wide.hip): the same contract as sp_launch_bcr_solve /
 // sp_launch_band_residual for half-bandwidths up to 64
-void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard);
+// keep: the reduction also leaves its forward multipliers in sp.bMr / sp.bMl (same solution bits)
+void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard,
+                        bool keep = false);
+// the KEEP reduction without a right-hand side (factors and pivot flags only)
+void sp_launch_bw_factor(hipStream_t s, const SparseDev &sp, int N, int *flags);
+// solve phase against the kept factors: the right-hand side in sp.brhs / a row-major panel P of kp
+// columns (a multiple of 16, at most 64; whole blocks, rows >= N zero), in place.  The pivot flags
+// are left as the reduction reported them.
+void sp_launch_bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard);
+void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp);
+// column j of a panel: P[pos[i]][j] = in[i] / out[g] = P[g][j]; the residual of sp.brhs against
+// sp.brhs0 with its pairs and flags written to `pairs` (3 nred + 4 doubles) instead of sp.bred
+void sp_launch_bw_panel_put(hipStream_t s, const SparseDev &sp, int N, const double *in, double *P, int kp,
+                            int j);
+void sp_launch_bw_panel_get(hipStream_t s, int N, const double *P, int kp, int j, double *out);
+void sp_launch_bw_residual_to(hipStream_t s, const SparseDev &sp, int N, const int *flags, double *pairs);
 void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 void sp_launch_band_axpy(hipStream_t s, int N, const double *a, double *x);
 void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, double fact,

@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .params import enum_name
-from .sparse import MAX_BANDWIDTH, BandPlan, border_key
+from .sparse import MAX_BANDWIDTH, BandPlan, apply_band_split, border_key
 from .step_solver import DENSE_LIMIT, POOL, HipStepSolver, residency_key, same_key
 
 
@@ -218,6 +218,8 @@ class DeviceNewton:
         key = residency_key(problem)
         stale = not same_key(key, self._hd.derivs_key)
         block = getattr(problem, "pgf_band_block", None)
+        if self.sparse:
+            apply_band_split(lib, h, problem)
         replan = self._hd.plan is not None and (
             self._hd.plan.block != (int(block) if block else None)
             or self._hd.plan.border_spec != border_key(border))
@@ -370,6 +372,14 @@ class DeviceNewton:
         a, b = C.c_int(0), C.c_int(0)
         _lib.check(self._lib.pgf_debug_tail_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
         return a.value, b.value
+
+    def band_stats(self):
+        """(reductions, solve phases, panel solves) of the wide banded solve enqueued on this handle
+        since its creation (``pgf_debug_band_stats``)."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_band_stats(self._hd.h, C.byref(a), C.byref(b), C.byref(c)),
+                   self._hd.h)
+        return a.value, b.value, c.value
 
     def border_stats(self):
         """(border size, factor phases, solve phases) of the bordered band on this handle

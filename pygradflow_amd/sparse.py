@@ -15,6 +15,7 @@ Replaces, for sparse problems, the scipy slicing + ``bmat`` assembly of the refe
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import scipy.sparse as sps
@@ -242,6 +243,37 @@ class BandPlan:
             _lib.check(lib.pgf_sparse_set_border(handle, self.k), handle, "pgf_sparse_set_border")
         rc = lib.pgf_sparse_set_block_size(handle, self.block or 0)
         _lib.check(rc, handle, f"pgf_sparse_set_block_size (half-bandwidth {self.bw})")
+
+
+def band_split(problem):
+    """``problem.pgf_band_split``: the factor / solve split of the wide banded solve
+    (``pgf_sparse_set_factor_split``).  None (not set): the library's default stays; otherwise a
+    bool (or 0 / 1)."""
+    v = getattr(problem, "pgf_band_split", None)
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and v in (0, 1)):
+        return bool(v)
+    raise ValueError(f"pgf_band_split must be a bool, not {v!r}")
+
+
+def _band_split_default():
+    """The library's default (``PGF_BW_SPLIT=0`` switches it off; pgf_api_band.hip reads it alike)."""
+    v = os.environ.get("PGF_BW_SPLIT")
+    if v is None:
+        return True
+    try:
+        return int(v.strip() or 0) != 0
+    except ValueError:
+        return False  # (atoi of a non-number is 0)
+
+
+def apply_band_split(lib, handle, problem):
+    """Set the handle's split to what the problem asks for, or back to the default: pooled handles
+    keep what their last user set."""
+    want = band_split(problem)
+    on = _band_split_default() if want is None else want
+    _lib.check(lib.pgf_sparse_set_factor_split(handle, int(on)), handle, "pgf_sparse_set_factor_split")
 
 
 def border_key(border):

@@ -25,7 +25,7 @@ import scipy.sparse as sps
 from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .linear_solver import HipLinearSolver
-from .sparse import BandPlan, MAX_BANDWIDTH, border_key
+from .sparse import BandPlan, MAX_BANDWIDTH, apply_band_split, border_key
 
 DENSE_LIMIT = 20000  # n + m above which sparse derivatives take the banded path
 DENSE_MAX = 60000    # largest n + m the dense path accepts (pgf_create; 28.8 GB of KKT matrix)
@@ -449,6 +449,7 @@ class HipStepSolver:
         hess = sps.csr_matrix(self._hess)
         jac = sps.csr_matrix(self._jac) if self.m else sps.csr_matrix((0, self.n))
         block = getattr(self.problem, "pgf_band_block", None)
+        apply_band_split(self._lib, hd.h, self.problem)
         if hd.plan is not None and (hd.plan.block != (int(block) if block else None)
                                     or hd.plan.border_spec != border_key(self._border)):
             hd.plan = None  # a different block size or border was asked for: upload again
@@ -510,6 +511,14 @@ class HipStepSolver:
         _lib.check(self._lib.pgf_refinement_stats(self._hd.h, C.byref(a), C.byref(b), C.byref(r)),
                    self._hd.h)
         return a.value, b.value, r.value
+
+    def band_stats(self):
+        """(reductions, solve phases, panel solves) of the wide banded solve enqueued on this
+        solver's handle since its creation (``pgf_debug_band_stats``)."""
+        a, b, c = C.c_int(0), C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_band_stats(self._hd.h, C.byref(a), C.byref(b), C.byref(c)),
+                   self._hd.h)
+        return a.value, b.value, c.value
 
     def border_stats(self):
         """(border size, factor phases, solve phases) of the bordered band on this solver's handle
@@ -599,7 +608,14 @@ class _DeviceFactorView:
         self._o = owner
 
     def solve(self, rhs, trans=False, initial_sol=None):
+        """``rhs``: one right-hand side (rows,) or several (rows, nrhs), as ``LUSolver.solve``
+        takes them; the result has the same shape."""
         o = self._o
+        rhs = np.asarray(rhs, dtype=np.float64)
+        if rhs.ndim == 2:
+            return self._solve_multi(rhs, trans)
+        if rhs.ndim != 1:
+            raise ValueError("rhs must have one or two dimensions")
         rhs = _lib.as_f64(rhs)
         if o.sparse:
             # the banded system keeps its full size (active variables are identity rows):
@@ -621,6 +637,39 @@ class _DeviceFactorView:
         rc = o._lib.pgf_linear_solve(o._hd.h, _lib.dptr(rhs), int(bool(trans)), _lib.dptr(sol))
         _lib.check(rc, o._hd.h, "pgf_linear_solve")
         return sol
+
+    def _rows(self):
+        """Length of a right-hand side of ``solve``."""
+        o = self._o
+        if o.sparse:
+            return int(o.n - np.count_nonzero(o.active_set)) + o.m
+        return o.n + o.m if o.formulation else o.reduced_dims()[1]
+
+    def _solve_multi(self, rhs, trans):
+        """(rows, nrhs) through ``pgf_linear_solve_multi``: the columns go to the library as
+        contiguous vectors (column j at ``j * ld``)."""
+        o = self._o
+        rows, nrhs = rhs.shape
+        if rows != self._rows():
+            raise ValueError("rhs shape mismatch")
+        if nrhs == 0:
+            return np.empty((rows, 0))
+        if o.sparse:
+            ina = np.logical_not(o.active_set)
+            ni = int(np.count_nonzero(ina))
+            full = np.zeros((nrhs, o.n + o.m))
+            full[:, : o.n][:, ina] = rhs[:ni].T
+            full[:, o.n:] = rhs[ni:].T
+        else:
+            full = np.ascontiguousarray(rhs.T)
+        out = np.empty_like(full)
+        ld = max(full.shape[1], 1)
+        rc = o._lib.pgf_linear_solve_multi(o._hd.h, _lib.dptr(full), nrhs, ld, int(bool(trans)),
+                                           _lib.dptr(out))
+        _lib.check(rc, o._hd.h, "pgf_linear_solve_multi")
+        if o.sparse:
+            return np.concatenate([out[:, : o.n][:, ina], out[:, o.n:]], axis=1).T.copy()
+        return out.T.copy()
 
     def num_neg_eigvals(self):
         o = self._o

@@ -4,7 +4,12 @@ steps from zero (median of --reps after --warmup warm-ups, the convention of SUR
   budget_box_qp(16 384)                 bordered route (pgf_border = "auto"), Full and Simplified
   the same problem                      dense route (no pgf_border: what the code did before), Full and Simplified
   budget_box_qp(100 000)                bordered route (no dense matrix of that size exists)
-  ocp_global_parameter(5000, 8, 4, 4)   bordered route, wide remainder (B = 32): Y by repeated solves
+  ocp_global_parameter(5000, 8, 4, 4)   bordered route, wide remainder (B = 32)
+  bordered_lq(20 000, bw 12, k = 16)    bordered route, wide remainder (B = 16), the tests' generator
+                                        (--wide-only: the two wide remainders alone)
+
+On a wide remainder Y = inv(B) C is one panel solve against the kept factors of one reduction of B
+(factor / solve split of pgf_band_wide.hip on), or k whole reductions (split off).
 
 Per workload: wall time of a step (each step waits for the device once, so this is device time plus
 the launch overhead), and from HIP events (pgf_profile_read_ex) the device time of the factor
@@ -107,13 +112,22 @@ def workload(name, prob, bordered, reps, warmup, check):
     n, m = prob.num_vars, prob.num_cons
     rec = {"workload": name, "n": n, "m": m, "route": "bordered" if bordered else "dense"}
     if bordered:
-        prob.pgf_border = "auto"
+        if getattr(prob, "pgf_border", None) is None:
+            prob.pgf_border = "auto"
         dn = pgf.DeviceNewton(prob, "Full", np.zeros(n), np.zeros(m), 1.0, 1.0)
         plan = dn._hd.plan
+        panels = 0
+        if hasattr(dn, "band_stats"):  # wide remainder: did the factor phase run a panel solve?
+            before = dn.band_stats()[2]
+            dn.step()
+            panels = dn.band_stats()[2] - before
         dn.close()
-        rec.update(k=plan.k, kp=plan.kp, Nb=plan.Nb, bw=plan.bw, block=plan.block_size,
-                   y_route="multi-rhs reduction" if plan.block_size == 8 and
-                   os.environ.get("PGF_BORDER_MULTI") != "0" else "repeated solves")
+        y_route = "repeated solves"
+        if plan.block_size == 8 and os.environ.get("PGF_BORDER_MULTI") != "0":
+            y_route = "multi-rhs reduction"
+        elif panels:
+            y_route = "panel solve against kept factors"
+        rec.update(k=plan.k, kp=plan.kp, Nb=plan.Nb, bw=plan.bw, block=plan.block_size, y_route=y_route)
         if check:
             rec["reference_agreement"] = agreement(prob)
     for pol in ("Full", "Simplified"):
@@ -133,10 +147,30 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dense-reps", type=int, default=5, help="repetitions of the dense route (about 10 ms a step)")
     ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--wide-only", action="store_true", help="only the wide-remainder workloads")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "border_band_timing.jsonl"))
     args = ap.parse_args()
     _lib.require_gpu()
     recs = []
+
+    def wide():
+        from tests.band_util import bordered_lq
+
+        recs.append(workload("ocp_global_parameter(5000,8,4,4)", problems.ocp_global_parameter(5000, 8, 4, 4),
+                             True, args.reps, args.warmup, not args.no_check))
+        recs.append(workload("bordered_lq(20000,bw=12,k=16,B=16)", bordered_lq(20000, 12, 0, 8, 8, 1, block=16),
+                             True, args.reps, args.warmup, not args.no_check))
+
+    def write():
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            for rec in recs:
+                f.write(json.dumps(rec, sort_keys=True) + "\n")
+        print(json.dumps({"written": args.out}))
+
+    if args.wide_only:
+        wide()
+        return write()
     a = workload("budget_box_qp(16384)", problems.budget_box_qp(16384), True, args.reps, args.warmup,
                  not args.no_check)
     recs.append(a)
@@ -146,13 +180,8 @@ def main():
     recs.append(b)
     recs.append(workload("budget_box_qp(100000)", problems.budget_box_qp(100000), True, args.reps, args.warmup,
                          not args.no_check))
-    recs.append(workload("ocp_global_parameter(5000,8,4,4)", problems.ocp_global_parameter(5000, 8, 4, 4), True,
-                         args.reps, args.warmup, not args.no_check))
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        for rec in recs:
-            f.write(json.dumps(rec, sort_keys=True) + "\n")
-    print(json.dumps({"written": args.out}))
+    wide()
+    write()
 
 
 if __name__ == "__main__":

@@ -2,9 +2,11 @@
 Simplified back-solve step of DeviceNewton, the dense path on the same problem where it fits
 (H and J handed over as dense arrays), and the CPU oracle's time per step beside each.
 
-    python tools/time_wide_band.py [--steps K] [--quick] [--narrow]
+    python tools/time_wide_band.py [--steps K] [--quick] [--narrow] [--split 0|1]
 
 --narrow: the bw 9 .. 10 problems instead (automatic block size: B = 16).
+--split:  the factor / solve split of the wide reduction off / on (``problem.pgf_band_split``;
+          not given: the library's default, on unless PGF_BW_SPLIT=0); recorded in every row.
 """
 import argparse
 import json
@@ -50,6 +52,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--quick", action="store_true", help="skip the oracle and the dense comparison")
     ap.add_argument("--narrow", action="store_true", help="the bw 9 .. 10 cases (implies --quick)")
+    ap.add_argument("--split", type=int, choices=(0, 1), default=None,
+                    help="factor / solve split of the wide reduction (default: the library's)")
     a = ap.parse_args()
     cases = [
         ("grid_box_qp(9, 320)", problems.grid_box_qp(9, 320), False),
@@ -64,9 +68,13 @@ def main():
     ]
     for name, prob, with_dense in cases:
         prob.pgf_force_band = True
+        if a.split is not None:
+            prob.pgf_band_split = bool(a.split)
         n, m = prob.num_vars, prob.num_cons
         plan = BandPlan(prob.hess_sparse(), prob.jac_sparse(), n, m)
         row = {"case": name, "N": n + m, "bw": plan.bw, "B": plan.block_size}
+        if a.split is not None:
+            row["split"] = a.split
         if a.narrow:
             a.quick = True
             row["route"] = f"bcr{plan.block_size}"
