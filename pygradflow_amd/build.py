@@ -25,6 +25,9 @@ SOURCES = [
     ("pgf_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api.hip", ["-ffp-contract=off"]),
     ("pgf_api_band.hip", ["-ffp-contract=off"]),
+    ("pgf_api_unsym.hip", ["-ffp-contract=off"]),
+    ("pgf_api_batch.hip", ["-ffp-contract=off"]),
+    ("pgf_api_aux.hip", ["-ffp-contract=off"]),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

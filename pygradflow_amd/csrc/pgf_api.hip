@@ -1,5 +1,6 @@
-// C ABI of libpgf_hip.so (include/pgf_hip.h): handle management and the per-step
-// orchestration of the kernels in pgf_kernels.hip / pgf_ldlt.hip.
+// C ABI of libpgf_hip.so (include/pgf_hip.h): the dense Symmetric handle and the per-step
+// orchestration of the kernels in pgf_kernels.hip / pgf_ldlt.hip, the device-resident LQ step
+// included.  (pgf_hip.h declares every entry point extern "C": the definitions follow it.)
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -10,28 +11,14 @@
 #include "pgf_kernels.h"
 #include "pgf_unsym.h"
 
-#define PGF_GEMVT_PARTS 32
-
-static const char *k_no_handle = "null handle";
-static const char *k_chain_msg = "chained triangular solve failed its placement / timeout check "
-                                 "and so did the per-block solve that replaced it";
-
 // PGF_EVAL_AHEAD=0: g and c at the new point are evaluated at the start of the next step, not
 // ahead of the host synchronisation of this one (newton_core_async, enqueue_qp_step, pgf_batch_step_async)
-static bool eval_ahead() {
-  static const bool ahead = !(getenv("PGF_EVAL_AHEAD") && atoi(getenv("PGF_EVAL_AHEAD")) == 0);
-  return ahead;
-}
+bool eval_ahead() { static const bool ahead = env_on("PGF_EVAL_AHEAD"); return ahead; }
 
 // PGF_STEP_FUSED=0: the launches in front of and behind the factorisation of a qp step as before --
 // k_mask_compact + k_residual_rhs; k_cond_y, k_step_update, the J and H row passes, k_sum_partials2,
 // k_kkt_residual; three launches in pgf_qp_advance_outer -- instead of the fused ones (same values)
-static bool step_fused() {
-  static const bool on = !(getenv("PGF_STEP_FUSED") && atoi(getenv("PGF_STEP_FUSED")) == 0);
-  return on;
-}
-
-extern "C" {
+static bool step_fused() { static const bool on = env_on("PGF_STEP_FUSED"); return on; }
 
 int pgf_version(void) { return 1; }
 
@@ -305,7 +292,7 @@ int pgf_set_derivs_csr(pgf_handle h, const int *Hptr, const int *Hidx, const dou
   return PGF_OK;
 }
 
-static void tau_factors(pgf_handle h, double tau, int *use_tau, double *f_x, double *f_x0,
+void tau_factors(pgf_handle h, double tau, int *use_tau, double *f_x, double *f_x0,
                         double *f_d) {
   // implicit_func.py:237-244
   *use_tau = std::isnan(tau) ? 0 : 1;
@@ -341,10 +328,7 @@ int pgf_active_set(pgf_handle h, const double *x, const double *g, double tau, u
 
 // PGF_STEP_SPEC=0: a step waits for the sizes of its index sets (one more host synchronisation
 // per step) instead of running with the last known ones
-static bool step_spec() {
-  static const bool on = !(getenv("PGF_STEP_SPEC") && atoi(getenv("PGF_STEP_SPEC")) == 0);
-  return on;
-}
+static bool step_spec() { static const bool on = env_on("PGF_STEP_SPEC"); return on; }
 
 // After the compaction of h->mask into index lists + counts (enqueued by the caller with
 // expect = h->nI when `spec', else -1).  spec: a step is being enqueued and will run with the last
@@ -362,10 +346,7 @@ static int adopt_index_sets(pgf_handle h, bool spec) {
   if ((rc = down(h, h->h_counts, h->counts, 2 * sizeof(int)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   ++h->stat_host_syncs;
-  h->nI = h->h_counts[0];
-  h->nA = h->h_counts[1];
-  h->N = h->nI + h->m;
-  h->counts_known = true;
+  adopt_counts(h);
   return PGF_OK;
 }
 static int refresh_index_sets(pgf_handle h, bool in_step) {
@@ -417,7 +398,7 @@ int pgf_reduced_dims(pgf_handle h, int *n_inactive, int *n_reduced) {
   return PGF_OK;
 }
 
-static int check_ready(pgf_handle h) {
+int check_ready(pgf_handle h) {
   if (!h->outer_set) return fail(h, PGF_NOT_READY, "pgf_set_outer first");
   if (h->sparse ? !h->sp.values_set : !h->derivs_set)
     return fail(h, PGF_NOT_READY, "pgf_set_derivs_* / pgf_sparse_set_values first");
@@ -444,14 +425,7 @@ static void assemble(pgf_handle h, double *K, int64_t ldk) {
 // (refine_if_needed) sees the full K either way.
 // PGF_CONDENSED: 0 never, 1 (default) when it saves a column block, 2 whenever the growth allows
 // (tests: the small golden cases).
-static int residual_norms(pgf_handle h);
-static int condensed_mode() {
-  static const int v = []() {
-    const char *e = getenv("PGF_CONDENSED");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+int condensed_mode() { static const int v = env_int("PGF_CONDENSED", 1); return v; }
 // The two a-priori bounds of the condensed order, from the norms of H and J in HBM (h_rs[4..6],
 // residual_norms): (i) growth g = ||J||_1 ||J||_inf / (delta (||H||_inf + lamb)) <= 1e3
 // (PGF_CONDENSED_GROWTH): the backward error of the block elimination is ~ eps g ||K||; (ii) the
@@ -459,15 +433,9 @@ static int condensed_mode() {
 // delta) (K quasi-definite, H positive semi-definite), must stay below 1e-11 (PGF_CONDENSED_ERR):
 // measured on the cond = 1.9e7 fixture (dt = 1e6, g = 100) the condensed order was 20 x less
 // accurate than the natural one, 1e-8 against the reference's 6e-11.
-static bool condensed_growth_ok(pgf_handle h) {
-  static const double gmax = []() {
-    const char *e = getenv("PGF_CONDENSED_GROWTH");
-    return e ? atof(e) : 1e3;
-  }();
-  static const double emax = []() {
-    const char *e = getenv("PGF_CONDENSED_ERR");
-    return e ? atof(e) : 1e-11;
-  }();
+bool condensed_growth_ok(pgf_handle h) {
+  static const double gmax = env_double("PGF_CONDENSED_GROWTH", 1e3);
+  static const double emax = env_double("PGF_CONDENSED_ERR", 1e-11);
   const double nH = h->h_rs[4] + h->lamb;
   const double g = h->h_rs[6] * h->h_rs[5] / (h->delta * nH);
   const double nK = std::max(nH + h->h_rs[6], h->h_rs[5] + h->delta);
@@ -482,14 +450,14 @@ static bool condensed_wanted(pgf_handle h) {
 }
 // row stride of the panel V: its depth rounded up to 32, plus 16 doubles -- at m = 1024 an 8 KB
 // stride would put the 64 / 128 rows a tile stages on the same HBM channels (as pick_ldk for K)
-static int64_t condensed_ldv(int m) {
-  const int mp = (m + 31) / 32 * 32;
-  static const bool pad = !(getenv("PGF_VPAD") && atoi(getenv("PGF_VPAD")) == 0);
+int64_t condensed_ldv(int m) {
+  const int mp = round_up32(m);
+  static const bool pad = env_on("PGF_VPAD");
   return pad ? mp + 16 : mp;
 }
-static hipError_t condensed_reserve(pgf_handle h) {
+hipError_t condensed_reserve(pgf_handle h) {
   DenseLdlt &f = h->fac;
-  const int mp = (h->m + 31) / 32 * 32;
+  const int mp = round_up32(h->m);
   const size_t need = (size_t)(h->n + 1) * condensed_ldv(h->m);
   hipError_t e = hipSuccess;
   if (f.vcap < need) {
@@ -519,17 +487,10 @@ static hipError_t condensed_reserve(pgf_handle h) {
 // PGF_CONDENSED_GRAM: 0 never (the virtual blocks, as before), 1 (default) G is built at the SECOND
 // condensed factorisation since the last upload -- a caller with fresh derivatives every step
 // never pays for it --, 2 at the first (tests).
-static int gram_mode() {
-  static const int v = []() {
-    const char *e = getenv("PGF_CONDENSED_GRAM");
-    return e ? atoi(e) : 1;
-  }();
-  return v;
-}
+static int gram_mode() { static const int v = env_int("PGF_CONDENSED_GRAM", 1); return v; }
 // true: h->G holds J^T J for the matrices in HBM (built now if the rule says so); false: this
 // factorisation takes the virtual-block path.  Never an error: a failed allocation switches the
 // Gram path off for the handle.  (condensed_reserve has been called: f.V, f.vd hold n + 1 rows.)
-static bool gram_build(pgf_handle h);
 static bool gram_prepare(pgf_handle h) {
   const int mode = gram_mode();
   if (!mode || h->gram_off) return false;
@@ -538,9 +499,9 @@ static bool gram_prepare(pgf_handle h) {
   return gram_build(h);
 }
 // the build itself (also asked for by the device-resident Standard formulation, unsym_gram)
-static bool gram_build(pgf_handle h) {
+bool gram_build(pgf_handle h) {
   DenseLdlt &f = h->fac;
-  const int n = h->n, mp = (h->m + 31) / 32 * 32;
+  const int n = h->n, mp = round_up32(h->m);
   if (!h->G) {
     int64_t ld = ((int64_t)n + 15) / 16 * 16;  // (as pick_ldk: row starts off one HBM channel)
     if (ld % 512 == 0) ld += 16;
@@ -636,93 +597,82 @@ static void count_head(pgf_handle h, bool fused) {
   h->fac_head = fused ? 1 : 2;
 }
 
-// enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in row N
+// enqueue assemble + factor; with_rhs: carry h->rhs through the elimination in the row behind the
+// matrix.  Where ldlt_head_wanted, the assembly is not launched here but described in hw.
 static int factor_async(pgf_handle h, bool with_rhs) {
   if (h->sparse) return band_factor_async(h);
+  DenseLdlt &f = h->fac;
   h->lu_active = false;
   h->condensed = condensed_wanted(h);
-  h->fac.vdepth = 0;
-  h->fac.vneg = 0;
+  f.vdepth = 0;
+  f.vneg = 0;
   h->fac_counted = h->fac_used_gram = false;
   h->fac_head = 0;
+  const int nI = h->nI, Nf = h->condensed ? nI : h->N;  // pivots of this factorisation
+  double *row = f.K + (int64_t)Nf * f.ldk;               // the row behind them: the right-hand side's
+  const double *row_src = with_rhs ? h->rhs : nullptr;
+  LdltHead hw;
+  bool head;
   if (h->condensed) {
-    DenseLdlt &f = h->fac;
     HIPCHK(h, condensed_reserve(h));
-    const int nI = h->nI, mp = (h->m + 31) / 32 * 32;
+    const int mp = round_up32(h->m);
     f.ldv = condensed_ldv(h->m);
     f.vneg = h->m;  // the eliminated block is -delta I
     const bool gram = gram_prepare(h);
     ++h->cond_since_upload;
     h->fac_counted = true;
-    f.flags_zeroed = nI > 0;
-    if (gram) {
-      // S = H[I,I] + lamb I + G[I,I] / delta in the assembly's one pass; V = J_I^T still serves the
-      // solves (launch_cond_rhs, launch_cond_y); row nI of K <- b_x + J_I^T b_y / delta, which the
-      // virtual blocks would have produced on the way (in place of k_virtual_diag: as many launches)
+    h->fac_used_gram = gram;
+    if (gram)
       ++h->stat_gram_factors;
-      h->fac_used_gram = true;
-      if (ldlt_head_wanted(f, nI)) {
-        // all of it beside the first diagonal chain, which reads the first 256 rows only
-        LdltHead hw = head_assembly(h, nI, 0);
-        hw.G = h->G;
-        hw.ldg = h->ldg;
-        hw.V = f.V;
-        hw.ldv = f.ldv;
-        hw.mp = mp;
-        hw.pm = h->m;
-        hw.vd = f.vd;
-        hw.rhs_y = with_rhs ? h->rhs + nI : nullptr;
-        if (with_rhs) {
-          hw.crhs = h->rhs;
-          hw.crhs_out = f.K + (int64_t)nI * f.ldk;
-        }
-        count_head(h, true);
-        HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0), &hw));
-        f.N = nI;
-        return PGF_OK;
+    else
+      f.vdepth = mp;  // the rank-m term as virtual blocks
+    const double *rhs_y = with_rhs ? h->rhs + nI : nullptr;
+    head = gram && ldlt_head_wanted(f, nI);
+    if (head) {
+      // Gram, all of it beside the first diagonal chain, which reads the first 256 rows only
+      hw = head_assembly(h, nI, 0);
+      hw.G = h->G;
+      hw.ldg = h->ldg;
+      hw.V = f.V;
+      hw.ldv = f.ldv;
+      hw.mp = mp;
+      hw.pm = h->m;
+      hw.vd = f.vd;
+      hw.rhs_y = rhs_y;
+      if (with_rhs) {
+        hw.crhs = h->rhs;
+        hw.crhs_out = row;
       }
-      count_head(h, false);
-      launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
-                          f.flags, 4 + LDLT_UPD_COUNTERS, nullptr, nullptr, 0, h->G, h->ldg);
-      launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta,
-                        with_rhs ? h->rhs + nI : nullptr);
-      if (with_rhs)
-        launch_cond_rhs(h->stream, nI, h->m, f.V, f.ldv, h->rhs, h->delta, f.K + (int64_t)nI * f.ldk);
-      HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0)));
-      f.N = nI;
-      return PGF_OK;
+    } else {
+      if (gram)  // S = H[I,I] + lamb I + G[I,I] / delta in the assembly's one pass
+        launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
+                            f.flags, 4 + LDLT_UPD_COUNTERS, nullptr, nullptr, 0, h->G, h->ldg);
+      else  // virtual blocks: A = H[I,I] + lamb I (no constraint rows), b_x into row nI
+        launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
+                            f.flags, 4 + LDLT_UPD_COUNTERS, row_src, row, nI);
+      // V = J_I^T (it also serves the solves: launch_cond_rhs, launch_cond_y), b_y in its row nI
+      launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta, rhs_y);
+      // Gram: row nI of K <- b_x + J_I^T b_y / delta, which the virtual blocks produce on the way (in
+      // place of k_virtual_diag: as many launches)
+      if (gram && with_rhs) launch_cond_rhs(h->stream, nI, h->m, f.V, f.ldv, h->rhs, h->delta, row);
     }
-    f.vdepth = mp;
-    count_head(h, false);
-    // A = H[I,I] + lamb I (the assembly kernel with no constraint rows), V = J_I^T, b_y in row nI
-    // (the assembly launch also clears the factorisation's flags and copies b_x into row nI)
-    launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, 0, h->lamb, h->delta,
-                        f.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
-                        f.K + (int64_t)nI * f.ldk, nI);
-    launch_cond_panel(h->stream, f.V, f.ldv, mp, f.vd, h->J, h->ldj, h->idxI, nI, h->m, h->delta,
-                      with_rhs ? h->rhs + nI : nullptr);
-    HIPCHK(h, ldlt_factor_async(f, nI, nI + (with_rhs ? 1 : 0)));
-    f.N = nI;
-    return PGF_OK;
-  }
-  // (the assembly launch also clears the factorisation's flags and copies the rhs into row N)
-  h->fac.flags_zeroed = h->N > 0;
-  if (ldlt_head_wanted(h->fac, h->N)) {
-    LdltHead hw = head_assembly(h, h->nI, h->m);
-    if (with_rhs) {
-      hw.row_src = h->rhs;
-      hw.row_dst = h->fac.K + (int64_t)h->N * h->fac.ldk;
-      hw.row_n = h->N;
+  } else {
+    head = ldlt_head_wanted(f, Nf);
+    if (head) {
+      hw = head_assembly(h, nI, h->m);
+      if (with_rhs) {
+        hw.row_src = h->rhs;
+        hw.row_dst = row;
+        hw.row_n = Nf;
+      }
+    } else {  // (the assembly launch also copies the rhs into row N)
+      launch_assemble_kkt(h->stream, f.K, f.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, nI, h->m, h->lamb, h->delta,
+                          f.flags, 4 + LDLT_UPD_COUNTERS, row_src, row, Nf);
     }
-    count_head(h, true);
-    HIPCHK(h, ldlt_factor_async(h->fac, h->N, h->N + (with_rhs ? 1 : 0), &hw));
-    return PGF_OK;
   }
-  count_head(h, false);
-  launch_assemble_kkt(h->stream, h->fac.K, h->fac.ldk, h->H, h->ldh, h->J, h->ldj, h->idxI, h->nI, h->m,
-                      h->lamb, h->delta, h->fac.flags, 4 + LDLT_UPD_COUNTERS, with_rhs ? h->rhs : nullptr,
-                      h->fac.K + (int64_t)h->N * h->fac.ldk, h->N);
-  HIPCHK(h, ldlt_factor_async(h->fac, h->N, h->N + (with_rhs ? 1 : 0)));
+  f.flags_zeroed = Nf > 0;  // (every assembly, launched or in hw, also clears the factorisation's flags)
+  count_head(h, head);
+  HIPCHK(h, ldlt_factor_async(f, Nf, Nf + (with_rhs ? 1 : 0), head ? &hw : nullptr));  // (sets f.N = Nf)
   return PGF_OK;
 }
 
@@ -769,7 +719,7 @@ static int factor_sync(pgf_handle h) {
 
 // (expand: also the residual check's expansion of the solution into rs_v, rs_lv and the zeroing of
 // its maxima, launch_residual_and_eval(..., prepared = true))
-static void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr) {
+void enqueue_step_update(pgf_handle h, bool expand, const StepCondY *cy) {
   DenseLdlt &f = h->fac;
   const int bits = f.status_words;  // deferred status words go to the status block
   f.status_words = 0;
@@ -794,7 +744,7 @@ static void absorb_status(pgf_handle h) {
 
 // r = rhs - K s of the solve just enqueued, with K applied from H, J and the mask (the factor
 // overwrote the assembled matrix); the three maxima reach the host with the next sync
-static void enqueue_residual(pgf_handle h, bool may_skip = false) {
+void enqueue_residual(pgf_handle h, bool may_skip) {
   if (!h->refine_mode) return;
   h->rs_skipped = may_skip && h->factor_clean;
   if (h->rs_skipped) return;
@@ -823,7 +773,7 @@ static double residual_rel(pgf_handle h) {
 }
 // the norms of H and J in HBM (one pass over both, one synchronisation; cached until the next
 // pgf_set_derivs_*)
-static int residual_norms(pgf_handle h) {
+int residual_norms(pgf_handle h) {
   if (h->norms_valid) return PGF_OK;
   launch_matrix_norms(h->stream, h->n, h->m, h->H, h->ldh, h->J, h->ldj, h->rs_red + 4);
   HIPCHK(h, hipMemcpyAsync(h->h_rs + 4, h->rs_red + 4, 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -842,7 +792,7 @@ static int residual_norms(pgf_handle h) {
 // partial pivoting of pgf_lu.hip (kept for the back-solve steps that follow).  Only when that
 // fails too does the call report PGF_SINGULAR -> LinearSolverError -> the step controller's
 // reject-and-halve path.
-static int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true) {
+int refine_if_needed(pgf_handle h, bool swapped, bool with_step) {
   if (h->sparse) return band_refine(h, swapped, with_step);
   if (!h->refine_mode || h->N == 0 || h->rs_skipped) return PGF_OK;
   double rel = residual_rel(h);
@@ -856,12 +806,7 @@ static int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true) {
   if (h->last_solve == 1) h->factor_clean = rel <= 1e-3 * h->refine_tol;
   if (rel <= h->refine_tol) return PGF_OK;
   hipStream_t s = h->stream;
-  auto unswap = [&]() {
-    if (swapped) {
-      std::swap(h->x, h->xn);
-      std::swap(h->y, h->yn);
-    }
-  };
+  auto unswap = [&]() { if (swapped) swap_point(h); };
   auto finish_round = [&]() -> int {
     enqueue_residual(h);
     h->eval_fresh = false;  // the point moves: what pgf_qp_step_async evaluated ahead is stale
@@ -922,250 +867,17 @@ static int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true) {
 static int chain_recover(pgf_handle h, bool swapped) {
   if (!ldlt_chain_check(h->fac)) return PGF_OK;  // (0 on a banded handle: it has no chain)
   h->eval_fresh = false;  // the point is computed again
-  if (swapped) {
-    std::swap(h->x, h->xn);
-    std::swap(h->y, h->yn);
-  }
+  if (swapped) swap_point(h);
   if (h->last_solve == 1)
     HIPCHK(h, kkt_backsolve_async(h, h->sol));
   else
     HIPCHK(h, kkt_solve_async(h, h->rhs, h->sol));
   enqueue_residual(h);
   enqueue_step_update(h);
-  if (swapped) {
-    std::swap(h->x, h->xn);
-    std::swap(h->y, h->yn);
-  }
+  if (swapped) swap_point(h);
   HIPCHK(h, hipMemcpyAsync(h->h_scal, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (ldlt_chain_check(h->fac)) return fail(h, PGF_HIP_ERROR, k_chain_msg);
-  return PGF_OK;
-}
-
-static void qp_eval(pgf_handle h);
-// ---------------------------------------------------------------- unsymmetric formulations
-// Standard / Extended / Asymmetric (pgf_set_formulation): the same Newton step through the
-// (n + m) x (n + m) matrix of the reference's alternative step solvers, assembled in HBM from the
-// resident H, J, mask and index lists (pgf_unsym.hip) straight into the array the pivoted LU
-// factorises in place.  The system always has n + m rows: no size depends on |I|, the kernels read
-// |A| on the device, so a step needs no host synchronisation for the index sets -- the one wait
-// inside a factorising step is lu_factor's own (it reads its pivots).  No LDL^T, no inertia
-// (n_neg = -1, LUSolver.num_neg_eigvals() is None), no accuracy guard: the LU pivots.
-static const double *unsym_lo(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->lb : h->slb; }
-static const double *unsym_hi(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->ub : h->sub; }
-
-// Device-resident Standard linearises with aug_lag_deriv_xx(rho) = H + rho J^T J: the Gram matrix
-// the condensed LDL^T keeps per derivative upload (gram_build) -- never rebuilt per step.
-static int unsym_gram(pgf_handle h, const double **G) {
-  *G = nullptr;
-  if (h->form != PGF_FORM_STANDARD || !h->h_has_lag_only || h->m == 0 || h->n == 0) return PGF_OK;
-  if (!h->gram_valid) {
-    HIPCHK(h, condensed_reserve(h));
-    if (h->gram_off || !gram_build(h))
-      return fail(h, PGF_HIP_ERROR, "Standard formulation: the Gram matrix J^T J could not be built");
-  }
-  *G = h->G;
-  return PGF_OK;
-}
-
-static int unsym_assemble(pgf_handle h, double *M, int64_t ld) {
-  const double *G;
-  int rc;
-  if ((rc = unsym_gram(h, &G))) return rc;
-  launch_assemble_unsym(h->stream, h->form, M, ld, h->n, h->m, h->H, h->ldh, h->J, h->ldj, G, h->ldg,
-                        h->rho, h->mask, h->idxI, h->idxA, h->counts, h->dt, h->lamb, h->delta);
-  return PGF_OK;
-}
-
-// assemble + factorise (waits: lu_factor reads its pivots)
-static int unsym_factor(pgf_handle h) {
-  const int Nf = h->n + h->m;
-  if (!h->ulu.A) {
-    const hipError_t ea = lu_alloc(h->ulu, Nf, h->stream);
-    if (ea != hipSuccess) {
-      lu_free(h->ulu);  // (nothing half allocated stays behind)
-      return hip_fail(h, ea, "lu_alloc");
-    }
-  }
-  h->ulu_ok = false;
-  int rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->prof.enabled) {
-    e0 = prof_event(&h->prof);
-    e1 = prof_event(&h->prof);
-    (void)hipEventRecord(e0, h->stream);
-  }
-  rc = unsym_assemble(h, h->ulu.A, h->ulu.ld);
-  if (e0) (void)hipEventRecord(e1, h->stream);
-  hipError_t e = hipSuccess;
-  const int st = rc ? 0 : lu_factor(h->ulu, &e);  // (waits for the stream)
-  if (e0) {
-    float ms = 0.f;
-    if (!rc && st >= 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) {
-      h->acc_unsym_asm_ms += ms;
-      ++h->acc_unsym_asm_launches;
-    }
-    h->prof.pool.push_back(e0);
-    h->prof.pool.push_back(e1);
-  }
-  if (rc) return rc;
-  ++h->stat_unsym_asm;
-  if (st < 0) return hip_fail(h, e, "LU of the Newton matrix");
-  ++h->stat_unsym_lu;
-  if (st == 1) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the LU of the Newton matrix");
-  h->ulu_ok = true;
-  return PGF_OK;
-}
-
-// the mask at (x, g) into `out' (Standard: unscaled)
-static void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint8_t *out) {
-  int use_tau;
-  double f_x, f_x0, f_d;
-  tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
-  if (h->form == PGF_FORM_STANDARD)
-    launch_unscaled_active_set(h->stream, h->n, use_tau, h->dt, use_tau ? 1.0 - tau * h->lamb : 0.0,
-                               use_tau ? tau * h->lamb : 0.0, use_tau ? tau : 0.0, h->xhat, x, g, h->lb,
-                               h->ub, out);
-  else
-    launch_active_set(h->stream, h->n, use_tau, h->lamb, f_x, f_x0, f_d, h->xhat, x, g, h->slb, h->sub, out);
-}
-
-// residual, right-hand side, (factorisation,) solve and step update for the point in
-// (h->x, h->y, h->g, h->c); scal[0] <- the step length.  Enqueued, except for lu_factor's wait.
-static int unsym_step_core(pgf_handle h) {
-  hipStream_t s = h->stream;
-  h->fused_eval_done = false;
-  launch_unsym_residual_rhs(s, h->form, h->n, h->m, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y,
-                            h->g, h->c, unsym_lo(h), unsym_hi(h), h->mask, h->pos, h->counts, h->F, h->rhs);
-  int rc;
-  if (!h->ulu_ok && (rc = unsym_factor(h))) return rc;
-  HIPCHK(h, lu_solve_async(h->ulu, h->rhs, h->sol, 0));
-  launch_unsym_step_update(s, h->form, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F, h->sol,
-                           h->dx, h->dy, h->xn, h->yn, h->red);
-  launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
-  return PGF_OK;
-}
-
-// mask at the device point; adopted (index lists rebuilt, factor dropped) when forced, when there
-// is none yet, or when it differs.  The sizes of the index sets are not awaited (wait_counts: they
-// are, outside a step).
-static int unsym_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, bool wait_counts) {
-  hipStream_t s = h->stream;
-  unsym_mask(h, tau, h->x, h->g, h->mask_new);
-  int changed = 1;
-  int rc;
-  if (h->mask_set && !force) {
-    HIPCHK(h, hipMemsetAsync(h->counts + 2, 0, sizeof(int), s));
-    launch_mask_diff(s, h->n, h->mask, h->mask_new, h->counts + 2);
-    if ((rc = down(h, h->h_counts + 2, h->counts + 2, sizeof(int)))) return rc;
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (!wait_counts) ++h->stat_host_syncs;
-    changed = h->h_counts[2] != 0;
-  }
-  if (changed_out) *changed_out = changed;
-  if (!changed) return PGF_OK;
-  launch_copy_u8(s, h->mask, h->mask_new, h->n);
-  launch_compact(s, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, -1);
-  h->mask_set = true;
-  invalidate_factor(h);
-  if (wait_counts) {
-    if ((rc = down(h, h->h_counts, h->counts, 2 * sizeof(int)))) return rc;
-    HIPCHK(h, hipStreamSynchronize(s));
-    h->nI = h->h_counts[0];
-    h->nA = h->h_counts[1];
-    h->N = h->nI + h->m;
-    h->counts_known = true;
-  } else {
-    h->counts_known = false;  // (they arrive with the step's status block, pgf_qp_sync)
-  }
-  return PGF_OK;
-}
-
-static int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau) {
-  int rc;
-  qp_eval(h);
-  if (policy & PGF_STEP_RECOMPUTE_MASK) {
-    const bool force = (policy & PGF_STEP_REFACTOR) != 0;
-    if ((rc = unsym_refresh_mask(h, tau, force, nullptr, false))) return rc;
-  }
-  if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first");
-  if (policy & PGF_STEP_REFACTOR) invalidate_factor(h);
-  if ((rc = unsym_step_core(h))) return rc;
-  std::swap(h->x, h->xn);
-  std::swap(h->y, h->yn);
-  h->eval_fresh = false;
-  if ((rc = down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double)))) return rc;
-  h->step_pending = true;
-  return PGF_OK;
-}
-
-static int unsym_qp_sync(pgf_handle h, int *n_neg, double *diff) {
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  ++h->stat_host_syncs;
-  h->nI = h->h_counts[0];
-  h->nA = h->h_counts[1];
-  h->N = h->nI + h->m;
-  h->counts_known = true;
-  if (n_neg) *n_neg = -1;
-  if (diff) *diff = h->h_scal[0];
-  return PGF_OK;
-}
-
-int pgf_set_formulation(pgf_handle h, int form) {
-  if (!h) return PGF_INVALID;
-  if (h->sparse) return fail(h, PGF_INVALID, "pgf_set_formulation: dense handles only");
-  if (form < PGF_FORM_SYMMETRIC || form > PGF_FORM_ASYMMETRIC)
-    return fail(h, PGF_INVALID, "pgf_set_formulation: unknown formulation");
-  if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the step in flight first");
-  h->form = form;
-  invalidate_factor(h);
-  // a handle that goes back to Symmetric gives the (n + m) x ld array of its LU back
-  if (form == PGF_FORM_SYMMETRIC && h->ulu.A) {
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    lu_free(h->ulu);
-  }
-  return PGF_OK;
-}
-
-int pgf_get_newton_matrix(pgf_handle h, double *M_out, int64_t ld) {
-  if (!h) return PGF_INVALID;
-  if (!h->form) return fail(h, PGF_INVALID, "pgf_get_newton_matrix: pgf_set_formulation first");
-  int rc;
-  if ((rc = check_ready(h))) return rc;
-  const int Nf = h->n + h->m;
-  if (Nf == 0) return PGF_OK;
-  if (!M_out || ld < Nf) return fail(h, PGF_INVALID, "bad output matrix");
-  (void)hipSetDevice(h->device);
-  double *tmp = nullptr;
-  HIPCHK(h, dalloc(&tmp, (size_t)Nf * Nf));
-  rc = unsym_assemble(h, tmp, Nf);
-  hipError_t e = hipSuccess;
-  if (!rc) {
-    e = hipMemcpy2DAsync(M_out, (size_t)ld * sizeof(double), tmp, (size_t)Nf * sizeof(double),
-                         (size_t)Nf * sizeof(double), Nf, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  } else {
-    (void)hipStreamSynchronize(h->stream);
-  }
-  (void)hipFree(tmp);
-  if (rc) return rc;
-  if (e != hipSuccess) return hip_fail(h, e, "pgf_get_newton_matrix");
-  return PGF_OK;
-}
-
-int pgf_debug_unsym_stats(pgf_handle h, int *assemblies, int *lu_factorisations,
-                          int64_t *matrix_bytes_from_host) {
-  if (!h) return PGF_INVALID;
-  if (assemblies) *assemblies = h->stat_unsym_asm;
-  if (lu_factorisations) *lu_factorisations = h->stat_unsym_lu;
-  if (matrix_bytes_from_host) *matrix_bytes_from_host = h->stat_unsym_bytes;
-  return PGF_OK;
-}
-
-int pgf_debug_unsym_note_upload(pgf_handle h, int64_t bytes) {
-  if (!h || bytes < 0) return PGF_INVALID;
-  h->stat_unsym_bytes += bytes;
   return PGF_OK;
 }
 
@@ -1529,7 +1241,7 @@ int pgf_qp_get_mask(pgf_handle h, uint8_t *mask) {
 }
 
 // c = A x - b ; w = rho c + y ; g = Q x + (q + A' w)   at the device point
-static void qp_eval(pgf_handle h) {
+void qp_eval(pgf_handle h) {
   if (h->eval_fresh) return;
   h->eval_fresh = true;
   if (h->sparse) return band_eval(h);
@@ -1644,9 +1356,7 @@ static int enqueue_qp_step(pgf_handle h) {
   h->fac.defer_status = false;
   h->step_took_inject = armed && !h->fac.inject_helper_failure;
   if (rc) return rc;
-  // (x, y) <- (xn, yn)
-  std::swap(h->x, h->xn);
-  std::swap(h->y, h->yn);
+  swap_point(h);  // (x, y) <- (xn, yn)
   h->eval_fresh = false;
   // g and c at the new point, enqueued NOW: the next step needs them first thing, and behind the
   // step's host synchronisation the four small launches would wait for the host one by one
@@ -1683,12 +1393,9 @@ static int settle_spec(pgf_handle h, bool *redone) {
   gram_uncount(h);
   h->fac.factored = false;
   h->lu_active = false;
-  std::swap(h->x, h->xn);
-  std::swap(h->y, h->yn);
+  swap_point(h);
   h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
-  h->nI = h->h_counts[0];
-  h->nA = h->h_counts[1];
-  h->N = h->nI + h->m;
+  adopt_counts(h);
   int rc;
   if ((rc = enqueue_qp_step(h))) return rc;
   *redone = true;
@@ -1745,8 +1452,7 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   if (st == 2) {
     // the chain's helper workgroups failed their checks (off now): the step is computed again
     // from the point it started at
-    std::swap(h->x, h->xn);
-    std::swap(h->y, h->yn);
+    swap_point(h);
     h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
     if ((rc = enqueue_qp_step(h))) return rc;
     if (!h->sparse) {
@@ -1834,7 +1540,7 @@ int pgf_debug_head_stats(pgf_handle h, int *fused, int *plain) {
 // tests are those of b_assemble_kkt and the panel's tile body.
 int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head, int *v_units, int *n_units) {
   if (nI < 0 || m < 0) return PGF_INVALID;
-  const int N = condensed ? nI : nI + m, mp = condensed ? (m + 31) / 32 * 32 : 0;
+  const int N = condensed ? nI : nI + m, mp = condensed ? round_up32(m) : 0;
   // (the list as head_unit defines it; ldlt_head_wanted fuses nothing for N <= 256, whose list is
   // the panel's tiles alone)
   const int total = head_asm_units(N) + head_panel_units(nI, mp);
@@ -1911,835 +1617,6 @@ int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev) {
   return PGF_OK;
 }
 
-// ---------------------------------------------------------------- batched mode
-struct pgf_batch_s {
-  std::vector<pgf_handle> hs;
-  int B = 0, n = 0, m = 0, device = 0;
-  hipStream_t stream = nullptr;
-  BInst *tab = nullptr;
-  int *ctl = nullptr, *flags_out = nullptr, *h_flags = nullptr;
-  double *diff_out = nullptr, *norm_out = nullptr, *h_diff = nullptr, *h_norm = nullptr;
-  double *red4 = nullptr, *meas_out = nullptr, *h_meas = nullptr;
-  double *ps = nullptr, *h_ps = nullptr;      // per-instance [dt, lambda, rho, fact, delta, ...]
-  uint8_t *bytes = nullptr, *h_bytes = nullptr;  // accept / frozen flags on their way to the device
-  BatchScalars sc{};
-  bool outer_set = false, eval_fresh = false, step_pending = false, have_mask = false;
-  bool all_factored = false;
-  // condensed order (constraint block eliminated first, as condensed_wanted for one instance):
-  // cond_ok = the panels exist and the batch runs one of the chain schedules; cond_wanted = the
-  // growth bound holds for every instance's delta (decided per outer step on the host: the
-  // device-resident controller, which moves lambda on the device, keeps the natural order);
-  // cond_last = how the factors the instances hold were made; cond_free = the next step
-  // refactorises every instance anyway and may choose
-  bool cond_ok = false, cond_wanted = false, cond_last = false, cond_free = true;
-  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond_last
-  int cond_mp = 0;
-  int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
-  int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
-  // device-resident step controller (pgf_batch_ctl_*): per-instance state, constants, and a
-  // log of (lambda used, lambda next, accepted) per outer iteration and instance
-  double *dctl_cs = nullptr, *dctl_cp = nullptr, *dctl_log = nullptr;
-  int dctl_log_cap = 0, dctl_logged = 0;
-  PgfProfile prof;
-  std::string err = "";
-};
-
-static int bfail(pgf_batch b, int code, const char *msg) {
-  if (b) b->err = msg;
-  return code;
-}
-
-#define BHIPCHK(b, expr)                                                 \
-  do {                                                                   \
-    hipError_t e_ = (expr);                                              \
-    if (e_ != hipSuccess) {                                              \
-      (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);      \
-      return PGF_HIP_ERROR + (int)e_;                                    \
-    }                                                                    \
-  } while (0)
-
-const char *pgf_batch_last_error(pgf_batch b) { return b ? b->err.c_str() : k_no_handle; }
-
-// ||H||_inf, ||J||_1, ||J||_inf of every instance into the host copy of ps (residual_norms: one
-// pass over H and J per handle, cached until its derivatives change)
-static int batch_store_norms(pgf_batch b) {
-  for (int i = 0; i < b->B; ++i) {
-    pgf_handle h = b->hs[i];
-    int rc = residual_norms(h);
-    if (rc) return rc;
-    double *p = b->h_ps + (size_t)BPS_STRIDE * i;
-    p[BPS_NORM_H] = h->h_rs[4];
-    p[BPS_NORM_J1] = h->h_rs[6];
-    p[BPS_NORM_JINF] = h->h_rs[5];
-  }
-  return PGF_OK;
-}
-
-int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
-  if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
-  const pgf_handle h0 = handles[0];
-  if (!h0) return PGF_INVALID;
-  for (int i = 0; i < count; ++i) {
-    const pgf_handle h = handles[i];
-    if (!h) return PGF_INVALID;
-    if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
-      return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
-    if (h->sparse) return fail(h, PGF_INVALID, "batch: dense handles only");
-    if (h->form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
-    if (!h->qp_mode || !h->bounds_set || !h->point_set)
-      return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_problem, pgf_qp_set_point first");
-    if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
-  }
-  pgf_batch b = new (std::nothrow) pgf_batch_s();
-  if (!b) return PGF_INVALID;
-  b->hs.assign(handles, handles + count);
-  b->B = count;
-  b->n = h0->n;
-  b->m = h0->m;
-  b->device = h0->device;
-  b->sc.n = b->n;
-  b->sc.m = b->m;
-  (void)hipSetDevice(b->device);
-  hipError_t e;
-  std::vector<BInst> tab(count);
-  if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc((void **)&b->tab, count * sizeof(BInst))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->ctl, (size_t)count * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->flags_out, ((size_t)count * 3 + 1) * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->diff_out, count * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->norm_out, count * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->red4,
-                     (size_t)count * 4 * ((h0->n + h0->m + 255) / 256 + 1) * sizeof(double))) !=
-          hipSuccess ||
-      (e = hipMalloc((void **)&b->meas_out, (size_t)count * 4 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->ps, (size_t)count * BPS_STRIDE * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_ps, (size_t)count * BPS_STRIDE * sizeof(double))) !=
-          hipSuccess ||
-      (e = hipMalloc((void **)&b->bytes, (size_t)count)) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_bytes, (size_t)count)) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_meas, (size_t)count * 4 * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_flags, (size_t)count * 3 * sizeof(int))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_diff, count * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_norm, count * sizeof(double))) != hipSuccess) {
-    pgf_batch_destroy(b);
-    return PGF_HIP_ERROR + (int)e;
-  }
-  // the condensed order: dense handles, a constraint block worth a column block
-  const bool cond_possible = condensed_mode() != 0 && !h0->sparse && h0->m > 0 && h0->m <= h0->n &&
-                             (condensed_mode() == 2 ||
-                              (h0->m >= 64 && (h0->n + h0->m + 255) / 256 > (h0->n + 255) / 256));
-  b->cond_ok = cond_possible;
-  b->cond_mp = (h0->m + 31) / 32 * 32;
-  for (int i = 0; i < count; ++i) {
-    const pgf_handle h = handles[i];
-    (void)hipStreamSynchronize(h->stream);
-    BInst &t = tab[i];
-    t.H = h->H;
-    t.J = h->J;
-    t.ldh = h->ldh;
-    t.ldj = h->ldj;
-    t.lb = h->lb;
-    t.ub = h->ub;
-    t.q = h->q;
-    t.b = h->b;
-    t.slb = h->slb;
-    t.sub = h->sub;
-    t.xhat = h->xhat;
-    t.yhat = h->yhat;
-    t.x = h->x;
-    t.y = h->y;
-    t.xn = h->xn;
-    t.yn = h->yn;
-    t.g = h->g;
-    t.c = h->c;
-    t.F = h->F;
-    t.b0full = h->b0full;
-    t.rhs = h->rhs;
-    t.sol = h->sol;
-    t.dx = h->dx;
-    t.dy = h->dy;
-    t.w = h->w;
-    t.tmpn = h->tmpn;
-    t.partial = h->partial;
-    t.red = h->red;
-    t.mask = h->mask;
-    t.mask_new = h->mask_new;
-    t.idxI = h->idxI;
-    t.idxA = h->idxA;
-    t.pos = h->pos;
-    t.counts = h->counts;
-    t.ctl = b->ctl + 4 * i;
-    t.ps = b->ps + (size_t)BPS_STRIDE * i;
-    t.K = h->fac.K;
-    t.ldk = h->fac.ldk;
-    t.W = h->fac.W;
-    t.wstride = (int64_t)h->fac.wstride;
-    t.dvec = h->fac.dvec;
-    t.dinv = h->fac.dinv;
-    t.zwork = h->fac.zwork;
-    t.Linv = h->fac.Linv;
-    t.LinvT = h->fac.LinvT;
-    t.flags = h->fac.flags;
-    t.hctl = h->fac.hctl;
-    t.xpub = h->fac.xpub;
-    t.cctl = h->fac.chain + 2 * h->fac.chain_stride;
-    t.capblk = h->fac.chain_stride;
-    t.V = nullptr;
-    t.vd = nullptr;
-    t.ldv = 0;
-    if (cond_possible) {
-      if ((e = condensed_reserve(h)) != hipSuccess) {
-        pgf_batch_destroy(b);
-        return PGF_HIP_ERROR + (int)e;
-      }
-      t.V = h->fac.V;
-      t.vd = h->fac.vd;
-      t.ldv = condensed_ldv(h->m);
-    }
-    // the batch owns the device-side state of the handle from here on
-    h->mask_set = false;
-    h->eval_fresh = false;
-    invalidate_factor(h);
-  }
-  if ((e = hipMemcpy(b->tab, tab.data(), count * sizeof(BInst), hipMemcpyHostToDevice)) !=
-          hipSuccess ||
-      (e = hipMemset(b->ctl, 0, (size_t)count * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipMemset(b->flags_out, 0, ((size_t)count * 3 + 1) * sizeof(int))) != hipSuccess) {
-    pgf_batch_destroy(b);
-    return PGF_HIP_ERROR + (int)e;
-  }
-  // the matrix norms of every instance are on the device before any step (the device-resident
-  // controller writes only lambda and its kin into ps)
-  std::memset(b->h_ps, 0, (size_t)count * BPS_STRIDE * sizeof(double));
-  int rc = batch_store_norms(b);
-  if (rc == PGF_OK &&
-      (e = hipMemcpy(b->ps, b->h_ps, (size_t)count * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) !=
-          hipSuccess)
-    rc = PGF_HIP_ERROR + (int)e;
-  if (rc) {
-    pgf_batch_destroy(b);
-    return rc;
-  }
-  *out = b;
-  return PGF_OK;
-}
-
-int pgf_batch_destroy(pgf_batch b) {
-  if (!b) return PGF_OK;
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  for (void *p : {(void *)b->tab, (void *)b->ctl, (void *)b->flags_out, (void *)b->diff_out,
-                  (void *)b->norm_out, (void *)b->red4, (void *)b->meas_out, (void *)b->ps,
-                  (void *)b->bytes, (void *)b->dctl_cs, (void *)b->dctl_cp, (void *)b->dctl_log})
-    if (p) (void)hipFree(p);
-  for (void *p : {(void *)b->h_flags, (void *)b->h_diff, (void *)b->h_norm, (void *)b->h_meas,
-                  (void *)b->h_ps, (void *)b->h_bytes})
-    if (p) (void)hipHostFree(p);
-  for (hipEvent_t e : b->prof.pool) (void)hipEventDestroy(e);
-  for (auto &sp : b->prof.update_spans) {
-    (void)hipEventDestroy(sp.first);
-    (void)hipEventDestroy(sp.second);
-  }
-  if (b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
-  return PGF_OK;
-}
-
-int pgf_batch_stream(pgf_batch b, void **stream_out) {
-  if (!b || !stream_out) return PGF_INVALID;
-  *stream_out = (void *)b->stream;
-  return PGF_OK;
-}
-
-// Start a new outer step for every instance with ITS OWN dt_i, rho_i (every instance has its
-// own step-size controller).  accept[i] != 0 (or accept == NULL): (x^, y^) <- (x, y), the
-// last steps were accepted; accept[i] == 0: (x, y) <- (x^, y^), the instance goes back to its
-// outer point and retries with the new dt_i (StepController.compute_step: rejected steps keep
-// the iterate, step_control.py:80-107).
-int pgf_batch_advance_outer_each(pgf_batch b, const double *dt, const double *rho,
-                                 const uint8_t *accept) {
-  if (!b || !dt || !rho) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  for (int i = 0; i < b->B; ++i)
-    if (!(dt[i] > 0.0) || !(rho[i] > 0.0))
-      return bfail(b, PGF_INVALID, "dt and rho must be positive");
-  if (accept && !b->outer_set)
-    for (int i = 0; i < b->B; ++i)
-      if (!accept[i]) return bfail(b, PGF_NOT_READY, "nothing to go back to before the first outer step");
-  (void)hipSetDevice(b->device);
-  // the pinned staging buffers may still be in flight from the previous call
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  // g = Qx + q + A'(rho c + y) and c only change when a point moves (a rejected instance goes
-  // back to its outer point) or its rho does: otherwise what the last step evaluated ahead stays
-  bool eval_stays = b->eval_fresh;
-  for (int i = 0; i < b->B; ++i) {
-    if ((accept && !accept[i]) || rho[i] != b->hs[i]->rho) eval_stays = false;
-    double *p = b->h_ps + (size_t)BPS_STRIDE * i;
-    const double lamb = 1.0 / dt[i];
-    p[BPS_DT] = dt[i];
-    p[BPS_LAMB] = lamb;
-    p[BPS_RHO] = rho[i];
-    p[BPS_FACT] = 1.0 / (1.0 + lamb * rho[i]);
-    p[BPS_DELTA] = lamb / (1.0 + lamb * rho[i]);
-    b->h_bytes[i] = accept ? (accept[i] ? 1 : 0) : 1;
-    pgf_handle h = b->hs[i];  // keep the handles' host-side view consistent
-    h->dt = dt[i];
-    h->lamb = lamb;
-    h->rho = rho[i];
-    h->fact = p[BPS_FACT];
-    h->delta = p[BPS_DELTA];
-    h->outer_set = true;
-  }
-  // condensed order for this outer step: the growth bound of condensed_wanted, for EVERY instance
-  // (one launch sequence serves them all)
-  b->cond_wanted = false;
-  if (b->cond_ok) {
-    bool all = true;
-    for (int i = 0; i < b->B && all; ++i) {
-      pgf_handle h = b->hs[i];
-      if (residual_norms(h)) {
-        all = false;
-        break;
-      }
-      all = condensed_growth_ok(h);
-    }
-    b->cond_wanted = all;
-  }
-  b->cond_free = true;  // every instance refactorises in the next step (new lambda)
-  if (int rc = batch_store_norms(b)) return bfail(b, rc, "matrix norms of an instance");
-  BHIPCHK(b, hipMemcpyAsync(b->ps, b->h_ps, (size_t)b->B * BPS_STRIDE * sizeof(double),
-                            hipMemcpyHostToDevice, b->stream));
-  BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
-  batch_launch_advance(b->stream, b->tab, b->B, b->sc, b->bytes);
-  b->eval_fresh = eval_stays;  // g depends on rho, and rejected instances moved
-  b->outer_set = true;
-  b->have_mask = false;
-  b->all_factored = false;
-  BHIPCHK(b, hipGetLastError());
-  return PGF_OK;
-}
-
-int pgf_batch_advance_outer(pgf_batch b, double dt, double rho) {
-  if (!b) return PGF_INVALID;
-  std::vector<double> dts(b->B, dt), rhos(b->B, rho);
-  return pgf_batch_advance_outer_each(b, dts.data(), rhos.data(), nullptr);
-}
-
-// frozen[i] != 0: instance i sits out the following Newton steps (until the next
-// pgf_batch_advance_outer*): the controller's early exits (converged after the first step,
-// failed factorisation) must not move the instance any further.  NULL clears all.
-int pgf_batch_set_frozen(pgf_batch b, const uint8_t *frozen) {
-  if (!b) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  for (int i = 0; i < b->B; ++i) b->h_bytes[i] = (frozen && frozen[i]) ? 1 : 0;
-  BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
-  batch_launch_set_frozen(b->stream, b->tab, b->B, b->bytes);
-  BHIPCHK(b, hipGetLastError());
-  return PGF_OK;
-}
-
-static void batch_eval(pgf_batch b) {
-  if (b->eval_fresh) return;
-  batch_launch_eval(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS);
-  b->eval_fresh = true;
-}
-
-int pgf_batch_update_active_set(pgf_batch b, double tau) {
-  if (!b) return PGF_INVALID;
-  if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  batch_eval(b);
-  batch_launch_mask(b->stream, b->tab, b->B, b->sc, 1, tau);
-  b->have_mask = true;
-  b->all_factored = false;
-  BHIPCHK(b, hipGetLastError());
-  return PGF_OK;
-}
-
-// everything of one batched Newton step, enqueued; host_knows_factored: the host's view that
-// every instance holds a valid factor (lets a Simplified step skip the factor launches)
-static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool host_knows_factored) {
-  const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
-  const bool force = (policy & PGF_STEP_REFACTOR) != 0;
-  batch_eval(b);
-  batch_launch_mask(b->stream, b->tab, b->B, b->sc, recompute ? (force ? 2 : 1) : 0, tau);
-  b->have_mask = true;
-  // pivot order: free to choose when every instance refactorises (Full, or the first step of an
-  // outer step); otherwise the one the factors in place were made with
-  const bool cond = (force || b->cond_free) ? b->cond_wanted : b->cond_last;
-  b->cond_last = cond;
-  b->cond_free = false;
-  b->stepped = true;
-  batch_launch_rhs_assemble(b->stream, b->tab, b->B, b->sc, cond ? b->cond_mp : 0);
-  // (condensed: the factor and solve kernels see nI rows -- their `m' is 0)
-  const int Nmax = cond ? b->n : b->n + b->m, mf = cond ? 0 : b->m;
-  // kernels of instances whose factor is still valid return at once (ctl[0] == 0); when the
-  // host knows that every instance refactorises (Full) or none does, skip the other half
-  const bool none_factor = !recompute && host_knows_factored;
-  if (!none_factor) {
-    ldlt_batch_factor_async(b->stream, b->tab, b->B, Nmax, mf, b->prof.enabled ? &b->prof : nullptr,
-                            cond ? b->cond_mp : 0);
-    if (b->inject_helper_failure) {
-      b->inject_helper_failure = 0;
-      ldlt_inject_helper_failure(b->stream, b->hs[0]->fac.flags);
-    }
-  }
-  if (cond && !force) batch_launch_cond_prep_fwd(b->stream, b->tab, b->B, b->sc);
-  ldlt_batch_solve_async(b->stream, b->tab, b->B, Nmax, mf, !force, cond);
-  if (cond) batch_launch_cond_y(b->stream, b->tab, b->B, b->sc);
-  batch_launch_step_update(b->stream, b->tab, b->B, b->sc, b->diff_out, b->flags_out);
-  b->eval_fresh = false;
-}
-
-int pgf_batch_debug_fail_next_helper(pgf_batch b) {
-  if (!b) return PGF_INVALID;
-  b->inject_helper_failure = 1;
-  return PGF_OK;
-}
-
-int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
-  if (!b) return PGF_INVALID;
-  if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
-  const bool force = (policy & PGF_STEP_REFACTOR) != 0;
-  if (!recompute && !b->have_mask)
-    return bfail(b, PGF_NOT_READY, "no active set: pgf_batch_update_active_set first");
-  if (!recompute && force)
-    return bfail(b, PGF_INVALID, "batch: PGF_STEP_REFACTOR needs PGF_STEP_RECOMPUTE_MASK");
-  batch_enqueue_step(b, policy, tau, b->all_factored);
-  // g and c at the new points, enqueued ahead of the host synchronisation (as pgf_qp_step_async):
-  // behind it the five small launches would wait for the host one by one
-  if (eval_ahead()) batch_eval(b);
-  BHIPCHK(b, hipMemcpyAsync(b->h_diff, b->diff_out, b->B * sizeof(double), hipMemcpyDeviceToHost,
-                            b->stream));
-  BHIPCHK(b, hipMemcpyAsync(b->h_flags, b->flags_out, (size_t)b->B * 3 * sizeof(int),
-                            hipMemcpyDeviceToHost, b->stream));
-  b->step_pending = true;
-  return PGF_OK;
-}
-
-// ---- device-resident DistanceRatioController ------------------------------
-int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *params,
-                       int max_iterations) {
-  if (!b || !params || !(lamb_init > 0.0) || !(rho > 0.0) || max_iterations < 1) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  const size_t ncs = (size_t)b->B * DCS_STRIDE;
-  if (!b->dctl_cs) BHIPCHK(b, dalloc(&b->dctl_cs, ncs));
-  if (!b->dctl_cp) BHIPCHK(b, dalloc(&b->dctl_cp, (size_t)DCP_COUNT));
-  if (b->dctl_log_cap < max_iterations) {
-    if (b->dctl_log) (void)hipFree(b->dctl_log);
-    b->dctl_log = nullptr;
-    BHIPCHK(b, dalloc(&b->dctl_log, (size_t)max_iterations * b->B * 3));
-    b->dctl_log_cap = max_iterations;
-  }
-  std::vector<double> cs(ncs, 0.0), cp(DCP_COUNT, 0.0);
-  for (int i = 0; i < b->B; ++i) {
-    cs[(size_t)DCS_STRIDE * i + DCS_LAMB] = lamb_init;
-    cs[(size_t)DCS_STRIDE * i + DCS_ACCEPTED] = 1.0;
-  }
-  cp[DCP_RHO] = rho;
-  // params: newton_tol, lamb_red, lamb_min, lamb_inc, theta_max, K_P, K_I, theta_ref
-  cp[DCP_NEWTON_TOL] = params[0];
-  cp[DCP_LAMB_RED] = params[1];
-  cp[DCP_LAMB_MIN] = params[2];
-  cp[DCP_LAMB_INC] = params[3];
-  cp[DCP_THETA_MAX] = params[4];
-  cp[DCP_K_P] = params[5];
-  cp[DCP_K_I] = params[6];
-  if (!(params[7] > 0.0)) return bfail(b, PGF_INVALID, "theta_ref must be positive");
-  cp[DCP_LOG_THETA_REF] = std::log(params[7]);
-  BHIPCHK(b, hipMemcpyAsync(b->dctl_cs, cs.data(), ncs * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  BHIPCHK(b, hipMemcpyAsync(b->dctl_cp, cp.data(), DCP_COUNT * sizeof(double), hipMemcpyHostToDevice,
-                            b->stream));
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  b->dctl_logged = 0;
-  return PGF_OK;
-}
-
-int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iterations) {
-  if (!b || iterations < 0) return PGF_INVALID;
-  if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  if (b->dctl_logged + iterations > b->dctl_log_cap)
-    return bfail(b, PGF_INVALID, "more iterations than pgf_batch_ctl_init reserved a log for");
-  const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
-  if (!recompute && (policy & PGF_STEP_REFACTOR))
-    return bfail(b, PGF_INVALID, "batch: PGF_STEP_REFACTOR needs PGF_STEP_RECOMPUTE_MASK");
-  (void)hipSetDevice(b->device);
-  hipStream_t s = b->stream;
-  for (int it = 0; it < iterations; ++it) {
-    // outer step of every instance at its own lambda; rejected instances go back first
-    batch_launch_dctl_begin(s, b->B, b->dctl_cs, b->dctl_cp, b->ps, b->bytes);
-    batch_launch_advance(s, b->tab, b->B, b->sc, b->bytes);
-    // (lambda lives on the device here: the host cannot bound the growth of the condensed order)
-    b->cond_wanted = false;
-    b->cond_free = true;
-    b->eval_fresh = false;
-    b->outer_set = true;
-    if (!recompute) {  // Simplified: mask and derivatives frozen at the outer point
-      batch_eval(b);
-      batch_launch_mask(s, b->tab, b->B, b->sc, 2, tau);
-    }
-    batch_enqueue_step(b, policy, tau, false);
-    batch_eval(b);
-    batch_launch_res_norm(s, b->tab, b->B, b->sc, b->norm_out);
-    batch_launch_dctl_mid(s, b->tab, b->B, b->dctl_cs, b->dctl_cp, b->diff_out, b->flags_out,
-                          b->norm_out);
-    batch_enqueue_step(b, policy, tau, false);
-    batch_launch_dctl_end(s, b->B, b->dctl_cs, b->dctl_cp, b->diff_out, b->flags_out,
-                          b->dctl_log + (size_t)b->dctl_logged * b->B * 3);
-    ++b->dctl_logged;
-  }
-  b->all_factored = false;
-  BHIPCHK(b, hipGetLastError());
-  return PGF_OK;
-}
-
-int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log3, int log_rows) {
-  if (!b) return PGF_INVALID;
-  if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
-  (void)hipSetDevice(b->device);
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  // A failed hand-over of a chain helper or of a chained solve looked like a singular matrix to
-  // the device-resident controller (kb_dctl_mid / _end: reject, 2 lambda) -- correct for that
-  // iteration, but with the helpers still on it could repeat every iteration and lambda would
-  // grow without bound.  The sticky word behind the flag triples says whether any
-  // step of the loop saw one: helpers and chained solves go off, as pgf_batch_sync does.
-  {
-    int sticky = 0;
-    BHIPCHK(b, hipMemcpy(&sticky, b->flags_out + 3 * (size_t)b->B, sizeof(int), hipMemcpyDeviceToHost));
-    if (sticky) {
-      ldlt_chain_helpers_off();
-      ldlt_chain_set_enabled(false);
-      for (int i = 0; i < b->B; ++i) {
-        DenseLdlt &f = b->hs[i]->fac;
-        BHIPCHK(b, hipMemsetAsync(f.xpub, 0xff, 2 * (size_t)f.chain_stride * 64 * sizeof(double), b->stream));
-      }
-      BHIPCHK(b, hipMemsetAsync(b->flags_out + 3 * (size_t)b->B, 0, sizeof(int), b->stream));
-      BHIPCHK(b, hipStreamSynchronize(b->stream));
-    }
-  }
-  std::vector<double> cs((size_t)b->B * DCS_STRIDE);
-  BHIPCHK(b, hipMemcpy(cs.data(), b->dctl_cs, cs.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int i = 0; i < b->B; ++i) {
-    if (lamb) lamb[i] = cs[(size_t)DCS_STRIDE * i + DCS_LAMB];
-    if (accepted) accepted[i] = cs[(size_t)DCS_STRIDE * i + DCS_ACCEPTED] != 0.0;
-    // the handles' host-side scalars follow the device's (the next host-driven call may use them)
-    pgf_handle h = b->hs[i];
-    const double l = cs[(size_t)DCS_STRIDE * i + DCS_USED];
-    if (l > 0.0) {
-      h->dt = 1.0 / l;
-      h->lamb = 1.0 / h->dt;
-      h->fact = 1.0 / (1.0 + h->lamb * h->rho);
-      h->delta = h->lamb / (1.0 + h->lamb * h->rho);
-    }
-  }
-  if (log3 && log_rows > 0) {
-    const int rows = std::min(log_rows, b->dctl_logged);
-    BHIPCHK(b, hipMemcpy(log3, b->dctl_log, (size_t)rows * b->B * 3 * sizeof(double),
-                         hipMemcpyDeviceToHost));
-  }
-  return PGF_OK;
-}
-
-// An instance whose sampled residual failed (kb_sample_residual; kb_step_update then left its point
-// alone): the single-instance accuracy guard on its handle -- full residual with K applied from H,
-// J and the mask, iterative refinement with the factor the batch made, the pivoted LU if that does
-// not contract (refine_if_needed) -- then the step update from the repaired solution.  The batch's
-// stream is idle (pgf_batch_sync); the handle's buffers ARE the instance's.  Returns 0 when the
-// instance's step is good now (its point, step length and factor state are in place).
-static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
-  pgf_handle h = b->hs[i];
-  if (h->sparse || !h->refine_mode) return PGF_SINGULAR;
-  const int nI = b->h_flags[3 * i + 2];
-  h->nI = nI;
-  h->nA = h->n - nI;
-  h->N = nI + h->m;
-  h->mask_set = true;
-  h->condensed = b->cond_last;
-  h->lu_active = false;
-  h->last_solve = 2;
-  DenseLdlt &f = h->fac;
-  f.N = h->condensed ? nI : h->N;
-  f.vdepth = h->condensed ? b->cond_mp : 0;
-  f.ldv = condensed_ldv(h->m);
-  f.vneg = h->condensed ? h->m : 0;
-  f.factored = true;
-  f.n_neg = b->h_flags[3 * i + 1] + (h->condensed ? h->m : 0);
-  enqueue_residual(h);
-  hipError_t e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return hip_fail(h, e, "batched repair");
-  int rc = refine_if_needed(h, /*swapped=*/false, /*with_step=*/false);
-  if (rc) return rc;
-  enqueue_step_update(h);  // (x, y) -> (xn, yn), dx, dy, ||d||
-  launch_copy(h->stream, h->x, h->xn, h->n);
-  launch_copy(h->stream, h->y, h->yn, h->m);
-  if ((e = hipMemcpyAsync(h->h_scal, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
-      (e = hipStreamSynchronize(h->stream)) != hipSuccess)
-    return hip_fail(h, e, "batched repair");
-  if (ldlt_chain_check(f)) return fail(h, PGF_HIP_ERROR, k_chain_msg);
-  *diff_out = h->h_scal[0];
-  // (host-side view only.  In the batch, kb_step_final left ctl[1] = 0 and pgf_batch_sync keeps
-  // all_factored false: the instance's next step assembles K again and launches the factorisation,
-  // a Simplified step included)
-  invalidate_factor(h);
-  return PGF_OK;
-}
-
-int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
-  if (!b) return PGF_INVALID;
-  if (!b->step_pending) return bfail(b, PGF_NOT_READY, "no step pending");
-  b->step_pending = false;
-  (void)hipSetDevice(b->device);
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  bool all_ok = true, any_repaired = false;
-  for (int i = 0; i < b->B; ++i) {
-    // bit 2 alone: the factorisation went through but the sampled residual of the solve is too
-    // large (element growth): repaired on the instance's handle where the reference's pivoted LU
-    // would simply have solved -- only an instance that cannot be repaired
-    // reports a failed step
-    if (b->h_flags[3 * i] == 4) {
-      double d = 0.0;
-      if (batch_repair_instance(b, i, &d) == PGF_OK) {
-        b->h_flags[3 * i] = 0;
-        b->h_diff[i] = d;
-        b->eval_fresh = false;  // the instance moved after the evaluation made ahead
-        ++b->repaired;
-        any_repaired = true;
-      }
-    }
-    const bool bad = b->h_flags[3 * i] != 0;
-    // bit 1: the instance's chain helpers failed a hand-over check (kb_step_final): the step is
-    // reported like a failed factorisation -- the controllers reject and repeat it -- and the
-    // helpers are off from here on
-    if (b->h_flags[3 * i] & 2) {
-      // (or one of its chained solves: those go off too, and the publication halves of the
-      // instance's handle get their sentinels back)
-      (void)hipMemsetAsync(b->flags_out + 3 * (size_t)b->B, 0, sizeof(int), b->stream);
-      ldlt_chain_helpers_off();
-      ldlt_chain_set_enabled(false);
-      DenseLdlt &f = b->hs[i]->fac;
-      (void)hipMemsetAsync(f.xpub, 0xff, 2 * (size_t)f.chain_stride * 64 * sizeof(double), b->stream);
-    }
-    all_ok = all_ok && !bad;
-    if (status) status[i] = bad ? PGF_SINGULAR : PGF_OK;
-    if (n_neg) n_neg[i] = b->h_flags[3 * i + 1] + (b->cond_last ? b->m : 0);  // (+ the m pivots -delta)
-    if (diff) diff[i] = b->h_diff[i];
-  }
-  // a repaired instance holds no factor the batch can reuse (its ctl[1] is 0): a following
-  // Simplified step must not skip the factor launch, or it would solve with the bare matrix
-  b->all_factored = all_ok && !any_repaired;
-  return PGF_OK;
-}
-
-// ---- RCCL without PyTorch: the all-gather of residual norms as a C entry point ---------------
-// (librccl.so through dlopen: a process that already runs torch.distributed keeps ITS copy of the
-// library, and a host that never gathers never loads one)
-#include <dlfcn.h>
-namespace {
-struct RcclApi {
-  void *lib = nullptr;
-  int (*GetUniqueId)(void *) = nullptr;
-  // ncclUniqueId is passed BY VALUE: a 128-byte struct
-  struct Id {
-    char b[PGF_COMM_ID_BYTES];
-  };
-  int (*CommInitRank)(void **, int, Id, int) = nullptr;
-  int (*CommDestroy)(void *) = nullptr;
-  int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-  bool ok = false;
-};
-RcclApi &rccl() {
-  static RcclApi a = []() {
-    RcclApi r;
-    for (const char *name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-      r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (r.lib) break;
-    }
-    if (!r.lib) return r;
-    r.GetUniqueId = (int (*)(void *))dlsym(r.lib, "ncclGetUniqueId");
-    r.CommInitRank = (int (*)(void **, int, RcclApi::Id, int))dlsym(r.lib, "ncclCommInitRank");
-    r.CommDestroy = (int (*)(void *))dlsym(r.lib, "ncclCommDestroy");
-    r.AllGather = (int (*)(const void *, void *, size_t, int, void *, hipStream_t))dlsym(r.lib, "ncclAllGather");
-    r.ok = r.GetUniqueId && r.CommInitRank && r.CommDestroy && r.AllGather;
-    return r;
-  }();
-  return a;
-}
-}  // namespace
-struct pgf_comm_s {
-  void *comm = nullptr;
-  int nranks = 0, rank = 0, device = 0;
-};
-
-int pgf_comm_unique_id(void *id_out) {
-  if (!id_out) return PGF_INVALID;
-  if (!rccl().ok) return PGF_NOT_READY;
-  return rccl().GetUniqueId(id_out) == 0 ? PGF_OK : PGF_HIP_ERROR;
-}
-
-int pgf_comm_create(int nranks, int rank, const void *id, int device, pgf_comm *out) {
-  if (!out || !id || nranks <= 0 || rank < 0 || rank >= nranks) return PGF_INVALID;
-  if (!rccl().ok) return PGF_NOT_READY;
-  if (hipSetDevice(device) != hipSuccess) return PGF_INVALID;
-  pgf_comm c = new (std::nothrow) pgf_comm_s();
-  if (!c) return PGF_HIP_ERROR;
-  RcclApi::Id uid;
-  std::memcpy(uid.b, id, PGF_COMM_ID_BYTES);
-  if (rccl().CommInitRank(&c->comm, nranks, uid, rank) != 0) {
-    delete c;
-    return PGF_HIP_ERROR;
-  }
-  c->nranks = nranks;
-  c->rank = rank;
-  c->device = device;
-  *out = c;
-  return PGF_OK;
-}
-
-int pgf_comm_destroy(pgf_comm c) {
-  if (!c) return PGF_OK;
-  if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
-  delete c;
-  return PGF_OK;
-}
-
-int pgf_batch_allgather_norms(pgf_batch b, pgf_comm c, double *all_dev) {
-  if (!b || !c || !all_dev) return PGF_INVALID;
-  if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  if (c->device != b->device) return bfail(b, PGF_INVALID, "communicator and batch live on different devices");
-  (void)hipSetDevice(b->device);
-  batch_eval(b);
-  batch_launch_res_norm(b->stream, b->tab, b->B, b->sc, b->norm_out);
-  double *slot = all_dev + (size_t)c->rank * b->B;
-  BHIPCHK(b, hipMemcpyAsync(slot, b->norm_out, b->B * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
-  // in place: every rank's send buffer is its own slot of the receive buffer (ncclFloat64 = 8)
-  if (rccl().AllGather(slot, all_dev, (size_t)b->B, /*ncclFloat64*/ 8, c->comm, b->stream) != 0)
-    return bfail(b, PGF_HIP_ERROR, "ncclAllGather failed");
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  return PGF_OK;
-}
-
-int pgf_batch_refinement_stats(pgf_batch b, int *repaired) {
-  if (!b) return PGF_INVALID;
-  if (repaired) *repaired = b->repaired;
-  return PGF_OK;
-}
-
-int pgf_batch_debug_factor_kind(pgf_batch b) {
-  if (!b || !b->stepped) return 0;
-  return b->cond_last ? 2 : 1;
-}
-
-int pgf_batch_profile_enable(pgf_batch b, int on) {
-  if (!b) return PGF_INVALID;
-  b->prof.enabled = on != 0;
-  return PGF_OK;
-}
-
-// Accumulated device time of the K = LDLT_OB trailing-update launches since the last call and
-// their algorithmic flops, from the reduced sizes of the last synchronised step.
-int pgf_batch_profile_read(pgf_batch b, double *update_ms, int64_t *update_launches,
-                           double *update_flops) {
-  if (!b) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  PgfProfile &p = b->prof;
-  double ms_sum = 0.0, fl_sum = 0.0;
-  for (size_t i = 0; i < p.update_spans.size(); ++i) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p.update_spans[i].first, p.update_spans[i].second) == hipSuccess)
-      ms_sum += ms;
-    // update_flops[i] >= 0: first row of the launch's trailing region, K-depth LDLT_OB; < 0: the rank-m
-    // launch of the condensed order over the whole lower triangle, K-depth = -value
-    const double start = p.update_flops[i];
-    for (int k = 0; k < b->B; ++k) {
-      const double Nk = (double)(b->h_flags[3 * k + 2] + (b->cond_last ? 0 : b->m));
-      const double T = start < 0 ? Nk : Nk - start;
-      const double depth = start < 0 ? -start : (double)LDLT_OB;
-      if (T > 0) fl_sum += 2.0 * depth * (0.5 * T * (T + 1.0) + T);
-    }
-    p.pool.push_back(p.update_spans[i].first);
-    p.pool.push_back(p.update_spans[i].second);
-  }
-  if (update_ms) *update_ms = ms_sum;
-  if (update_launches) *update_launches = (int64_t)p.update_spans.size();
-  if (update_flops) *update_flops = fl_sum;
-  p.update_spans.clear();
-  p.update_flops.clear();
-  return PGF_OK;
-}
-
-int pgf_batch_residual_norms(pgf_batch b, double *norms_out, double *norms_out_dev) {
-  if (!b) return PGF_INVALID;
-  if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  batch_eval(b);
-  batch_launch_res_norm(b->stream, b->tab, b->B, b->sc, b->norm_out);
-  if (norms_out_dev)
-    BHIPCHK(b, hipMemcpyAsync(norms_out_dev, b->norm_out, b->B * sizeof(double),
-                              hipMemcpyDeviceToDevice, b->stream));
-  BHIPCHK(b, hipMemcpyAsync(b->h_norm, b->norm_out, b->B * sizeof(double), hipMemcpyDeviceToHost,
-                            b->stream));
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  if (norms_out) std::memcpy(norms_out, b->h_norm, b->B * sizeof(double));
-  return PGF_OK;
-}
-
-int pgf_batch_measures(pgf_batch b, double active_tol, double *out) {
-  if (!b || !out) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
-  batch_eval(b);
-  batch_launch_measures(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS, active_tol, b->red4,
-                        b->meas_out);
-  b->eval_fresh = false;  // tmpn / w were reused
-  BHIPCHK(b, hipMemcpyAsync(b->h_meas, b->meas_out, (size_t)b->B * 4 * sizeof(double),
-                            hipMemcpyDeviceToHost, b->stream));
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  std::memcpy(out, b->h_meas, (size_t)b->B * 4 * sizeof(double));
-  return PGF_OK;
-}
-
-int pgf_batch_get_points(pgf_batch b, double *x, double *y) {
-  if (!b) return PGF_INVALID;
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  for (int i = 0; i < b->B; ++i) {
-    if (x && b->n)
-      BHIPCHK(b, hipMemcpyAsync(x + (size_t)i * b->n, b->hs[i]->x, b->n * sizeof(double),
-                                hipMemcpyDeviceToHost, b->stream));
-    if (y && b->m)
-      BHIPCHK(b, hipMemcpyAsync(y + (size_t)i * b->m, b->hs[i]->y, b->m * sizeof(double),
-                                hipMemcpyDeviceToHost, b->stream));
-  }
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  return PGF_OK;
-}
-
-int pgf_batch_get_masks(pgf_batch b, uint8_t *mask) {
-  if (!b || !mask) return PGF_INVALID;
-  if (!b->have_mask) return bfail(b, PGF_NOT_READY, "no active set");
-  if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  (void)hipSetDevice(b->device);
-  for (int i = 0; i < b->B; ++i)
-    if (b->n)
-      BHIPCHK(b, hipMemcpyAsync(mask + (size_t)i * b->n, b->hs[i]->mask, b->n,
-                                hipMemcpyDeviceToHost, b->stream));
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  return PGF_OK;
-}
-
 int pgf_qp_measures(pgf_handle h, double active_tol, double *out) {
   if (!h || !out) return PGF_INVALID;
   if (!h->qp_mode || !h->point_set || !h->bounds_set)
@@ -2768,246 +1645,3 @@ int pgf_qp_measures(pgf_handle h, double active_tol, double *out) {
   return PGF_OK;
 }
 
-int pgf_stream(pgf_handle h, void **stream_out) {
-  if (!h || !stream_out) return PGF_INVALID;
-  *stream_out = (void *)h->stream;
-  return PGF_OK;
-}
-
-int pgf_profile_enable(pgf_handle h, int on) {
-  if (!h) return PGF_INVALID;
-  h->prof.enabled = on != 0;
-  h->prof.mode = on == 2 ? 2 : 1;
-  return PGF_OK;
-}
-
-static void profile_collect(PgfProfile &p) {
-  for (size_t i = 0; i < p.update_spans.size(); ++i) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p.update_spans[i].first, p.update_spans[i].second) == hipSuccess)
-      p.acc_update_ms += ms;
-    p.acc_update_flops += p.update_flops[i];
-    if (i < p.update_bytes.size()) p.acc_update_bytes += p.update_bytes[i];
-    p.acc_update_launches += 1;
-    p.pool.push_back(p.update_spans[i].first);
-    p.pool.push_back(p.update_spans[i].second);
-  }
-  p.update_spans.clear();
-  p.update_flops.clear();
-  p.update_bytes.clear();
-  auto drain = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &acc, int64_t *cnt) {
-    for (auto &sp : v) {
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, sp.first, sp.second) == hipSuccess) acc += ms;
-      if (cnt) *cnt += 1;
-      p.pool.push_back(sp.first);
-      p.pool.push_back(sp.second);
-    }
-    v.clear();
-  };
-  for (size_t i = 0; i < p.fused_spans.size(); ++i) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, p.fused_spans[i].first, p.fused_spans[i].second) == hipSuccess)
-      p.acc_fused_ms += ms;
-    p.acc_fused_flops += p.fused_flops[i];
-    p.acc_fused_bytes += p.fused_bytes[i];
-    p.acc_fused_launches += 1;
-    p.pool.push_back(p.fused_spans[i].first);
-    p.pool.push_back(p.fused_spans[i].second);
-  }
-  p.fused_spans.clear();
-  p.fused_flops.clear();
-  p.fused_bytes.clear();
-  drain(p.trsmud_spans, p.acc_trsmud_ms, nullptr);
-  drain(p.factor_spans, p.acc_factor_ms, nullptr);
-  drain(p.chain_spans, p.acc_chain_ms, &p.acc_chain_launches);
-  drain(p.trsm_spans, p.acc_trsm_ms, nullptr);
-  drain(p.udiag_spans, p.acc_udiag_ms, nullptr);
-}
-
-static void profile_reset(PgfProfile &p) {
-  p.acc_update_ms = p.acc_update_flops = p.acc_update_bytes = p.acc_factor_ms = 0;
-  p.acc_chain_ms = p.acc_trsm_ms = p.acc_udiag_ms = 0;
-  p.acc_update_launches = p.acc_chain_launches = 0;
-  p.acc_fused_ms = p.acc_fused_flops = p.acc_fused_bytes = p.acc_trsmud_ms = 0;
-  p.acc_fused_launches = 0;
-}
-
-int pgf_profile_read(pgf_handle h, double *update_ms, int64_t *update_launches,
-                     double *update_flops, double *factor_ms) {
-  if (!h) return PGF_INVALID;
-  (void)hipSetDevice(h->device);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  PgfProfile &p = h->prof;
-  profile_collect(p);
-  if (update_ms) *update_ms = p.acc_update_ms;
-  if (update_launches) *update_launches = p.acc_update_launches;
-  if (update_flops) *update_flops = p.acc_update_flops;
-  if (factor_ms) *factor_ms = p.acc_factor_ms;
-  profile_reset(p);
-  return PGF_OK;
-}
-
-int pgf_profile_read_ex(pgf_handle h, double *out, int count) {
-  if (!h || !out || count < PGF_PROF_COUNT) return PGF_INVALID;
-  (void)hipSetDevice(h->device);
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  PgfProfile &p = h->prof;
-  profile_collect(p);
-  out[PGF_PROF_UPDATE_MS] = p.acc_update_ms;
-  out[PGF_PROF_UPDATE_LAUNCHES] = (double)p.acc_update_launches;
-  out[PGF_PROF_UPDATE_FLOPS] = p.acc_update_flops;
-  out[PGF_PROF_UPDATE_BYTES] = p.acc_update_bytes;
-  out[PGF_PROF_FACTOR_MS] = p.acc_factor_ms;
-  out[PGF_PROF_CHAIN_MS] = p.acc_chain_ms;
-  out[PGF_PROF_CHAIN_LAUNCHES] = (double)p.acc_chain_launches;
-  out[PGF_PROF_TRSM_MS] = p.acc_trsm_ms;
-  out[PGF_PROF_UDIAG_MS] = p.acc_udiag_ms;
-  if (count >= PGF_PROF_COUNT2) {
-    out[PGF_PROF_FUSED_MS] = p.acc_fused_ms;
-    out[PGF_PROF_FUSED_LAUNCHES] = (double)p.acc_fused_launches;
-    out[PGF_PROF_FUSED_FLOPS] = p.acc_fused_flops;
-    out[PGF_PROF_FUSED_BYTES] = p.acc_fused_bytes;
-    out[PGF_PROF_TRSMUD_MS] = p.acc_trsmud_ms;
-  }
-  if (count >= PGF_PROF_COUNT3) {
-    out[PGF_PROF_UNSYM_ASM_MS] = h->acc_unsym_asm_ms;
-    out[PGF_PROF_UNSYM_ASM_LAUNCHES] = (double)h->acc_unsym_asm_launches;
-    h->acc_unsym_asm_ms = 0;
-    h->acc_unsym_asm_launches = 0;
-  }
-  profile_reset(p);
-  return PGF_OK;
-}
-
-// ---------------------------------------------------------------- stand-alone linear solver
-int pgf_ls_create_dense(int N, const double *A, int64_t lda, int symmetric, int device,
-                        pgf_ls_handle *out) {
-  if (!out || N < 0 || N > 60000 || (N && (!A || lda < N))) return PGF_INVALID;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) return PGF_HIP_ERROR + (int)e;
-  pgf_ls_handle ls = new (std::nothrow) pgf_linsolver();
-  if (!ls) return PGF_INVALID;
-  ls->N = N;
-  ls->device = device;
-  ls->symmetric = symmetric != 0;
-  int rc = PGF_OK;
-  do {
-    if ((e = hipStreamCreateWithFlags(&ls->stream, hipStreamNonBlocking)) != hipSuccess) break;
-    if ((e = dalloc(&ls->rhs, (size_t)N + 1)) != hipSuccess) break;
-    if ((e = dalloc(&ls->sol, (size_t)N + 1)) != hipSuccess) break;
-    if (!ls->symmetric) {  // LU with partial pivoting of the full matrix
-      if ((e = lu_alloc(ls->lu, N, ls->stream)) != hipSuccess) break;
-      if (N) {
-        e = hipMemcpy2DAsync(ls->lu.A, (size_t)ls->lu.ld * sizeof(double), A,
-                             (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
-                             hipMemcpyHostToDevice, ls->stream);
-        if (e != hipSuccess) break;
-      }
-      const int st = lu_factor(ls->lu, &e);
-      if (st < 0) break;
-      if (st == 1) rc = PGF_SINGULAR;
-      break;
-    }
-    if ((e = ldlt_alloc(ls->fac, N, ls->stream)) != hipSuccess) break;
-    if (N) {
-      e = hipMemcpy2DAsync(ls->fac.K, (size_t)ls->fac.ldk * sizeof(double), A,
-                           (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
-                           hipMemcpyHostToDevice, ls->stream);
-      if (e != hipSuccess) break;
-    }
-    if ((e = ldlt_factor_async(ls->fac, N, N)) != hipSuccess) break;
-    int st = ldlt_finish(ls->fac, &e);
-    if (st == 2) {  // chain helpers failed their checks (off now): upload and factorise again
-      if (N) {
-        e = hipMemcpy2DAsync(ls->fac.K, (size_t)ls->fac.ldk * sizeof(double), A,
-                             (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
-                             hipMemcpyHostToDevice, ls->stream);
-        if (e != hipSuccess) break;
-      }
-      if ((e = ldlt_factor_async(ls->fac, N, N)) != hipSuccess) break;
-      st = ldlt_finish(ls->fac, &e);
-      if (st == 2) rc = PGF_HIP_ERROR;
-    }
-    if (st < 0) break;
-    if (st == 1) rc = PGF_SINGULAR;
-  } while (0);
-  if (e != hipSuccess) rc = PGF_HIP_ERROR + (int)e;
-  if (rc != PGF_OK) {
-    pgf_ls_destroy(ls);
-    return rc;
-  }
-  *out = ls;
-  return PGF_OK;
-}
-
-int pgf_ls_solve(pgf_ls_handle ls, const double *rhs, int trans, double *sol) {
-  if (!ls || (ls->N && (!rhs || !sol))) return PGF_INVALID;
-  if (ls->N == 0) return PGF_OK;
-  (void)hipSetDevice(ls->device);
-  hipError_t e = hipMemcpyAsync(ls->rhs, rhs, ls->N * sizeof(double), hipMemcpyHostToDevice,
-                                ls->stream);
-  if (!ls->symmetric) {
-    if (e == hipSuccess) e = lu_solve_async(ls->lu, ls->rhs, ls->sol, trans);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
-    return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
-  }
-  if (e == hipSuccess) e = ldlt_solve_async(ls->fac, ls->rhs, ls->sol);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
-  if (e == hipSuccess && ldlt_chain_check(ls->fac)) {  // chain off now: per-block kernels
-    e = ldlt_solve_async(ls->fac, ls->rhs, ls->sol);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
-    if (e == hipSuccess && ldlt_chain_check(ls->fac)) return PGF_HIP_ERROR;
-  }
-  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
-}
-
-int pgf_ls_get_factor(pgf_ls_handle ls, double *LD_out, int64_t ld) {
-  if (!ls || (ls->N && (!LD_out || ld < ls->N))) return PGF_INVALID;
-  if (ls->N == 0) return PGF_OK;
-  (void)hipSetDevice(ls->device);
-  const double *src = ls->symmetric ? ls->fac.K : ls->lu.A;
-  const int64_t lds = ls->symmetric ? ls->fac.ldk : ls->lu.ld;
-  hipError_t e = hipMemcpy2DAsync(LD_out, (size_t)ld * sizeof(double), src,
-                                  (size_t)lds * sizeof(double),
-                                  (size_t)ls->N * sizeof(double), ls->N, hipMemcpyDeviceToHost,
-                                  ls->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
-  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
-}
-
-int pgf_ls_num_neg(pgf_ls_handle ls, int *out) {
-  if (!ls || !out) return PGF_INVALID;
-  if (!ls->symmetric) return PGF_NOT_READY;  // an LU has no inertia (LUSolver returns None)
-  *out = ls->fac.n_neg;
-  return PGF_OK;
-}
-
-int pgf_ls_destroy(pgf_ls_handle ls) {
-  if (!ls) return PGF_OK;
-  (void)hipSetDevice(ls->device);
-  if (ls->stream) (void)hipStreamSynchronize(ls->stream);
-  ldlt_free(ls->fac);
-  lu_free(ls->lu);
-  if (ls->rhs) (void)hipFree(ls->rhs);
-  if (ls->sol) (void)hipFree(ls->sol);
-  if (ls->stream) (void)hipStreamDestroy(ls->stream);
-  delete ls;
-  return PGF_OK;
-}
-
-int pgf_bench_update(int N, int KB, int variant, int reps, int device, double *ms_out,
-                     double *flops_out) {
-  if (N <= 0 || KB <= 0 || KB % 16 || reps <= 0 || !ms_out || !flops_out) return PGF_INVALID;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = ldlt_bench_update(N, KB, variant, reps, ms_out, flops_out);
-  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
-}
-
-}  // extern "C"

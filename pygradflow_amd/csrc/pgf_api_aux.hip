@@ -1,0 +1,247 @@
+// Entry points of the C ABI that need nothing of the dense step: the handle's stream, the
+// profiling read-out, the stand-alone linear solver pgf_ls_* and pgf_bench_update.
+#include <new>
+
+#include "pgf_api_internal.h"
+
+int pgf_stream(pgf_handle h, void **stream_out) {
+  if (!h || !stream_out) return PGF_INVALID;
+  *stream_out = (void *)h->stream;
+  return PGF_OK;
+}
+
+int pgf_profile_enable(pgf_handle h, int on) {
+  if (!h) return PGF_INVALID;
+  h->prof.enabled = on != 0;
+  h->prof.mode = on == 2 ? 2 : 1;
+  return PGF_OK;
+}
+
+static void profile_collect(PgfProfile &p) {
+  for (size_t i = 0; i < p.update_spans.size(); ++i) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, p.update_spans[i].first, p.update_spans[i].second) == hipSuccess)
+      p.acc_update_ms += ms;
+    p.acc_update_flops += p.update_flops[i];
+    if (i < p.update_bytes.size()) p.acc_update_bytes += p.update_bytes[i];
+    p.acc_update_launches += 1;
+    p.pool.push_back(p.update_spans[i].first);
+    p.pool.push_back(p.update_spans[i].second);
+  }
+  p.update_spans.clear();
+  p.update_flops.clear();
+  p.update_bytes.clear();
+  auto drain = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &acc, int64_t *cnt) {
+    for (auto &sp : v) {
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, sp.first, sp.second) == hipSuccess) acc += ms;
+      if (cnt) *cnt += 1;
+      p.pool.push_back(sp.first);
+      p.pool.push_back(sp.second);
+    }
+    v.clear();
+  };
+  for (size_t i = 0; i < p.fused_spans.size(); ++i) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, p.fused_spans[i].first, p.fused_spans[i].second) == hipSuccess)
+      p.acc_fused_ms += ms;
+    p.acc_fused_flops += p.fused_flops[i];
+    p.acc_fused_bytes += p.fused_bytes[i];
+    p.acc_fused_launches += 1;
+    p.pool.push_back(p.fused_spans[i].first);
+    p.pool.push_back(p.fused_spans[i].second);
+  }
+  p.fused_spans.clear();
+  p.fused_flops.clear();
+  p.fused_bytes.clear();
+  drain(p.trsmud_spans, p.acc_trsmud_ms, nullptr);
+  drain(p.factor_spans, p.acc_factor_ms, nullptr);
+  drain(p.chain_spans, p.acc_chain_ms, &p.acc_chain_launches);
+  drain(p.trsm_spans, p.acc_trsm_ms, nullptr);
+  drain(p.udiag_spans, p.acc_udiag_ms, nullptr);
+}
+
+static void profile_reset(PgfProfile &p) {
+  p.acc_update_ms = p.acc_update_flops = p.acc_update_bytes = p.acc_factor_ms = 0;
+  p.acc_chain_ms = p.acc_trsm_ms = p.acc_udiag_ms = 0;
+  p.acc_update_launches = p.acc_chain_launches = 0;
+  p.acc_fused_ms = p.acc_fused_flops = p.acc_fused_bytes = p.acc_trsmud_ms = 0;
+  p.acc_fused_launches = 0;
+}
+
+int pgf_profile_read(pgf_handle h, double *update_ms, int64_t *update_launches,
+                     double *update_flops, double *factor_ms) {
+  if (!h) return PGF_INVALID;
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  PgfProfile &p = h->prof;
+  profile_collect(p);
+  if (update_ms) *update_ms = p.acc_update_ms;
+  if (update_launches) *update_launches = p.acc_update_launches;
+  if (update_flops) *update_flops = p.acc_update_flops;
+  if (factor_ms) *factor_ms = p.acc_factor_ms;
+  profile_reset(p);
+  return PGF_OK;
+}
+
+int pgf_profile_read_ex(pgf_handle h, double *out, int count) {
+  if (!h || !out || count < PGF_PROF_COUNT) return PGF_INVALID;
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  PgfProfile &p = h->prof;
+  profile_collect(p);
+  out[PGF_PROF_UPDATE_MS] = p.acc_update_ms;
+  out[PGF_PROF_UPDATE_LAUNCHES] = (double)p.acc_update_launches;
+  out[PGF_PROF_UPDATE_FLOPS] = p.acc_update_flops;
+  out[PGF_PROF_UPDATE_BYTES] = p.acc_update_bytes;
+  out[PGF_PROF_FACTOR_MS] = p.acc_factor_ms;
+  out[PGF_PROF_CHAIN_MS] = p.acc_chain_ms;
+  out[PGF_PROF_CHAIN_LAUNCHES] = (double)p.acc_chain_launches;
+  out[PGF_PROF_TRSM_MS] = p.acc_trsm_ms;
+  out[PGF_PROF_UDIAG_MS] = p.acc_udiag_ms;
+  if (count >= PGF_PROF_COUNT2) {
+    out[PGF_PROF_FUSED_MS] = p.acc_fused_ms;
+    out[PGF_PROF_FUSED_LAUNCHES] = (double)p.acc_fused_launches;
+    out[PGF_PROF_FUSED_FLOPS] = p.acc_fused_flops;
+    out[PGF_PROF_FUSED_BYTES] = p.acc_fused_bytes;
+    out[PGF_PROF_TRSMUD_MS] = p.acc_trsmud_ms;
+  }
+  if (count >= PGF_PROF_COUNT3) {
+    out[PGF_PROF_UNSYM_ASM_MS] = h->acc_unsym_asm_ms;
+    out[PGF_PROF_UNSYM_ASM_LAUNCHES] = (double)h->acc_unsym_asm_launches;
+    h->acc_unsym_asm_ms = 0;
+    h->acc_unsym_asm_launches = 0;
+  }
+  profile_reset(p);
+  return PGF_OK;
+}
+
+// ---------------------------------------------------------------- stand-alone linear solver
+int pgf_ls_create_dense(int N, const double *A, int64_t lda, int symmetric, int device,
+                        pgf_ls_handle *out) {
+  if (!out || N < 0 || N > 60000 || (N && (!A || lda < N))) return PGF_INVALID;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return PGF_HIP_ERROR + (int)e;
+  pgf_ls_handle ls = new (std::nothrow) pgf_linsolver();
+  if (!ls) return PGF_INVALID;
+  ls->N = N;
+  ls->device = device;
+  ls->symmetric = symmetric != 0;
+  int rc = PGF_OK;
+  do {
+    if ((e = hipStreamCreateWithFlags(&ls->stream, hipStreamNonBlocking)) != hipSuccess) break;
+    if ((e = dalloc(&ls->rhs, (size_t)N + 1)) != hipSuccess) break;
+    if ((e = dalloc(&ls->sol, (size_t)N + 1)) != hipSuccess) break;
+    if (!ls->symmetric) {  // LU with partial pivoting of the full matrix
+      if ((e = lu_alloc(ls->lu, N, ls->stream)) != hipSuccess) break;
+      if (N) {
+        e = hipMemcpy2DAsync(ls->lu.A, (size_t)ls->lu.ld * sizeof(double), A,
+                             (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
+                             hipMemcpyHostToDevice, ls->stream);
+        if (e != hipSuccess) break;
+      }
+      const int st = lu_factor(ls->lu, &e);
+      if (st < 0) break;
+      if (st == 1) rc = PGF_SINGULAR;
+      break;
+    }
+    if ((e = ldlt_alloc(ls->fac, N, ls->stream)) != hipSuccess) break;
+    if (N) {
+      e = hipMemcpy2DAsync(ls->fac.K, (size_t)ls->fac.ldk * sizeof(double), A,
+                           (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
+                           hipMemcpyHostToDevice, ls->stream);
+      if (e != hipSuccess) break;
+    }
+    if ((e = ldlt_factor_async(ls->fac, N, N)) != hipSuccess) break;
+    int st = ldlt_finish(ls->fac, &e);
+    if (st == 2) {  // chain helpers failed their checks (off now): upload and factorise again
+      if (N) {
+        e = hipMemcpy2DAsync(ls->fac.K, (size_t)ls->fac.ldk * sizeof(double), A,
+                             (size_t)lda * sizeof(double), (size_t)N * sizeof(double), N,
+                             hipMemcpyHostToDevice, ls->stream);
+        if (e != hipSuccess) break;
+      }
+      if ((e = ldlt_factor_async(ls->fac, N, N)) != hipSuccess) break;
+      st = ldlt_finish(ls->fac, &e);
+      if (st == 2) rc = PGF_HIP_ERROR;
+    }
+    if (st < 0) break;
+    if (st == 1) rc = PGF_SINGULAR;
+  } while (0);
+  if (e != hipSuccess) rc = PGF_HIP_ERROR + (int)e;
+  if (rc != PGF_OK) {
+    pgf_ls_destroy(ls);
+    return rc;
+  }
+  *out = ls;
+  return PGF_OK;
+}
+
+int pgf_ls_solve(pgf_ls_handle ls, const double *rhs, int trans, double *sol) {
+  if (!ls || (ls->N && (!rhs || !sol))) return PGF_INVALID;
+  if (ls->N == 0) return PGF_OK;
+  (void)hipSetDevice(ls->device);
+  hipError_t e = hipMemcpyAsync(ls->rhs, rhs, ls->N * sizeof(double), hipMemcpyHostToDevice,
+                                ls->stream);
+  if (!ls->symmetric) {
+    if (e == hipSuccess) e = lu_solve_async(ls->lu, ls->rhs, ls->sol, trans);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
+    return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+  }
+  if (e == hipSuccess) e = ldlt_solve_async(ls->fac, ls->rhs, ls->sol);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
+  if (e == hipSuccess && ldlt_chain_check(ls->fac)) {  // chain off now: per-block kernels
+    e = ldlt_solve_async(ls->fac, ls->rhs, ls->sol);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(sol, ls->sol, ls->N * sizeof(double), hipMemcpyDeviceToHost, ls->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
+    if (e == hipSuccess && ldlt_chain_check(ls->fac)) return PGF_HIP_ERROR;
+  }
+  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+}
+
+int pgf_ls_get_factor(pgf_ls_handle ls, double *LD_out, int64_t ld) {
+  if (!ls || (ls->N && (!LD_out || ld < ls->N))) return PGF_INVALID;
+  if (ls->N == 0) return PGF_OK;
+  (void)hipSetDevice(ls->device);
+  const double *src = ls->symmetric ? ls->fac.K : ls->lu.A;
+  const int64_t lds = ls->symmetric ? ls->fac.ldk : ls->lu.ld;
+  hipError_t e = hipMemcpy2DAsync(LD_out, (size_t)ld * sizeof(double), src,
+                                  (size_t)lds * sizeof(double),
+                                  (size_t)ls->N * sizeof(double), ls->N, hipMemcpyDeviceToHost,
+                                  ls->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
+  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+}
+
+int pgf_ls_num_neg(pgf_ls_handle ls, int *out) {
+  if (!ls || !out) return PGF_INVALID;
+  if (!ls->symmetric) return PGF_NOT_READY;  // an LU has no inertia (LUSolver returns None)
+  *out = ls->fac.n_neg;
+  return PGF_OK;
+}
+
+int pgf_ls_destroy(pgf_ls_handle ls) {
+  if (!ls) return PGF_OK;
+  (void)hipSetDevice(ls->device);
+  if (ls->stream) (void)hipStreamSynchronize(ls->stream);
+  ldlt_free(ls->fac);
+  lu_free(ls->lu);
+  if (ls->rhs) (void)hipFree(ls->rhs);
+  if (ls->sol) (void)hipFree(ls->sol);
+  if (ls->stream) (void)hipStreamDestroy(ls->stream);
+  delete ls;
+  return PGF_OK;
+}
+
+int pgf_bench_update(int N, int KB, int variant, int reps, int device, double *ms_out,
+                     double *flops_out) {
+  if (N <= 0 || KB <= 0 || KB % 16 || reps <= 0 || !ms_out || !flops_out) return PGF_INVALID;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = ldlt_bench_update(N, KB, variant, reps, ms_out, flops_out);
+  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+}

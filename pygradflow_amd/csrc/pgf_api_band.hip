@@ -14,10 +14,7 @@
 #include "pgf_kernels.h"
 
 // PGF_BW_SPLIT=0: new handles start with the wide band's factor / solve split off
-bool band_split_default() {
-  static const bool on = !(getenv("PGF_BW_SPLIT") && atoi(getenv("PGF_BW_SPLIT")) == 0);
-  return on;
-}
+bool band_split_default() { static const bool on = env_on("PGF_BW_SPLIT"); return on; }
 
 // Wide band without a border: against the kept factors when there are some (sp.kept == 2),
 // otherwise the fused KEEP reduction, which solves as ever and leaves the factors.  Its pivot
@@ -125,12 +122,7 @@ int band_refine(pgf_handle h, bool swapped, bool with_step) {
   if (rel <= h->refine_tol) return PGF_OK;
   hipStream_t s = h->stream;
   SparseDev &sp = h->sp;
-  auto unswap = [&]() {
-    if (swapped) {
-      std::swap(h->x, h->xn);
-      std::swap(h->y, h->yn);
-    }
-  };
+  auto unswap = [&]() { if (swapped) swap_point(h); };
   for (int it = 0; it < 2 && rel > h->refine_tol && rel < 1.0; ++it) {
     HIPCHK(h, hipMemcpyAsync(sp.bsol, sp.brhs, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(sp.brhs, sp.bres, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));

@@ -1,10 +1,12 @@
-// What the translation units behind the C ABI share (pgf_api.hip: dense, batch, unsymmetric and
-// profile sections; pgf_api_band.hip: the banded driver): the handles, the error helpers and the
-// small interface through which the dense functions hand a banded handle over.
+// What the translation units behind the C ABI share -- pgf_api.hip: the dense Symmetric handle and
+// the LQ step; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the unsymmetric formulations;
+// pgf_api_batch.hip: the batch driver; pgf_api_aux.hip: profiling read-out and the stand-alone
+// linear solver -- the handles, the error helpers and the small interfaces between the files.
 #pragma once
 
 #include <cstdio>
 #include <string>
+#include <utility>
 
 #include "../../include/pgf_hip.h"
 #include "pgf_internal.h"
@@ -19,6 +21,8 @@
 //   [16, 17) two tickets of the last-workgroup reductions (never copied)
 #define STAT_COPY 16
 #define STAT_ALLOC 17
+
+#define PGF_GEMVT_PARTS 32  // row chunks of the J^T products' partial sums (pgf_solver::partial)
 
 struct pgf_solver {
   int n = 0, m = 0, device = 0;
@@ -114,7 +118,7 @@ struct pgf_solver {
   // pgf_debug_head_stats counts both kinds
   int fac_head = 0;
   int stat_head_fused = 0, stat_head_plain = 0;
-  // The unsymmetric formulations (pgf_set_formulation; the section in front of pgf_factor): form --
+  // The unsymmetric formulations (pgf_set_formulation, pgf_api_unsym.hip): form --
   // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
   // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric
   // path and is never touched here); ulu_ok -- it holds the factor of the current matrix;
@@ -141,6 +145,10 @@ struct pgf_linsolver {
   DenseLu lu;
   double *rhs = nullptr, *sol = nullptr;
 };
+
+static const char *const k_no_handle = "null handle";
+static const char *const k_chain_msg = "chained triangular solve failed its placement / timeout check "
+                                       "and so did the per-block solve that replaced it";
 
 static inline int fail(pgf_handle h, int code, const char *msg) {
   if (h) h->err = msg;
@@ -190,6 +198,21 @@ static inline int down(pgf_handle h, void *dst, const void *src, size_t bytes) {
   return PGF_OK;
 }
 
+// (x, y) <-> (xn, yn): a step's new point becomes the point, or a discarded step's point goes back
+static inline void swap_point(pgf_handle h) {
+  std::swap(h->x, h->xn);
+  std::swap(h->y, h->yn);
+}
+// the index-set sizes the compaction left in the pinned counts, after the wait that brought them
+static inline void adopt_counts(pgf_handle h) {
+  h->nI = h->h_counts[0];
+  h->nA = h->h_counts[1];
+  h->N = h->nI + h->m;
+  h->counts_known = true;
+}
+// the depth of the panel V: the constraint count in whole 32-column tiles
+static inline int round_up32(int m) { return (m + 31) / 32 * 32; }
+
 static inline void invalidate_factor(pgf_handle h) {
   h->fac.factored = false;
   h->condensed_veto = false;
@@ -214,3 +237,30 @@ void band_kept_resolve(pgf_handle h);                          // finish_factor_
 bool band_split_default();                                     // pgf_create (PGF_BW_SPLIT)
 void band_eval(pgf_handle h);                                  // qp_eval
 void band_measures_eval(pgf_handle h);                         // pgf_qp_measures
+
+// ---- the unsymmetric formulations (pgf_api_unsym.hip), for handles with h->form != 0 -------------
+// Each is the unsymmetric half of the dense function named beside it, which hands over in one line.
+int unsym_factor(pgf_handle h);                                           // pgf_factor, pgf_linear_solve
+int unsym_step_core(pgf_handle h);                                        // pgf_newton_solve
+void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint8_t *out);  // pgf_residual
+int unsym_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, bool wait_counts);  // pgf_qp_update_active_set
+int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau);       // pgf_qp_step_async
+int unsym_qp_sync(pgf_handle h, int *n_neg, double *diff);                // pgf_qp_sync
+// what they take from pgf_api.hip
+void tau_factors(pgf_handle h, double tau, int *use_tau, double *f_x, double *f_x0, double *f_d);  // unsym_mask
+void qp_eval(pgf_handle h);                                               // unsym_qp_step_async
+bool gram_build(pgf_handle h);                                            // unsym_gram (Standard: H + rho J^T J)
+int check_ready(pgf_handle h);                                            // pgf_get_newton_matrix
+
+// ---- what the batch driver (pgf_api_batch.hip) takes from pgf_api.hip --------------------------
+int residual_norms(pgf_handle h);           // batch_store_norms, pgf_batch_advance_outer_each
+int condensed_mode();                       // pgf_batch_create
+hipError_t condensed_reserve(pgf_handle h); // pgf_batch_create (and unsym_gram)
+int64_t condensed_ldv(int m);               // pgf_batch_create, batch_repair_instance
+bool condensed_growth_ok(pgf_handle h);     // pgf_batch_advance_outer_each
+bool eval_ahead();                          // pgf_batch_step_async
+// batch_repair_instance: the single-instance accuracy guard on an instance's own handle
+struct StepCondY;
+void enqueue_residual(pgf_handle h, bool may_skip = false);
+int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true);
+void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr);

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "pgf_bcr_dev.h"
+#include "pgf_internal.h"
 #include "pgf_sparse.h"
 
 static inline dim3 g1(int n, int b = 256) { return dim3((n + b - 1) / b); }
@@ -543,7 +544,7 @@ void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
   ++sp.stat_bfactor;
   // PGF_BORDER_MULTI=0: Y column by column through the single-right-hand-side solves at every B:
   // slower, and an independent check of the panel kernels
-  static const bool multi = !(getenv("PGF_BORDER_MULTI") && atoi(getenv("PGF_BORDER_MULTI")) == 0);
+  static const bool multi = env_on("PGF_BORDER_MULTI");
   if (sp.B == 8 && multi) {
     mbcr_solve(s, sp);
   } else if (wide_kept(sp)) {

@@ -1983,7 +1983,7 @@ void ldlt_batch_launch_trsm(hipStream_t s, const BInst *tab, int B, int per, int
 static bool g_help_off = false;
 static bool g_fused_ud_off = false;
 static bool chain_helpers() {
-  static const bool on = !(getenv("PGF_CHAIN_HELP") && atoi(getenv("PGF_CHAIN_HELP")) == 0);
+  static const bool on = env_on("PGF_CHAIN_HELP");
   return on && !g_help_off;
 }
 void ldlt_chain_helpers_off() {
@@ -2008,7 +2008,7 @@ void ldlt_inject_helper_failure(hipStream_t s, int *flags) {
 // one each per ~47 us) and the number of pending blocks an optional job may take at once;
 // PGF_LAZY_BUDGET=0: no limit = the eager schedule (every launch applies block k everywhere)
 static int lazy_budget() {
-  static const int b = getenv("PGF_LAZY_BUDGET") ? atoi(getenv("PGF_LAZY_BUDGET")) : 420;
+  static const int b = env_int("PGF_LAZY_BUDGET", 420);
   return b > 0 ? b : (1 << 30);
 }
 // pending blocks an optional job takes at once: 2 in the natural order; 4 with a pre-eliminated
@@ -2022,19 +2022,19 @@ static int lazy_cap(int vdepth = 0) {
 // T(k) and the next diagonal block's update in one launch (k_trsm_ud); PGF_FUSED_UD=0 or a failed
 // placement check: two launches
 static bool fused_ud() {
-  static const bool on = !(getenv("PGF_FUSED_UD") && atoi(getenv("PGF_FUSED_UD")) == 0);
+  static const bool on = env_on("PGF_FUSED_UD");
   return on && !g_fused_ud_off;
 }
 
 static bool fused() {
-  static const bool on = !(getenv("PGF_FUSED") && atoi(getenv("PGF_FUSED")) == 0);
+  static const bool on = env_on("PGF_FUSED");
   return on;
 }
 
 // the step's head beside the first chain (k_chain_head); PGF_HEAD_FUSED=0: the assembly and the
 // panel as launches of their own in front of a plain first chain
 static bool head_fused() {
-  static const bool on = !(getenv("PGF_HEAD_FUSED") && atoi(getenv("PGF_HEAD_FUSED")) == 0);
+  static const bool on = env_on("PGF_HEAD_FUSED");
   return on;
 }
 bool ldlt_head_wanted(const DenseLdlt &f, int N) {

@@ -5,8 +5,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <string>
 #include <vector>
+
+// The PGF_* environment switches (host).  Each call site keeps its value in a `static const', so a
+// variable is read once per process, the first time its code path runs.
+inline bool env_on(const char *name) {  // on unless set to 0
+  const char *e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline double env_double(const char *name, double dflt) {
+  const char *e = getenv(name);
+  return e ? atof(e) : dflt;
+}
 
 #define PGF_NB 64  // diagonal-block / triangular-solve block size (one wavefront of rows)
 
@@ -238,7 +254,7 @@ struct BInst {
   double *xpub;
   int *cctl;
   int capblk;
-  // condensed order (pgf_api.hip, batch_condensed_wanted): the instance's panel V = J_I^T
+  // condensed order (pgf_api_batch.hip, pgf_batch_s::cond_wanted): the instance's panel V = J_I^T
   // ((n + 1) x ldv, row nI = the constraint part of the right-hand side) and its scaling -1 / delta
   double *V;
   int64_t ldv;

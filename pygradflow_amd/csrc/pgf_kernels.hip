@@ -1562,7 +1562,7 @@ __global__ __launch_bounds__(256) void kb_step_update(const BInst *__restrict__ 
                 I.sol, I.dx, I.dy, I.xn, I.yn, I.red);
   // the new point replaces the current one in place (each lane re-reads its own entry) -- unless
   // the sampled residual of the solve failed: the host repairs such an instance from the point it
-  // started at (batch_repair_instance, pgf_api.hip)
+  // started at (batch_repair_instance, pgf_api_batch.hip)
   if (I.flags[3]) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n)
@@ -1910,7 +1910,7 @@ void batch_launch_rhs_assemble(hipStream_t s, const BInst *tab, int B, const Bat
   const int n = sc.n, m = sc.m, Nmax = n + m;
   if (!Nmax) return;
   hipLaunchKernelGGL(kb_residual, gb(Nmax, 256, B), dim3(256), 0, s, tab, n, m);
-  // (the scratch `partial' holds 32 n doubles per instance: PGF_GEMVT_PARTS in pgf_api.hip)
+  // (the scratch `partial' holds 32 n doubles per instance: PGF_GEMVT_PARTS in pgf_api_internal.h)
   if (n) hipLaunchKernelGGL(kb_active_rows_partial, dim3((n + 255) / 256, 32, B), dim3(256), 0, s, tab, n, 32);
   hipLaunchKernelGGL(kb_reduced_rhs, gb(Nmax, 4, B), dim3(256), 0, s, tab, n, m, 32);
   if (cond_mp > 0) {

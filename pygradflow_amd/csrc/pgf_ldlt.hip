@@ -702,7 +702,7 @@ int ldlt_finish(DenseLdlt &f, hipError_t *err) {
 // solve reports a placement / timeout problem (ldlt_chain_check)
 static bool g_chain_off = false;
 static bool use_chain() {
-  static const bool on = !(getenv("PGF_TRSV_CHAIN") && atoi(getenv("PGF_TRSV_CHAIN")) == 0);
+  static const bool on = env_on("PGF_TRSV_CHAIN");
   return on && !g_chain_off;
 }
 
@@ -801,7 +801,7 @@ hipError_t ldlt_solve_async(DenseLdlt &f, const double *rhs, double *sol) {
 
 // ------------------------------------------------------------------ batched host schedule
 static int batch_fused_max() {
-  static const int v = getenv("PGF_BATCH_FUSED_MAX") ? atoi(getenv("PGF_BATCH_FUSED_MAX")) : 64;
+  static const int v = env_int("PGF_BATCH_FUSED_MAX", 64);
   return v;
 }
 
@@ -811,7 +811,7 @@ static int batch_fused_max() {
 // tile, rows below) pairs per block), a rank of an 8-GPU run of BASELINE config 4 holds 32
 // instances: 1.98 -> 1.71 ms per batched step; 256 instances: 8.48 -> 8.17 ms.
 // vdepth > 0: every instance's K is preceded by a pre-eliminated block with panel BInst::V (the
-// condensed order, pgf_api.hip); m is then 0 for the factor kernels
+// condensed order, pgf_api_batch.hip); m is then 0 for the factor kernels
 void ldlt_batch_factor_async(hipStream_t s, const BInst *tab, int B, int Nmax, int m, PgfProfile *p,
                              int vdepth) {
   if (Nmax <= 0 || B <= 0) return;

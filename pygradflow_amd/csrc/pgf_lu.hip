@@ -509,7 +509,7 @@ int lu_factor(DenseLu &f, hipError_t *err) {
     hipLaunchKernelGGL(k_lu_panel_load, dim3(gr), dim3(256), 0, s, f.A, f.ld, N, c0, pb, f.PT, f.ldp);
     // rows in registers while the panel is at most 5 x 1024 rows tall (PGF_LU_PANEL=1: always the
     // streaming kernel)
-    static const bool regs = !(getenv("PGF_LU_PANEL") && atoi(getenv("PGF_LU_PANEL")) == 1);
+    static const bool regs = env_int("PGF_LU_PANEL", 0) != 1;
     const int R = (N - c0 + 1023) / 1024;
     if (regs && R <= 5) {
       switch (R) {

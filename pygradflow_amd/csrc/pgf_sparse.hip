@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off like pgf_kernels.hip (explicit fma() only).
 #include "pgf_sparse.h"
 #include "pgf_bcr_dev.h"
+#include "pgf_internal.h"
 
 #define ACTIVE_EPS 1e-8
 
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(256) void k_band_residual(const double *__restrict_
                                                        double *__restrict__ rsmax,
                                                        const int *__restrict__ flags, int nred) {
   // the pivot flags of the solve ride along behind the pairs and the step update's partial sums
-  // (one device-to-host copy for all three, pgf_api.hip)
+  // (one device-to-host copy for all three, pgf_api_band.hip)
   if (blockIdx.x == 0 && threadIdx.x < 4) rsmax[3 * nred + threadIdx.x] = (double)flags[threadIdx.x];
   // rows [i0, i0 + 256 + bw) of the band (contiguous in memory: coalesced) and x[i0 - bw,
   // i0 + 256 + bw) staged in LDS: row i needs its own band row and, for the upper triangle, the
@@ -826,10 +827,10 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
   // levels with many blocks: one workgroup per block; from the first level with at most
   // BCR_TAIL_BLOCKS blocks left: everything in one workgroup, in LDS
   // PGF_BCR_FUSED=0: separate invert / reduce launches per level
-  static const bool fused_levels = !(getenv("PGF_BCR_FUSED") && atoi(getenv("PGF_BCR_FUSED")) == 0);
+  static const bool fused_levels = env_on("PGF_BCR_FUSED");
   // PGF_BCR_PAIRS=0: one level per launch throughout (two per launch where two more levels
   // are due before the tail and the level is launch-bound: at most BCR_PAIR_MAX blocks in play)
-  static const bool pairs = !(getenv("PGF_BCR_PAIRS") && atoi(getenv("PGF_BCR_PAIRS")) == 0);
+  static const bool pairs = env_on("PGF_BCR_PAIRS");
   struct Lev {
     int s, set;     // stride; block set holding the eliminated blocks' L, U, F
     int pair_set2;  // >= 0: first level of a fused pair, second level's blocks are in this set
@@ -847,7 +848,7 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
     const int left = (nb + st - 1) / st;  // blocks still in play before this level
     if (left <= BCR_TAIL_BLOCKS) break;
     const int left2 = (nb + 2 * st - 1) / (2 * st);
-    static const int pair_max = getenv("PGF_BCR_PAIR_MAX") ? atoi(getenv("PGF_BCR_PAIR_MAX")) : BCR_PAIR_MAX;
+    static const int pair_max = env_int("PGF_BCR_PAIR_MAX", BCR_PAIR_MAX);
     if (fused_levels && pairs && left <= pair_max && left2 > BCR_TAIL_BLOCKS && 2 * st < nb) {
       const int nk2 = (nb + 4 * st - 1) / (4 * st);  // kept through both: 0, 4st, ...
       hipLaunchKernelGGL(k_bcr_level2, dim3(nk2), dim3(192), 0, s, Dp(cur), Lp(cur), Up(cur), Fp(cur),
