@@ -480,6 +480,27 @@ int pgf_debug_tail_stats(pgf_handle h, int *fused_steps, int *plain_steps);
  * n_units -- the length of the list (for N <= 256 the panel's tiles alone; no head is fused for
  * such a size).  Any pointer may be NULL. */
 int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head, int *v_units, int *n_units);
+/* The lazy trailing-update plan of the dense LDL^T, walked on the host: no handle,
+ * no GPU.  N x N lower triangle plus rows up to nrows (N or N + 1), a pre-eliminated block of depth
+ * vdepth (a multiple of 32, 0: none).  budget: tile-blocks per launch, 0 = no limit (the eager
+ * plan), with `cap' pending blocks per optional job; budget < 0: the plan production factorises this
+ * size with -- the same selection and caches, PGF_LAZY_BUDGET and PGF_LAZY_CAP ignored, cap ignored.
+ * Stage -1 runs beside the first diagonal chain (virtual blocks only), stage k >= 0 beside the chain
+ * of column block k + 1.
+ *   jobs      PGF_UPDATE_PLAN_JOB_INTS ints per job, at most jobs_cap jobs: stage, col0, ntc,
+ *             rowstart, kc0v, KBv, kc0, KB, first tile number, one past its last -- stage by stage, in
+ *             the order of the stage's job table
+ *   tiles     4 ints per tile, at most tiles_cap tiles: stage, job (index in its stage), i0, j0 --
+ *             every tile number of every stage from 0 until the device's own numbering (one shared
+ *             host / device function) reports the end; NULL or tiles_cap <= 0: not walked
+ *   n_jobs, n_tiles   the numbers there are (whatever the capacities)
+ *   stage_jobs        ceil(N / 256) ints: the jobs of stage -1, 0, 1, ...
+ *   budget_out        the budget of the plan returned (0: no limit)
+ * Any pointer may be NULL. */
+#define PGF_UPDATE_PLAN_JOB_INTS 10
+int pgf_debug_update_plan(int N, int nrows, int vdepth, int budget, int cap, int *jobs, int jobs_cap,
+                          int *n_jobs, int *tiles, int tiles_cap, int *n_tiles, int *stage_jobs,
+                          int *budget_out);
 /* the handle's border size and the factor / solve phases of the bordered route enqueued since
  * pgf_sparse_set_border (tests: a step that keeps its factor runs the solve phase only) */
 int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves);

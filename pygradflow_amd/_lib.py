@@ -113,6 +113,8 @@ SIGNATURES = {
     "pgf_debug_head_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_tail_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_head_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip]),
+    "pgf_debug_update_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip,
+                                        _ip, C.c_int, _ip, _ip, _ip]),
     "pgf_debug_border_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_debug_band_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),

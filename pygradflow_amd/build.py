@@ -21,6 +21,7 @@ SOURCES = [
     ("pgf_border.hip", ["-ffp-contract=off"]),
     ("pgf_ldlt.hip", ["-DPGF_RECIP_ONE_STEP"] if os.environ.get("PGF_BUILD_RECIP1") else []),
     ("pgf_factor2.hip", []),
+    ("pgf_update_plan.hip", []),
     ("pgf_lu.hip", []),
     ("pgf_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api.hip", ["-ffp-contract=off"]),

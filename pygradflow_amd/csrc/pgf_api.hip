@@ -10,6 +10,7 @@
 #include "pgf_api_internal.h"
 #include "pgf_kernels.h"
 #include "pgf_unsym.h"
+#include "pgf_update_plan.h"
 
 // PGF_EVAL_AHEAD=0: g and c at the new point are evaluated at the start of the next step, not
 // ahead of the host synchronisation of this one (newton_core_async, enqueue_qp_step, pgf_batch_step_async)
@@ -1566,6 +1567,47 @@ int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head,
     }
     if (hu.kind < 0) return PGF_INVALID;
   }
+  return PGF_OK;
+}
+
+// The lazy update plan of a dense factorisation, walked on the host (no GPU, no handle): the
+// jobs of every stage, and on request every tile of them as upd_tile -- the mapping the device
+// workers run -- numbers it.
+int pgf_debug_update_plan(int N, int nrows, int vdepth, int budget, int cap, int *jobs, int jobs_cap,
+                          int *n_jobs, int *tiles, int tiles_cap, int *n_tiles, int *stage_jobs,
+                          int *budget_out) {
+  if (N < 1 || nrows < N || nrows > N + 1 || vdepth < 0 || vdepth % 32 || (budget >= 0 && cap < 1))
+    return PGF_INVALID;
+  UpdPlan made;
+  if (budget >= 0) plan_updates(made, N, nrows, LDLT_OB, budget ? budget : UPD_NO_LIMIT, cap, vdepth);
+  const UpdPlan &pl = budget >= 0 ? made : update_plan_for(N, nrows, vdepth, false);
+  if (budget_out) *budget_out = pl.budget == UPD_NO_LIMIT ? 0 : pl.budget;
+  const int nblk = (N + LDLT_OB - 1) / LDLT_OB;
+  int nj = 0, nt = 0;
+  for (int st = -1; st < nblk - 1; ++st) {
+    UpdJobs none;
+    none.njobs = 0;
+    none.tile_begin[0] = 0;
+    const UpdJobs &js = st >= 0 ? pl.launch[st] : (vdepth > 0 ? pl.first : none);
+    if (stage_jobs) stage_jobs[st + 1] = js.njobs;
+    for (int q = 0; q < js.njobs; ++q, ++nj) {
+      if (!jobs || nj >= jobs_cap) continue;
+      const int rec[PGF_UPDATE_PLAN_JOB_INTS] = {st,         js.col0[q], js.ntc[q], js.rowstart[q],     js.kc0v[q],
+                                                 js.KBv[q],  js.kc0[q],  js.KB[q],  js.tile_begin[q],
+                                                 js.tile_begin[q + 1]};
+      std::memcpy(jobs + (size_t)PGF_UPDATE_PLAN_JOB_INTS * nj, rec, sizeof rec);
+    }
+    if (!tiles || tiles_cap <= 0) continue;
+    for (int t = 0;; ++t, ++nt) {  // until the mapping itself says "past the end"
+      int q, i0, j0;
+      if (!upd_tile(js, t, N, nrows, q, i0, j0)) break;
+      if (nt >= tiles_cap) continue;
+      const int rec[4] = {st, q, i0, j0};
+      std::memcpy(tiles + (size_t)4 * nt, rec, sizeof rec);
+    }
+  }
+  if (n_jobs) *n_jobs = nj;
+  if (n_tiles) *n_tiles = nt;
   return PGF_OK;
 }
 
