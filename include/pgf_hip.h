@@ -348,6 +348,11 @@ int pgf_ls_solve(pgf_ls_handle ls, const double *rhs, int trans, double *sol);
 int pgf_ls_num_neg(pgf_ls_handle ls, int *out);
 /* debug / parity: copy the factor (unit-lower L below the diagonal, D on it) to host */
 int pgf_ls_get_factor(pgf_ls_handle ls, double *LD_out, int64_t ld);
+/* debug / parity, LU handles only (PGF_NOT_READY for an LDL^T): perm_out[N] -- row i of P A is
+ * row perm_out[i] of A; the number of 32-column panels the last factorisation took with the rows
+ * in registers (k_lu_panel_reg) / through the streaming kernel (k_lu_panel: panels taller than
+ * 5120 rows, or all of them under PGF_LU_PANEL=1).  Any pointer may be NULL. */
+int pgf_ls_debug_lu(pgf_ls_handle ls, int *perm_out, int *reg_panels, int *streamed_panels);
 int pgf_ls_destroy(pgf_ls_handle ls);
 
 /* ---- kernel micro-benchmark hook (tools/, bench diagnostics) ------------------ */

@@ -94,6 +94,7 @@ SIGNATURES = {
     "pgf_ls_solve": (C.c_int, [_h, _dp, C.c_int, _dp]),
     "pgf_ls_num_neg": (C.c_int, [_h, _ip]),
     "pgf_ls_get_factor": (C.c_int, [_h, _dp, C.c_int64]),
+    "pgf_ls_debug_lu": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_ls_destroy": (C.c_int, [_h]),
     "pgf_bench_update": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "pgf_profile_read_ex": (C.c_int, [_h, _dp, C.c_int]),

@@ -225,6 +225,19 @@ int pgf_ls_num_neg(pgf_ls_handle ls, int *out) {
   return PGF_OK;
 }
 
+int pgf_ls_debug_lu(pgf_ls_handle ls, int *perm_out, int *reg_panels, int *streamed_panels) {
+  if (!ls) return PGF_INVALID;
+  if (ls->symmetric) return PGF_NOT_READY;  // an LDL^T does not pivot
+  if (reg_panels) *reg_panels = ls->lu.reg_panels;
+  if (streamed_panels) *streamed_panels = ls->lu.streamed_panels;
+  if (!perm_out || ls->N == 0) return PGF_OK;
+  (void)hipSetDevice(ls->device);
+  hipError_t e = hipMemcpyAsync(perm_out, ls->lu.perm, (size_t)ls->N * sizeof(int),
+                                hipMemcpyDeviceToHost, ls->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ls->stream);
+  return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+}
+
 int pgf_ls_destroy(pgf_ls_handle ls) {
   if (!ls) return PGF_OK;
   (void)hipSetDevice(ls->device);

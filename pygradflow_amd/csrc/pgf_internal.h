@@ -219,6 +219,7 @@ struct DenseLu {
   int *flags = nullptr;    // [0] zero / non-finite pivot
   hipStream_t stream = nullptr;
   bool factored = false;
+  int reg_panels = 0, streamed_panels = 0;  // of the last factorisation: k_lu_panel_reg / k_lu_panel
 };
 hipError_t lu_alloc(DenseLu &f, int N, hipStream_t stream);
 void lu_free(DenseLu &f);

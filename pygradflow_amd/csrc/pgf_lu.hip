@@ -503,6 +503,7 @@ int lu_factor(DenseLu &f, hipError_t *err) {
   const int N = f.N;
   hipStream_t s = f.stream;
   hipError_t e = hipMemsetAsync(f.flags, 0, 4 * sizeof(int), s);
+  f.reg_panels = f.streamed_panels = 0;
   for (int c0 = 0; c0 < N && e == hipSuccess; c0 += LU_PB) {
     const int pb = std::min(LU_PB, N - c0);
     const int gr = (N - c0 + 255) / 256;
@@ -512,6 +513,7 @@ int lu_factor(DenseLu &f, hipError_t *err) {
     static const bool regs = env_int("PGF_LU_PANEL", 0) != 1;
     const int R = (N - c0 + 1023) / 1024;
     if (regs && R <= 5) {
+      ++f.reg_panels;
       switch (R) {
         case 1: hipLaunchKernelGGL(k_lu_panel_reg<1>, dim3(1), dim3(1024), 0, s, f.PT, f.ldp, N, c0, pb, f.piv, f.flags); break;
         case 2: hipLaunchKernelGGL(k_lu_panel_reg<2>, dim3(1), dim3(1024), 0, s, f.PT, f.ldp, N, c0, pb, f.piv, f.flags); break;
@@ -520,6 +522,7 @@ int lu_factor(DenseLu &f, hipError_t *err) {
         default: hipLaunchKernelGGL(k_lu_panel_reg<5>, dim3(1), dim3(1024), 0, s, f.PT, f.ldp, N, c0, pb, f.piv, f.flags); break;
       }
     } else {
+      ++f.streamed_panels;
       hipLaunchKernelGGL(k_lu_panel, dim3(1), dim3(1024), 0, s, f.PT, f.ldp, N, c0, pb, f.piv, f.flags);
     }
     hipLaunchKernelGGL(k_lu_panel_store, dim3(gr), dim3(256), 0, s, f.A, f.ld, N, c0, pb, f.PT, f.ldp);

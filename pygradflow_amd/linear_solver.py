@@ -62,6 +62,16 @@ class HipLinearSolver:
             _lib.check(self._lib.pgf_ls_get_factor(self._h, _lib.dptr(out), n), None, "pgf_ls_get_factor")
         return np.tril(out) if self.symmetric else out
 
+    def lu_debug(self):
+        """LU only: ``(perm, reg_panels, streamed_panels)`` of the factorisation -- row i of P A is
+        row ``perm[i]`` of A; panels taken with the rows in registers / by the streaming kernel."""
+        perm = np.zeros(self.shape[0], dtype=np.intc)
+        reg, streamed = C.c_int(0), C.c_int(0)
+        rc = self._lib.pgf_ls_debug_lu(self._h, perm.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg),
+                                       C.byref(streamed))
+        _lib.check(rc, None, "pgf_ls_debug_lu")
+        return perm, reg.value, streamed.value
+
     def rcond(self):
         return None
 
