@@ -256,7 +256,20 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * device (each set up through pgf_set_bounds / pgf_qp_set_problem / pgf_qp_set_point);
  * every kernel of the Newton step then runs over all instances at once (instance =
  * blockIdx.z, reduced sizes read on the device: no host round trip inside a step).
- * While a handle belongs to a batch, drive it only through the batch. */
+ * While a handle belongs to a batch, drive it only through the batch.
+ *
+ * A BAND batch: every handle banded (PGF_CREATE_SPARSE) on the narrow route -- half-bandwidth
+ * <= 8, block size 8, no border -- with pattern and values set, the same n, m and device, and ONE
+ * sparsity pattern (the 64-bit hash of what pgf_sparse_set_pattern received, bw, the band's row
+ * stride and the entry counts are compared).  Values of H and J, q, b, bounds, points, dt and rho
+ * are the instance's own.  Every banded kernel of the step then runs over all instances at once
+ * (instance = blockIdx.y), with one host synchronisation per step and one status copy for the
+ * batch; an instance whose solve misses refine_tol is refined on its own handle
+ * (pgf_batch_refinement_stats counts it), and only one that cannot be repaired or met a zero
+ * pivot reports PGF_SINGULAR, its point unchanged.  Refused with PGF_INVALID and a message that
+ * names the reason: dense and banded handles mixed, different patterns, a wide band (block size
+ * above 8), a border, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* and
+ * pgf_batch_debug_fail_next_helper return PGF_INVALID and pgf_batch_debug_factor_kind 0. */
 typedef struct pgf_batch_s *pgf_batch;
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
@@ -513,6 +526,16 @@ int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int
  * (fused or factor-only), solve phases for one right-hand side against kept factors, panel
  * solves.  Any pointer may be NULL. */
 int pgf_debug_band_stats(pgf_handle h, int *reductions, int *solve_phases, int *panel_solves);
+/* A band batch's batched launch sequences enqueued since its creation (tests: the batched route
+ * ran, not a loop over the handles): reductions -- one per step, for all instances; assemblies --
+ * steps that enqueued the band assembly.  Zeros on a dense batch.  Any pointer may be NULL. */
+int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *assemblies);
+/* The 64-bit hash a banded handle keeps of its pattern (host only, no device needed): FNV-1a over
+ * n, m, bw, the entry counts and every index array as pgf_sparse_set_pattern receives them. */
+int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,
+                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
+                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
+                            const int *JTrow, const int *JTmap, uint64_t *hash_out);
 
 #ifdef __cplusplus
 }

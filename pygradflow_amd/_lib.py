@@ -119,6 +119,9 @@ SIGNATURES = {
     "pgf_debug_border_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_debug_band_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
+    "pgf_batch_debug_band_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_sparse_pattern_hash": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
+                                          _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "pgf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "pgf_comm_destroy": (C.c_int, [C.c_void_p]),

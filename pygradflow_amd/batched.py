@@ -57,6 +57,16 @@ def gather_residual_norms(local_norms, num_instances: int, group=None):
     return torch.cat(keep) if keep else out[:0]
 
 
+def batch_kind(shapes):
+    """``"dense"`` or ``"band"`` for the ``(n, m, sparse)`` triples of a device batch's instances.
+    One ``(n, m)`` is needed whatever the kind; whether banded instances fit together (pattern,
+    bandwidth, border) and whether kinds are mixed is the library's to say, with its message."""
+    shapes = list(shapes)
+    if len({(n, m) for n, m, _ in shapes}) != 1:
+        raise ValueError("a device batch needs instances of one (n, m)")
+    return "band" if all(sp for _, _, sp in shapes) else "dense"
+
+
 class BatchedDeviceNewton:
     """This rank's shard of a batch of linear-quadratic instances, all resident in HBM.
 
@@ -67,6 +77,13 @@ class BatchedDeviceNewton:
     norms of the whole batch (one all-gather, nothing else crosses ranks).
     ``sequential=True`` drives the instances one after another through their own handles
     instead (the same kernels without the batch dimension; kept as the cross-check).
+
+    Banded instances (``pgf_force_band``, or ``n + m`` above the dense limit: ``DeviceNewton``
+    decides) form a BAND batch when all of them are banded on the narrow route (half-bandwidth
+    <= 8, no border) with one sparsity pattern; values, vectors, bounds, ``dt`` and ``rho`` are
+    each instance's own.  What the library refuses (dense and banded mixed, different patterns,
+    a wide band, a border) is raised as ``ValueError`` with its message.  ``self.band`` tells
+    which kind the device batch is.
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
@@ -100,12 +117,11 @@ class BatchedDeviceNewton:
         self.device = torch.device("cuda", device)
         self.norms = torch.zeros(max(1, self.count), dtype=torch.float64, device=self.device)
         self._b = None
+        self.band = False
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
         if self.count and not self.sequential:
-            shapes = {(s.n, s.m, s.sparse) for s in self.solvers}
-            if len(shapes) != 1 or next(iter(shapes))[2]:
-                raise ValueError("a device batch needs dense instances of one (n, m)")
+            self.band = batch_kind([(s.n, s.m, s.sparse) for s in self.solvers]) == "band"
             self.n, self.m = self.solvers[0].n, self.solvers[0].m
             lib = _lib.load()
             arr = (C.c_void_p * self.count)(*[s._hd.h for s in self.solvers])
@@ -254,6 +270,8 @@ class BatchedDeviceNewton:
         """Arm the device-resident ``DistanceRatioController`` of every local instance."""
         if self._b is None:
             raise NotImplementedError("device batch only")
+        if self.band:
+            raise NotImplementedError("dense batch only")
         vals = np.array([params.newton_tol, params.lamb_red, params.lamb_min, params.lamb_inc,
                          params.theta_max, params.K_P, params.K_I, params.theta_ref], dtype=np.float64)
         rho = self.rho if rho is None else float(rho)
@@ -290,6 +308,17 @@ class BatchedDeviceNewton:
         if self._b is not None:
             self._lib.check(self._lib.load().pgf_batch_refinement_stats(self._b, C.byref(k)), batch=self._b)
         return k.value
+
+    def band_stats(self):
+        """(reductions, assemblies): batched launch sequences of a band batch enqueued so far
+        (``pgf_batch_debug_band_stats``; zeros on a dense batch).  Device batch only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        C = self._C
+        a, b = C.c_int(0), C.c_int(0)
+        self._lib.check(self._lib.load().pgf_batch_debug_band_stats(self._b, C.byref(a), C.byref(b)),
+                        batch=self._b)
+        return a.value, b.value
 
     def factor_kind(self):
         """Pivot order of the factors the batch's instances hold: 0 none yet, 1 the natural

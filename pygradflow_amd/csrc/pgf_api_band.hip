@@ -101,7 +101,7 @@ int band_status_sync(pgf_handle h) {
 // reduction on the residual each -- and PGF_SINGULAR when the residual stays above refine_fail:
 // the step controller then rejects the step and doubles lambda, which is what makes the
 // matrix quasi-definite again (the reference's own recovery path, step_control.py:80-107).
-static double residual_rel_of(const double *pairs, int nred) {
+double band_residual_rel_of(const double *pairs, int nred) {
   double r = 0.0, b = 0.0;
   for (int i = 0; i < nred; ++i) {
     const double ri = pairs[2 * i];
@@ -111,7 +111,7 @@ static double residual_rel_of(const double *pairs, int nred) {
   }
   return r / (b > 0.0 ? b : 1.0);
 }
-static double sparse_residual_rel(pgf_handle h) { return residual_rel_of(h->sp.h_bred, h->sp.nred); }
+static double sparse_residual_rel(pgf_handle h) { return band_residual_rel_of(h->sp.h_bred, h->sp.nred); }
 
 int band_refine(pgf_handle h, bool swapped, bool with_step) {
   if (!h->refine_mode || !h->sp.guarded) return PGF_OK;
@@ -309,7 +309,7 @@ int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t l
     HIPCHK(h, hipStreamSynchronize(s));
     if (!guard) continue;
     for (int j = 0; j < nc; ++j) {
-      const double rel = residual_rel_of(sp.h_bredm + (size_t)j * pairs, sp.nred);
+      const double rel = band_residual_rel_of(sp.h_bredm + (size_t)j * pairs, sp.nred);
       if (rel > h->refine_tol) {  // this column once more, guarded and refined
         if ((rc = band_linear_solve(h, rhs + (int64_t)(c0 + j) * ld, sol + (int64_t)(c0 + j) * ld))) return rc;
         worst = std::max(worst, h->stat_last_rel);
@@ -424,6 +424,35 @@ void band_free(pgf_handle h) {
 
 extern "C" {
 
+int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,
+                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
+                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
+                            const int *JTrow, const int *JTmap, uint64_t *hash_out) {
+  if (!hash_out || n < 0 || m < 0 || nnzH < 0 || nnzJ < 0 || !pos || !Hptr || !Jptr || !JTptr ||
+      (nnzH && (!Hrow || !Hcol || !Hslot)) || (nnzJ && (!Jcol || !Jslot || !JTrow || !JTmap)))
+    return PGF_INVALID;
+  uint64_t hsh = 1469598103934665603ull;  // FNV-1a, 64 bit
+  auto eat = [&](const int *a, size_t count) {
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(a);
+    for (size_t k = 0; k < count * sizeof(int); ++k) hsh = (hsh ^ p[k]) * 1099511628211ull;
+  };
+  const int head[5] = {n, m, bw, nnzH, nnzJ};
+  eat(head, 5);
+  eat(pos, (size_t)n + m);
+  eat(Hptr, (size_t)n + 1);
+  eat(Hrow, (size_t)nnzH);
+  eat(Hcol, (size_t)nnzH);
+  eat(Hslot, (size_t)nnzH);
+  eat(Jptr, (size_t)m + 1);
+  eat(Jcol, (size_t)nnzJ);
+  eat(Jslot, (size_t)nnzJ);
+  eat(JTptr, (size_t)n + 1);
+  eat(JTrow, (size_t)nnzJ);
+  eat(JTmap, (size_t)nnzJ);
+  *hash_out = hsh;
+  return PGF_OK;
+}
+
 int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const int *Hptr,
                            const int *Hrow, const int *Hcol, const int *Hslot, int nnzJ,
                            const int *Jptr, const int *Jcol, const int *Jslot, const int *JTptr,
@@ -470,6 +499,10 @@ int pgf_sparse_set_pattern(pgf_handle h, int bw, const int *pos, int nnzH, const
   sp_border_free(sp);  // (a border is declared after the pattern: pgf_sparse_set_border)
   if ((rc = sp_alloc_blocks(h, auto_block_size(bw)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  // (what a banded batch compares: its instances share one pattern)
+  if (pgf_sparse_pattern_hash(n, m, bw, pos, nnzH, Hptr, Hrow, Hcol, Hslot, nnzJ, Jptr, Jcol, Jslot, JTptr,
+                              JTrow, JTmap, &sp.pat_hash) != PGF_OK)
+    return fail(h, PGF_INVALID, "null pattern");
   sp.active = true;
   sp.values_set = false;
   invalidate_factor(h);

@@ -1,0 +1,329 @@
+// The banded half of the batch driver: pgf_batch_* for narrow banded handles of one sparsity
+// pattern (pgf_api_batch.hip hands over in one line each; pgf_api_internal.h lists what is shared).
+// One launch sequence per Newton step for every instance -- the batched twins of the banded kernels
+// (pgf_band_batch.hip) around the vector kernels the dense batch already has -- one host
+// synchronisation per step (pgf_batch_sync) and one status copy for the whole batch.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "pgf_api_internal.h"
+#include "pgf_kernels.h"
+
+static const char *const k_zero_pivot = "zero or non-finite pivot in the banded KKT factorisation";
+
+int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
+  const pgf_handle h0 = handles[0];
+  // the reason goes to the offending handle and to the first one, where a caller of
+  // pgf_batch_create looks for it
+  auto fail = [&](pgf_handle h, int code, const char *msg) {
+    h0->err = msg;
+    return ::fail(h, code, msg);
+  };
+  for (int i = 0; i < count; ++i) {
+    const pgf_handle h = handles[i];
+    if (!h) return PGF_INVALID;
+    if (!h->sparse || !h0->sparse)
+      return fail(h, PGF_INVALID, "batch: dense and banded handles cannot share a batch");
+    if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
+      return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
+    if (h->form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
+    const SparseDev &sp = h->sp;
+    if (!sp.active || !sp.values_set)
+      return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
+    if (sp.bk) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
+    if (sp.B != 8)
+      return fail(h, PGF_INVALID, "batch: a wide band (block size above 8) cannot join a device batch");
+    const SparseDev &s0 = h0->sp;
+    if (sp.pat_hash != s0.pat_hash || sp.bw != s0.bw || sp.ldb != s0.ldb || sp.nnzH != s0.nnzH ||
+        sp.nnzJ != s0.nnzJ)
+      return fail(h, PGF_INVALID, "batch: banded instances must share one sparsity pattern");
+    if (!h->qp_mode || !h->bounds_set || !h->point_set)
+      return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_vectors, pgf_qp_set_point first");
+    if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
+  }
+  pgf_batch b = new (std::nothrow) pgf_batch_s();
+  if (!b) return PGF_INVALID;
+  b->band = true;
+  b->hs.assign(handles, handles + count);
+  b->B = count;
+  b->n = h0->n;
+  b->m = h0->m;
+  b->device = h0->device;
+  b->sc.n = b->n;
+  b->sc.m = b->m;
+  b->frozen.assign(count, 0);
+  b->last_neg.assign(count, 0);
+  const int N = b->n + b->m;
+  BandShape &sh = b->bsh;
+  const SparseDev &s0 = h0->sp;
+  sh.n = b->n;
+  sh.m = b->m;
+  sh.N = N;
+  sh.nb = (N + 7) / 8;
+  sh.bw = s0.bw;
+  sh.ldb = s0.ldb;
+  sh.nnzH = s0.nnzH;
+  sh.nnzJ = s0.nnzJ;
+  sh.nred = (N + 255) / 256;
+  sh.bstride = s0.bstride;
+  sh.pos = s0.pos;
+  sh.Hptr = s0.Hptr;
+  sh.Hrow = s0.Hrow;
+  sh.Hcol = s0.Hcol;
+  sh.Hslot = s0.Hslot;
+  sh.Jptr = s0.Jptr;
+  sh.Jcol = s0.Jcol;
+  sh.Jslot = s0.Jslot;
+  sh.JTptr = s0.JTptr;
+  sh.JTrow = s0.JTrow;
+  sh.JTmap = s0.JTmap;
+  const size_t cnt = (size_t)count, S = (size_t)3 * sh.nred + 4;
+  (void)hipSetDevice(b->device);
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipMalloc((void **)&b->tab, cnt * sizeof(BInst))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->btab, cnt * sizeof(BandInst))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->ctl, cnt * 4 * sizeof(int))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->norm_out, cnt * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->red4, cnt * 4 * ((size_t)(N + 255) / 256 + 1) * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->meas_out, cnt * 4 * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->ps, cnt * BPS_STRIDE * sizeof(double))) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_ps, cnt * BPS_STRIDE * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->bytes, cnt)) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_bytes, cnt)) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_meas, cnt * 4 * sizeof(double))) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_flags, cnt * 3 * sizeof(int))) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_norm, cnt * sizeof(double))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->bstat, cnt * S * sizeof(double))) != hipSuccess ||
+      (e = hipHostMalloc((void **)&b->h_bstat, cnt * S * sizeof(double))) != hipSuccess) {
+    pgf_batch_destroy(b);
+    return PGF_HIP_ERROR + (int)e;
+  }
+  std::memset(b->h_flags, 0, cnt * 3 * sizeof(int));
+  std::vector<BInst> tab(count);
+  std::vector<BandInst> btab(count);
+  std::memset(tab.data(), 0, cnt * sizeof(BInst));
+  for (int i = 0; i < count; ++i) {
+    const pgf_handle h = handles[i];
+    (void)hipStreamSynchronize(h->stream);
+    const SparseDev &sp = h->sp;
+    // what the vector kernels shared with the dense batch read (no dense matrix, no factor)
+    BInst &t = tab[i];
+    t.lb = h->lb;
+    t.ub = h->ub;
+    t.q = h->q;
+    t.b = h->b;
+    t.slb = h->slb;
+    t.sub = h->sub;
+    t.xhat = h->xhat;
+    t.yhat = h->yhat;
+    t.x = h->x;
+    t.y = h->y;
+    t.xn = h->xn;
+    t.yn = h->yn;
+    t.g = h->g;
+    t.c = h->c;
+    t.F = h->F;
+    t.b0full = h->b0full;
+    t.rhs = h->rhs;
+    t.sol = h->sol;
+    t.dx = h->dx;
+    t.dy = h->dy;
+    t.w = h->w;
+    t.tmpn = h->tmpn;
+    t.partial = h->partial;
+    t.red = h->red;
+    t.mask = h->mask;
+    t.mask_new = h->mask_new;
+    t.idxI = h->idxI;
+    t.idxA = h->idxA;
+    t.pos = h->pos;
+    t.counts = h->counts;
+    t.ctl = b->ctl + 4 * i;
+    t.ps = b->ps + (size_t)BPS_STRIDE * i;
+    t.flags = h->fac.flags;
+    BandInst &u = btab[i];
+    u.Hval = sp.Hval;
+    u.Jval = sp.Jval;
+    u.band = sp.band;
+    u.brhs = sp.brhs;
+    u.brhs0 = sp.brhs0;
+    u.bres = sp.bres;
+    u.bD = sp.bD;
+    u.bL = sp.bL;
+    u.bU = sp.bU;
+    u.bDinv = sp.bDinv;
+    u.bF = sp.bF;
+    u.bneg = sp.bneg;
+    u.flags = h->fac.flags;
+    u.stat = b->bstat + S * i;
+    u.lb = h->lb;
+    u.ub = h->ub;
+    u.q = h->q;
+    u.b = h->b;
+    u.x = h->x;
+    u.y = h->y;
+    u.xn = h->xn;
+    u.yn = h->yn;
+    u.g = h->g;
+    u.c = h->c;
+    u.w = h->w;
+    u.F = h->F;
+    u.b0full = h->b0full;
+    u.dx = h->dx;
+    u.dy = h->dy;
+    u.tmpn = h->tmpn;
+    u.mask = h->mask;
+    u.ctl = b->ctl + 4 * i;
+    u.ps = b->ps + (size_t)BPS_STRIDE * i;
+    // the batch owns the device-side state of the handle from here on
+    h->mask_set = false;
+    h->eval_fresh = false;
+    h->sp.stat_pending = false;
+    invalidate_factor(h);
+  }
+  std::memset(b->h_ps, 0, cnt * BPS_STRIDE * sizeof(double));
+  if ((e = hipMemcpy(b->tab, tab.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemcpy(b->btab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess ||
+      (e = hipMemset(b->ctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
+      (e = hipMemset(b->bstat, 0, cnt * S * sizeof(double))) != hipSuccess ||
+      (e = hipMemcpy(b->ps, b->h_ps, cnt * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) {
+    pgf_batch_destroy(b);
+    return PGF_HIP_ERROR + (int)e;
+  }
+  *out = b;
+  return PGF_OK;
+}
+
+void band_batch_free(pgf_batch b) {
+  if (b->btab) (void)hipFree(b->btab);
+  if (b->bstat) (void)hipFree(b->bstat);
+  if (b->h_bstat) (void)hipHostFree(b->h_bstat);
+}
+
+// c = A x - b ; w = rho c + y ; g = Q x + (q + A' w) at every instance's point
+void band_batch_eval(pgf_batch b) { bandb_launch_eval(b->stream, b->btab, b->B, b->bsh); }
+
+// c = A x - b and F = Q x + q + A' y for the termination measures (no rho term)
+void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->stream, b->btab, b->B, b->bsh); }
+
+// The step sequence of batch_enqueue_step for banded instances: eval, mask, rhs, assembly where
+// needed, reduction, residual, step update, the evaluation made ahead of the sync, and the copy
+// that brings the batch's status block to the host.
+int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
+  const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
+  const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+  hipStream_t s = b->stream;
+  if (!b->eval_fresh) {
+    band_batch_eval(b);
+    b->eval_fresh = true;
+  }
+  batch_launch_mask(s, b->tab, b->B, b->sc, recompute ? (force ? 2 : 1) : 0, tau);
+  b->have_mask = true;
+  b->stepped = true;
+  batch_launch_residual(s, b->tab, b->B, b->sc);
+  bandb_launch_rhs(s, b->btab, b->B, b->bsh);
+  // instances whose band is still valid return at once (ctl[0] == 0); when the host knows that
+  // none assembles (a Simplified step behind a good one), the launches are skipped
+  if (recompute || !b->all_factored) {
+    bandb_launch_assemble(s, b->btab, b->B, b->bsh);
+    ++b->stat_band_assemblies;
+  }
+  // (the 8 x 8 reduction keeps no factors: every step runs it, on the band as it stands)
+  bandb_launch_solve(s, b->btab, b->B, b->bsh);
+  ++b->stat_band_reductions;
+  bandb_launch_step_update(s, b->btab, b->B, b->bsh);
+  b->eval_fresh = false;
+  // g and c at the new points, ahead of the host synchronisation (as pgf_batch_step_async)
+  if (eval_ahead()) {
+    band_batch_eval(b);
+    b->eval_fresh = true;
+  }
+  BHIPCHK(b, hipMemcpyAsync(b->h_bstat, b->bstat, (size_t)b->B * ((size_t)3 * b->bsh.nred + 4) * sizeof(double),
+                            hipMemcpyDeviceToHost, s));
+  BHIPCHK(b, hipGetLastError());
+  b->step_pending = true;
+  return PGF_OK;
+}
+
+// An instance whose normwise backward error misses refine_tol, on its own handle: the handle's
+// buffers ARE the instance's, the band is intact, the solution is in sp.brhs and its residual in
+// sp.bres.  The step update left the point the step started from in (xn, yn): it goes back, and
+// band_refine corrects the solution and takes the step again from there.  The batch's stream is
+// idle (band_batch_sync).  Returns 0 when the instance's step is good now.
+static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out) {
+  pgf_handle h = b->hs[i];
+  SparseDev &sp = h->sp;
+  hipStream_t s = h->stream;
+  const size_t S = (size_t)3 * sp.nred + 4;
+  launch_copy(s, h->x, h->xn, h->n);
+  launch_copy(s, h->y, h->yn, h->m);
+  std::memcpy(sp.h_bred, st, S * sizeof(double));
+  sp.guarded = true;
+  h->mask_set = true;
+  int rc = band_refine(h, /*swapped=*/false, /*with_step=*/true);
+  h->mask_set = false;
+  if (rc) {
+    (void)hipStreamSynchronize(s);  // (the point the step started from is back in place)
+    return rc;
+  }
+  launch_copy(s, h->x, h->xn, h->n);
+  launch_copy(s, h->y, h->yn, h->m);
+  HIPCHK(h, hipStreamSynchronize(s));
+  *diff_out = h->h_scal[0];
+  return PGF_OK;
+}
+
+int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
+  BHIPCHK(b, hipStreamSynchronize(b->stream));
+  const int nred = b->bsh.nred;
+  const size_t S = (size_t)3 * nred + 4;
+  bool all_ok = true;
+  for (int i = 0; i < b->B; ++i) {
+    pgf_handle h = b->hs[i];
+    if (b->frozen[i]) {  // no step was taken
+      all_ok = false;    // (whether its band is valid is the device's knowledge: ctl[1])
+      if (status) status[i] = PGF_OK;
+      if (n_neg) n_neg[i] = b->last_neg[i];
+      if (diff) diff[i] = 0.0;
+      continue;
+    }
+    const double *st = b->h_bstat + S * i;
+    int rc = PGF_OK;
+    double d = 0.0;
+    if (b->bsh.N > 0) {
+      const int bad = (int)st[3 * nred];
+      b->last_neg[i] = (int)st[3 * nred + 1];
+      if (bad) {
+        rc = fail(h, PGF_SINGULAR, k_zero_pivot);  // (the step update left the point alone)
+      } else {
+        double sum = 0.0;
+        for (int k = 0; k < nred; ++k) sum += st[2 * nred + k];
+        d = std::sqrt(sum);
+        const double rel = band_residual_rel_of(st, nred);
+        h->stat_last_rel = rel;
+        if (h->refine_mode && !(rel <= h->refine_tol)) {
+          rc = band_batch_repair(b, i, st, &d);
+          b->eval_fresh = false;  // the instance moved after the evaluation made ahead
+          if (rc == PGF_OK) ++b->repaired;
+          else if (rc != PGF_SINGULAR) return bfail(b, rc, pgf_last_error(h));
+        }
+      }
+    }
+    if (rc) all_ok = false;
+    if (status) status[i] = rc ? PGF_SINGULAR : PGF_OK;
+    if (n_neg) n_neg[i] = b->last_neg[i];
+    if (diff) diff[i] = rc ? 0.0 : d;
+  }
+  b->all_factored = all_ok;
+  return PGF_OK;
+}
+
+extern "C" int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *assemblies) {
+  if (!b) return PGF_INVALID;
+  if (reductions) *reductions = b->stat_band_reductions;
+  if (assemblies) *assemblies = b->stat_band_assemblies;
+  return PGF_OK;
+}

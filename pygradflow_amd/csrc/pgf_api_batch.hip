@@ -1,6 +1,8 @@
 // The batch driver behind the C ABI: pgf_batch_* (one launch sequence for many dense handles), the
 // device-resident step controller pgf_batch_ctl_* and the RCCL communicator pgf_comm_*.  What it
-// needs of the dense step is listed in pgf_api_internal.h.
+// needs of the dense step is listed in pgf_api_internal.h.  A batch of banded handles (b->band)
+// shares the entry points and the vector kernels; its own half is pgf_api_band_batch.hip, and each
+// entry point that differs hands over in one line.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -12,52 +14,7 @@
 #include "pgf_kernels.h"
 
 // ---------------------------------------------------------------- batched mode
-struct pgf_batch_s {
-  std::vector<pgf_handle> hs;
-  int B = 0, n = 0, m = 0, device = 0;
-  hipStream_t stream = nullptr;
-  BInst *tab = nullptr;
-  int *ctl = nullptr, *flags_out = nullptr, *h_flags = nullptr;
-  double *diff_out = nullptr, *norm_out = nullptr, *h_diff = nullptr, *h_norm = nullptr;
-  double *red4 = nullptr, *meas_out = nullptr, *h_meas = nullptr;
-  double *ps = nullptr, *h_ps = nullptr;      // per-instance [dt, lambda, rho, fact, delta, ...]
-  uint8_t *bytes = nullptr, *h_bytes = nullptr;  // accept / frozen flags on their way to the device
-  BatchScalars sc{};
-  bool outer_set = false, eval_fresh = false, step_pending = false, have_mask = false;
-  bool all_factored = false;
-  // condensed order (constraint block eliminated first, as condensed_wanted for one instance):
-  // cond_ok = the panels exist and the batch runs one of the chain schedules; cond_wanted = the
-  // growth bound holds for every instance's delta (decided per outer step on the host: the
-  // device-resident controller, which moves lambda on the device, keeps the natural order);
-  // cond_last = how the factors the instances hold were made; cond_free = the next step
-  // refactorises every instance anyway and may choose
-  bool cond_ok = false, cond_wanted = false, cond_last = false, cond_free = true;
-  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond_last
-  int cond_mp = 0;
-  int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
-  int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
-  // device-resident step controller (pgf_batch_ctl_*): per-instance state, constants, and a
-  // log of (lambda used, lambda next, accepted) per outer iteration and instance
-  double *dctl_cs = nullptr, *dctl_cp = nullptr, *dctl_log = nullptr;
-  int dctl_log_cap = 0, dctl_logged = 0;
-  PgfProfile prof;
-  std::string err = "";
-};
-
-static int bfail(pgf_batch b, int code, const char *msg) {
-  if (b) b->err = msg;
-  return code;
-}
-
-#define BHIPCHK(b, expr)                                                 \
-  do {                                                                   \
-    hipError_t e_ = (expr);                                              \
-    if (e_ != hipSuccess) {                                              \
-      (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);      \
-      return PGF_HIP_ERROR + (int)e_;                                    \
-    }                                                                    \
-  } while (0)
-
+// (pgf_batch_s, bfail, BHIPCHK: pgf_api_internal.h -- shared with the banded half, pgf_api_band_batch.hip)
 const char *pgf_batch_last_error(pgf_batch b) { return b ? b->err.c_str() : k_no_handle; }
 
 // ||H||_inf, ||J||_1, ||J||_inf of every instance into the host copy of ps (residual_norms: one
@@ -79,6 +36,8 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
   const pgf_handle h0 = handles[0];
   if (!h0) return PGF_INVALID;
+  for (int i = 0; i < count; ++i)  // any banded handle: a band batch, or its refusal
+    if (handles[i] && handles[i]->sparse) return band_batch_create(handles, count, out);
   for (int i = 0; i < count; ++i) {
     const pgf_handle h = handles[i];
     if (!h) return PGF_INVALID;
@@ -228,6 +187,7 @@ int pgf_batch_destroy(pgf_batch b) {
   if (!b) return PGF_OK;
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
+  band_batch_free(b);
   for (void *p : {(void *)b->tab, (void *)b->ctl, (void *)b->flags_out, (void *)b->diff_out,
                   (void *)b->norm_out, (void *)b->red4, (void *)b->meas_out, (void *)b->ps,
                   (void *)b->bytes, (void *)b->dctl_cs, (void *)b->dctl_cp, (void *)b->dctl_log})
@@ -306,7 +266,10 @@ int pgf_batch_advance_outer_each(pgf_batch b, const double *dt, const double *rh
     b->cond_wanted = all;
   }
   b->cond_free = true;  // every instance refactorises in the next step (new lambda)
-  if (int rc = batch_store_norms(b)) return bfail(b, rc, "matrix norms of an instance");
+  // (a band batch guards with the full residual of every instance: no norm bound needed)
+  if (!b->band)
+    if (int rc = batch_store_norms(b)) return bfail(b, rc, "matrix norms of an instance");
+  b->frozen.assign(b->B, 0);  // kb_advance clears ctl[3]
   BHIPCHK(b, hipMemcpyAsync(b->ps, b->h_ps, (size_t)b->B * BPS_STRIDE * sizeof(double),
                             hipMemcpyHostToDevice, b->stream));
   BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
@@ -334,6 +297,7 @@ int pgf_batch_set_frozen(pgf_batch b, const uint8_t *frozen) {
   (void)hipSetDevice(b->device);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
   for (int i = 0; i < b->B; ++i) b->h_bytes[i] = (frozen && frozen[i]) ? 1 : 0;
+  b->frozen.assign(b->h_bytes, b->h_bytes + b->B);
   BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
   batch_launch_set_frozen(b->stream, b->tab, b->B, b->bytes);
   BHIPCHK(b, hipGetLastError());
@@ -342,7 +306,10 @@ int pgf_batch_set_frozen(pgf_batch b, const uint8_t *frozen) {
 
 static void batch_eval(pgf_batch b) {
   if (b->eval_fresh) return;
-  batch_launch_eval(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS);
+  if (b->band)
+    band_batch_eval(b);
+  else
+    batch_launch_eval(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS);
   b->eval_fresh = true;
 }
 
@@ -396,6 +363,7 @@ static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool ho
 
 int pgf_batch_debug_fail_next_helper(pgf_batch b) {
   if (!b) return PGF_INVALID;
+  if (b->band) return bfail(b, PGF_INVALID, "band batch: no chain helpers");
   b->inject_helper_failure = 1;
   return PGF_OK;
 }
@@ -411,6 +379,7 @@ int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
     return bfail(b, PGF_NOT_READY, "no active set: pgf_batch_update_active_set first");
   if (!recompute && force)
     return bfail(b, PGF_INVALID, "batch: PGF_STEP_REFACTOR needs PGF_STEP_RECOMPUTE_MASK");
+  if (b->band) return band_batch_step_async(b, policy, tau);
   batch_enqueue_step(b, policy, tau, b->all_factored);
   // g and c at the new points, enqueued ahead of the host synchronisation (as pgf_qp_step_async):
   // behind it the five small launches would wait for the host one by one
@@ -424,9 +393,13 @@ int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 }
 
 // ---- device-resident DistanceRatioController ------------------------------
+static const char *const k_band_ctl =
+    "band batch: the device-resident controller is for dense batches (drive dt per instance with "
+    "pgf_batch_advance_outer_each)";
 int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *params,
                        int max_iterations) {
   if (!b || !params || !(lamb_init > 0.0) || !(rho > 0.0) || max_iterations < 1) return PGF_INVALID;
+  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
   (void)hipSetDevice(b->device);
   const size_t ncs = (size_t)b->B * DCS_STRIDE;
@@ -464,6 +437,7 @@ int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *
 
 int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iterations) {
   if (!b || iterations < 0) return PGF_INVALID;
+  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
   if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
   if (b->dctl_logged + iterations > b->dctl_log_cap)
@@ -503,6 +477,7 @@ int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iteratio
 
 int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log3, int log_rows) {
   if (!b) return PGF_INVALID;
+  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
   if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
   (void)hipSetDevice(b->device);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -597,6 +572,7 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
   if (!b->step_pending) return bfail(b, PGF_NOT_READY, "no step pending");
   b->step_pending = false;
   (void)hipSetDevice(b->device);
+  if (b->band) return band_batch_sync(b, status, n_neg, diff);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
   bool all_ok = true, any_repaired = false;
   for (int i = 0; i < b->B; ++i) {
@@ -733,7 +709,7 @@ int pgf_batch_refinement_stats(pgf_batch b, int *repaired) {
 }
 
 int pgf_batch_debug_factor_kind(pgf_batch b) {
-  if (!b || !b->stepped) return 0;
+  if (!b || !b->stepped || b->band) return 0;
   return b->cond_last ? 2 : 1;
 }
 
@@ -800,8 +776,13 @@ int pgf_batch_measures(pgf_batch b, double active_tol, double *out) {
   (void)hipSetDevice(b->device);
   if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
   batch_eval(b);
-  batch_launch_measures(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS, active_tol, b->red4,
-                        b->meas_out);
+  if (b->band) {
+    band_batch_measures_eval(b);
+    batch_launch_measures_final(b->stream, b->tab, b->B, b->sc, active_tol, b->red4, b->meas_out);
+  } else {
+    batch_launch_measures(b->stream, b->tab, b->B, b->sc, PGF_GEMVT_PARTS, active_tol, b->red4,
+                          b->meas_out);
+  }
   b->eval_fresh = false;  // tmpn / w were reused
   BHIPCHK(b, hipMemcpyAsync(b->h_meas, b->meas_out, (size_t)b->B * 4 * sizeof(double),
                             hipMemcpyDeviceToHost, b->stream));

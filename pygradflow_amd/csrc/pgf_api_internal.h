@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "../../include/pgf_hip.h"
 #include "pgf_internal.h"
@@ -264,3 +265,75 @@ struct StepCondY;
 void enqueue_residual(pgf_handle h, bool may_skip = false);
 int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true);
 void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr);
+
+// ---- the batch (pgf_api_batch.hip: the dense half and the dispatch; pgf_api_band_batch.hip: the
+// banded half) ----------------------------------------------------------------------------------
+struct pgf_batch_s {
+  std::vector<pgf_handle> hs;
+  int B = 0, n = 0, m = 0, device = 0;
+  hipStream_t stream = nullptr;
+  BInst *tab = nullptr;
+  int *ctl = nullptr, *flags_out = nullptr, *h_flags = nullptr;
+  double *diff_out = nullptr, *norm_out = nullptr, *h_diff = nullptr, *h_norm = nullptr;
+  double *red4 = nullptr, *meas_out = nullptr, *h_meas = nullptr;
+  double *ps = nullptr, *h_ps = nullptr;      // per-instance [dt, lambda, rho, fact, delta, ...]
+  uint8_t *bytes = nullptr, *h_bytes = nullptr;  // accept / frozen flags on their way to the device
+  BatchScalars sc{};
+  bool outer_set = false, eval_fresh = false, step_pending = false, have_mask = false;
+  bool all_factored = false;
+  // condensed order (constraint block eliminated first, as condensed_wanted for one instance):
+  // cond_ok = the panels exist and the batch runs one of the chain schedules; cond_wanted = the
+  // growth bound holds for every instance's delta (decided per outer step on the host: the
+  // device-resident controller, which moves lambda on the device, keeps the natural order);
+  // cond_last = how the factors the instances hold were made; cond_free = the next step
+  // refactorises every instance anyway and may choose
+  bool cond_ok = false, cond_wanted = false, cond_last = false, cond_free = true;
+  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond_last
+  int cond_mp = 0;
+  int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
+  int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
+  // device-resident step controller (pgf_batch_ctl_*): per-instance state, constants, and a
+  // log of (lambda used, lambda next, accepted) per outer iteration and instance
+  double *dctl_cs = nullptr, *dctl_cp = nullptr, *dctl_log = nullptr;
+  int dctl_log_cap = 0, dctl_logged = 0;
+  // A banded batch (pgf_api_band_batch.hip): narrow banded handles of one pattern.  btab: the
+  // instances' BandInst records beside the BInst ones in tab; bsh: what they share; bstat / h_bstat:
+  // ONE status block for the whole batch, 3 nred + 4 doubles per instance (residual pairs, partial
+  // sums of the step update, pivot flags) and its pinned mirror, read with one copy per step;
+  // frozen / last_neg: the host's view of pgf_batch_set_frozen and of the inertia last reported.
+  bool band = false;
+  BandInst *btab = nullptr;
+  BandShape bsh{};
+  double *bstat = nullptr, *h_bstat = nullptr;
+  std::vector<uint8_t> frozen;
+  std::vector<int> last_neg;
+  int stat_band_reductions = 0, stat_band_assemblies = 0;  // pgf_batch_debug_band_stats
+  PgfProfile prof;
+  std::string err = "";
+};
+
+static inline int bfail(pgf_batch b, int code, const char *msg) {
+  if (b) b->err = msg;
+  return code;
+}
+
+#define BHIPCHK(b, expr)                                                 \
+  do {                                                                   \
+    hipError_t e_ = (expr);                                              \
+    if (e_ != hipSuccess) {                                              \
+      (b)->err = std::string(#expr) + ": " + hipGetErrorString(e_);      \
+      return PGF_HIP_ERROR + (int)e_;                                    \
+    }                                                                    \
+  } while (0)
+
+
+// The banded half, each beside the entry point that hands over to it in one line.
+int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out);  // pgf_batch_create
+void band_batch_free(pgf_batch b);                                            // pgf_batch_destroy
+void band_batch_eval(pgf_batch b);                                            // batch_eval
+int band_batch_step_async(pgf_batch b, unsigned policy, double tau);          // pgf_batch_step_async
+int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff);      // pgf_batch_sync
+void band_batch_measures_eval(pgf_batch b);                                   // pgf_batch_measures
+// what it takes from pgf_api_band.hip: the guard's measure over nred residual pairs, and the hash
+// of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat_hash)
+double band_residual_rel_of(const double *pairs, int nred);

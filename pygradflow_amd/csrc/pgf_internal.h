@@ -277,6 +277,48 @@ struct BatchScalars {
 #define BPS_NORM_JINF 7
 #define BPS_STRIDE 8
 
+// ---- banded batch (pgf_band_batch.hip) ---------------------------------------
+// One entry per instance of a batch of narrow banded handles (block size 8, no border, ONE sparsity
+// pattern): what differs between the instances -- the values of H and J, the band, the work blocks
+// of the cyclic reduction, the vectors, the flags.  The batched twins of the banded kernels pick
+// their instance with blockIdx.y; the pattern arrays, equal by construction, come from instance 0
+// (BandShape) so that every workgroup hits the same lines.  The vector kernels shared with the
+// dense batch (kb_advance, kb_mask_adopt, kb_residual, ...) read the same instance from the BInst
+// table beside it.  ctl, ps: as in BInst (ctl[0]: assemble the band this step).
+struct BandInst {
+  const double *Hval, *Jval;
+  double *band, *brhs, *brhs0, *bres;
+  double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev)
+  int *bneg, *flags;
+  // the instance's slice of the batch's status block: [0, 2 nred) residual pairs, [2 nred, 3 nred)
+  // partial sums of the step update, [3 nred, 3 nred + 4) pivot flags (as SparseDev::bred)
+  double *stat;
+  const double *lb, *ub, *q, *b;
+  double *x, *y, *xn, *yn, *g, *c, *w, *F, *b0full, *dx, *dy, *tmpn;
+  const uint8_t *mask;
+  int *ctl;
+  const double *ps;
+};
+struct BandShape {
+  int n, m, N, nb, bw, ldb, nnzH, nnzJ, nred;
+  int64_t bstride;
+  const int *pos, *Hptr, *Hrow, *Hcol, *Hslot, *Jptr, *Jcol, *Jslot, *JTptr, *JTrow, *JTmap;
+};
+// c, w, g at every instance's point
+void bandb_launch_eval(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// permuted right-hand side from F, b0full (kb_residual before it)
+void bandb_launch_rhs(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// band of the instances with ctl[0] != 0: zero, diagonal, entries of H and J
+void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// cyclic reduction of every instance that is not frozen (one launch plan: it depends on N only),
+// then the residual of the solution into the status block
+void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// (xn, yn), dx, dy and the partial sums; the new point replaces the old one, which stays in
+// (xn, yn), unless the instance met a bad pivot
+void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// c = J x - b and F[0:n] = H x + q + J' y for the termination measures
+void bandb_launch_measures_eval(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+
 // device-resident step controller: per-instance state (cs) and constants (cp)
 #define DCS_LAMB 0      // lambda of the next outer iteration
 #define DCS_INTEGRAL 1  // integral of the PI law (log scale)
@@ -318,6 +360,7 @@ void batch_launch_rhs_assemble(hipStream_t s, const BInst *tab, int B, const Bat
                                int cond_mp = 0);
 // condensed order: zwork <- b_x + V b_y / delta before a forward solve (instances that reuse their
 // factor), sol_y <- (V^T sol_x - b_y) / delta after the backward solve (all instances)
+void batch_launch_residual(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc);
 void batch_launch_cond_prep_fwd(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc);
 void batch_launch_cond_y(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc);
 // flags_out: [3 i] zero-pivot flag, [3 i + 1] negative pivots, [3 i + 2] |I| of instance i
@@ -327,6 +370,8 @@ void batch_launch_res_norm(hipStream_t s, const BInst *tab, int B, const BatchSc
                            double *norm_out);
 void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
                            int nparts, double active_tol, double *red4, double *out);
+void batch_launch_measures_final(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
+                                 double active_tol, double *red4, double *out);
 // pgf_ldlt.hip
 // batched wrappers of the look-ahead schedule's chain and T(k) kernels (pgf_factor2.hip)
 // helpers: 3 B workgroups of 1024 threads must be resident together (small batches only)

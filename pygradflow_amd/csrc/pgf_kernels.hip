@@ -1906,10 +1906,16 @@ __global__ __launch_bounds__(1024) void kb_cond_y(const BInst *__restrict__ tab,
   }
 }
 
+// F and b0full of every instance that is not frozen (the banded batch assembles its own system)
+void batch_launch_residual(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc) {
+  const int Nmax = sc.n + sc.m;
+  if (Nmax) hipLaunchKernelGGL(kb_residual, gb(Nmax, 256, B), dim3(256), 0, s, tab, sc.n, sc.m);
+}
+
 void batch_launch_rhs_assemble(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc, int cond_mp) {
   const int n = sc.n, m = sc.m, Nmax = n + m;
   if (!Nmax) return;
-  hipLaunchKernelGGL(kb_residual, gb(Nmax, 256, B), dim3(256), 0, s, tab, n, m);
+  batch_launch_residual(s, tab, B, sc);
   // (the scratch `partial' holds 32 n doubles per instance: PGF_GEMVT_PARTS in pgf_api_internal.h)
   if (n) hipLaunchKernelGGL(kb_active_rows_partial, dim3((n + 255) / 256, 32, B), dim3(256), 0, s, tab, n, 32);
   hipLaunchKernelGGL(kb_reduced_rhs, gb(Nmax, 4, B), dim3(256), 0, s, tab, n, m, 32);
@@ -1977,7 +1983,6 @@ __global__ __launch_bounds__(256) void kb_measures_final(const double *__restric
 void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
                            int nparts, double active_tol, double *red4, double *out) {
   const int n = sc.n, m = sc.m;
-  const int nb = (n + m + 255) / 256;
   if (n) {
     int used = 0;
     if (m) {
@@ -1990,6 +1995,14 @@ void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchSc
     hipLaunchKernelGGL(kb_sum_partials, gb(n, 256, B), dim3(256), 0, s, tab, n, used);
     hipLaunchKernelGGL(kb_gemv_stat, gb(n, 4, B), dim3(256), 0, s, tab, n);
   }
+  batch_launch_measures_final(s, tab, B, sc, active_tol, red4, out);
+}
+
+// the four measures of every instance from x, y, c and the stationarity residual in F[0:n]
+void batch_launch_measures_final(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
+                                 double active_tol, double *red4, double *out) {
+  const int n = sc.n, m = sc.m;
+  const int nb = (n + m + 255) / 256;
   if (nb)
     hipLaunchKernelGGL(kb_measures, dim3(nb, 1, B), dim3(256), 0, s, tab, n, m, active_tol, red4,
                        nb);

@@ -48,6 +48,7 @@ struct SparseDev {
   // that does two cyclic-reduction levels at once reads one set and writes the other
   int64_t bstride = 0;
   bool values_set = false;
+  uint64_t pat_hash = 0;  // of what pgf_sparse_set_pattern received (pgf_sparse_pattern_hash)
   // Bordered band (pgf_border.hip): the last bk positions of `pos` are border nodes, the band
   // holds the Nb = n + m - bk others.  K = [[B, C], [C', D]]: C (Nb x bkp, row-major) and the lower
   // triangle of D (bkp x bkp; bkp = bk rounded up to 16, padding = identity) lie behind the band
@@ -80,6 +81,27 @@ void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8
 void sp_launch_permute(hipStream_t s, const SparseDev &sp, int N, const double *in, double *out,
                        int gather);
 void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard = true);
+// The launch plan of the 8 x 8 reduction for nb blocks: the levels before the LDS tail in launch
+// order (s: stride; set: the block set holding the level's eliminated blocks' L, U, F; pair_set2 >=
+// 0: first level of a fused pair whose second level's blocks are in that set), the stride and set
+// the tail starts with, and whether a single level is one launch (fused) or invert + reduce.  It
+// depends on nb only: sp_launch_bcr_solve and the batched driver (pgf_band_batch.hip) walk the same.
+struct BcrPlan {
+  struct Lev {
+    int s, set, pair_set2;
+  };
+  Lev lev[40];
+  int nlev = 0;
+  int tail_s = 1, tail_set = 0;
+  bool fused = true;
+};
+BcrPlan sp_bcr_plan(int nb);
+// workgroups of a level with stride s over nb blocks
+static inline int bcr_kept(int nb, int s) { return (nb + 2 * s - 1) / (2 * s); }            // 0, 2s, ...
+static inline int bcr_eliminated(int nb, int s) { return (nb - s + 2 * s - 1) / (2 * s); }  // s, 3s, ...
+static inline int bcr_pair_groups(int nb, int s) { return (nb + 4 * s - 1) / (4 * s); }     // kept through both: 0, 4s, ...
+// j = 2 s + 4 s q with j - s < nb
+static inline int bcr_back_pair_groups(int nb, int s) { return (nb + s - 2 * s + 4 * s - 1) / (4 * s); }
 void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags);
 // B = 16, 32, 64 (pgf_band_wide.hip): the same contract as sp_launch_bcr_solve /
 // sp_launch_band_residual for half-bandwidths up to 64

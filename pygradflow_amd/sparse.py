@@ -232,6 +232,19 @@ class BandPlan:
         out.data = np.asarray(full.data, dtype=np.float64)
         return out
 
+    def pattern_hash(self, lib=None):
+        """The 64-bit hash a handle keeps of this plan's pattern (``pgf_sparse_pattern_hash``, host
+        only): the instances of a banded device batch must agree in it."""
+        lib = _lib.load() if lib is None else lib
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
+        out = C.c_uint64(0)
+        rc = lib.pgf_sparse_pattern_hash(
+            self.n, self.m, self.bw, ip(self.pos), self.nnzH, ip(self.Hptr), ip(self.Hrow), ip(self.Hcol),
+            ip(self.Hslot), self.nnzJ, ip(self.Jptr), ip(self.Jcol), ip(self.Jslot), ip(self.JTptr),
+            ip(self.JTrow), ip(self.JTmap), C.byref(out))
+        _lib.check(rc, None, "pgf_sparse_pattern_hash")
+        return out.value
+
     def upload(self, lib, handle):
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int))  # noqa: E731
         rc = lib.pgf_sparse_set_pattern(
