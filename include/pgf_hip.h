@@ -269,9 +269,23 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * pivot reports PGF_SINGULAR, its point unchanged.  Refused with PGF_INVALID and a message that
  * names the reason: dense and banded handles mixed, different patterns, a wide band (block size
  * above 8), a border, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* and
- * pgf_batch_debug_fail_next_helper return PGF_INVALID and pgf_batch_debug_factor_kind 0. */
+ * pgf_batch_debug_fail_next_helper return PGF_INVALID and pgf_batch_debug_factor_kind 0.
+ *
+ * pgf_batch_create_ex takes flags; pgf_batch_create is pgf_batch_create_ex with flags 0, and unknown
+ * flag bits are PGF_INVALID.  PGF_BATCH_WIDE_BAND also admits a band batch on the WIDE route:
+ * every handle with block size 16, 32 or 64 (half-bandwidths up to 64), under the conditions above
+ * and, in addition, ONE block size and ONE setting of the factor / solve split
+ * (pgf_sparse_set_factor_split) -- refused otherwise with "batch: banded instances must share the
+ * block size and the factor / solve split".  With the split on, each instance decides on the device
+ * whether its step reduces (its matrix changed, or its last reduction met a bad pivot) or runs the
+ * solve phase against the factors it kept, inside the one launch sequence of the batch; an
+ * instance above refine_tol is refined on its handle by solve phases against those factors.  The
+ * results are, bit for bit, those of the single handles.  Narrow and dense batches behave with the
+ * flag as without it. */
 typedef struct pgf_batch_s *pgf_batch;
+#define PGF_BATCH_WIDE_BAND 1u
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
+int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
 const char *pgf_batch_last_error(pgf_batch b);
 /* pgf_qp_advance_outer for every instance: (x^, y^) <- (x, y), new dt and rho */
@@ -530,6 +544,10 @@ int pgf_debug_band_stats(pgf_handle h, int *reductions, int *solve_phases, int *
  * ran, not a loop over the handles): reductions -- one per step, for all instances; assemblies --
  * steps that enqueued the band assembly.  Zeros on a dense batch.  Any pointer may be NULL. */
 int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *assemblies);
+/* per instance: wide reductions and solve phases the instance's workgroups ran since the batch was
+ * created (arrays of `count` ints, synchronises); *lean_steps: steps enqueued without inversion
+ * launches.  Zeros on a dense or narrow batch.  Any pointer may be NULL. */
+int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_phases, int *lean_steps);
 /* The 64-bit hash a banded handle keeps of its pattern (host only, no device needed): FNV-1a over
  * n, m, bw, the entry counts and every index array as pgf_sparse_set_pattern receives them. */
 int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,

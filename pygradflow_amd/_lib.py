@@ -24,6 +24,7 @@ PGF_OK, PGF_SINGULAR, PGF_INERTIA, PGF_INVALID, PGF_NOT_READY, PGF_HIP_ERROR = 0
 PGF_HOST, PGF_DEVICE = 0, 1
 STEP_RECOMPUTE_MASK, STEP_REFACTOR, STEP_REFACTOR_ON_CHANGE = 1, 2, 4
 CREATE_SPARSE = 1
+BATCH_WIDE_BAND = 1
 FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
 FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 
@@ -75,6 +76,7 @@ SIGNATURES = {
     "pgf_profile_enable": (C.c_int, [_h, C.c_int]),
     "pgf_profile_read": (C.c_int, [_h, _dp, C.POINTER(C.c_int64), _dp, _dp]),
     "pgf_batch_create": (C.c_int, [C.POINTER(_h), C.c_int, C.POINTER(_h)]),
+    "pgf_batch_create_ex": (C.c_int, [C.POINTER(_h), C.c_int, C.c_uint, C.POINTER(_h)]),
     "pgf_batch_destroy": (C.c_int, [_h]),
     "pgf_batch_last_error": (C.c_char_p, [_h]),
     "pgf_batch_advance_outer": (C.c_int, [_h, C.c_double, C.c_double]),
@@ -120,6 +122,7 @@ SIGNATURES = {
     "pgf_debug_band_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
     "pgf_batch_debug_band_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_batch_debug_band_wide_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_sparse_pattern_hash": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                           _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),

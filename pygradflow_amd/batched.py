@@ -81,13 +81,16 @@ class BatchedDeviceNewton:
     Banded instances (``pgf_force_band``, or ``n + m`` above the dense limit: ``DeviceNewton``
     decides) form a BAND batch when all of them are banded on the narrow route (half-bandwidth
     <= 8, no border) with one sparsity pattern; values, vectors, bounds, ``dt`` and ``rho`` are
-    each instance's own.  What the library refuses (dense and banded mixed, different patterns,
-    a wide band, a border) is raised as ``ValueError`` with its message.  ``self.band`` tells
-    which kind the device batch is.
+    each instance's own.  ``wide_band=True`` creates the batch through ``pgf_batch_create_ex`` with
+    ``PGF_BATCH_WIDE_BAND``: instances on the wide route (block size 16, 32 or 64) are admitted
+    too, when they share the block size and the setting of the factor / solve split.  What the
+    library refuses (dense and banded mixed, different patterns, a wide band without the flag, a
+    border) is raised as ``ValueError`` with its message.  ``self.band`` tells which kind the
+    device batch is, ``self.band_block`` the block size of a band batch (``None`` otherwise).
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
-                 world=1, group=None, tau=None, sequential=False):
+                 world=1, group=None, tau=None, sequential=False, wide_band=False):
         import ctypes as C
         import math
 
@@ -118,6 +121,8 @@ class BatchedDeviceNewton:
         self.norms = torch.zeros(max(1, self.count), dtype=torch.float64, device=self.device)
         self._b = None
         self.band = False
+        self.band_block = None
+        self.wide_band = bool(wide_band)
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
         if self.count and not self.sequential:
@@ -126,10 +131,19 @@ class BatchedDeviceNewton:
             lib = _lib.load()
             arr = (C.c_void_p * self.count)(*[s._hd.h for s in self.solvers])
             b = C.c_void_p()
-            rc = lib.pgf_batch_create(arr, self.count, C.byref(b))
+            rc = self._create(lib, arr, C.byref(b))
             _lib.check(rc, self.solvers[0]._hd.h, "pgf_batch_create")
             self._b = b
+            if self.band:
+                self.band_block = int(self.solvers[0]._hd.plan.block_size)
             self._begin_outer()
+
+    def _create(self, lib, handles, out):
+        """The device batch over ``handles``: through ``pgf_batch_create_ex`` with
+        ``PGF_BATCH_WIDE_BAND`` when ``wide_band`` was asked for, ``pgf_batch_create`` otherwise."""
+        if self.wide_band:
+            return lib.pgf_batch_create_ex(handles, self.count, self._lib.BATCH_WIDE_BAND, out)
+        return lib.pgf_batch_create(handles, self.count, out)
 
     def _begin_outer(self):
         lib, b = self._lib.load(), self._b
@@ -319,6 +333,22 @@ class BatchedDeviceNewton:
         self._lib.check(self._lib.load().pgf_batch_debug_band_stats(self._b, C.byref(a), C.byref(b)),
                         batch=self._b)
         return a.value, b.value
+
+    def band_wide_stats(self):
+        """(reductions[count], solve_phases[count], lean_steps) of a wide band batch
+        (``pgf_batch_debug_band_wide_stats``): per instance the wide reductions and the solve
+        phases against kept factors its workgroups ran since the batch was created, and the steps
+        enqueued without inversion launches.  Zeros on a dense or narrow batch.  Device batch only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        C = self._C
+        red = np.zeros(self.count, dtype=np.int32)
+        sol = np.zeros(self.count, dtype=np.int32)
+        lean = C.c_int(0)
+        ip = C.POINTER(C.c_int)
+        self._lib.check(self._lib.load().pgf_batch_debug_band_wide_stats(
+            self._b, red.ctypes.data_as(ip), sol.ctypes.data_as(ip), C.byref(lean)), batch=self._b)
+        return red, sol, lean.value
 
     def factor_kind(self):
         """Pivot order of the factors the batch's instances hold: 0 none yet, 1 the natural

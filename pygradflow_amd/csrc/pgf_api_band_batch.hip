@@ -1,8 +1,9 @@
-// The banded half of the batch driver: pgf_batch_* for narrow banded handles of one sparsity
-// pattern (pgf_api_batch.hip hands over in one line each; pgf_api_internal.h lists what is shared).
-// One launch sequence per Newton step for every instance -- the batched twins of the banded kernels
-// (pgf_band_batch.hip) around the vector kernels the dense batch already has -- one host
-// synchronisation per step (pgf_batch_sync) and one status copy for the whole batch.
+// The banded half of the batch driver: pgf_batch_* for banded handles of one sparsity pattern, all
+// on the narrow route or (PGF_BATCH_WIDE_BAND) all on the wide one (pgf_api_batch.hip hands over in
+// one line each; pgf_api_internal.h lists what is shared).  One launch sequence per Newton step for
+// every instance -- the batched twins of the banded kernels (pgf_band_batch.hip, and
+// pgf_band_wide_batch.hip for the wide reduction) around the vector kernels the dense batch already
+// has -- one host synchronisation per step (pgf_batch_sync) and one status copy for the whole batch.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,7 +14,8 @@
 
 static const char *const k_zero_pivot = "zero or non-finite pivot in the banded KKT factorisation";
 
-int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
+int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
+  const bool wide_ok = (flags & PGF_BATCH_WIDE_BAND) != 0;
   const pgf_handle h0 = handles[0];
   // the reason goes to the offending handle and to the first one, where a caller of
   // pgf_batch_create looks for it
@@ -33,12 +35,16 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     if (!sp.active || !sp.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
     if (sp.bk) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
-    if (sp.B != 8)
+    if (sp.B != 8 && !wide_ok)
       return fail(h, PGF_INVALID, "batch: a wide band (block size above 8) cannot join a device batch");
     const SparseDev &s0 = h0->sp;
     if (sp.pat_hash != s0.pat_hash || sp.bw != s0.bw || sp.ldb != s0.ldb || sp.nnzH != s0.nnzH ||
         sp.nnzJ != s0.nnzJ)
       return fail(h, PGF_INVALID, "batch: banded instances must share one sparsity pattern");
+    // (the split matters on the wide route only, and is in force only where the multipliers are
+    // allocated: sp_cyclic_solve)
+    if (sp.B != s0.B || (sp.B > 8 && (sp.split != s0.split || (sp.bMr != nullptr) != (s0.bMr != nullptr))))
+      return fail(h, PGF_INVALID, "batch: banded instances must share the block size and the factor / solve split");
     if (!h->qp_mode || !h->bounds_set || !h->point_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_vectors, pgf_qp_set_point first");
     if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
@@ -61,7 +67,9 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
   sh.n = b->n;
   sh.m = b->m;
   sh.N = N;
-  sh.nb = (N + 7) / 8;
+  sh.B = s0.B;
+  sh.split = (s0.B > 8 && s0.split && s0.bMr) ? 1 : 0;
+  sh.nb = (N + sh.B - 1) / sh.B;
   sh.bw = s0.bw;
   sh.ldb = s0.ldb;
   sh.nnzH = s0.nnzH;
@@ -86,6 +94,7 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
       (e = hipMalloc((void **)&b->tab, cnt * sizeof(BInst))) != hipSuccess ||
       (e = hipMalloc((void **)&b->btab, cnt * sizeof(BandInst))) != hipSuccess ||
       (e = hipMalloc((void **)&b->ctl, cnt * 4 * sizeof(int))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->wcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
       (e = hipMalloc((void **)&b->norm_out, cnt * sizeof(double))) != hipSuccess ||
       (e = hipMalloc((void **)&b->red4, cnt * 4 * ((size_t)(N + 255) / 256 + 1) * sizeof(double))) != hipSuccess ||
       (e = hipMalloc((void **)&b->meas_out, cnt * 4 * sizeof(double))) != hipSuccess ||
@@ -156,6 +165,9 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     u.bU = sp.bU;
     u.bDinv = sp.bDinv;
     u.bF = sp.bF;
+    u.bMr = sp.bMr;
+    u.bMl = sp.bMl;
+    u.wcnt = b->wcnt + 2 * i;
     u.bneg = sp.bneg;
     u.flags = h->fac.flags;
     u.stat = b->bstat + S * i;
@@ -182,12 +194,14 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
     h->mask_set = false;
     h->eval_fresh = false;
     h->sp.stat_pending = false;
+    h->sp.kept = 0;  // (the batch's reductions write the handle's block arrays)
     invalidate_factor(h);
   }
   std::memset(b->h_ps, 0, cnt * BPS_STRIDE * sizeof(double));
   if ((e = hipMemcpy(b->tab, tab.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemcpy(b->btab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemset(b->ctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
+      (e = hipMemset(b->wcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
       (e = hipMemset(b->bstat, 0, cnt * S * sizeof(double))) != hipSuccess ||
       (e = hipMemcpy(b->ps, b->h_ps, cnt * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) {
     pgf_batch_destroy(b);
@@ -199,6 +213,7 @@ int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
 
 void band_batch_free(pgf_batch b) {
   if (b->btab) (void)hipFree(b->btab);
+  if (b->wcnt) (void)hipFree(b->wcnt);
   if (b->bstat) (void)hipFree(b->bstat);
   if (b->h_bstat) (void)hipHostFree(b->h_bstat);
 }
@@ -211,7 +226,9 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 
 // The step sequence of batch_enqueue_step for banded instances: eval, mask, rhs, assembly where
 // needed, reduction, residual, step update, the evaluation made ahead of the sync, and the copy
-// that brings the batch's status block to the host.
+// that brings the batch's status block to the host.  On the wide route the reduction is the launch
+// sequence of pgf_band_wide_batch.hip: extract, one invert + one reduce launch per level, last, one
+// back launch per level, residual -- each instance in the phase its ctl[0] says.
 int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;
@@ -231,8 +248,17 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
     bandb_launch_assemble(s, b->btab, b->B, b->bsh);
     ++b->stat_band_assemblies;
   }
-  // (the 8 x 8 reduction keeps no factors: every step runs it, on the band as it stands)
-  bandb_launch_solve(s, b->btab, b->B, b->bsh);
+  if (b->bsh.B > 8) {
+    // With the split on, an instance whose band is still valid solves against its kept factors.  When
+    // the host knows that none reduces (a Simplified step behind a good one) the inversion launches
+    // are left out: their workgroups would all return.
+    const bool lean = b->bsh.split && !recompute && b->all_factored;
+    bandb_launch_wide_solve(s, b->btab, b->B, b->bsh, lean);
+    if (lean && b->bsh.N) ++b->stat_band_lean;
+  } else {
+    // (the 8 x 8 reduction keeps no factors: every step runs it, on the band as it stands)
+    bandb_launch_solve(s, b->btab, b->B, b->bsh);
+  }
   ++b->stat_band_reductions;
   bandb_launch_step_update(s, b->btab, b->B, b->bsh);
   b->eval_fresh = false;
@@ -252,7 +278,10 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 // buffers ARE the instance's, the band is intact, the solution is in sp.brhs and its residual in
 // sp.bres.  The step update left the point the step started from in (xn, yn): it goes back, and
 // band_refine corrects the solution and takes the step again from there.  The batch's stream is
-// idle (band_batch_sync).  Returns 0 when the instance's step is good now.
+// idle (band_batch_sync).  On the wide route with the split on, the handle holds the factors the
+// batch's reduction left (the instance's flags were clean, or it would not be here): sp.kept says so
+// for the length of the repair, and the corrections are solve phases against the instance's own
+// multipliers, as the single handle's would be.  Returns 0 when the instance's step is good now.
 static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out) {
   pgf_handle h = b->hs[i];
   SparseDev &sp = h->sp;
@@ -263,7 +292,9 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
   std::memcpy(sp.h_bred, st, S * sizeof(double));
   sp.guarded = true;
   h->mask_set = true;
+  sp.kept = b->bsh.split ? 2 : 0;
   int rc = band_refine(h, /*swapped=*/false, /*with_step=*/true);
+  sp.kept = 0;  // (outside a repair the handle's own view stays: no factors of its making)
   h->mask_set = false;
   if (rc) {
     (void)hipStreamSynchronize(s);  // (the point the step started from is back in place)
@@ -325,5 +356,23 @@ extern "C" int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *ass
   if (!b) return PGF_INVALID;
   if (reductions) *reductions = b->stat_band_reductions;
   if (assemblies) *assemblies = b->stat_band_assemblies;
+  return PGF_OK;
+}
+
+extern "C" int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_phases,
+                                               int *lean_steps) {
+  if (!b) return PGF_INVALID;
+  if (lean_steps) *lean_steps = b->stat_band_lean;
+  if (!reductions && !solve_phases) return PGF_OK;
+  std::vector<int> cnt((size_t)2 * b->B, 0);
+  if (b->band && b->wcnt) {
+    (void)hipSetDevice(b->device);
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    BHIPCHK(b, hipMemcpy(cnt.data(), b->wcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < b->B; ++i) {
+    if (reductions) reductions[i] = cnt[2 * i];
+    if (solve_phases) solve_phases[i] = cnt[2 * i + 1];
+  }
   return PGF_OK;
 }

@@ -33,11 +33,16 @@ static int batch_store_norms(pgf_batch b) {
 }
 
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
+  return pgf_batch_create_ex(handles, count, 0u, out);
+}
+
+int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
+  if (flags & ~PGF_BATCH_WIDE_BAND) return PGF_INVALID;
   const pgf_handle h0 = handles[0];
   if (!h0) return PGF_INVALID;
   for (int i = 0; i < count; ++i)  // any banded handle: a band batch, or its refusal
-    if (handles[i] && handles[i]->sparse) return band_batch_create(handles, count, out);
+    if (handles[i] && handles[i]->sparse) return band_batch_create(handles, count, flags, out);
   for (int i = 0; i < count; ++i) {
     const pgf_handle h = handles[i];
     if (!h) return PGF_INVALID;

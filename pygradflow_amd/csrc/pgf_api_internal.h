@@ -296,7 +296,7 @@ struct pgf_batch_s {
   // log of (lambda used, lambda next, accepted) per outer iteration and instance
   double *dctl_cs = nullptr, *dctl_cp = nullptr, *dctl_log = nullptr;
   int dctl_log_cap = 0, dctl_logged = 0;
-  // A banded batch (pgf_api_band_batch.hip): narrow banded handles of one pattern.  btab: the
+  // A banded batch (pgf_api_band_batch.hip): banded handles of one pattern, all narrow or all wide.  btab: the
   // instances' BandInst records beside the BInst ones in tab; bsh: what they share; bstat / h_bstat:
   // ONE status block for the whole batch, 3 nred + 4 doubles per instance (residual pairs, partial
   // sums of the step update, pivot flags) and its pinned mirror, read with one copy per step;
@@ -308,6 +308,10 @@ struct pgf_batch_s {
   std::vector<uint8_t> frozen;
   std::vector<int> last_neg;
   int stat_band_reductions = 0, stat_band_assemblies = 0;  // pgf_batch_debug_band_stats
+  // wide route: per instance (reductions, solve phases) counted on the device, and the steps enqueued
+  // without inversion launches (pgf_batch_debug_band_wide_stats)
+  int *wcnt = nullptr;
+  int stat_band_lean = 0;
   PgfProfile prof;
   std::string err = "";
 };
@@ -328,7 +332,7 @@ static inline int bfail(pgf_batch b, int code, const char *msg) {
 
 
 // The banded half, each beside the entry point that hands over to it in one line.
-int band_batch_create(const pgf_handle *handles, int count, pgf_batch *out);  // pgf_batch_create
+int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);  // pgf_batch_create_ex
 void band_batch_free(pgf_batch b);                                            // pgf_batch_destroy
 void band_batch_eval(pgf_batch b);                                            // batch_eval
 int band_batch_step_async(pgf_batch b, unsigned policy, double tau);          // pgf_batch_step_async

@@ -278,8 +278,8 @@ struct BatchScalars {
 #define BPS_STRIDE 8
 
 // ---- banded batch (pgf_band_batch.hip) ---------------------------------------
-// One entry per instance of a batch of narrow banded handles (block size 8, no border, ONE sparsity
-// pattern): what differs between the instances -- the values of H and J, the band, the work blocks
+// One entry per instance of a batch of banded handles (no border, ONE sparsity pattern; block size 8,
+// or 16 / 32 / 64 for every instance -- the wide route, pgf_band_wide_batch.hip): what differs between the instances -- the values of H and J, the band, the work blocks
 // of the cyclic reduction, the vectors, the flags.  The batched twins of the banded kernels pick
 // their instance with blockIdx.y; the pattern arrays, equal by construction, come from instance 0
 // (BandShape) so that every workgroup hits the same lines.  The vector kernels shared with the
@@ -288,8 +288,10 @@ struct BatchScalars {
 struct BandInst {
   const double *Hval, *Jval;
   double *band, *brhs, *brhs0, *bres;
-  double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev)
+  double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev; wide: one)
+  double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
+  int *wcnt;  // wide route: [0] reductions, [1] solve phases this instance's workgroups ran
   // the instance's slice of the batch's status block: [0, 2 nred) residual pairs, [2 nred, 3 nred)
   // partial sums of the step update, [3 nred, 3 nred + 4) pivot flags (as SparseDev::bred)
   double *stat;
@@ -301,6 +303,7 @@ struct BandInst {
 };
 struct BandShape {
   int n, m, N, nb, bw, ldb, nnzH, nnzJ, nred;
+  int B, split;  // block size of the reduction; wide route: the factor / solve split is on
   int64_t bstride;
   const int *pos, *Hptr, *Hrow, *Hcol, *Hslot, *Jptr, *Jcol, *Jslot, *JTptr, *JTrow, *JTmap;
 };
@@ -313,6 +316,9 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 // cyclic reduction of every instance that is not frozen (one launch plan: it depends on N only),
 // then the residual of the solution into the status block
 void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// the same on the wide route (sh.B > 8): per instance the reduction, or with the split on and
+// ctl[0] == 0 the solve phase against its kept factors; lean: the host knows that no instance reduces
+void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean);
 // (xn, yn), dx, dy and the partial sums; the new point replaces the old one, which stays in
 // (xn, yn), unless the instance met a bad pivot
 void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
