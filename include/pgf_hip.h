@@ -268,8 +268,9 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * (pgf_batch_refinement_stats counts it), and only one that cannot be repaired or met a zero
  * pivot reports PGF_SINGULAR, its point unchanged.  Refused with PGF_INVALID and a message that
  * names the reason: dense and banded handles mixed, different patterns, a wide band (block size
- * above 8), a border, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* and
- * pgf_batch_debug_fail_next_helper return PGF_INVALID and pgf_batch_debug_factor_kind 0.
+ * above 8), a border, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* (unless it was
+ * created with PGF_BATCH_BAND_CTL, below) and pgf_batch_debug_fail_next_helper return PGF_INVALID
+ * and pgf_batch_debug_factor_kind 0.
  *
  * pgf_batch_create_ex takes flags; pgf_batch_create is pgf_batch_create_ex with flags 0, and unknown
  * flag bits are PGF_INVALID.  PGF_BATCH_WIDE_BAND also admits a band batch on the WIDE route:
@@ -281,9 +282,23 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * solve phase against the factors it kept, inside the one launch sequence of the batch; an
  * instance above refine_tol is refined on its handle by solve phases against those factors.  The
  * results are, bit for bit, those of the single handles.  Narrow and dense batches behave with the
- * flag as without it. */
+ * flag as without it.
+ *
+ * PGF_BATCH_BAND_CTL (alone or with PGF_BATCH_WIDE_BAND) opens the device-resident controller
+ * pgf_batch_ctl_* to a band batch, narrow or wide; without it they return PGF_INVALID as said above,
+ * and on a dense batch the flag changes nothing.  Inside pgf_batch_ctl_iterate the banded step is
+ * finished per instance on the device (kernel kbb_step_final): step length, pivot flag, and the
+ * guard's measure against the refine_tol the instance's handle had at pgf_batch_ctl_init (never
+ * when its refine_mode is off).  An instance above its tolerance cannot be refined on its handle
+ * inside a loop without host round trips: its step counts as FAILED, the controller rejects it with
+ * 2 lambda and the instance goes back to its outer point at the next iteration -- the reference's
+ * own recovery, a larger lambda makes K quasi-definite again (step_control.py:80-107).
+ * pgf_batch_debug_ctl_stats counts such steps.  pgf_batch_ctl_read brings the device's frozen
+ * flags to the host, so that a pgf_batch_step_async behind it reports the instances the last
+ * iteration froze as frozen (status PGF_OK, diff 0) until the next pgf_batch_advance_outer*. */
 typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BAND 1u
+#define PGF_BATCH_BAND_CTL 2u
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
@@ -548,6 +563,11 @@ int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *assemblies);
  * created (arrays of `count` ints, synchronises); *lean_steps: steps enqueued without inversion
  * launches.  Zeros on a dense or narrow batch.  Any pointer may be NULL. */
 int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_phases, int *lean_steps);
+/* per instance: Newton steps that pgf_batch_ctl_iterate's loop on a band batch (PGF_BATCH_BAND_CTL)
+ * rejected for a zero or non-finite pivot, and steps it rejected because the guard's measure missed
+ * the instance's refine_tol, since the batch was created (arrays of `count` ints, synchronises).
+ * Zeros on a dense batch and on a band batch without the flag.  Any pointer may be NULL. */
+int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *guard_rejects);
 /* The 64-bit hash a banded handle keeps of its pattern (host only, no device needed): FNV-1a over
  * n, m, bw, the entry counts and every index array as pgf_sparse_set_pattern receives them. */
 int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,

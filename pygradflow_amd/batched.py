@@ -87,10 +87,17 @@ class BatchedDeviceNewton:
     library refuses (dense and banded mixed, different patterns, a wide band without the flag, a
     border) is raised as ``ValueError`` with its message.  ``self.band`` tells which kind the
     device batch is, ``self.band_block`` the block size of a band batch (``None`` otherwise).
+
+    ``band_ctl=True`` (``PGF_BATCH_BAND_CTL``, alone or with ``wide_band``) opens the device-resident
+    step controller (``ctl_init / ctl_iterate / ctl_read``) to a band batch; without it a band batch
+    refuses ``ctl_init`` as before, and a dense batch takes no notice of it.  Inside ``ctl_iterate``
+    an instance whose solve misses its handle's ``refine_tol`` is not repaired on its handle (that
+    needs the host): its step is rejected with 2 lambda, like a failed factorisation.
+    ``ctl_stats()`` counts such steps.
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
-                 world=1, group=None, tau=None, sequential=False, wide_band=False):
+                 world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False):
         import ctypes as C
         import math
 
@@ -123,6 +130,7 @@ class BatchedDeviceNewton:
         self.band = False
         self.band_block = None
         self.wide_band = bool(wide_band)
+        self.band_ctl = bool(band_ctl)
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
         if self.count and not self.sequential:
@@ -140,9 +148,12 @@ class BatchedDeviceNewton:
 
     def _create(self, lib, handles, out):
         """The device batch over ``handles``: through ``pgf_batch_create_ex`` with
-        ``PGF_BATCH_WIDE_BAND`` when ``wide_band`` was asked for, ``pgf_batch_create`` otherwise."""
-        if self.wide_band:
-            return lib.pgf_batch_create_ex(handles, self.count, self._lib.BATCH_WIDE_BAND, out)
+        ``PGF_BATCH_WIDE_BAND`` and / or ``PGF_BATCH_BAND_CTL`` when ``wide_band`` / ``band_ctl`` was
+        asked for, ``pgf_batch_create`` otherwise."""
+        flags = (self._lib.BATCH_WIDE_BAND if self.wide_band else 0) | \
+            (self._lib.BATCH_BAND_CTL if getattr(self, "band_ctl", False) else 0)
+        if flags:
+            return lib.pgf_batch_create_ex(handles, self.count, flags, out)
         return lib.pgf_batch_create(handles, self.count, out)
 
     def _begin_outer(self):
@@ -284,7 +295,7 @@ class BatchedDeviceNewton:
         """Arm the device-resident ``DistanceRatioController`` of every local instance."""
         if self._b is None:
             raise NotImplementedError("device batch only")
-        if self.band:
+        if self.band and not self.band_ctl:
             raise NotImplementedError("dense batch only")
         vals = np.array([params.newton_tol, params.lamb_red, params.lamb_min, params.lamb_inc,
                          params.theta_max, params.K_P, params.K_I, params.theta_ref], dtype=np.float64)
@@ -349,6 +360,20 @@ class BatchedDeviceNewton:
         self._lib.check(self._lib.load().pgf_batch_debug_band_wide_stats(
             self._b, red.ctypes.data_as(ip), sol.ctypes.data_as(ip), C.byref(lean)), batch=self._b)
         return red, sol, lean.value
+
+    def ctl_stats(self):
+        """(pivot_rejects[count], guard_rejects[count]) of a ``band_ctl`` batch
+        (``pgf_batch_debug_ctl_stats``): per instance the Newton steps ``ctl_iterate`` rejected for
+        a zero or non-finite pivot and those it rejected because the solve missed ``refine_tol``.
+        Zeros on any other batch.  Device batch only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        piv = np.zeros(self.count, dtype=np.int32)
+        grd = np.zeros(self.count, dtype=np.int32)
+        ip = self._C.POINTER(self._C.c_int)
+        self._lib.check(self._lib.load().pgf_batch_debug_ctl_stats(
+            self._b, piv.ctypes.data_as(ip), grd.ctypes.data_as(ip)), batch=self._b)
+        return piv, grd
 
     def factor_kind(self):
         """Pivot order of the factors the batch's instances hold: 0 none yet, 1 the natural

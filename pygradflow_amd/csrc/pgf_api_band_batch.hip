@@ -52,6 +52,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   pgf_batch b = new (std::nothrow) pgf_batch_s();
   if (!b) return PGF_INVALID;
   b->band = true;
+  b->band_ctl = (flags & PGF_BATCH_BAND_CTL) != 0;
   b->hs.assign(handles, handles + count);
   b->B = count;
   b->n = h0->n;
@@ -107,6 +108,20 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       (e = hipHostMalloc((void **)&b->h_norm, cnt * sizeof(double))) != hipSuccess ||
       (e = hipMalloc((void **)&b->bstat, cnt * S * sizeof(double))) != hipSuccess ||
       (e = hipHostMalloc((void **)&b->h_bstat, cnt * S * sizeof(double))) != hipSuccess) {
+    pgf_batch_destroy(b);
+    return PGF_HIP_ERROR + (int)e;
+  }
+  // what kbb_step_final writes for kb_dctl_mid / kb_dctl_end (zeroed: the guard is off and nothing
+  // is counted until pgf_batch_ctl_init)
+  if (b->band_ctl &&
+      ((e = hipMalloc((void **)&b->flags_out, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->diff_out, cnt * sizeof(double))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->band_guard, cnt * 2 * sizeof(double))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->band_rejects, cnt * 2 * sizeof(int))) != hipSuccess ||
+       (e = hipMemset(b->flags_out, 0, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
+       (e = hipMemset(b->diff_out, 0, cnt * sizeof(double))) != hipSuccess ||
+       (e = hipMemset(b->band_guard, 0, cnt * 2 * sizeof(double))) != hipSuccess ||
+       (e = hipMemset(b->band_rejects, 0, cnt * 2 * sizeof(int))) != hipSuccess)) {
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
   }
@@ -188,6 +203,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     u.dy = h->dy;
     u.tmpn = h->tmpn;
     u.mask = h->mask;
+    u.counts = h->counts;
     u.ctl = b->ctl + 4 * i;
     u.ps = b->ps + (size_t)BPS_STRIDE * i;
     // the batch owns the device-side state of the handle from here on
@@ -216,6 +232,8 @@ void band_batch_free(pgf_batch b) {
   if (b->wcnt) (void)hipFree(b->wcnt);
   if (b->bstat) (void)hipFree(b->bstat);
   if (b->h_bstat) (void)hipHostFree(b->h_bstat);
+  if (b->band_guard) (void)hipFree(b->band_guard);
+  if (b->band_rejects) (void)hipFree(b->band_rejects);
 }
 
 // c = A x - b ; w = rho c + y ; g = Q x + (q + A' w) at every instance's point
@@ -229,7 +247,12 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 // that brings the batch's status block to the host.  On the wide route the reduction is the launch
 // sequence of pgf_band_wide_batch.hip: extract, one invert + one reduce launch per level, last, one
 // back launch per level, residual -- each instance in the phase its ctl[0] says.
-int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
+//
+// band_batch_enqueue_step is the sequence up to the step update, for pgf_batch_step_async and for the
+// device-resident controller's loop alike.  lean_allowed: the caller knows that every instance
+// still live holds a clean factor of its band -- pgf_batch_step_async after a sync that found all
+// instances good (all_factored), pgf_batch_ctl_iterate in front of the second step of an iteration.
+void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed) {
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;
   hipStream_t s = b->stream;
@@ -244,7 +267,7 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   bandb_launch_rhs(s, b->btab, b->B, b->bsh);
   // instances whose band is still valid return at once (ctl[0] == 0); when the host knows that
   // none assembles (a Simplified step behind a good one), the launches are skipped
-  if (recompute || !b->all_factored) {
+  if (recompute || !lean_allowed) {
     bandb_launch_assemble(s, b->btab, b->B, b->bsh);
     ++b->stat_band_assemblies;
   }
@@ -252,7 +275,7 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
     // With the split on, an instance whose band is still valid solves against its kept factors.  When
     // the host knows that none reduces (a Simplified step behind a good one) the inversion launches
     // are left out: their workgroups would all return.
-    const bool lean = b->bsh.split && !recompute && b->all_factored;
+    const bool lean = b->bsh.split && !recompute && lean_allowed;
     bandb_launch_wide_solve(s, b->btab, b->B, b->bsh, lean);
     if (lean && b->bsh.N) ++b->stat_band_lean;
   } else {
@@ -262,6 +285,11 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   ++b->stat_band_reductions;
   bandb_launch_step_update(s, b->btab, b->B, b->bsh);
   b->eval_fresh = false;
+}
+
+int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
+  hipStream_t s = b->stream;
+  band_batch_enqueue_step(b, policy, tau, b->all_factored);
   // g and c at the new points, ahead of the host synchronisation (as pgf_batch_step_async)
   if (eval_ahead()) {
     band_batch_eval(b);
@@ -349,6 +377,59 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
     if (diff) diff[i] = rc ? 0.0 : d;
   }
   b->all_factored = all_ok;
+  return PGF_OK;
+}
+
+// ---- the device-resident controller on a band batch (PGF_BATCH_BAND_CTL) ------------------------
+// The loop itself is pgf_batch_ctl_iterate's; a banded step in it is band_batch_enqueue_step and,
+// where band_batch_sync would finish the step on the host, kbb_step_final on the device.
+void band_batch_enqueue_final(pgf_batch b) {
+  bandb_launch_step_final(b->stream, b->btab, b->B, b->bsh, b->band_guard, b->diff_out, b->flags_out,
+                          b->band_rejects);
+}
+
+// the guard's setting of every handle, as it stands now (pgf_set_refinement), for kbb_step_final
+int band_batch_ctl_init(pgf_batch b) {
+  std::vector<double> g((size_t)2 * b->B);
+  for (int i = 0; i < b->B; ++i) {
+    g[2 * (size_t)i] = b->hs[i]->refine_mode ? 1.0 : 0.0;
+    g[2 * (size_t)i + 1] = b->hs[i]->refine_tol;
+  }
+  BHIPCHK(b, hipMemcpyAsync(b->band_guard, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice,
+                            b->stream));
+  BHIPCHK(b, hipStreamSynchronize(b->stream));
+  return PGF_OK;
+}
+
+// Behind the loop, stream idle: the host's view follows the device's.  The instances the controller
+// froze in the last iteration stay frozen until the next pgf_batch_advance_outer*, so a host-driven
+// pgf_batch_step_async right behind reports them as band_batch_sync reports frozen instances, with
+// the inertia of the last step they took.  (No chain helpers here: the sticky word stays unused.)
+int band_batch_ctl_read(pgf_batch b) {
+  std::vector<int> ctl((size_t)4 * b->B), fl((size_t)3 * b->B);
+  BHIPCHK(b, hipMemcpy(ctl.data(), b->ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost));
+  BHIPCHK(b, hipMemcpy(fl.data(), b->flags_out, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int i = 0; i < b->B; ++i) {
+    b->frozen[i] = ctl[4 * (size_t)i + 3] ? 1 : 0;
+    if (b->dctl_logged > 0) b->last_neg[i] = fl[3 * (size_t)i + 1];
+  }
+  b->all_factored = false;
+  return PGF_OK;
+}
+
+extern "C" int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *guard_rejects) {
+  if (!b) return PGF_INVALID;
+  if (!pivot_rejects && !guard_rejects) return PGF_OK;
+  std::vector<int> cnt((size_t)2 * b->B, 0);
+  if (b->band_rejects) {
+    (void)hipSetDevice(b->device);
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    BHIPCHK(b, hipMemcpy(cnt.data(), b->band_rejects, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < b->B; ++i) {
+    if (pivot_rejects) pivot_rejects[i] = cnt[2 * (size_t)i];
+    if (guard_rejects) guard_rejects[i] = cnt[2 * (size_t)i + 1];
+  }
   return PGF_OK;
 }
 

@@ -38,7 +38,7 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
 
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
-  if (flags & ~PGF_BATCH_WIDE_BAND) return PGF_INVALID;
+  if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL)) return PGF_INVALID;
   const pgf_handle h0 = handles[0];
   if (!h0) return PGF_INVALID;
   for (int i = 0; i < count; ++i)  // any banded handle: a band batch, or its refusal
@@ -404,7 +404,7 @@ static const char *const k_band_ctl =
 int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *params,
                        int max_iterations) {
   if (!b || !params || !(lamb_init > 0.0) || !(rho > 0.0) || max_iterations < 1) return PGF_INVALID;
-  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
+  if (b->band && !b->band_ctl) return bfail(b, PGF_INVALID, k_band_ctl);
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
   (void)hipSetDevice(b->device);
   const size_t ncs = (size_t)b->B * DCS_STRIDE;
@@ -437,12 +437,25 @@ int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *
                             b->stream));
   BHIPCHK(b, hipStreamSynchronize(b->stream));
   b->dctl_logged = 0;
+  if (b->band) return band_batch_ctl_init(b);
   return PGF_OK;
+}
+
+// One Newton step of the loop below, finished on the device: diff_out and flags_out are what
+// kb_dctl_mid / kb_dctl_end read.  The host cannot know all_factored inside the loop; lean (band
+// batches): what it can still know, see there.
+static void ctl_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean) {
+  if (b->band) {
+    band_batch_enqueue_step(b, policy, tau, lean);
+    band_batch_enqueue_final(b);
+  } else {
+    batch_enqueue_step(b, policy, tau, false);
+  }
 }
 
 int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iterations) {
   if (!b || iterations < 0) return PGF_INVALID;
-  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
+  if (b->band && !b->band_ctl) return bfail(b, PGF_INVALID, k_band_ctl);
   if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
   if (b->dctl_logged + iterations > b->dctl_log_cap)
@@ -465,12 +478,19 @@ int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iteratio
       batch_eval(b);
       batch_launch_mask(s, b->tab, b->B, b->sc, 2, tau);
     }
-    batch_enqueue_step(b, policy, tau, false);
+    // lambda has changed: every instance assembles and factorises (ctl[0], decided on the device)
+    ctl_enqueue_step(b, policy, tau, false);
     batch_eval(b);
     batch_launch_res_norm(s, b->tab, b->B, b->sc, b->norm_out);
     batch_launch_dctl_mid(s, b->tab, b->B, b->dctl_cs, b->dctl_cp, b->diff_out, b->flags_out,
                           b->norm_out);
-    batch_enqueue_step(b, policy, tau, false);
+    // Band batches, a policy that keeps the mask: the second step is enqueued without the assembly
+    // and, on the wide route with the split on, without the inversion launches.  Every instance
+    // still live has a clean factor of the band step one assembled: a bad pivot or a miss of the
+    // guard in step one set its flag word, and kb_dctl_mid has frozen it for this step; the mask
+    // is kept, so the band stays valid (ctl[1] = 1 from step one's update, ctl[0] = 0 here), and
+    // the workgroups of the launches left out would all return.
+    ctl_enqueue_step(b, policy, tau, !recompute);
     batch_launch_dctl_end(s, b->B, b->dctl_cs, b->dctl_cp, b->diff_out, b->flags_out,
                           b->dctl_log + (size_t)b->dctl_logged * b->B * 3);
     ++b->dctl_logged;
@@ -482,7 +502,7 @@ int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iteratio
 
 int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log3, int log_rows) {
   if (!b) return PGF_INVALID;
-  if (b->band) return bfail(b, PGF_INVALID, k_band_ctl);
+  if (b->band && !b->band_ctl) return bfail(b, PGF_INVALID, k_band_ctl);
   if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
   (void)hipSetDevice(b->device);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
@@ -491,7 +511,9 @@ int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log
   // iteration, but with the helpers still on it could repeat every iteration and lambda would
   // grow without bound.  The sticky word behind the flag triples says whether any
   // step of the loop saw one: helpers and chained solves go off, as pgf_batch_sync does.
-  {
+  if (b->band) {
+    if (int rc = band_batch_ctl_read(b)) return rc;  // (no helpers: the frozen flags instead)
+  } else {
     int sticky = 0;
     BHIPCHK(b, hipMemcpy(&sticky, b->flags_out + 3 * (size_t)b->B, sizeof(int), hipMemcpyDeviceToHost));
     if (sticky) {

@@ -312,6 +312,13 @@ struct pgf_batch_s {
   // without inversion launches (pgf_batch_debug_band_wide_stats)
   int *wcnt = nullptr;
   int stat_band_lean = 0;
+  // created with PGF_BATCH_BAND_CTL: the device-resident controller is open to this band batch.
+  // flags_out / diff_out are allocated as for a dense batch and written by kbb_step_final;
+  // band_guard: per instance (guard on, refine_tol) as pgf_batch_ctl_init found them on the handles;
+  // band_rejects: per instance, steps the loop rejected for a pivot / by the guard
+  bool band_ctl = false;
+  double *band_guard = nullptr;
+  int *band_rejects = nullptr;
   PgfProfile prof;
   std::string err = "";
 };
@@ -337,6 +344,12 @@ void band_batch_free(pgf_batch b);                                            //
 void band_batch_eval(pgf_batch b);                                            // batch_eval
 int band_batch_step_async(pgf_batch b, unsigned policy, double tau);          // pgf_batch_step_async
 int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff);      // pgf_batch_sync
+// the launches of one banded step, without the evaluation made ahead and the status copy;
+// lean_allowed: the caller knows that every instance still live holds a clean factor of its band
+void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed);  // pgf_batch_ctl_iterate
+void band_batch_enqueue_final(pgf_batch b);                                   // pgf_batch_ctl_iterate
+int band_batch_ctl_init(pgf_batch b);                                         // pgf_batch_ctl_init
+int band_batch_ctl_read(pgf_batch b);                                         // pgf_batch_ctl_read
 void band_batch_measures_eval(pgf_batch b);                                   // pgf_batch_measures
 // what it takes from pgf_api_band.hip: the guard's measure over nred residual pairs, and the hash
 // of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat_hash)

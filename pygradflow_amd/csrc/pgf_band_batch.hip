@@ -11,6 +11,9 @@
 // reduction -- the 8 x 8 reduction keeps no factors, and leaves the band intact.  Pivot flags and
 // negative-pivot counts are the instance's own arrays.
 //
+// kbb_step_final has no twin: it is what band_batch_sync does on the host after a step, one wavefront
+// per instance, for the device-resident controller's loop (narrow and wide route alike).
+//
 // Grid shape of the one-workgroup LDS tail: (1, B) workgroups of 1024 threads.  The tail holds
 // 94 KB of the CU's 160 KB of LDS, so a CU takes one at a time: up to 256 instances the tails run
 // side by side, one per CU, beyond that in waves of 256.
@@ -186,6 +189,21 @@ __global__ __launch_bounds__(256) void kbb_band_step_update(const BandInst *__re
   }
 }
 
+// The device-resident controller's end of a step: one wavefront per instance, four instances per
+// workgroup, grid ceil(B / 4).  A frozen instance took no step: its outputs stay as they are
+// (kb_dctl_end reads them only for an instance that was live in step two).
+__global__ __launch_bounds__(256) void kbb_step_final(const BandInst *__restrict__ tab, int B, BandShape sh,
+                                                      const double *__restrict__ guard,
+                                                      double *__restrict__ diff_out,
+                                                      int *__restrict__ flags_out, int *__restrict__ rejects) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= B) return;
+  const BandInst &I = tab[i];
+  if (I.ctl[3]) return;
+  b_band_step_final(I.stat, sh.nred, I.counts[0], guard[2 * i] != 0.0, guard[2 * i + 1], diff_out + i,
+                    flags_out + 3 * i, rejects + 2 * i);
+}
+
 // ---------------------------------------------------------------- launch wrappers
 static inline dim3 gy(int64_t cnt, int per, int B) { return dim3((unsigned)((cnt + per - 1) / per), B); }
 
@@ -255,4 +273,11 @@ void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandSha
 
 void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
   if (sh.N) hipLaunchKernelGGL(kbb_band_step_update, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh);
+}
+
+void bandb_launch_step_final(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
+                             const double *guard, double *diff_out, int *flags_out, int *rejects) {
+  if (sh.N)
+    hipLaunchKernelGGL(kbb_step_final, dim3((B + 3) / 4), dim3(256), 0, s, tab, B, sh, guard, diff_out,
+                       flags_out, rejects);
 }

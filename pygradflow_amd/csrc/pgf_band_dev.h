@@ -652,3 +652,55 @@ __device__ __forceinline__ void b_band_residual(const double *__restrict__ band,
     rsmax[2 * blockIdx.x + 1] = fmax(fmax(pb[0], pb[1]), fmax(pb[2], pb[3]));
   }
 }
+
+// ---------------------------------------------------------------- the step finished on the device
+// What band_batch_sync (pgf_api_band_batch.hip) does on the host after a step's synchronisation, for
+// the device-resident controller, which has no synchronisation to do it behind.  ONE wavefront per
+// instance (the caller picks the instance from its wavefront's index); stat: the instance's status
+// block as b_band_residual and b_band_step_update left it.
+//   *diff_out   sqrt of the sum of the step update's partial sums, taken by lane 0 in index order --
+//               the order of band_batch_sync, so the bits agree (nred = ceil(N / 256) adds); 0 after
+//               a bad pivot, when no step was taken
+//   flags_out   [0] bit 0: zero or non-finite pivot; bit 2: the guard's measure (band_residual_rel_of:
+//               max |r| / max (|K| |x| + |rhs|) over the pairs, +inf for a NaN or overflowed numerator,
+//               denominator 1 when it is 0; a max is order-free, so lane strides and shuffles) misses
+//               tol -- only when guard_on, and only behind a clean pivot, as on the host;
+//               [1] negative pivots; [2] |I|
+//   rejects     [0] += bit 0, [1] += bit 2: the instance's own words, no atomics
+// The host repairs an instance above its tolerance on its handle.  Here the step counts as failed:
+// kb_dctl_mid / kb_dctl_end reject it with 2 lambda and kb_advance puts the instance back on its
+// outer point, over the inaccurate point the step update swapped in -- the reference's own recovery,
+// a larger lambda makes K quasi-definite again (step_control.py:80-107).
+__device__ __forceinline__ void b_band_step_final(const double *__restrict__ stat, int nred, int n_inner,
+                                                  bool guard_on, double tol, double *__restrict__ diff_out,
+                                                  int *__restrict__ flags_out, int *__restrict__ rejects) {
+  const int lane = threadIdx.x & 63;
+  double r = 0.0, den = 0.0;
+  int broken = 0;
+  for (int k = lane; k < nred; k += 64) {
+    const double rk = stat[2 * k];
+    if (!(rk == rk) || !(rk <= 1.79e308))
+      broken = 1;
+    else
+      r = fmax(r, rk);
+    den = fmax(den, stat[2 * k + 1]);  // (fmax drops a NaN, as std::max(den, NaN) does)
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    r = fmax(r, __shfl_xor(r, off));
+    den = fmax(den, __shfl_xor(den, off));
+    broken |= __shfl_xor(broken, off);
+  }
+  if (lane != 0) return;
+  const double rel = broken ? __builtin_huge_val() : r / (den > 0.0 ? den : 1.0);
+  const int bad = stat[3 * nred] != 0.0 ? 1 : 0;
+  double sum = 0.0;
+  for (int k = 0; k < nred; ++k) sum += stat[2 * nred + k];
+  const int miss = (!bad && guard_on && !(rel <= tol)) ? 4 : 0;
+  *diff_out = bad ? 0.0 : sqrt(sum);
+  flags_out[0] = bad | miss;
+  flags_out[1] = (int)stat[3 * nred + 1];
+  flags_out[2] = n_inner;
+  if (bad) ++rejects[0];
+  if (miss) ++rejects[1];
+}

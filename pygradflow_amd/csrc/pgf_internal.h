@@ -298,6 +298,7 @@ struct BandInst {
   const double *lb, *ub, *q, *b;
   double *x, *y, *xn, *yn, *g, *c, *w, *F, *b0full, *dx, *dy, *tmpn;
   const uint8_t *mask;
+  const int *counts;  // [0] |I| (reported by kbb_step_final, as kb_step_final does)
   int *ctl;
   const double *ps;
 };
@@ -322,6 +323,13 @@ void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const Ba
 // (xn, yn), dx, dy and the partial sums; the new point replaces the old one, which stays in
 // (xn, yn), unless the instance met a bad pivot
 void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// The step finished per instance on the device, behind the step update (the device-resident
+// controller; what band_batch_sync does on the host): diff_out[i] the step length; flags_out[3 i]
+// bit 0 a zero or non-finite pivot, bit 2 the guard's measure above the instance's tolerance
+// (guard[2 i] != 0: the guard is on, guard[2 i + 1]: refine_tol), [3 i + 1] negative pivots,
+// [3 i + 2] |I|; rejects[2 i], [2 i + 1]: steps that set bit 0 / bit 2, counted
+void bandb_launch_step_final(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
+                             const double *guard, double *diff_out, int *flags_out, int *rejects);
 // c = J x - b and F[0:n] = H x + q + J' y for the termination measures
 void bandb_launch_measures_eval(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 

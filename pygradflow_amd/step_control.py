@@ -283,7 +283,11 @@ class DeviceResidentDistanceRatioController:
     lambda, PI integral, accept / reject with restore and the early exits live in HBM
     (``pgf_batch_ctl_*``, kernels ``kb_dctl_begin / _mid / _end``) -- and the host synchronises
     once, at the end, instead of reading two step lengths and a residual norm per iteration.
-    ``history`` then holds (lambda used, lambda next, accepted) per iteration and instance."""
+    ``history`` then holds (lambda used, lambda next, accepted) per iteration and instance.
+
+    Works unchanged on a band batch made with ``BatchedDeviceNewton(..., band_ctl=True)``, narrow or
+    wide.  There a solve that misses the accuracy guard's tolerance is a rejected step (2 lambda)
+    where the host-driven controller's batch would repair the instance on its handle."""
 
     def __init__(self, batch, params, rho=None, max_iterations=64):
         self.bd = batch

@@ -5,6 +5,9 @@ session.
     python tools/time_band_batch.py [--steps 200] [--warmup 20] [--reps 7] [--batches 1,8,64,256]
                                     [--workloads sparse_ocp,multistate_ocp,box_qp] [--out FILE]
                                     [--policy Full|Simplified] [--routes batch,sequential]
+    python tools/time_band_batch.py --controller [--iterations 20] [--warmup 3] [--reps 5]
+                                    [--batches 1,8,64,256] [--workloads sparse_ocp,multistate_ocp_w32]
+                                    [--policies Full,Simplified] [--lamb-min 1e-3] [--out FILE]
 
 The workloads ``multistate_ocp_w16``, ``_w32``, ``_w64`` are on the wide route (block sizes 16, 32,
 64): their batch is created with ``wide_band=True`` and their rows go to
@@ -19,6 +22,22 @@ step and the instance-steps per second at the median, appended to --out (default
 profiles/band_batch_timing.jsonl) and printed; after both routes of a (workload, B) a line
 ``"route": "ratio"`` with sequential / batch and whether the batch's median lies below the
 sequential one by more than both spreads (max - min) together.
+
+--controller times the step controller that drives such a batch instead: one outer iteration (two
+Newton steps and the controller's decisions) of the host-driven ``BatchedDistanceRatioController``
+on a band batch against ``DeviceResidentDistanceRatioController`` on its twin created with
+``band_ctl=True``, alternated in one session.  A repetition is ``--iterations`` outer iterations: on
+the host route that many ``step()`` calls (three host synchronisations each), on the device route one
+``run(iterations)`` -- one ``ctl_iterate`` and one ``ctl_read``.  One JSON line per (workload,
+policy, B, route) with the median, minimum and maximum time per outer iteration, appended to --out
+(default profiles/band_batch_ctl_timing.jsonl); the ratio line also says whether the accept flags
+of all iterations were equal on both routes and the largest relative difference of lambda.
+--lamb-min is the controller's floor for lambda (``Params.lamb_min``; the library's default is 1e-12).
+These workloads converge after one Newton step in most iterations, so lambda halves until it reaches
+the floor; left to the default it falls to where the accuracy guard fires (from about 1e-6), and
+then the host route repairs instances on their handles where the device route rejects the step: the
+two routes no longer do the same work, which the ratio line shows (``host_repaired``,
+``device_guard_rejects``, ``accept_flags_equal``).
 """
 import argparse
 import json
@@ -55,23 +74,103 @@ def timed(run, steps):
     return dt
 
 
+def controller_rows(a, emit):
+    """--controller: see the module docstring."""
+    from pygradflow_amd import step_control as SC
+    from pygradflow_amd.params import Params
+
+    total = a.warmup + a.reps * a.iterations
+    for key in a.workloads.split(","):
+        name, make = WORKLOADS[key]
+        probs = []
+        for pol in a.policies.split(","):
+            for B in [int(v) for v in a.batches.split(",")]:
+                while len(probs) < B:
+                    p = make(len(probs))
+                    p.pgf_force_band = True
+                    probs.append(p)
+                par = Params(newton_type=pol, lamb_init=1.0, lamb_min=a.lamb_min)
+                host_b, dev_b = (BatchedDeviceNewton(lambda i: probs[i], B, pol, 1.0, 1.0, wide_band=key in WIDE,
+                                                     band_ctl=ctl) for ctl in (False, True))
+                assert host_b.band and dev_b.band
+                host = SC.BatchedDistanceRatioController(host_b, par, rho=1.0)
+                dev = SC.DeviceResidentDistanceRatioController(dev_b, par, rho=1.0, max_iterations=total)
+                rec = []
+
+                def host_iters(k):
+                    t0 = time.perf_counter()
+                    for _ in range(k):
+                        rec.append(host.step())
+                    return (time.perf_counter() - t0) / k
+
+                def dev_iters(k):
+                    t0 = time.perf_counter()
+                    dev.run(k)  # (ends in ctl_read: the one host synchronisation)
+                    return (time.perf_counter() - t0) / k
+
+                routes = {"host_driven": host_iters, "device_resident": dev_iters}
+                for run in routes.values():
+                    run(a.warmup)
+                times = {r: [] for r in routes}
+                for _ in range(a.reps):  # alternated: other people's work shares the host
+                    for r, run in routes.items():
+                        times[r].append(run(a.iterations))
+                used = np.array([r[0] for r in rec])
+                nxt = np.array([r[1] for r in rec])
+                acc = np.array([r[2] for r in rec])
+                h = dev.history
+                flags_equal = bool(np.array_equal(h[:, :, 2] != 0.0, acc))
+                lamb_diff = float(max(np.max(np.abs(h[:, :, 0] - used) / used), np.max(np.abs(h[:, :, 1] - nxt) / nxt)))
+                piv, grd = dev_b.ctl_stats()
+                N = probs[0].num_vars + probs[0].num_cons
+                rows = {}
+                for r, ts in times.items():
+                    med = statistics.median(ts)
+                    rows[r] = {"workload": name, "N": N, "B": B, "route": r, "policy": pol, "lamb_min": a.lamb_min,
+                               "iterations": a.iterations, "warmup": a.warmup, "reps": a.reps,
+                               "median_ms": 1e3 * med, "min_ms": 1e3 * min(ts), "max_ms": 1e3 * max(ts)}
+                    emit(rows[r])
+                d, s = rows["device_resident"], rows["host_driven"]
+                spreads = (d["max_ms"] - d["min_ms"]) + (s["max_ms"] - s["min_ms"])
+                emit({"workload": name, "N": N, "B": B, "route": "ratio", "policy": pol,
+                      "host_over_device": s["median_ms"] / d["median_ms"],
+                      "device_below_host_by_more_than_both_spreads": bool(s["median_ms"] - d["median_ms"] > spreads),
+                      "accept_flags_equal": flags_equal, "max_rel_lambda_diff": lamb_diff,
+                      "accepted_share": float(acc.mean()), "host_repaired": host_b.repaired(),
+                      "device_pivot_rejects": int(piv.sum()), "device_guard_rejects": int(grd.sum())})
+                host_b.close()
+                dev_b.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--controller", action="store_true")
+    ap.add_argument("--iterations", type=int, default=20)
+    ap.add_argument("--policies", default="Full,Simplified")
+    ap.add_argument("--lamb-min", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--batches", default="1,8,64,256")
-    ap.add_argument("--workloads", default="sparse_ocp,multistate_ocp,box_qp")
+    ap.add_argument("--workloads", default=None)
     ap.add_argument("--out", default=None)
     ap.add_argument("--policy", default="Full", choices=("Full", "Simplified"))
     ap.add_argument("--routes", default="batch,sequential")
     a = ap.parse_args()
+    if a.warmup is None:
+        a.warmup = 3 if a.controller else 20
+    if a.reps is None:
+        a.reps = 5 if a.controller else 7
+    if a.workloads is None:
+        a.workloads = "sparse_ocp,multistate_ocp_w32" if a.controller else "sparse_ocp,multistate_ocp,box_qp"
     batches = [int(v) for v in a.batches.split(",")]
     keys = a.workloads.split(",")
     routes = a.routes.split(",")
     assert routes and set(routes) <= {"batch", "sequential"}, routes
     if a.out is None:
         name = "band_batch_wide_timing.jsonl" if all(k in WIDE for k in keys) else "band_batch_timing.jsonl"
+        if a.controller:
+            name = "band_batch_ctl_timing.jsonl"
         a.out = os.path.join(REPO, "profiles", name)
     out = open(a.out, "a")
 
@@ -81,6 +180,10 @@ def main():
         out.write(line + "\n")
         out.flush()
 
+    if a.controller:
+        controller_rows(a, emit)
+        out.close()
+        return
     for key in keys:
         name, make = WORKLOADS[key]
         probs = []
