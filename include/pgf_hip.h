@@ -259,7 +259,7 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * While a handle belongs to a batch, drive it only through the batch.
  *
  * A BAND batch: every handle banded (PGF_CREATE_SPARSE) on the narrow route -- half-bandwidth
- * <= 8, block size 8, no border -- with pattern and values set, the same n, m and device, and ONE
+ * <= 8, block size 8, no border (unless created with PGF_BATCH_BORDER, below) -- with pattern and values set, the same n, m and device, and ONE
  * sparsity pattern (the 64-bit hash of what pgf_sparse_set_pattern received, bw, the band's row
  * stride and the entry counts are compared).  Values of H and J, q, b, bounds, points, dt and rho
  * are the instance's own.  Every banded kernel of the step then runs over all instances at once
@@ -268,7 +268,7 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * (pgf_batch_refinement_stats counts it), and only one that cannot be repaired or met a zero
  * pivot reports PGF_SINGULAR, its point unchanged.  Refused with PGF_INVALID and a message that
  * names the reason: dense and banded handles mixed, different patterns, a wide band (block size
- * above 8), a border, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* (unless it was
+ * above 8) or a border without its flag, an unsymmetric formulation.  On a band batch pgf_batch_ctl_* (unless it was
  * created with PGF_BATCH_BAND_CTL, below) and pgf_batch_debug_fail_next_helper return PGF_INVALID
  * and pgf_batch_debug_factor_kind 0.
  *
@@ -295,10 +295,29 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * own recovery, a larger lambda makes K quasi-definite again (step_control.py:80-107).
  * pgf_batch_debug_ctl_stats counts such steps.  pgf_batch_ctl_read brings the device's frozen
  * flags to the host, so that a pgf_batch_step_async behind it reports the instances the last
- * iteration froze as frozen (status PGF_OK, diff 0) until the next pgf_batch_advance_outer*. */
+ * iteration froze as frozen (status PGF_OK, diff 0) until the next pgf_batch_advance_outer*.
+ *
+ * PGF_BATCH_BORDER admits BORDERED instances on the narrow route: a band of half-bandwidth <= 8
+ * (block size 8) plus 1 <= k <= 64 border nodes (pgf_sparse_set_border), under the conditions above
+ * and, in addition, ONE border size k for every handle -- refused otherwise with "batch: banded
+ * instances must share the border size".  Each instance decides on the device whether its step
+ * runs the factor phase (clear and assembly of band, C and D, Y = inv(B) C by the panel reduction,
+ * S = D - C' Y and its factor): where its matrix changed or its last factor phase met a bad pivot
+ * in B or S, which is where the single handle factors.  Every live instance runs the solve phase
+ * every step, and a step behind a good one whose policy keeps the mask is enqueued without any
+ * factor-phase launch.  An instance above refine_tol is refined on its handle by solve phases
+ * against the Y and the factor of S the batch left there.  The results are, bit for bit, those of
+ * the single handles on their panel route (PGF_BORDER_MULTI=0, the column-by-column cross-check,
+ * stays a single-handle switch: under it the two are not bit-comparable).
+ * pgf_batch_debug_border_stats counts the phases per instance.  Still refused: a border on a wide
+ * remainder, with or without PGF_BATCH_WIDE_BAND ("batch: a bordered band joins a device batch on
+ * the narrow route only (block size 8)"), and PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL on handles
+ * that have a border ("batch: the device-resident controller does not drive a bordered band
+ * batch").  Handles without a border behave with the flag as without it. */
 typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BAND 1u
 #define PGF_BATCH_BAND_CTL 2u
+#define PGF_BATCH_BORDER 4u
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
@@ -568,6 +587,10 @@ int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_pha
  * the instance's refine_tol, since the batch was created (arrays of `count` ints, synchronises).
  * Zeros on a dense batch and on a band batch without the flag.  Any pointer may be NULL. */
 int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *guard_rejects);
+/* per instance: factor phases and solve phases of the bordered route the instance ran since the
+ * batch was created (PGF_BATCH_BORDER; arrays of `count` ints, counted on the device, synchronises).
+ * Zeros on a batch that is not bordered.  Any pointer may be NULL. */
+int pgf_batch_debug_border_stats(pgf_batch b, int *factor_phases, int *solve_phases);
 /* The 64-bit hash a banded handle keeps of its pattern (host only, no device needed): FNV-1a over
  * n, m, bw, the entry counts and every index array as pgf_sparse_set_pattern receives them. */
 int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,

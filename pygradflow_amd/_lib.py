@@ -26,6 +26,7 @@ STEP_RECOMPUTE_MASK, STEP_REFACTOR, STEP_REFACTOR_ON_CHANGE = 1, 2, 4
 CREATE_SPARSE = 1
 BATCH_WIDE_BAND = 1
 BATCH_BAND_CTL = 2
+BATCH_BORDER = 4
 FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
 FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 
@@ -125,6 +126,7 @@ SIGNATURES = {
     "pgf_batch_debug_band_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_debug_band_wide_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_debug_ctl_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_batch_debug_border_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_sparse_pattern_hash": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                           _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),

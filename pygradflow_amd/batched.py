@@ -80,13 +80,20 @@ class BatchedDeviceNewton:
 
     Banded instances (``pgf_force_band``, or ``n + m`` above the dense limit: ``DeviceNewton``
     decides) form a BAND batch when all of them are banded on the narrow route (half-bandwidth
-    <= 8, no border) with one sparsity pattern; values, vectors, bounds, ``dt`` and ``rho`` are
+    <= 8, no border unless ``border=True``) with one sparsity pattern; values, vectors, bounds, ``dt`` and ``rho`` are
     each instance's own.  ``wide_band=True`` creates the batch through ``pgf_batch_create_ex`` with
     ``PGF_BATCH_WIDE_BAND``: instances on the wide route (block size 16, 32 or 64) are admitted
     too, when they share the block size and the setting of the factor / solve split.  What the
-    library refuses (dense and banded mixed, different patterns, a wide band without the flag, a
-    border) is raised as ``ValueError`` with its message.  ``self.band`` tells which kind the
+    library refuses (dense and banded mixed, different patterns, a wide band or a border without
+    its flag) is raised as ``ValueError`` with its message.  ``self.band`` tells which kind the
     device batch is, ``self.band_block`` the block size of a band batch (``None`` otherwise).
+
+    ``border=True`` (``PGF_BATCH_BORDER``) admits bordered instances on the narrow route: block size
+    8 and one border size k (1..64) for all of them.  Each instance runs the factor phase of the
+    bordered solve only where its matrix changed, the solve phase every step; the results are those
+    of the single handles bit for bit.  ``self.band_border`` is k for a band batch (0 without a
+    border, ``None`` on a dense batch), ``border_stats()`` counts the phases per instance.  A border
+    on a wide remainder and a border under ``band_ctl`` are refused.
 
     ``band_ctl=True`` (``PGF_BATCH_BAND_CTL``, alone or with ``wide_band``) opens the device-resident
     step controller (``ctl_init / ctl_iterate / ctl_read``) to a band batch; without it a band batch
@@ -97,7 +104,8 @@ class BatchedDeviceNewton:
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
-                 world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False):
+                 world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False,
+                 border=False):
         import ctypes as C
         import math
 
@@ -131,6 +139,8 @@ class BatchedDeviceNewton:
         self.band_block = None
         self.wide_band = bool(wide_band)
         self.band_ctl = bool(band_ctl)
+        self.border = bool(border)
+        self.band_border = None
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
         if self.count and not self.sequential:
@@ -144,14 +154,16 @@ class BatchedDeviceNewton:
             self._b = b
             if self.band:
                 self.band_block = int(self.solvers[0]._hd.plan.block_size)
+                self.band_border = int(self.solvers[0]._hd.plan.k)
             self._begin_outer()
 
     def _create(self, lib, handles, out):
         """The device batch over ``handles``: through ``pgf_batch_create_ex`` with
-        ``PGF_BATCH_WIDE_BAND`` and / or ``PGF_BATCH_BAND_CTL`` when ``wide_band`` / ``band_ctl`` was
-        asked for, ``pgf_batch_create`` otherwise."""
+        ``PGF_BATCH_WIDE_BAND``, ``PGF_BATCH_BAND_CTL`` and / or ``PGF_BATCH_BORDER`` when ``wide_band``
+        / ``band_ctl`` / ``border`` was asked for, ``pgf_batch_create`` otherwise."""
         flags = (self._lib.BATCH_WIDE_BAND if self.wide_band else 0) | \
-            (self._lib.BATCH_BAND_CTL if getattr(self, "band_ctl", False) else 0)
+            (self._lib.BATCH_BAND_CTL if getattr(self, "band_ctl", False) else 0) | \
+            (self._lib.BATCH_BORDER if getattr(self, "border", False) else 0)
         if flags:
             return lib.pgf_batch_create_ex(handles, self.count, flags, out)
         return lib.pgf_batch_create(handles, self.count, out)
@@ -360,6 +372,20 @@ class BatchedDeviceNewton:
         self._lib.check(self._lib.load().pgf_batch_debug_band_wide_stats(
             self._b, red.ctypes.data_as(ip), sol.ctypes.data_as(ip), C.byref(lean)), batch=self._b)
         return red, sol, lean.value
+
+    def border_stats(self):
+        """(factor_phases[count], solve_phases[count]) of a bordered band batch
+        (``pgf_batch_debug_border_stats``): per instance the factor phases (assembly, Y, S and its
+        factor) and the solve phases it ran since the batch was created, counted on the device.
+        Zeros on any other batch.  Device batch only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        fac = np.zeros(self.count, dtype=np.int32)
+        sol = np.zeros(self.count, dtype=np.int32)
+        ip = self._C.POINTER(self._C.c_int)
+        self._lib.check(self._lib.load().pgf_batch_debug_border_stats(
+            self._b, fac.ctypes.data_as(ip), sol.ctypes.data_as(ip)), batch=self._b)
+        return fac, sol
 
     def ctl_stats(self):
         """(pivot_rejects[count], guard_rejects[count]) of a ``band_ctl`` batch

@@ -1,8 +1,9 @@
 // The banded half of the batch driver: pgf_batch_* for banded handles of one sparsity pattern, all
-// on the narrow route or (PGF_BATCH_WIDE_BAND) all on the wide one (pgf_api_batch.hip hands over in
-// one line each; pgf_api_internal.h lists what is shared).  One launch sequence per Newton step for
+// on the narrow route -- with (PGF_BATCH_BORDER) one size of border or none -- or
+// (PGF_BATCH_WIDE_BAND) all on the wide one (pgf_api_batch.hip hands over in one line each;
+// pgf_api_internal.h lists what is shared).  One launch sequence per Newton step for
 // every instance -- the batched twins of the banded kernels (pgf_band_batch.hip, and
-// pgf_band_wide_batch.hip for the wide reduction) around the vector kernels the dense batch already
+// pgf_band_wide_batch.hip for the wide reduction, pgf_border_batch.hip for a border) around the vector kernels the dense batch already
 // has -- one host synchronisation per step (pgf_batch_sync) and one status copy for the whole batch.
 #include <algorithm>
 #include <cmath>
@@ -16,6 +17,7 @@ static const char *const k_zero_pivot = "zero or non-finite pivot in the banded 
 
 int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   const bool wide_ok = (flags & PGF_BATCH_WIDE_BAND) != 0;
+  const bool border_ok = (flags & PGF_BATCH_BORDER) != 0;
   const pgf_handle h0 = handles[0];
   // the reason goes to the offending handle and to the first one, where a caller of
   // pgf_batch_create looks for it
@@ -34,7 +36,13 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     const SparseDev &sp = h->sp;
     if (!sp.active || !sp.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
-    if (sp.bk) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
+    if (sp.bk && !border_ok) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
+    if (sp.bk != h0->sp.bk) return fail(h, PGF_INVALID, "batch: banded instances must share the border size");
+    if (sp.bk && sp.B != 8)
+      return fail(h, PGF_INVALID,
+                  "batch: a bordered band joins a device batch on the narrow route only (block size 8)");
+    if (sp.bk && (flags & PGF_BATCH_BAND_CTL))
+      return fail(h, PGF_INVALID, "batch: the device-resident controller does not drive a bordered band batch");
     if (sp.B != 8 && !wide_ok)
       return fail(h, PGF_INVALID, "batch: a wide band (block size above 8) cannot join a device batch");
     const SparseDev &s0 = h0->sp;
@@ -76,6 +84,13 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   sh.nnzH = s0.nnzH;
   sh.nnzJ = s0.nnzJ;
   sh.nred = (N + 255) / 256;
+  // a border: the sizes every instance shares (bk was compared; bkp, Nb, bnchunk, nred follow from
+  // it and N), the status block with the handle's own stride 3 nred + 4
+  sh.bk = s0.bk;
+  sh.bkp = s0.bkp;
+  sh.Nb = s0.bk ? s0.Nb : N;
+  sh.bnchunk = s0.bnchunk;
+  if (s0.bk) sh.nred = s0.nred;
   sh.bstride = s0.bstride;
   sh.pos = s0.pos;
   sh.Hptr = s0.Hptr;
@@ -96,6 +111,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       (e = hipMalloc((void **)&b->btab, cnt * sizeof(BandInst))) != hipSuccess ||
       (e = hipMalloc((void **)&b->ctl, cnt * 4 * sizeof(int))) != hipSuccess ||
       (e = hipMalloc((void **)&b->wcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
+      (e = hipMalloc((void **)&b->bcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
       (e = hipMalloc((void **)&b->norm_out, cnt * sizeof(double))) != hipSuccess ||
       (e = hipMalloc((void **)&b->red4, cnt * 4 * ((size_t)(N + 255) / 256 + 1) * sizeof(double))) != hipSuccess ||
       (e = hipMalloc((void **)&b->meas_out, cnt * 4 * sizeof(double))) != hipSuccess ||
@@ -183,6 +199,16 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     u.bMr = sp.bMr;
     u.bMl = sp.bMl;
     u.wcnt = b->wcnt + 2 * i;
+    u.bC = sp.bC;
+    u.bDd = sp.bDd;
+    u.bY = sp.bY;
+    u.bS = sp.bS;
+    u.bpart = sp.bpart;
+    u.bpartv = sp.bpartv;
+    u.brb = sp.brb;
+    u.bz = sp.bz;
+    u.bsflags = sp.bsflags;
+    u.bcnt = b->bcnt + 2 * i;
     u.bneg = sp.bneg;
     u.flags = h->fac.flags;
     u.stat = b->bstat + S * i;
@@ -218,6 +244,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       (e = hipMemcpy(b->btab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess ||
       (e = hipMemset(b->ctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
       (e = hipMemset(b->wcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
+      (e = hipMemset(b->bcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
       (e = hipMemset(b->bstat, 0, cnt * S * sizeof(double))) != hipSuccess ||
       (e = hipMemcpy(b->ps, b->h_ps, cnt * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) {
     pgf_batch_destroy(b);
@@ -230,6 +257,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
 void band_batch_free(pgf_batch b) {
   if (b->btab) (void)hipFree(b->btab);
   if (b->wcnt) (void)hipFree(b->wcnt);
+  if (b->bcnt) (void)hipFree(b->bcnt);
   if (b->bstat) (void)hipFree(b->bstat);
   if (b->h_bstat) (void)hipHostFree(b->h_bstat);
   if (b->band_guard) (void)hipFree(b->band_guard);
@@ -246,7 +274,10 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 // needed, reduction, residual, step update, the evaluation made ahead of the sync, and the copy
 // that brings the batch's status block to the host.  On the wide route the reduction is the launch
 // sequence of pgf_band_wide_batch.hip: extract, one invert + one reduce launch per level, last, one
-// back launch per level, residual -- each instance in the phase its ctl[0] says.
+// back launch per level, residual -- each instance in the phase its ctl[0] says.  With a border
+// (narrow route only) the assembly is the bordered one with its factor phase behind it -- Y, S and
+// the factor of S, for the instances with ctl[0] != 0 -- and the reduction sits inside the solve
+// phase, which every live instance runs (pgf_border_batch.hip).
 //
 // band_batch_enqueue_step is the sequence up to the step update, for pgf_batch_step_async and for the
 // device-resident controller's loop alike.  lean_allowed: the caller knows that every instance
@@ -267,6 +298,21 @@ void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean
   bandb_launch_rhs(s, b->btab, b->B, b->bsh);
   // instances whose band is still valid return at once (ctl[0] == 0); when the host knows that
   // none assembles (a Simplified step behind a good one), the launches are skipped
+  if (b->bsh.bk) {
+    // The factor phase's workgroups return at once where the band, Y and the factor of S are still
+    // valid; when the host knows that no instance factors, all its launches are left out.
+    if (recompute || !lean_allowed) {
+      borderb_launch_factor(s, b->btab, b->B, b->bsh);
+      ++b->stat_band_assemblies;
+    } else {
+      ++b->stat_band_lean;
+    }
+    borderb_launch_solve(s, b->btab, b->B, b->bsh);
+    ++b->stat_band_reductions;
+    bandb_launch_step_update(s, b->btab, b->B, b->bsh);
+    b->eval_fresh = false;
+    return;
+  }
   if (recompute || !lean_allowed) {
     bandb_launch_assemble(s, b->btab, b->B, b->bsh);
     ++b->stat_band_assemblies;
@@ -309,7 +355,12 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 // idle (band_batch_sync).  On the wide route with the split on, the handle holds the factors the
 // batch's reduction left (the instance's flags were clean, or it would not be here): sp.kept says so
 // for the length of the repair, and the corrections are solve phases against the instance's own
-// multipliers, as the single handle's would be.  Returns 0 when the instance's step is good now.
+// multipliers, as the single handle's would be.  With a border, band_refine -> sp_cyclic_solve ->
+// sp_border_solve and sp_cyclic_residual -> sp_border_residual run the solve phase against the
+// handle's bY, bS and bsflags, which ARE the instance's and hold what the batch's factor phase left
+// (valid: the instance's flags were clean); nothing on that path tests fac.factored or assembles
+// again (read: band_refine, sp_cyclic_solve, sp_border_solve).  Returns 0 when the instance's step
+// is good now.
 static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out) {
   pgf_handle h = b->hs[i];
   SparseDev &sp = h->sp;
@@ -454,6 +505,22 @@ extern "C" int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int
   for (int i = 0; i < b->B; ++i) {
     if (reductions) reductions[i] = cnt[2 * i];
     if (solve_phases) solve_phases[i] = cnt[2 * i + 1];
+  }
+  return PGF_OK;
+}
+
+extern "C" int pgf_batch_debug_border_stats(pgf_batch b, int *factor_phases, int *solve_phases) {
+  if (!b) return PGF_INVALID;
+  if (!factor_phases && !solve_phases) return PGF_OK;
+  std::vector<int> cnt((size_t)2 * b->B, 0);
+  if (b->band && b->bsh.bk && b->bcnt) {
+    (void)hipSetDevice(b->device);
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    BHIPCHK(b, hipMemcpy(cnt.data(), b->bcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < b->B; ++i) {
+    if (factor_phases) factor_phases[i] = cnt[2 * (size_t)i];
+    if (solve_phases) solve_phases[i] = cnt[2 * (size_t)i + 1];
   }
   return PGF_OK;
 }

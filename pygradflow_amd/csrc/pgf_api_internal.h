@@ -312,6 +312,9 @@ struct pgf_batch_s {
   // without inversion launches (pgf_batch_debug_band_wide_stats)
   int *wcnt = nullptr;
   int stat_band_lean = 0;
+  // bordered narrow route: per instance (factor phases, solve phases) counted on the device
+  // (pgf_batch_debug_border_stats); stat_band_lean counts the steps enqueued without factor-phase launches
+  int *bcnt = nullptr;
   // created with PGF_BATCH_BAND_CTL: the device-resident controller is open to this band batch.
   // flags_out / diff_out are allocated as for a dense batch and written by kbb_step_final;
   // band_guard: per instance (guard on, refine_tol) as pgf_batch_ctl_init found them on the handles;

@@ -233,7 +233,8 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 }
 
 // the walk of sp_launch_bcr_solve over the same plan, every launch with the instances in grid.y
-void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
+// (a bordered batch passes a shape whose N, nb are those of the band rows, and residual == false)
+void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual) {
   if (!sh.N) return;
   const int nb = sh.nb;
   const unsigned Bu = (unsigned)B;
@@ -268,7 +269,7 @@ void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandSha
     if (ne > 0)
       hipLaunchKernelGGL(kbb_bcr_back, dim3(ne, Bu), dim3(64), 0, s, tab, sh, plan.lev[q].set, bs, bs, 2 * bs);
   }
-  hipLaunchKernelGGL(kbb_band_residual, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh);
+  if (residual) hipLaunchKernelGGL(kbb_band_residual, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh);
 }
 
 void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {

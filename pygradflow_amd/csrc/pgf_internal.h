@@ -278,8 +278,9 @@ struct BatchScalars {
 #define BPS_STRIDE 8
 
 // ---- banded batch (pgf_band_batch.hip) ---------------------------------------
-// One entry per instance of a batch of banded handles (no border, ONE sparsity pattern; block size 8,
-// or 16 / 32 / 64 for every instance -- the wide route, pgf_band_wide_batch.hip): what differs between the instances -- the values of H and J, the band, the work blocks
+// One entry per instance of a batch of banded handles (ONE sparsity pattern; block size 8, with the
+// same border of up to 64 nodes or none -- pgf_border_batch.hip -- or 16 / 32 / 64 for every instance
+// -- the wide route, pgf_band_wide_batch.hip): what differs between the instances -- the values of H and J, the band, the work blocks
 // of the cyclic reduction, the vectors, the flags.  The batched twins of the banded kernels pick
 // their instance with blockIdx.y; the pattern arrays, equal by construction, come from instance 0
 // (BandShape) so that every workgroup hits the same lines.  The vector kernels shared with the
@@ -292,6 +293,11 @@ struct BandInst {
   double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
   int *wcnt;  // wide route: [0] reductions, [1] solve phases this instance's workgroups ran
+  // bordered narrow route (pgf_border_batch.hip; SparseDev names them): C and D behind the band, Y,
+  // the factor of S, the chunk sums, the border part of the right-hand side / solution, the flags
+  // of S; bcnt: [0] factor phases, [1] solve phases this instance ran
+  double *bC, *bDd, *bY, *bS, *bpart, *bpartv, *brb, *bz;
+  int *bsflags, *bcnt;
   // the instance's slice of the batch's status block: [0, 2 nred) residual pairs, [2 nred, 3 nred)
   // partial sums of the step update, [3 nred, 3 nred + 4) pivot flags (as SparseDev::bred)
   double *stat;
@@ -305,6 +311,9 @@ struct BandInst {
 struct BandShape {
   int n, m, N, nb, bw, ldb, nnzH, nnzJ, nred;
   int B, split;  // block size of the reduction; wide route: the factor / solve split is on
+  // bordered band (bk != 0): N = n + m is the size of the vector kernels, the reduction runs over
+  // the Nb = N - bk band rows, nred = max(ceil(N / 256), ceil(Nb / 256) + 1) as on the handle
+  int bk, bkp, Nb, bnchunk;
   int64_t bstride;
   const int *pos, *Hptr, *Hrow, *Hcol, *Hslot, *Jptr, *Jcol, *Jslot, *JTptr, *JTrow, *JTmap;
 };
@@ -315,8 +324,15 @@ void bandb_launch_rhs(hipStream_t s, const BandInst *tab, int B, const BandShape
 // band of the instances with ctl[0] != 0: zero, diagonal, entries of H and J
 void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // cyclic reduction of every instance that is not frozen (one launch plan: it depends on N only),
-// then the residual of the solution into the status block
-void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// then the residual of the solution into the status block (residual == false: left out; the
+// bordered route reduces over sh.N = Nb rows and has a residual of its own)
+void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual = true);
+// bordered narrow route (pgf_border_batch.hip).  Factor phase of the instances with ctl[0] != 0:
+// band, C and D cleared and assembled, Y = inv(B) C by the panel reduction, S and its factor.
+void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// solve phase of every instance that is not frozen, guard included: the border part of the
+// right-hand side and the whole of it saved, the 8 x 8 reduction of B, z, x_a, the residual
+void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // the same on the wide route (sh.B > 8): per instance the reduction, or with the split on and
 // ctl[0] == 0 the solve phase against its kept factors; lean: the host knows that no instance reduces
 void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean);

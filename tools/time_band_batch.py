@@ -3,7 +3,8 @@ one pattern, ``BatchedDeviceNewton`` as a band batch and with ``sequential=True`
 session.
 
     python tools/time_band_batch.py [--steps 200] [--warmup 20] [--reps 7] [--batches 1,8,64,256]
-                                    [--workloads sparse_ocp,multistate_ocp,box_qp] [--out FILE]
+                                    [--workloads sparse_ocp,multistate_ocp,box_qp,budget_box_qp,bordered_lq_k4,...]
+                                    [--out FILE]
                                     [--policy Full|Simplified] [--routes batch,sequential]
     python tools/time_band_batch.py --controller [--iterations 20] [--warmup 3] [--reps 5]
                                     [--batches 1,8,64,256] [--workloads sparse_ocp,multistate_ocp_w32]
@@ -14,6 +15,13 @@ The workloads ``multistate_ocp_w16``, ``_w32``, ``_w64`` are on the wide route (
 profiles/band_batch_wide_timing.jsonl unless --out says otherwise.  --policy Simplified times the
 steps behind the first one of an outer step: the solve phase against kept factors on the wide
 route (the batch's lean step).  --routes with one route times that route alone (no ratio line).
+
+The workloads ``budget_box_qp`` (k = 1), ``bordered_lq_k4`` and ``bordered_lq_k64`` are BORDERED bands
+on the narrow route: their batch is created with ``border=True`` and their rows go to
+profiles/band_batch_border_timing.jsonl unless --out says otherwise.  (``bordered_lq`` with a band
+of half-width 3 in H comes out of the plan's ordering with half-bandwidth 9, the wide route, which
+a bordered batch refuses: the two workloads have half-width 2, half-bandwidth 6.)  Under Simplified
+every step behind the first runs the solve phase alone, without a factor-phase launch.
 
 A step is ``step_local()``: the Newton step of every instance, its host synchronisation and the
 residual norms of the new points -- what a controller pays per step on either route.  One JSON line
@@ -61,8 +69,24 @@ WORKLOADS = {
     "multistate_ocp_w16": ("multistate_ocp(200, 4, 2)", lambda i: problems.multistate_ocp(200, 4, 2, seed=i)),  # N = 2000
     "multistate_ocp_w32": ("multistate_ocp(200, 8, 4)", lambda i: problems.multistate_ocp(200, 8, 4, seed=i)),  # N = 4000
     "multistate_ocp_w64": ("multistate_ocp(100, 16, 8)", lambda i: problems.multistate_ocp(100, 16, 8, seed=i)),  # N = 4000
+    # bordered bands on the narrow route: k = 1, 4, 64 border nodes
+    "budget_box_qp": ("budget_box_qp(4096)", lambda i: _bordered(problems.budget_box_qp(4096, seed=i))),  # N = 4097
+    "bordered_lq_k4": ("bordered_lq(3000, 2, 1000, 2, 2)", lambda i: _bordered_lq(3000, 2, 1000, 2, 2, i)),  # N = 4004
+    "bordered_lq_k64": ("bordered_lq(3000, 2, 1000, 32, 32)", lambda i: _bordered_lq(3000, 2, 1000, 32, 32, i)),  # N = 4064
 }
 WIDE = ("multistate_ocp_w16", "multistate_ocp_w32", "multistate_ocp_w64")
+BORDERED = ("budget_box_qp", "bordered_lq_k4", "bordered_lq_k64")
+
+
+def _bordered(prob):
+    prob.pgf_border = "auto"
+    return prob
+
+
+def _bordered_lq(n0, bw, mloc, kv, kc, seed):
+    from tests.band_util import bordered_lq  # (the generator the bordered tests share)
+
+    return bordered_lq(n0, bw, mloc, kv, kc, seed)
 
 
 def timed(run, steps):
@@ -169,6 +193,8 @@ def main():
     assert routes and set(routes) <= {"batch", "sequential"}, routes
     if a.out is None:
         name = "band_batch_wide_timing.jsonl" if all(k in WIDE for k in keys) else "band_batch_timing.jsonl"
+        if all(k in BORDERED for k in keys):
+            name = "band_batch_border_timing.jsonl"
         if a.controller:
             name = "band_batch_ctl_timing.jsonl"
         a.out = os.path.join(REPO, "profiles", name)
@@ -193,8 +219,9 @@ def main():
                 p.pgf_force_band = True
                 probs.append(p)
             runs = {r: BatchedDeviceNewton(lambda i: probs[i], B, a.policy, 1.0, 1.0, sequential=(r == "sequential"),
-                                           wide_band=key in WIDE) for r in routes}
+                                           wide_band=key in WIDE, border=key in BORDERED) for r in routes}
             assert "batch" not in runs or runs["batch"].band
+            assert "batch" not in runs or (runs["batch"].band_border > 0) == (key in BORDERED)
             N = probs[0].num_vars + probs[0].num_cons
             for run in runs.values():
                 timed(run, a.warmup)
