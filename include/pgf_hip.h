@@ -309,15 +309,32 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * against the Y and the factor of S the batch left there.  The results are, bit for bit, those of
  * the single handles on their panel route (PGF_BORDER_MULTI=0, the column-by-column cross-check,
  * stays a single-handle switch: under it the two are not bit-comparable).
- * pgf_batch_debug_border_stats counts the phases per instance.  Still refused: a border on a wide
- * remainder, with or without PGF_BATCH_WIDE_BAND ("batch: a bordered band joins a device batch on
- * the narrow route only (block size 8)"), and PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL on handles
- * that have a border ("batch: the device-resident controller does not drive a bordered band
- * batch").  Handles without a border behave with the flag as without it. */
+ * pgf_batch_debug_border_stats counts the phases per instance.  Refused under these flags: a border
+ * on a wide remainder, with or without PGF_BATCH_WIDE_BAND ("batch: a bordered band joins a device
+ * batch on the narrow route only (block size 8)"; PGF_BATCH_WIDE_BORDER, below, admits it), and
+ * PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL on handles that have a border ("batch: the device-resident
+ * controller does not drive a bordered band batch").  Handles without a border behave with the flag
+ * as without it.
+ *
+ * PGF_BATCH_WIDE_BORDER, valid only as PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND | PGF_BATCH_WIDE_BORDER
+ * (the bit without both of the others is PGF_INVALID), admits BORDERED instances whose remainder
+ * is on the WIDE route: block size 16, 32 or 64, ONE block size and ONE border size 1 <= k <= 64,
+ * and the factor / solve split in force on every handle (refused otherwise with "batch: a bordered
+ * wide band needs the factor / solve split").  The factor phase of an instance whose matrix
+ * changed: assembly, B factorised once by the factor-only reduction that keeps its multipliers,
+ * Y = inv(B) C as one panel solve against them on the FP64 matrix pipes, S and its factor.  The
+ * solve phase of every live instance, every step: v = inv(B) r_a against the kept factors, then the
+ * border part as on the narrow route.  Driven by pgf_batch_step_async / pgf_batch_sync; the results
+ * are, bit for bit, those of the single handles (PGF_BORDER_MULTI=0 stays a single-handle switch:
+ * the batch always takes the panel route).  pgf_batch_debug_border_stats counts the phases, and
+ * pgf_batch_debug_band_wide_stats the factor-only reductions and kept-factor solve phases of B,
+ * which equal them.  A border under PGF_BATCH_BAND_CTL stays refused as above.  Narrow bordered
+ * instances and instances without a border behave with the bit as under the other two alone. */
 typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BAND 1u
 #define PGF_BATCH_BAND_CTL 2u
 #define PGF_BATCH_BORDER 4u
+#define PGF_BATCH_WIDE_BORDER 8u
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);

@@ -27,6 +27,7 @@ CREATE_SPARSE = 1
 BATCH_WIDE_BAND = 1
 BATCH_BAND_CTL = 2
 BATCH_BORDER = 4
+BATCH_WIDE_BORDER = 8
 FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
 FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 

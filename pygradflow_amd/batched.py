@@ -93,7 +93,16 @@ class BatchedDeviceNewton:
     bordered solve only where its matrix changed, the solve phase every step; the results are those
     of the single handles bit for bit.  ``self.band_border`` is k for a band batch (0 without a
     border, ``None`` on a dense batch), ``border_stats()`` counts the phases per instance.  A border
-    on a wide remainder and a border under ``band_ctl`` are refused.
+    on a wide remainder (without ``wide_border``) and a border under ``band_ctl`` are refused.
+
+    ``wide_border=True`` (``PGF_BATCH_WIDE_BORDER``; it sets ``wide_band`` and ``border`` too, the
+    three bits go together) admits bordered instances whose remainder is on the wide route: one
+    block size (16, 32 or 64), one border size k, the factor / solve split on for every handle.  An
+    instance whose matrix changed factorises its band once and forms Y by one panel solve against
+    the kept factors; every step solves against them.  ``band_block`` is 16, 32 or 64 and
+    ``band_border`` is k; ``border_stats()`` counts the phases and ``band_wide_stats()`` the
+    factor-only reductions and kept-factor solves of the band, which equal them.  Host-driven steps
+    only (``band_ctl`` refuses a border); no effect with ``sequential=True``.
 
     ``band_ctl=True`` (``PGF_BATCH_BAND_CTL``, alone or with ``wide_band``) opens the device-resident
     step controller (``ctl_init / ctl_iterate / ctl_read``) to a band batch; without it a band batch
@@ -105,7 +114,7 @@ class BatchedDeviceNewton:
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
                  world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False,
-                 border=False):
+                 border=False, wide_border=False):
         import ctypes as C
         import math
 
@@ -137,9 +146,10 @@ class BatchedDeviceNewton:
         self._b = None
         self.band = False
         self.band_block = None
-        self.wide_band = bool(wide_band)
+        self.wide_border = bool(wide_border)
+        self.wide_band = bool(wide_band) or self.wide_border
         self.band_ctl = bool(band_ctl)
-        self.border = bool(border)
+        self.border = bool(border) or self.wide_border
         self.band_border = None
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
@@ -159,11 +169,14 @@ class BatchedDeviceNewton:
 
     def _create(self, lib, handles, out):
         """The device batch over ``handles``: through ``pgf_batch_create_ex`` with
-        ``PGF_BATCH_WIDE_BAND``, ``PGF_BATCH_BAND_CTL`` and / or ``PGF_BATCH_BORDER`` when ``wide_band``
-        / ``band_ctl`` / ``border`` was asked for, ``pgf_batch_create`` otherwise."""
+        ``PGF_BATCH_WIDE_BAND``, ``PGF_BATCH_BAND_CTL``, ``PGF_BATCH_BORDER`` and / or
+        ``PGF_BATCH_WIDE_BORDER`` when ``wide_band`` / ``band_ctl`` / ``border`` / ``wide_border`` was
+        asked for (``wide_border`` has set the first and the third as well: the library takes its bit
+        only with both), ``pgf_batch_create`` otherwise."""
         flags = (self._lib.BATCH_WIDE_BAND if self.wide_band else 0) | \
             (self._lib.BATCH_BAND_CTL if getattr(self, "band_ctl", False) else 0) | \
-            (self._lib.BATCH_BORDER if getattr(self, "border", False) else 0)
+            (self._lib.BATCH_BORDER if getattr(self, "border", False) else 0) | \
+            (self._lib.BATCH_WIDE_BORDER if getattr(self, "wide_border", False) else 0)
         if flags:
             return lib.pgf_batch_create_ex(handles, self.count, flags, out)
         return lib.pgf_batch_create(handles, self.count, out)
@@ -361,7 +374,10 @@ class BatchedDeviceNewton:
         """(reductions[count], solve_phases[count], lean_steps) of a wide band batch
         (``pgf_batch_debug_band_wide_stats``): per instance the wide reductions and the solve
         phases against kept factors its workgroups ran since the batch was created, and the steps
-        enqueued without inversion launches.  Zeros on a dense or narrow batch.  Device batch only."""
+        enqueued without inversion launches.  Zeros on a dense or narrow batch.  On a bordered wide
+        batch (``wide_border``): the factor-only reductions of the band and the solve phases against
+        its kept factors, equal to the columns of ``border_stats()``, and the steps enqueued without
+        any factor-phase launch.  Device batch only."""
         if self._b is None:
             raise NotImplementedError("device batch only")
         C = self._C

@@ -1,6 +1,7 @@
 // The banded half of the batch driver: pgf_batch_* for banded handles of one sparsity pattern, all
 // on the narrow route -- with (PGF_BATCH_BORDER) one size of border or none -- or
-// (PGF_BATCH_WIDE_BAND) all on the wide one (pgf_api_batch.hip hands over in one line each;
+// (PGF_BATCH_WIDE_BAND) all on the wide one, there with one size of border only under
+// PGF_BATCH_WIDE_BORDER (pgf_api_batch.hip hands over in one line each;
 // pgf_api_internal.h lists what is shared).  One launch sequence per Newton step for
 // every instance -- the batched twins of the banded kernels (pgf_band_batch.hip, and
 // pgf_band_wide_batch.hip for the wide reduction, pgf_border_batch.hip for a border) around the vector kernels the dense batch already
@@ -18,6 +19,8 @@ static const char *const k_zero_pivot = "zero or non-finite pivot in the banded 
 int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   const bool wide_ok = (flags & PGF_BATCH_WIDE_BAND) != 0;
   const bool border_ok = (flags & PGF_BATCH_BORDER) != 0;
+  // (pgf_batch_create_ex has seen to it that the bit comes with the other two)
+  const bool wide_border_ok = (flags & PGF_BATCH_WIDE_BORDER) != 0;
   const pgf_handle h0 = handles[0];
   // the reason goes to the offending handle and to the first one, where a caller of
   // pgf_batch_create looks for it
@@ -38,11 +41,15 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
     if (sp.bk && !border_ok) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
     if (sp.bk != h0->sp.bk) return fail(h, PGF_INVALID, "batch: banded instances must share the border size");
-    if (sp.bk && sp.B != 8)
+    if (sp.bk && sp.B != 8 && !wide_border_ok)
       return fail(h, PGF_INVALID,
                   "batch: a bordered band joins a device batch on the narrow route only (block size 8)");
     if (sp.bk && (flags & PGF_BATCH_BAND_CTL))
       return fail(h, PGF_INVALID, "batch: the device-resident controller does not drive a bordered band batch");
+    // (the wide border's phases are those of the handle under wide_kept, pgf_border.hip: B factorised
+    // once, every solve against the kept factors)
+    if (sp.bk && sp.B != 8 && !(sp.split && sp.bMr))
+      return fail(h, PGF_INVALID, "batch: a bordered wide band needs the factor / solve split");
     if (sp.B != 8 && !wide_ok)
       return fail(h, PGF_INVALID, "batch: a wide band (block size above 8) cannot join a device batch");
     const SparseDev &s0 = h0->sp;
@@ -275,9 +282,11 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 // that brings the batch's status block to the host.  On the wide route the reduction is the launch
 // sequence of pgf_band_wide_batch.hip: extract, one invert + one reduce launch per level, last, one
 // back launch per level, residual -- each instance in the phase its ctl[0] says.  With a border
-// (narrow route only) the assembly is the bordered one with its factor phase behind it -- Y, S and
-// the factor of S, for the instances with ctl[0] != 0 -- and the reduction sits inside the solve
-// phase, which every live instance runs (pgf_border_batch.hip).
+// (either route) the assembly is the bordered one with its factor phase behind it -- Y, S and
+// the factor of S, for the instances with ctl[0] != 0; on the wide route B is factorised there, once,
+// by the factor-only KEEP reduction -- and the solve with B sits inside the solve phase, which every
+// live instance runs: the 8 x 8 reduction, or on the wide route the solve against the kept factors
+// (pgf_border_batch.hip branches on the block size).
 //
 // band_batch_enqueue_step is the sequence up to the step update, for pgf_batch_step_async and for the
 // device-resident controller's loop alike.  lean_allowed: the caller knows that every instance
@@ -359,8 +368,14 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 // sp_border_solve and sp_cyclic_residual -> sp_border_residual run the solve phase against the
 // handle's bY, bS and bsflags, which ARE the instance's and hold what the batch's factor phase left
 // (valid: the instance's flags were clean); nothing on that path tests fac.factored or assembles
-// again (read: band_refine, sp_cyclic_solve, sp_border_solve).  Returns 0 when the instance's step
-// is good now.
+// again (read: band_refine, sp_cyclic_solve, sp_border_solve).  With a border on a wide remainder
+// sp_cyclic_solve takes its sp.bk branch before it looks at sp.kept, and sp_border_solve takes
+// wide_kept(sp) -- B > 8, split on, multipliers allocated: what band_batch_create admitted -- which
+// puts the flags of B back from bsflags[2, 4) and runs sp_launch_bw_backsolve against bMr, bMl, bL,
+// bU, bDinv: load, forward, x_0, backward, no inversion and no reduction of B (sp_launch_bw_factor
+// is called from sp_border_factor alone, which only sp_assemble reaches, and band_refine never
+// assembles).  All of these are the instance's arrays as the batch's factor phase left them.
+// Returns 0 when the instance's step is good now.
 static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out) {
   pgf_handle h = b->hs[i];
   SparseDev &sp = h->sp;

@@ -38,7 +38,12 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
 
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
-  if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER)) return PGF_INVALID;
+  if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER | PGF_BATCH_WIDE_BORDER))
+    return PGF_INVALID;
+  // (a border on a wide remainder: only together with the two flags it combines)
+  if ((flags & PGF_BATCH_WIDE_BORDER) &&
+      (flags & (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND)) != (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND))
+    return PGF_INVALID;
   const pgf_handle h0 = handles[0];
   if (!h0) return PGF_INVALID;
   for (int i = 0; i < count; ++i)  // any banded handle: a band batch, or its refusal

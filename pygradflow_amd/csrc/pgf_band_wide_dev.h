@@ -380,6 +380,78 @@ __device__ __forceinline__ void bw_x0_block(const double *__restrict__ Dinv, con
   if (tid % P == 0) X[tid / P] = x;
 }
 
+// ---- solve phase against the kept factors, a panel of kp right-hand sides (row-major, row stride
+// kp, a block's B x kp rows contiguous; kp a multiple of 16, at most 64), in place, on
+// v_mfma_f64_16x16x4_f64: (B / 16) (kp / 16) <= 16 output tiles, at most four per wavefront.
+// Forward step of one level for the kept block i: P_i -= Mr[i-s] P_{i-s} + Ml[i+s] P_{i+s}.
+template <int B>
+__device__ __forceinline__ void bw_fwd_panel_block(const double *__restrict__ Mr,
+                                                   const double *__restrict__ Ml, double *__restrict__ P,
+                                                   int kp, int nb, int s, int i) {
+  constexpr int BB = B * B;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l4 = lane >> 4, l15 = lane & 15;
+  const int le = i - s, ri = i + s;
+  const int tc = kp / 16, nt = (B / 16) * tc;
+  double *Pi = P + (int64_t)i * B * kp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;  // (uniform over the wavefront)
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
+    if (le >= 0)
+      acc = bw_tile<B>(Mr + (int64_t)le * BB, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
+    if (ri < nb)
+      acc = bw_tile<B>(Ml + (int64_t)ri * BB, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+  }
+}
+
+// X_e = inv(D_e) (F_e - L_e X_{e-s} - U_e X_{e+s}) for the eliminated block e; s == 0: the last
+// block, no neighbours.  T = F_e - ... in LDS (B x 65 doubles, row stride kp + 1), then the product.
+template <int B>
+__device__ __forceinline__ void bw_back_panel_block(const double *__restrict__ Dinv,
+                                                    const double *__restrict__ L,
+                                                    const double *__restrict__ U, double *__restrict__ P,
+                                                    int kp, int nb, int s, int e, double *T) {
+  constexpr int BB = B * B;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l4 = lane >> 4, l15 = lane & 15;
+  const int le = e - s, ri = e + s, ldt = kp + 1;
+  const bool hl = s > 0 && le >= 0, hr = s > 0 && ri < nb;
+  const int tc = kp / 16, nt = (B / 16) * tc;
+  const int64_t be = (int64_t)e * BB;
+  double *Pe = P + (int64_t)e * B * kp;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc[g] = Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
+    if (hl) acc = bw_tile<B>(L + be, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
+    if (hr) acc = bw_tile<B>(U + be, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) T[(r0 + l4 + 4 * g) * ldt + c0 + l15] = acc[g];
+  }
+  __syncthreads();  // T complete (every tile of X_e reads all its rows)
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int tt = wave + 4 * t;
+    if (tt >= nt) break;
+    const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
+    bw_double4 acc = {0.0, 0.0, 0.0, 0.0};
+    acc = bw_tile<B>(Dinv + be, B, T, ldt, r0, c0, acc, lane, false);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+  }
+}
+
 // Accuracy guard for bw <= 64: the same (max |r|, max (|K| |x| + |rhs0|)) pair per 256 rows as
 // k_band_residual (pgf_sparse.hip), which stages its rows in LDS for bw <= 10; here a row reads
 // its band entries straight from memory (up to 2 x 65 of them, L2-resident neighbours).

@@ -1,5 +1,6 @@
 // Bordered band in a device batch: the kernels of pgf_border.hip with a batch dimension, for the
-// narrow route (block size 8).  Every kernel here is the twin of a kernel of one handle: instance =
+// narrow route (block size 8) and, with the band part handed to pgf_band_wide_batch.hip, for a wide
+// remainder (block size 16, 32, 64; "wide remainder" below).  Every kernel here is the twin of a kernel of one handle: instance =
 // blockIdx.y, its pointers from the BandInst table, the pattern arrays from instance 0 and the sizes
 // (bk, bkp, Nb, bnchunk -- equal across the instances by construction) through BandShape, and then
 // the SAME device function from pgf_border_dev.h with the same arguments in the same order: the
@@ -14,6 +15,17 @@
 //
 // What the single handle does with memsets and copies is ONE twin kernel each here (B copies would
 // be B launches): kbd_border_zero, kbd_border_save.
+//
+// Wide remainder: the handle's panel route under wide_kept (pgf_border.hip).  Factor phase: assembly
+// as above, the factor-only KEEP reduction of B (bandb_launch_wide_factor), its pivot flags parked in
+// bsflags[2, 4) (kbd_border_bflags_save), Y <- C in whole B-row blocks (kbd_border_ycopy), Y <-
+// inv(B) Y as one panel solve against the kept factors (bandb_launch_wide_panel), gram, factor_S:
+// 11 + 4 L launches for L = ceil(log2(ceil(Nb / B))) levels.  Solve phase: save with the flags of B
+// put back (kbd_border_save_wide), v = inv(B) r_a against the kept factors
+// (bandb_launch_wide_kept_solve: load, L forward, x_0, L backward), then ctv, small_solve, update,
+// ctv, residual as on the narrow route: 8 + 2 L launches.  The copies and the flag kernels are
+// integer or plain moves: the contraction rules of this file do not touch them; everything that
+// multiplies on the band lives in pgf_band_wide_batch.hip beside the kernels it mirrors.
 //
 // Grid shape of the one-workgroup kernels: (1, B).  kbd_border_factor_S holds at most 32.5 KB of LDS
 // (kp = 64), kbd_border_small_solve the same: several share a CU.
@@ -78,6 +90,25 @@ __global__ __launch_bounds__(64) void kbd_mbcr_back(const BandInst *__restrict__
   b_mbcr_back(I.bD, I.bDinv, I.bL, I.bU, I.bY, sh.bkp, nb, s);
 }
 
+// ---------------------------------------------------------------- wide remainder (block 16, 32, 64)
+// The pivot flags of B, parked behind those of S once the factor-only reduction has run
+// (k_border_bflags, save): integers only.
+__global__ void kbd_border_bflags_save(const BandInst *__restrict__ tab) {
+  FINST(I);
+  if (threadIdx.x != 0) return;
+  I.bsflags[2] = I.flags[0];
+  I.bsflags[3] = I.flags[1];
+}
+
+// Y <- C over the Nb band rows, the padding rows up to whole B-row blocks zero (the handle's copy
+// and memset in front of its panel solve); rows: ceil(Nb / B) B
+__global__ void kbd_border_ycopy(const BandInst *__restrict__ tab, BandShape sh, int rows) {
+  FINST(I);
+  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= (int64_t)rows * sh.bkp) return;
+  I.bY[p] = p < (int64_t)sh.Nb * sh.bkp ? I.bC[p] : 0.0;
+}
+
 // ---------------------------------------------------------------- S and its factor
 __global__ __launch_bounds__(256) void kbd_border_gram(const BandInst *__restrict__ tab, BandShape sh) {
   FINST(I);
@@ -96,6 +127,23 @@ __global__ __launch_bounds__(256) void kbd_border_factor_S(const BandInst *__res
 __global__ void kbd_border_save(const BandInst *__restrict__ tab, BandShape sh) {
   SINST(I);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sh.Nb + sh.bk) return;
+  const double v = I.brhs[i];
+  I.brhs0[i] = v;
+  if (i >= sh.Nb) I.brb[i - sh.Nb] = v;
+}
+
+// the same in front of the wide solve phase, which leaves the pivot flags alone: those of B come
+// back from bsflags[2, 4) and flags[2], flags[3] are cleared (k_border_bflags, restore)
+__global__ void kbd_border_save_wide(const BandInst *__restrict__ tab, BandShape sh) {
+  SINST(I);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    I.flags[0] = I.bsflags[2];
+    I.flags[1] = I.bsflags[3];
+    I.flags[2] = 0;
+    I.flags[3] = 0;
+  }
   if (i >= sh.Nb + sh.bk) return;
   const double v = I.brhs[i];
   I.brhs0[i] = v;
@@ -136,6 +184,22 @@ void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const Band
   hipLaunchKernelGGL(kbd_border_set_diag, gy(sh.N + sh.bkp - sh.bk, 256, B), dim3(256), 0, s, tab, sh);
   if (sh.nnzH) hipLaunchKernelGGL(kbd_border_scatter_H, gy(sh.nnzH, 256, B), dim3(256), 0, s, tab, sh);
   if (sh.nnzJ) hipLaunchKernelGGL(kbd_border_scatter_J, gy(sh.nnzJ, 256, B), dim3(256), 0, s, tab, sh);
+  if (sh.B > 8) {
+    // Wide remainder, the panel route of sp_border_factor under wide_kept: B factorised once by the
+    // factor-only KEEP reduction, its flags parked, Y = inv(B) C as one panel solve against the
+    // kept factors (pgf_band_wide_batch.hip), all for the instances with ctl[0] != 0.
+    BandShape shB = sh;
+    shB.N = sh.Nb;
+    shB.nb = (sh.Nb + sh.B - 1) / sh.B;
+    bandb_launch_wide_factor(s, tab, B, shB);
+    hipLaunchKernelGGL(kbd_border_bflags_save, dim3(1, Bu), dim3(64), 0, s, tab);
+    const int rows = shB.nb * sh.B;
+    hipLaunchKernelGGL(kbd_border_ycopy, gy((int64_t)rows * sh.bkp, 256, B), dim3(256), 0, s, tab, sh, rows);
+    bandb_launch_wide_panel(s, tab, B, shB);
+    hipLaunchKernelGGL(kbd_border_gram, dim3(sh.bnchunk, Bu), dim3(256), 0, s, tab, sh);
+    hipLaunchKernelGGL(kbd_border_factor_S, dim3(1, Bu), dim3(256), 0, s, tab, sh);
+    return;
+  }
   const int nb = (sh.Nb + 7) / 8;
   hipLaunchKernelGGL(kbd_mbcr_extract, dim3(nb, Bu), dim3(64), 0, s, tab, sh, nb);
   int st = 1;
@@ -155,11 +219,17 @@ void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const Band
 // sp_border_solve with the guard on
 void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
   const unsigned Bu = (unsigned)B;
-  hipLaunchKernelGGL(kbd_border_save, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
-  BandShape shB = sh;  // v = inv(B) ra: the plain band's reduction over the Nb band rows
+  BandShape shB = sh;  // v = inv(B) ra over the Nb band rows
   shB.N = sh.Nb;
-  shB.nb = (sh.Nb + 7) / 8;
-  bandb_launch_solve(s, tab, B, shB, /*residual=*/false);
+  if (sh.B > 8) {  // against the factors the instance kept, with the flags of B as parked
+    hipLaunchKernelGGL(kbd_border_save_wide, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    shB.nb = (sh.Nb + sh.B - 1) / sh.B;
+    bandb_launch_wide_kept_solve(s, tab, B, shB);
+  } else {  // the plain band's reduction
+    hipLaunchKernelGGL(kbd_border_save, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    shB.nb = (sh.Nb + 7) / 8;
+    bandb_launch_solve(s, tab, B, shB, /*residual=*/false);
+  }
   hipLaunchKernelGGL(kbd_border_ctv, dim3(sh.bnchunk, Bu), dim3(256), 0, s, tab, sh);
   hipLaunchKernelGGL(kbd_border_small_solve, dim3(1, Bu), dim3(64), 0, s, tab, sh);
   hipLaunchKernelGGL(kbd_border_update, gy(sh.Nb, 256, B), dim3(256), 0, s, tab, sh);

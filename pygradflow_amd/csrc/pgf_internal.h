@@ -293,7 +293,8 @@ struct BandInst {
   double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
   int *wcnt;  // wide route: [0] reductions, [1] solve phases this instance's workgroups ran
-  // bordered narrow route (pgf_border_batch.hip; SparseDev names them): C and D behind the band, Y,
+  // bordered routes, narrow and wide (pgf_border_batch.hip; SparseDev names them): C and D behind
+  // the band, Y (whole B-row blocks on the wide route),
   // the factor of S, the chunk sums, the border part of the right-hand side / solution, the flags
   // of S; bcnt: [0] factor phases, [1] solve phases this instance ran
   double *bC, *bDd, *bY, *bS, *bpart, *bpartv, *brb, *bz;
@@ -327,15 +328,25 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 // then the residual of the solution into the status block (residual == false: left out; the
 // bordered route reduces over sh.N = Nb rows and has a residual of its own)
 void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual = true);
-// bordered narrow route (pgf_border_batch.hip).  Factor phase of the instances with ctl[0] != 0:
-// band, C and D cleared and assembled, Y = inv(B) C by the panel reduction, S and its factor.
+// bordered routes (pgf_border_batch.hip; both wrappers branch on sh.B > 8).  Factor phase of the
+// instances with ctl[0] != 0: band, C and D cleared and assembled, Y = inv(B) C by the panel reduction
+// (wide: B factorised once, Y by one panel solve against the kept factors), S and its factor.
 void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // solve phase of every instance that is not frozen, guard included: the border part of the
-// right-hand side and the whole of it saved, the 8 x 8 reduction of B, z, x_a, the residual
+// right-hand side and the whole of it saved, the 8 x 8 reduction of B (wide: the solve against the
+// kept factors), z, x_a, the residual
 void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // the same on the wide route (sh.B > 8): per instance the reduction, or with the split on and
 // ctl[0] == 0 the solve phase against its kept factors; lean: the host knows that no instance reduces
 void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean);
+// The band part of a bordered batch on the wide route (sh: the copy with N = Nb, nb = ceil(Nb / B)),
+// each phase fixed by the caller instead of read from ctl[0] alone.  For the instances with ctl[0]
+// != 0: the factor-only KEEP reduction of B (flags, inertia, kept multipliers; brhs survives), and
+// Y <- inv(B) Y as one panel solve of sh.bkp columns against those factors.  For every live
+// instance: brhs[0, Nb) <- inv(B) brhs[0, Nb) against the kept factors, flags untouched, no residual.
+void bandb_launch_wide_factor(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+void bandb_launch_wide_panel(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+void bandb_launch_wide_kept_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // (xn, yn), dx, dy and the partial sums; the new point replaces the old one, which stays in
 // (xn, yn), unless the instance met a bad pivot
 void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);

@@ -3,7 +3,8 @@ one pattern, ``BatchedDeviceNewton`` as a band batch and with ``sequential=True`
 session.
 
     python tools/time_band_batch.py [--steps 200] [--warmup 20] [--reps 7] [--batches 1,8,64,256]
-                                    [--workloads sparse_ocp,multistate_ocp,box_qp,budget_box_qp,bordered_lq_k4,...]
+                                    [--workloads sparse_ocp,multistate_ocp,box_qp,budget_box_qp,bordered_lq_k4,
+                                                 ocp_gp_w32,...]
                                     [--out FILE]
                                     [--policy Full|Simplified] [--routes batch,sequential]
     python tools/time_band_batch.py --controller [--iterations 20] [--warmup 3] [--reps 5]
@@ -22,6 +23,12 @@ profiles/band_batch_border_timing.jsonl unless --out says otherwise.  (``bordere
 of half-width 3 in H comes out of the plan's ordering with half-bandwidth 9, the wide route, which
 a bordered batch refuses: the two workloads have half-width 2, half-bandwidth 6.)  Under Simplified
 every step behind the first runs the solve phase alone, without a factor-phase launch.
+
+The workloads ``ocp_gp_w16``, ``_w32``, ``_w64`` (``ocp_global_parameter`` with three global
+parameters and the automatic border: k = 3 on block sizes 16, 32, 64) and ``bordered_lq_w16``
+(``bordered_lq(3000, 3, 1000, 2, 2)``: k = 4, half-bandwidth 9, block size 16) are BORDERED bands on
+the WIDE route: their batch is created with ``wide_border=True`` and their rows go to
+profiles/band_batch_wide_border_timing.jsonl unless --out says otherwise.
 
 A step is ``step_local()``: the Newton step of every instance, its host synchronisation and the
 residual norms of the new points -- what a controller pays per step on either route.  One JSON line
@@ -73,9 +80,18 @@ WORKLOADS = {
     "budget_box_qp": ("budget_box_qp(4096)", lambda i: _bordered(problems.budget_box_qp(4096, seed=i))),  # N = 4097
     "bordered_lq_k4": ("bordered_lq(3000, 2, 1000, 2, 2)", lambda i: _bordered_lq(3000, 2, 1000, 2, 2, i)),  # N = 4004
     "bordered_lq_k64": ("bordered_lq(3000, 2, 1000, 32, 32)", lambda i: _bordered_lq(3000, 2, 1000, 32, 32, i)),  # N = 4064
+    # bordered bands on the wide route: k = 3 global parameters on blocks 16, 32, 64; k = 4 on block 16
+    "ocp_gp_w16": ("ocp_global_parameter(200, 4, 2, 3)",
+                   lambda i: _bordered(problems.ocp_global_parameter(200, 4, 2, 3, seed=i))),  # N = 2003
+    "ocp_gp_w32": ("ocp_global_parameter(200, 8, 4, 3)",
+                   lambda i: _bordered(problems.ocp_global_parameter(200, 8, 4, 3, seed=i))),  # N = 4003
+    "ocp_gp_w64": ("ocp_global_parameter(100, 16, 8, 3)",
+                   lambda i: _bordered(problems.ocp_global_parameter(100, 16, 8, 3, seed=i))),  # N = 4003
+    "bordered_lq_w16": ("bordered_lq(3000, 3, 1000, 2, 2)", lambda i: _bordered_lq(3000, 3, 1000, 2, 2, i)),  # N = 4004
 }
 WIDE = ("multistate_ocp_w16", "multistate_ocp_w32", "multistate_ocp_w64")
 BORDERED = ("budget_box_qp", "bordered_lq_k4", "bordered_lq_k64")
+WIDE_BORDERED = ("ocp_gp_w16", "ocp_gp_w32", "ocp_gp_w64", "bordered_lq_w16")
 
 
 def _bordered(prob):
@@ -195,6 +211,8 @@ def main():
         name = "band_batch_wide_timing.jsonl" if all(k in WIDE for k in keys) else "band_batch_timing.jsonl"
         if all(k in BORDERED for k in keys):
             name = "band_batch_border_timing.jsonl"
+        if all(k in WIDE_BORDERED for k in keys):
+            name = "band_batch_wide_border_timing.jsonl"
         if a.controller:
             name = "band_batch_ctl_timing.jsonl"
         a.out = os.path.join(REPO, "profiles", name)
@@ -219,9 +237,11 @@ def main():
                 p.pgf_force_band = True
                 probs.append(p)
             runs = {r: BatchedDeviceNewton(lambda i: probs[i], B, a.policy, 1.0, 1.0, sequential=(r == "sequential"),
-                                           wide_band=key in WIDE, border=key in BORDERED) for r in routes}
+                                           wide_band=key in WIDE, border=key in BORDERED,
+                                           wide_border=key in WIDE_BORDERED) for r in routes}
             assert "batch" not in runs or runs["batch"].band
-            assert "batch" not in runs or (runs["batch"].band_border > 0) == (key in BORDERED)
+            assert "batch" not in runs or (runs["batch"].band_border > 0) == (key in BORDERED + WIDE_BORDERED)
+            assert "batch" not in runs or key not in WIDE_BORDERED or runs["batch"].band_block > 8
             N = probs[0].num_vars + probs[0].num_cons
             for run in runs.values():
                 timed(run, a.warmup)
