@@ -17,11 +17,8 @@ ARCH = "gfx950"
 SOURCES = [
     ("pgf_kernels.hip", ["-ffp-contract=off"]),
     ("pgf_sparse.hip", ["-ffp-contract=off"]),
-    ("pgf_band_batch.hip", ["-ffp-contract=off"]),
     ("pgf_band_wide.hip", []),
-    ("pgf_band_wide_batch.hip", []),  # (the contraction rules of the kernels it mirrors)
     ("pgf_border.hip", ["-ffp-contract=off"]),
-    ("pgf_border_batch.hip", ["-ffp-contract=off"]),
     ("pgf_ldlt.hip", ["-DPGF_RECIP_ONE_STEP"] if os.environ.get("PGF_BUILD_RECIP1") else []),
     ("pgf_factor2.hip", []),
     ("pgf_update_plan.hip", []),

@@ -3,9 +3,10 @@
 // (PGF_BATCH_WIDE_BAND) all on the wide one, there with one size of border only under
 // PGF_BATCH_WIDE_BORDER (pgf_api_batch.hip hands over in one line each;
 // pgf_api_internal.h lists what is shared).  One launch sequence per Newton step for
-// every instance -- the batched twins of the banded kernels (pgf_band_batch.hip, and
-// pgf_band_wide_batch.hip for the wide reduction, pgf_border_batch.hip for a border) around the vector kernels the dense batch already
-// has -- one host synchronisation per step (pgf_batch_sync) and one status copy for the whole batch.
+// every instance -- the batched twins of the banded kernels (pgf_sparse.hip, pgf_band_wide.hip for
+// the wide reduction, pgf_border.hip for a border) around the vector kernels the dense batch
+// already has -- one host synchronisation per step (pgf_batch_sync) and one status copy for the whole
+// batch.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -80,36 +81,11 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   const int N = b->n + b->m;
   BandShape &sh = b->bsh;
   const SparseDev &s0 = h0->sp;
+  // the sizes every instance shares, a border's included (bk was compared; bkp, Nb, bnchunk, nred
+  // follow from it and N), the status block with the handle's own stride 3 nred + 4
+  sh = band_shape_of(s0, N);
   sh.n = b->n;
   sh.m = b->m;
-  sh.N = N;
-  sh.B = s0.B;
-  sh.split = (s0.B > 8 && s0.split && s0.bMr) ? 1 : 0;
-  sh.nb = (N + sh.B - 1) / sh.B;
-  sh.bw = s0.bw;
-  sh.ldb = s0.ldb;
-  sh.nnzH = s0.nnzH;
-  sh.nnzJ = s0.nnzJ;
-  sh.nred = (N + 255) / 256;
-  // a border: the sizes every instance shares (bk was compared; bkp, Nb, bnchunk, nred follow from
-  // it and N), the status block with the handle's own stride 3 nred + 4
-  sh.bk = s0.bk;
-  sh.bkp = s0.bkp;
-  sh.Nb = s0.bk ? s0.Nb : N;
-  sh.bnchunk = s0.bnchunk;
-  if (s0.bk) sh.nred = s0.nred;
-  sh.bstride = s0.bstride;
-  sh.pos = s0.pos;
-  sh.Hptr = s0.Hptr;
-  sh.Hrow = s0.Hrow;
-  sh.Hcol = s0.Hcol;
-  sh.Hslot = s0.Hslot;
-  sh.Jptr = s0.Jptr;
-  sh.Jcol = s0.Jcol;
-  sh.Jslot = s0.Jslot;
-  sh.JTptr = s0.JTptr;
-  sh.JTrow = s0.JTrow;
-  sh.JTmap = s0.JTmap;
   const size_t cnt = (size_t)count, S = (size_t)3 * sh.nred + 4;
   (void)hipSetDevice(b->device);
   hipError_t e;
@@ -192,33 +168,9 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     t.ps = b->ps + (size_t)BPS_STRIDE * i;
     t.flags = h->fac.flags;
     BandInst &u = btab[i];
-    u.Hval = sp.Hval;
-    u.Jval = sp.Jval;
-    u.band = sp.band;
-    u.brhs = sp.brhs;
-    u.brhs0 = sp.brhs0;
-    u.bres = sp.bres;
-    u.bD = sp.bD;
-    u.bL = sp.bL;
-    u.bU = sp.bU;
-    u.bDinv = sp.bDinv;
-    u.bF = sp.bF;
-    u.bMr = sp.bMr;
-    u.bMl = sp.bMl;
+    u = band_inst_of(sp, h->fac.flags, b->bstat + S * i);
     u.wcnt = b->wcnt + 2 * i;
-    u.bC = sp.bC;
-    u.bDd = sp.bDd;
-    u.bY = sp.bY;
-    u.bS = sp.bS;
-    u.bpart = sp.bpart;
-    u.bpartv = sp.bpartv;
-    u.brb = sp.brb;
-    u.bz = sp.bz;
-    u.bsflags = sp.bsflags;
     u.bcnt = b->bcnt + 2 * i;
-    u.bneg = sp.bneg;
-    u.flags = h->fac.flags;
-    u.stat = b->bstat + S * i;
     u.lb = h->lb;
     u.ub = h->ub;
     u.q = h->q;
@@ -280,13 +232,13 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 // The step sequence of batch_enqueue_step for banded instances: eval, mask, rhs, assembly where
 // needed, reduction, residual, step update, the evaluation made ahead of the sync, and the copy
 // that brings the batch's status block to the host.  On the wide route the reduction is the launch
-// sequence of pgf_band_wide_batch.hip: extract, one invert + one reduce launch per level, last, one
+// sequence of pgf_band_wide.hip: extract, one invert + one reduce launch per level, last, one
 // back launch per level, residual -- each instance in the phase its ctl[0] says.  With a border
 // (either route) the assembly is the bordered one with its factor phase behind it -- Y, S and
 // the factor of S, for the instances with ctl[0] != 0; on the wide route B is factorised there, once,
 // by the factor-only KEEP reduction -- and the solve with B sits inside the solve phase, which every
 // live instance runs: the 8 x 8 reduction, or on the wide route the solve against the kept factors
-// (pgf_border_batch.hip branches on the block size).
+// (pgf_border.hip branches on the block size).
 //
 // band_batch_enqueue_step is the sequence up to the step update, for pgf_batch_step_async and for the
 // device-resident controller's loop alike.  lean_allowed: the caller knows that every instance

@@ -1,5 +1,5 @@
 // Device bodies of the narrow banded step (half-bandwidth <= 8, 8 x 8 block cyclic reduction).
-// pgf_sparse.hip wraps each in the kernel of a single handle, pgf_band_batch.hip in its batched
+// pgf_sparse.hip wraps each in the kernel of a single handle and, further down, in its batched
 // twin (instance = blockIdx.y, pointers from the instance's BandInst): the same function with the
 // same arguments in the same order, so that both routes compute the same bits.  The bodies index
 // their work with blockIdx.x / threadIdx.x only.

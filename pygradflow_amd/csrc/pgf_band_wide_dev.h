@@ -1,6 +1,6 @@
 // Device-side bodies of the wide block cyclic reduction (B x B blocks, B in {16, 32, 64}): shared by
 // the kernels of one handle (pgf_band_wide.hip, which describes the algorithm and the storage) and
-// their batched twins (pgf_band_wide_batch.hip: instance = blockIdx.y, pointers from the instance's
+// their batched twins (the same file: instance = blockIdx.y, pointers from the instance's
 // BandInst).  Each body takes its block index, its pointers and its LDS scratch as arguments; both
 // callers pass the same arguments in the same order, so an instance of a batch computes the bits the
 // single handle computes.  Both files are compiled with the same contraction rules (no

@@ -1,6 +1,6 @@
 // Device-side bodies of the bordered band's kernels: shared by the kernels of one handle
 // (pgf_border.hip, which describes the block elimination and the storage) and their batched twins
-// (pgf_border_batch.hip: instance = blockIdx.y, pointers from the instance's BandInst, the sizes
+// (the same file: instance = blockIdx.y, pointers from the instance's BandInst, the sizes
 // from BandShape).  Every body takes the arguments its kernel took, in the same order, and reads its
 // place from blockIdx.x / threadIdx.x; both callers pass the same arguments, so an instance of a
 // batch computes the bits the single handle computes -- which keeps the deterministic, atomics-free

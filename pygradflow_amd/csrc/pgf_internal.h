@@ -9,6 +9,8 @@
 #include <string>
 #include <vector>
 
+#include "pgf_sparse.h"
+
 // The PGF_* environment switches (host).  Each call site keeps its value in a `static const', so a
 // variable is read once per process, the first time its code path runs.
 inline bool env_on(const char *name) {  // on unless set to 0
@@ -277,15 +279,16 @@ struct BatchScalars {
 #define BPS_NORM_JINF 7
 #define BPS_STRIDE 8
 
-// ---- banded batch (pgf_band_batch.hip) ---------------------------------------
-// One entry per instance of a batch of banded handles (ONE sparsity pattern; block size 8, with the
-// same border of up to 64 nodes or none -- pgf_border_batch.hip -- or 16 / 32 / 64 for every instance
-// -- the wide route, pgf_band_wide_batch.hip): what differs between the instances -- the values of H and J, the band, the work blocks
-// of the cyclic reduction, the vectors, the flags.  The batched twins of the banded kernels pick
-// their instance with blockIdx.y; the pattern arrays, equal by construction, come from instance 0
-// (BandShape) so that every workgroup hits the same lines.  The vector kernels shared with the
-// dense batch (kb_advance, kb_mask_adopt, kb_residual, ...) read the same instance from the BInst
-// table beside it.  ctl, ps: as in BInst (ctl[0]: assemble the band this step).
+// ---- banded batch (pgf_sparse.hip, pgf_band_wide.hip, pgf_border.hip) ----------
+// One entry per banded instance: what differs between the instances of a batch of banded handles
+// (ONE sparsity pattern; block size 8, with the same border of up to 64 nodes or none, or 16 / 32 / 64
+// for every instance -- the wide route) -- the values of H and J, the band, the work blocks of the
+// cyclic reduction, the vectors, the flags.  The pattern arrays, equal by construction, come from
+// instance 0 (BandShape) so that every workgroup hits the same lines.  The batched twins of the banded
+// kernels (the second halves of pgf_sparse.hip, pgf_band_wide.hip, pgf_border.hip) pick their
+// instance with blockIdx.y; the vector kernels shared with the dense batch (kb_advance,
+// kb_mask_adopt, kb_residual, ...) read the same instance from the BInst table beside it.  ctl, ps:
+// as in BInst (ctl[0]: assemble the band this step).
 struct BandInst {
   const double *Hval, *Jval;
   double *band, *brhs, *brhs0, *bres;
@@ -293,7 +296,7 @@ struct BandInst {
   double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
   int *wcnt;  // wide route: [0] reductions, [1] solve phases this instance's workgroups ran
-  // bordered routes, narrow and wide (pgf_border_batch.hip; SparseDev names them): C and D behind
+  // bordered routes, narrow and wide (pgf_border.hip; SparseDev names them): C and D behind
   // the band, Y (whole B-row blocks on the wide route),
   // the factor of S, the chunk sums, the border part of the right-hand side / solution, the flags
   // of S; bcnt: [0] factor phases, [1] solve phases this instance ran
@@ -318,6 +321,71 @@ struct BandShape {
   int64_t bstride;
   const int *pos, *Hptr, *Hrow, *Hcol, *Hslot, *Jptr, *Jcol, *Jslot, *JTptr, *JTrow, *JTmap;
 };
+// The SparseDev part of a BandInst: the arrays of one handle.  flags: where the reduction reports
+// its pivots; stat: where the residual pairs go (SparseDev::bred, or a batch's status slice).  The
+// vectors of the step, ctl, ps and the counters stay null: band_batch_create adds them.
+inline BandInst band_inst_of(const SparseDev &sp, int *flags, double *stat) {
+  BandInst u{};
+  u.Hval = sp.Hval;
+  u.Jval = sp.Jval;
+  u.band = sp.band;
+  u.brhs = sp.brhs;  // (SparseDev::bX is brhs: the back-substitution writes the solution there)
+  u.brhs0 = sp.brhs0;
+  u.bres = sp.bres;
+  u.bD = sp.bD;
+  u.bL = sp.bL;
+  u.bU = sp.bU;
+  u.bDinv = sp.bDinv;
+  u.bF = sp.bF;
+  u.bMr = sp.bMr;
+  u.bMl = sp.bMl;
+  u.bneg = sp.bneg;
+  u.flags = flags;
+  u.bC = sp.bC;
+  u.bDd = sp.bDd;
+  u.bY = sp.bY;
+  u.bS = sp.bS;
+  u.bpart = sp.bpart;
+  u.bpartv = sp.bpartv;
+  u.brb = sp.brb;
+  u.bz = sp.bz;
+  u.bsflags = sp.bsflags;
+  u.stat = stat;
+  return u;
+}
+// The SparseDev part of a BandShape for a reduction over N rows (n + m, or the Nb band rows under a
+// border); n and m are the caller's.  split: the factor / solve split is in force only where the
+// multipliers are allocated.  sp.B is the block size of a pattern that is set (8, 16, 32 or 64), never
+// the 0 of a fresh SparseDev.
+inline BandShape band_shape_of(const SparseDev &sp, int N) {
+  BandShape sh{};
+  sh.N = N;
+  sh.B = sp.B;
+  sh.split = (sp.B > 8 && sp.split && sp.bMr) ? 1 : 0;
+  sh.nb = (N + sp.B - 1) / sp.B;
+  sh.bw = sp.bw;
+  sh.ldb = sp.ldb;
+  sh.nnzH = sp.nnzH;
+  sh.nnzJ = sp.nnzJ;
+  sh.nred = sp.nred;
+  sh.bk = sp.bk;
+  sh.bkp = sp.bkp;
+  sh.Nb = sp.bk ? sp.Nb : N;
+  sh.bnchunk = sp.bnchunk;
+  sh.bstride = sp.bstride;
+  sh.pos = sp.pos;
+  sh.Hptr = sp.Hptr;
+  sh.Hrow = sp.Hrow;
+  sh.Hcol = sp.Hcol;
+  sh.Hslot = sp.Hslot;
+  sh.Jptr = sp.Jptr;
+  sh.Jcol = sp.Jcol;
+  sh.Jslot = sp.Jslot;
+  sh.JTptr = sp.JTptr;
+  sh.JTrow = sp.JTrow;
+  sh.JTmap = sp.JTmap;
+  return sh;
+}
 // c, w, g at every instance's point
 void bandb_launch_eval(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // permuted right-hand side from F, b0full (kb_residual before it)
@@ -328,7 +396,7 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 // then the residual of the solution into the status block (residual == false: left out; the
 // bordered route reduces over sh.N = Nb rows and has a residual of its own)
 void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual = true);
-// bordered routes (pgf_border_batch.hip; both wrappers branch on sh.B > 8).  Factor phase of the
+// bordered routes (pgf_border.hip; both wrappers branch on sh.B > 8).  Factor phase of the
 // instances with ctl[0] != 0: band, C and D cleared and assembled, Y = inv(B) C by the panel reduction
 // (wide: B factorised once, Y by one panel solve against the kept factors), S and its factor.
 void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);

@@ -85,7 +85,7 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
 // order (s: stride; set: the block set holding the level's eliminated blocks' L, U, F; pair_set2 >=
 // 0: first level of a fused pair whose second level's blocks are in that set), the stride and set
 // the tail starts with, and whether a single level is one launch (fused) or invert + reduce.  It
-// depends on nb only: sp_launch_bcr_solve and the batched driver (pgf_band_batch.hip) walk the same.
+// depends on nb only: sp_launch_bcr_solve and the batched driver (bandb_launch_solve) walk the same.
 struct BcrPlan {
   struct Lev {
     int s, set, pair_set2;

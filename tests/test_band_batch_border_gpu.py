@@ -1,4 +1,4 @@
-"""Bordered instances in the banded device batch (csrc/pgf_border_batch.hip, PGF_BATCH_BORDER): a
+"""Bordered instances in the banded device batch (csrc/pgf_border.hip, PGF_BATCH_BORDER): a
 band of block size 8 plus 1 <= k <= 64 border nodes per instance, one launch sequence per Newton
 step, factor phase per instance only where its matrix changed.
 

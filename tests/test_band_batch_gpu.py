@@ -1,4 +1,4 @@
-"""Banded device batch (csrc/pgf_band_batch.hip, csrc/pgf_api_band_batch.hip): many banded instances
+"""Banded device batch (csrc/pgf_sparse.hip, csrc/pgf_api_band_batch.hip): many banded instances
 of one sparsity pattern advanced by one launch sequence per Newton step.
 
 Two references.  ``sequential=True`` drives the same instances one by one through their own handles:

@@ -1,5 +1,5 @@
 """Bordered instances on the WIDE route in the banded device batch (PGF_BATCH_WIDE_BORDER;
-csrc/pgf_border_batch.hip around the twins of csrc/pgf_band_wide_batch.hip): a band of block size 16,
+csrc/pgf_border.hip around the twins in csrc/pgf_band_wide.hip): a band of block size 16,
 32 or 64 plus 1 <= k <= 64 border nodes per instance, one launch sequence per Newton step.  An
 instance whose matrix changed factorises B once (the factor-only reduction that keeps its
 multipliers) and forms Y = inv(B) C by one panel solve on the matrix pipes; every live instance

@@ -1,4 +1,4 @@
-"""Wide bands (block sizes 16, 32, 64) in the banded device batch (csrc/pgf_band_wide_batch.hip,
+"""Wide bands (block sizes 16, 32, 64) in the banded device batch (csrc/pgf_band_wide.hip,
 csrc/pgf_api_band_batch.hip): instances of one pattern on the wide route share every launch of the
 Newton step, each in the phase its own state asks for -- the reduction, or with the factor / solve
 split on the solve phase against the factors it kept.
