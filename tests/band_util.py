@@ -1,5 +1,5 @@
-"""Helpers shared by the banded-path GPU tests (test_band_wide_gpu.py, test_band_narrow_gpu.py,
-test_border_gpu.py, test_border_edges_gpu.py).
+"""Problem builders and CPU references shared by the banded-path tests (test_band*.py,
+test_border*.py; band_batch_util.py has the batch harness).
 
 Bars as in test_gpu_parity.py: masks bit-identical, x and y within 1e-10 relative."""
 
@@ -10,6 +10,7 @@ from oracle import newton_oracle as O
 from tests import golden_util as G
 
 TOL = 1e-10
+COND_MAX = 1e4  # cond(K) asserted on the host where eps cond is to leave TOL two orders of headroom
 
 # sizes of the 8 x 8 cyclic reduction's edge sweep (test_band_narrow_gpu.py has the table of launch
 # plan branches they hit; check_band.py --sweep runs them under the schedule switches)
@@ -42,6 +43,24 @@ def bcr_launch_plan_from_env(nb, env):
     off = lambda name: name in env and int(env[name]) == 0  # noqa: E731
     return bcr_launch_plan(nb, pair_max=int(env.get("PGF_BCR_PAIR_MAX", 4096)),
                            pairs=not off("PGF_BCR_PAIRS"), fused=not off("PGF_BCR_FUSED"))
+
+
+def forced(prob, block=None, split=None):
+    """``prob`` sent down the banded path (pgf_force_band), with a forced block size and the
+    factor / solve split of the wide reduction switched on or off if given."""
+    prob.pgf_force_band = True
+    if block is not None:
+        prob.pgf_band_block = block
+    if split is not None:
+        prob.pgf_band_split = split
+    return prob
+
+
+def multistate_ocp(T, nx, nu, seed, block=None, split=None):
+    """problems.multistate_ocp(T, nx, nu, seed=seed), forced."""
+    from pygradflow_amd import problems
+
+    return forced(problems.multistate_ocp(T, nx, nu, seed=seed), block, split)
 
 
 def _as_sparse_lq(problem, block=None):
@@ -90,12 +109,18 @@ def _against_oracle(pgf, prob, policies, dt=1.0, rho=1.0, step_solver=True, n_ne
     return churn
 
 
-def mask_changes(prob, pol, steps, dt=1.0, rho=1.0):
-    """Number of oracle steps of the policy whose active set differs from the step before."""
+def mask_change_steps(prob, pol, steps, dt=1.0, rho=1.0):
+    """Per oracle step of the policy from zero after the first: its active set differs from that of
+    the step before."""
     n, m = prob.num_vars, prob.num_cons
     x0, y0 = np.zeros(n), np.zeros(m)
     recs = O.NewtonOracle(prob, pol, x0, y0, dt, rho).run(x0, y0, steps)
-    return sum(int(not np.array_equal(a["mask"], b["mask"])) for a, b in zip(recs, recs[1:]))
+    return [not np.array_equal(a["mask"], b["mask"]) for a, b in zip(recs, recs[1:])]
+
+
+def mask_changes(prob, pol, steps, dt=1.0, rho=1.0):
+    """Number of oracle steps of the policy whose active set differs from the step before."""
+    return sum(mask_change_steps(prob, pol, steps, dt, rho))
 
 
 def simplified_mask_goes_stale(prob, dt=1.0, rho=1.0):
@@ -123,6 +148,28 @@ def band_problem(n, d, seed, bw, lb=None, ub=None):
     ub = np.full(n, np.inf) if ub is None else ub
     return problems.LinearQuadraticProblem(H, rng.standard_normal(n), sps.csr_matrix((0, n)), np.zeros(0),
                                            lb, ub)
+
+
+def wide_band_problem(n, d, seed, block=None):
+    """band_problem of half-width 12 (block size 16 by the plan), m = 0, no bounds; forced."""
+    return forced(band_problem(n, d, seed, 12), block)
+
+
+def _decoupled_hess(prob, v):
+    H = sps.csr_matrix(prob.hess_sparse(), copy=True)
+    rows = np.repeat(np.arange(H.shape[0]), np.diff(H.indptr))
+    H.data[(rows == v) | (H.indices == v)] = 0.0
+    H.data[(rows == v) & (H.indices == v)] = -1.0
+    return H
+
+
+def decoupled(good, v):
+    """``good`` with variable v decoupled and H[v, v] = -1 (K[v, v] = 0 at dt = 1) ON THE SAME
+    PATTERN: the entries of row and column v stay stored, as zeros."""
+    from pygradflow_amd import problems
+
+    return problems.LinearQuadraticProblem(_decoupled_hess(good, v), good.q, good.jac_sparse(), good.b,
+                                           good.var_lb, good.var_ub)
 
 
 def bordered_lq(n0, bw, mloc, kv, kc, seed, block=None, bound=0.5):
@@ -182,6 +229,74 @@ def head_of_first_eliminated(prob, block):
     return int(np.nonzero(plan.pos[: prob.num_vars] == block)[0][0])
 
 
+def case(k, Nb, bw=2, block=None, mloc=None, seed=None, bound=0.5):
+    """bordered_lq with k border nodes (a third of them variables) and Nb band rows (a quarter of
+    them local constraints unless mloc is given)."""
+    mloc = Nb // 4 if mloc is None else mloc
+    kv = k // 3
+    return bordered_lq(Nb - mloc, bw, mloc, kv, k - kv, 1000 * k + Nb if seed is None else seed,
+                       block=block, bound=bound)
+
+
+def reduced_kkt(prob, mask, lamb=1.0, rho=1.0):
+    return O.kkt_matrix(O.shifted_hess_rows(prob.hess_sparse(), lamb, mask), prob.jac_sparse().tocsc(), mask,
+                        lamb, rho).toarray()
+
+
+def with_hess_diagonal(prob, v, value):
+    """The same problem with H[v, v] = value; border and block settings kept."""
+    from pygradflow_amd import problems
+
+    H = sps.lil_matrix(prob.hess_sparse())
+    H[v, v] = value
+    new = problems.LinearQuadraticProblem(sps.csr_matrix(H), prob.q, prob.jac_sparse(),
+                                          prob.b, prob.var_lb, prob.var_ub)
+    new.pgf_border = list(prob.pgf_border)
+    if getattr(prob, "pgf_band_block", None):
+        new.pgf_band_block = prob.pgf_band_block
+    return new
+
+
+def guard_case(k, block, pivot):
+    """Nb = 300 band variables with a full band of half-width 8 and no local constraints, the
+    layout of the narrow test one bandwidth down.  The variable v at the head of block 1 of B
+    (inverted as it stands by level one of either reduction) gets K[v, v] = pivot at lambda = 1;
+    the box is +-1e6, so no variable is active and v keeps its in-block couplings c = 0.04 U(0.5, 1).
+    With pivot = 1e-9 the unpivoted inverse of that block adds c^2 / pivot, about 1e6, to entries
+    of order one: a relative error near 1e6 u = 1e-10, ten times refine_tol, before the reduction
+    has done anything else."""
+    kv = k // 3
+    base = bordered_lq(300, 8, 0, kv, k - kv, 77 + k + block, block=None if block == 8 else block, bound=1e6)
+    v = head_of_first_eliminated(base, block)
+    assert v < 300  # a band variable
+    prob = with_hess_diagonal(base, v, -1.0 + pivot)
+    assert plan_of(prob).block_size == block and head_of_first_eliminated(prob, block) == v
+    return prob, v
+
+
+def singular_schur(base):
+    """The construction of test_border_edges_gpu.py::test_singular_schur_complement_is_an_error ON THE
+    PATTERN of ``base``: the last border variable v decoupled (its row and column of H and its
+    column of J stay stored, as zeros), H[v, v] = -1 = -lambda at dt = 1, q[v] = 0."""
+    from pygradflow_amd import problems
+
+    v = base.num_vars - 1
+    A = sps.csr_matrix(base.jac_sparse(), copy=True)
+    A.data[A.indices == v] = 0.0
+    q = np.array(base.q)
+    q[v] = 0.0
+    prob = problems.LinearQuadraticProblem(_decoupled_hess(base, v), q, A, base.b, base.var_lb, base.var_ub)
+    prob.pgf_border = list(base.pgf_border)
+    return prob, v
+
+
+def singular_schur_wide(base):
+    """singular_schur with the forced block size carried over."""
+    prob, v = singular_schur(base)
+    prob.pgf_band_block = base.pgf_band_block
+    return prob, v
+
+
 def refined_solve(K, rhs):
     """float64 solve followed by two refinement steps whose residual is accumulated in
     np.longdouble; returns (refined, plain float64) solutions.  rhs: a vector, or right-hand sides
@@ -193,3 +308,41 @@ def refined_solve(K, rhs):
         r = bl - Kl @ x
         x = x + np.linalg.solve(K, np.asarray(r, dtype=np.float64)).astype(np.longdouble)
     return np.asarray(x, dtype=np.float64), plain
+
+
+def normwise(K, x, b):
+    """The guard's measure (band_residual_rel_of): max |b - K x| / max (|K| |x| + |b|)."""
+    return np.abs(b - K @ x).max() / (np.abs(K) @ np.abs(x) + np.abs(b)).max()
+
+
+def gj_inverse(M):
+    """Unpivoted Gauss-Jordan inverse in float64 (gj_inverse8 of pgf_bcr_dev.h, bw_gj_inverse of
+    pgf_band_wide_dev.h)."""
+    M = M.copy()
+    for k in range(M.shape[0]):
+        d = 1.0 / M[k, k]
+        row, col = M[k, :].copy(), M[:, k].copy()
+        M -= np.outer(col * d, row)
+        M[k, :] = row * d
+        M[:, k] = -col * d
+        M[k, k] = d
+    return M
+
+
+def level_one_solve(Kp, f, block=8):
+    """The first level of the cyclic reduction with blocks of ``block`` rows on the permuted matrix,
+    in float64: the odd blocks are inverted unpivoted as they stand and eliminated; what is left is
+    solved by LAPACK."""
+    N = Kp.shape[0]
+    blk = np.arange(N) // block
+    o, e = np.nonzero(blk % 2 == 1)[0], np.nonzero(blk % 2 == 0)[0]
+    Dinv = np.zeros((o.size, o.size))
+    for b in np.unique(blk[o]):
+        idx = np.nonzero(blk[o] == b)[0]
+        Dinv[np.ix_(idx, idx)] = gj_inverse(Kp[np.ix_(o[idx], o[idx])])
+    Keo, Koe = Kp[np.ix_(e, o)], Kp[np.ix_(o, e)]
+    xe = np.linalg.solve(Kp[np.ix_(e, e)] - Keo @ Dinv @ Koe, f[e] - Keo @ (Dinv @ f[o]))
+    x = np.zeros(N)
+    x[e] = xe
+    x[o] = Dinv @ (f[o] - Koe @ xe)
+    return x

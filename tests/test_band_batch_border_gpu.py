@@ -2,11 +2,9 @@
 band of block size 8 plus 1 <= k <= 64 border nodes per instance, one launch sequence per Newton
 step, factor phase per instance only where its matrix changed.
 
-Two references, as in test_band_batch_gpu.py.  ``sequential=True`` drives the same instances one by
-one through their own handles: both routes run the same device functions (pgf_border_dev.h,
-pgf_band_dev.h) in the same order, so masks, x and y are compared bit for bit (``np.array_equal``),
-the inertia exactly, and the step length within 1e-14 relative (its sum is taken in another order).
-The CPU oracle: masks identical, x and y within ``band_util.TOL`` (1e-10), n_neg = m.
+Two references, with the bars of band_batch_util.py: ``sequential=True``, which drives the same
+instances one by one through their own handles (both routes run the same device functions of
+pgf_border_dev.h and pgf_band_dev.h in the same order), and the CPU oracle.
 
 Shapes, each checked on the host with ``plan_of`` (block size 8, plan supported) before it was put
 here, as (k, Nb, bw, block):
@@ -25,25 +23,22 @@ the plan's ordering with half-bandwidth 9, block size 16: the wide route, which 
 refuses.  They serve as the refusal's case below; the batches step their half-width 2 neighbours.
 """
 
+import functools
+
 import numpy as np
 import pytest
-import scipy.sparse as sps
 
 from oracle import newton_oracle as O
 from tests import golden_util as G
-from tests.band_util import TOL, bordered_lq, plan_of
-from tests.test_border_edges_gpu import case, guard_case
+from tests.band_batch_util import against_oracle, churn_of, handle_stats, make_batch, same_as_sequential, same_step
+from tests.band_util import (TOL, bordered_lq, case, forced, guard_case, mask_change_steps, plan_of,
+                             singular_schur)
 
 pytestmark = pytest.mark.gpu
 
 POLICIES = ("Simplified", "Full", "ActiveSet")
 
-
-def _batch(probs, pol, dt=1.0, rho=1.0, sequential=False, border=True, **kw):
-    from pygradflow_amd.batched import BatchedDeviceNewton
-
-    return BatchedDeviceNewton(lambda i: probs[i], len(probs), pol, dt, rho, sequential=sequential,
-                               border=border, **kw)
+_batch = functools.partial(make_batch, border=True)
 
 
 def _narrow(probs, k=None):
@@ -56,41 +51,18 @@ def _narrow(probs, k=None):
     return plans[0]
 
 
-def _same_step(bd, ref, tag, ok=True):
-    """One step of the batch and of the sequential loop: the bars of the module docstring."""
-    st, nn, df = bd.step_local()
-    st2, nn2, df2 = ref.step_local()
-    assert np.array_equal(st, st2), (tag, st, st2)
-    if ok:
-        assert not st.any(), (tag, st)
-    assert np.array_equal(bd.masks(), ref.masks()), tag
-    (x, y), (x2, y2) = bd.points(), ref.points()
-    assert np.array_equal(x, x2), (tag, G.rel_err(x, x2))
-    assert np.array_equal(y, y2), (tag, G.rel_err(y, y2))
-    good = st == 0
-    assert np.array_equal(nn[good], nn2[good]), (tag, nn, nn2)
-    assert np.all(np.abs(df - df2) <= 1e-14 * np.abs(df2)), (tag, df, df2)
-    return st, nn
-
-
-def _same_as_sequential(probs, policies=(("Full", 2), ("Simplified", 1))):
-    """Fresh instances per policy, batch against sequential=True."""
+def _as_one_by_one(probs):
+    """same_as_sequential with the border's width, block size and phase counters."""
     k = plan_of(probs[0]).k
-    for pol, steps in policies:
-        bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
-        assert bd.band and bd.band_border == k and bd.band_block == 8
-        for s in range(steps):
-            _, nn = _same_step(bd, ref, (pol, s))
-            assert np.all(nn == probs[0].num_cons), (pol, s, nn)
-        assert bd.band_stats()[0] == steps
+
+    def opened(bd):
+        assert bd.band_border == k and bd.band_block == 8
+
+    def after(bd, pol, steps):
         fac, sol = bd.border_stats()
         assert np.all(sol == steps) and np.all(fac == (steps if pol == "Full" else 1)), (pol, fac, sol)
-        bd.close()
-        ref.close()
 
-
-def _handle_stats(ref):
-    return np.array([s.border_stats()[1:] for s in ref.solvers]).T  # (factor phases, solve phases)
+    same_as_sequential(_batch, probs, opened=opened, after=after)
 
 
 # ------------------------------------------------------------------ 1: the batch exists
@@ -119,7 +91,7 @@ def test_border_widths_as_one_by_one(pgf, k, heavy):
     probs = [bordered_lq(200, 3, 65, kv, kc, seed=100 * k + i) for i in range(3)]
     plan = _narrow(probs, k=k)
     assert plan.Nb == 265 and plan.kp == (k + 15) // 16 * 16
-    _same_as_sequential(probs)
+    _as_one_by_one(probs)
 
 
 # ------------------------------------------------------------------ 3: row counts
@@ -131,39 +103,25 @@ def test_row_counts_as_one_by_one(pgf, Nb):
     probs = [bordered_lq(Nb - mloc, 2, mloc, 5, 12, seed=17000 + Nb + i) for i in range(3)]
     plan = _narrow(probs, k=17)
     assert plan.Nb == Nb
-    _same_as_sequential(probs)
+    _as_one_by_one(probs)
 
 
 # ------------------------------------------------------------------ 4: against the oracle
-def _against_oracle(probs, steps=3, dt=1.0, rho=1.0):
-    n, m = probs[0].num_vars, probs[0].num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    churn = 0
-    for pol in POLICIES:
-        recs = [O.NewtonOracle(p, pol, x0, y0, dt, rho).run(x0, y0, steps) for p in probs]
+def _oracle_run(probs):
+    def check_recs(pol, recs):
         if pol != "Simplified":  # (which keeps its mask by definition)
-            assert any(not np.array_equal(a["mask"], b["mask"]) for r in recs for a, b in zip(r, r[1:])), pol
-        bd = _batch(probs, pol, dt, rho)
-        assert bd.band and bd.band_border
-        for k in range(steps):
-            st, nn, _ = bd.step_local()
-            assert not st.any(), (pol, k, st)
-            mk = bd.masks()
-            x, y = bd.points()
-            for i, rec in enumerate(recs):
-                assert np.array_equal(mk[i], rec[k]["mask"]), (pol, k, i)
-                assert G.rel_err(x[i], rec[k]["xn"]) <= TOL, (pol, k, i)
-                assert G.rel_err(y[i], rec[k]["yn"]) <= TOL, (pol, k, i)
-                assert nn[i] == m, (pol, k, i, nn[i])
-        bd.close()
-        churn += sum(int(not np.array_equal(a["mask"], b["mask"])) for r in recs for a, b in zip(r, r[1:]))
-    return churn
+            assert churn_of(recs) > 0, pol
+
+    def opened(bd):
+        assert bd.band_border
+
+    return against_oracle(_batch, probs, tuple((p, 3) for p in POLICIES), check_recs=check_recs, opened=opened)
 
 
 def test_against_the_oracle_bordered_lq(pgf):
     probs = [bordered_lq(200, 2, 40, 2, 2, seed=i) for i in range(3)]
     _narrow(probs, k=4)
-    assert _against_oracle(probs) > 0
+    assert _oracle_run(probs) > 0
 
 
 def test_against_the_oracle_budget_box_qp(pgf):
@@ -174,30 +132,23 @@ def test_against_the_oracle_budget_box_qp(pgf):
         p.pgf_force_band = True
         p.pgf_border = "auto"
     assert _narrow(probs, k=1).Nb == 1003
-    assert _against_oracle(probs) > 0
+    assert _oracle_run(probs) > 0
 
 
 # ------------------------------------------------------------------ 5: phases per instance
-def _mask_change_steps(prob, pol, steps):
-    n, m = prob.num_vars, prob.num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    recs = O.NewtonOracle(prob, pol, x0, y0, 1.0, 1.0).run(x0, y0, steps)
-    return [not np.array_equal(a["mask"], b["mask"]) for a, b in zip(recs, recs[1:])]
-
-
 def test_factor_phase_only_where_the_matrix_changed(pgf):
     """One pattern, three boxes: +-0.5 (the mask changes at every step), +-1 (at the second step
     only), +-3 (never active).  Under ActiveSet each instance factors where its own mask changed."""
     probs = [bordered_lq(200, 2, 40, 2, 2, seed=s, bound=b) for s, b in ((0, 0.5), (1, 1.0), (2, 3.0))]
     _narrow(probs, k=4)
-    ch = [_mask_change_steps(p, "ActiveSet", 4) for p in probs]
+    ch = [mask_change_steps(p, "ActiveSet", 4) for p in probs]
     assert ch == [[True, True, True], [True, False, False], [False, False, False]]
     bd, ref = _batch(probs, "ActiveSet"), _batch(probs, "ActiveSet", sequential=True)
-    base = _handle_stats(ref)
+    base = handle_stats(ref, ("border",))
     for k in range(4):
-        _same_step(bd, ref, k)
+        same_step(bd, ref, k)
         fac, sol = bd.border_stats()
-        hf, hs = _handle_stats(ref) - base
+        hf, hs = handle_stats(ref, ("border",)) - base
         assert np.array_equal(fac, hf) and np.array_equal(sol, hs), (k, fac, hf, sol, hs)
     fac, sol = bd.border_stats()
     assert list(sol) == [4, 4, 4] and list(fac) == [4, 2, 1]
@@ -207,7 +158,7 @@ def test_factor_phase_only_where_the_matrix_changed(pgf):
     # Simplified: one factor phase, then two steps without a factor-phase launch
     bd, ref = _batch(probs, "Simplified"), _batch(probs, "Simplified", sequential=True)
     for k in range(3):
-        _same_step(bd, ref, ("Simplified", k))
+        same_step(bd, ref, ("Simplified", k))
     fac, sol = bd.border_stats()
     assert list(fac) == [1, 1, 1] and list(sol) == [3, 3, 3]
     assert bd.band_wide_stats()[2] == 2 and bd.band_stats() == (3, 1)
@@ -226,7 +177,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
         run.advance_outer_each(dt, 1.0)
     outer = bd.points()
     for k in range(2):
-        _same_step(bd, ref, ("dt", k))
+        same_step(bd, ref, ("dt", k))
     # instance 1 is rejected: back to its outer point, bit for bit; the others go on
     moved, m0 = bd.points(), bd.masks()
     for run in (bd, ref):
@@ -257,7 +208,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
     for run in (bd, ref):
         run.advance_outer_each(dt, 1.0)
     ref.set_frozen(None)  # (the sequential loop keeps its own list until told otherwise)
-    _same_step(bd, ref, "thawed")
+    same_step(bd, ref, "thawed")
     fac, sol = bd.border_stats()
     assert list(fac - fac0) == [3, 1, 3] and list(sol - sol0) == [3, 1, 3]
     bd.close()
@@ -274,7 +225,7 @@ def test_measures_and_norms_as_one_by_one(pgf):
     for k in range(2):
         assert close(bd.residual_norms_local(), ref.residual_norms_local()), k
         assert close(bd.measures(), ref.measures()), k
-        _same_step(bd, ref, k)
+        same_step(bd, ref, k)
     assert close(bd.measures(), ref.measures()) and close(bd.residual_norms_local(), ref.residual_norms_local())
     assert bd.measures()[:, 3].max() > 0.0
     bd.close()
@@ -282,31 +233,11 @@ def test_measures_and_norms_as_one_by_one(pgf):
 
 
 # ------------------------------------------------------------------ 7: singular S in one instance
-def _singular_schur(base):
-    """The construction of test_border_edges_gpu.py::test_singular_schur_complement_is_an_error ON THE
-    PATTERN of ``base``: the last border variable v decoupled (its row and column of H and its
-    column of J stay stored, as zeros), H[v, v] = -1 = -lambda at dt = 1, q[v] = 0."""
-    from pygradflow_amd import problems
-
-    v = base.num_vars - 1
-    H = sps.csr_matrix(base.hess_sparse(), copy=True)
-    rows = np.repeat(np.arange(H.shape[0]), np.diff(H.indptr))
-    H.data[(rows == v) | (H.indices == v)] = 0.0
-    H.data[(rows == v) & (H.indices == v)] = -1.0
-    A = sps.csr_matrix(base.jac_sparse(), copy=True)
-    A.data[A.indices == v] = 0.0
-    q = np.array(base.q)
-    q[v] = 0.0
-    prob = problems.LinearQuadraticProblem(H, q, A, base.b, base.var_lb, base.var_ub)
-    prob.pgf_border = list(base.pgf_border)
-    return prob, v
-
-
 def test_a_singular_schur_complement_in_one_instance(pgf):
     from pygradflow_amd import _lib
 
     goods = [case(6, 203, seed=6203 + i) for i in range(3)]
-    bad, v = _singular_schur(goods[1])
+    bad, v = singular_schur(goods[1])
     probs = [goods[0], bad, goods[2]]
     plan = _narrow(probs, k=6)
     assert plan.Nb == 203 and plan.pos[v] == 203 + 1  # a border node: B is as regular as ever
@@ -329,7 +260,7 @@ def test_a_singular_schur_complement_in_one_instance(pgf):
     # against a second time) and steps cleanly
     for run in (bd, ref):
         run.advance_outer_each(np.array([1.0, 0.5, 1.0]), 1.0, accepted=[True, False, True])
-    st, nn = _same_step(bd, ref, "regular")
+    st, nn = same_step(bd, ref, "regular")
     assert np.all(nn == m)
     x, _ = bd.points()
     assert x[1].any()
@@ -345,7 +276,7 @@ def test_a_bad_factor_phase_is_repeated_before_the_next_solve(pgf):
     from pygradflow_amd import _lib
 
     goods = [case(6, 203, seed=6203 + i) for i in range(3)]
-    bad, _ = _singular_schur(goods[1])
+    bad, _ = singular_schur(goods[1])
     bd = _batch([goods[0], bad, goods[2]], "Simplified")
     for k in range(3):
         st, _, _ = bd.step_local()
@@ -358,7 +289,7 @@ def test_a_bad_factor_phase_is_repeated_before_the_next_solve(pgf):
 
 # ------------------------------------------------------------------ 8: guard repair
 def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
-    """guard_case(1, 8, 1e-9) of test_border_edges_gpu.py as instance 1 of three: a 1e-9 pivot at the
+    """band_util.guard_case(1, 8, 1e-9) as instance 1 of three: a 1e-9 pivot at the
     head of block 1 of B, an instability chosen on the CPU (K is regular, cond < 1e5)."""
     prob, v = guard_case(1, 8, 1e-9)
     others = [bordered_lq(300, 8, 0, 0, 1, 186 + 100 * i, bound=1e6) for i in range(2)]
@@ -409,7 +340,7 @@ def test_seventy_tiny_instances(pgf):
     _narrow(probs, k=2)
     bd, ref = _batch(probs, "Full"), _batch(probs, "Full", sequential=True)
     for k in range(2):
-        _same_step(bd, ref, k)
+        same_step(bd, ref, k)
     fac, sol = bd.border_stats()
     assert np.all(fac == 2) and np.all(sol == 2) and fac.size == 70
     bd.close()
@@ -420,15 +351,12 @@ def test_without_a_border_the_flag_changes_nothing(pgf):
     from pygradflow_amd import problems
 
     def make():
-        ps = [problems.box_qp(264, seed=i) for i in range(3)]
-        for p in ps:
-            p.pgf_force_band = True
-        return ps
+        return [forced(problems.box_qp(264, seed=i)) for i in range(3)]
 
     bd, plain = _batch(make(), "Full", border=True), _batch(make(), "Full", border=False)
     assert bd.band and bd.band_border == 0 and plain.band_border == 0
     for k in range(2):
-        _same_step(bd, plain, k)
+        same_step(bd, plain, k)
     assert bd.band_stats() == plain.band_stats() == (2, 2)
     fac, sol = bd.border_stats()
     assert not fac.any() and not sol.any()
@@ -445,7 +373,7 @@ def test_what_a_bordered_batch_refuses(pgf):
     def steps_correctly():
         probs = [bordered_lq(100, 2, 10, 1, 1, seed=40 + i) for i in range(2)]
         bd, ref = _batch(probs, "Full"), _batch(probs, "Full", sequential=True)
-        _same_step(bd, ref, "after a refusal")
+        same_step(bd, ref, "after a refusal")
         bd.close()
         ref.close()
 

@@ -17,10 +17,10 @@ import ctypes as C
 
 import numpy as np
 import pytest
-import scipy.sparse as sps
 
 from tests import golden_util as G
-from tests.band_util import band_problem, head_of_first_eliminated, plan_of
+from tests.band_batch_util import make_batch
+from tests.band_util import band_problem, decoupled, forced, head_of_first_eliminated, multistate_ocp, plan_of
 from tests.oracle_step_solver import OracleStepSolver
 
 from pygradflow_amd import step_control as SC
@@ -29,18 +29,7 @@ from pygradflow_amd.params import Params
 
 pytestmark = pytest.mark.gpu
 
-
-def _forced(prob, split=None):
-    prob.pgf_force_band = True
-    if split is not None:
-        prob.pgf_band_split = split
-    return prob
-
-
-def _batch(probs, pol, ctl, wide=False):
-    from pygradflow_amd.batched import BatchedDeviceNewton
-
-    return BatchedDeviceNewton(lambda i: probs[i], len(probs), pol, 1.0, 1.0, wide_band=wide, band_ctl=ctl)
+_batch = make_batch
 
 
 def _host_run(host_b, par, iters, lamb=None):
@@ -91,7 +80,7 @@ def _against_host(probs, pol, lamb_init, iters, wide=False):
     """The comparison of the module docstring; returns (device history, host record, live, device
     batch -- still open, for the counters of the caller)."""
     par = Params(newton_type=pol, lamb_init=lamb_init)
-    host_b, dev_b = _batch(probs, pol, False, wide), _batch(probs, pol, True, wide)
+    host_b, dev_b = _batch(probs, pol, wide_band=wide), _batch(probs, pol, wide_band=wide, band_ctl=True)
     assert dev_b.band and host_b.band
     host, rec, live = _host_run(host_b, par, iters)
     dev = SC.DeviceResidentDistanceRatioController(dev_b, par, rho=1.0, max_iterations=iters)
@@ -119,7 +108,7 @@ def _cpu_kinds(prob, pol, lamb_init, iters):
 def _narrow(kind, i):
     from pygradflow_amd import problems
 
-    return _forced(problems.box_qp(264, seed=i) if kind == "box" else problems.sparse_ocp(30, seed=i))
+    return forced(problems.box_qp(264, seed=i) if kind == "box" else problems.sparse_ocp(30, seed=i))
 
 
 # (problem, lamb_init, what the CPU controller shows somewhere in the case).  box_qp(264) from
@@ -150,12 +139,6 @@ def test_narrow_route_against_the_host_driven_controller(pgf, kind, lamb_init, w
 
 
 # ------------------------------------------------------------------ 2: wide route
-def _wide(args, i, split=None):
-    from pygradflow_amd import problems
-
-    return _forced(problems.multistate_ocp(*args, seed=i), split)
-
-
 # T = 5: N = 50, 100, 200, four blocks of 16, 32, 64 rows (a left and a right neighbour missing at
 # level one, one level with a single kept block: the edges of test_band_split_gpu.py's (5, 4, 2)).
 # lamb_init: one at which the CPU controller keeps lambda above 0.2 over four iterations.
@@ -166,7 +149,7 @@ WIDE = [((5, 4, 2), 16, 4.0), ((5, 8, 4), 32, 1.0), ((5, 16, 8), 64, 1.0)]
 @pytest.mark.parametrize("args,block,lamb_init", WIDE)
 def test_wide_route_against_the_host_driven_controller(pgf, args, block, lamb_init, pol):
     iters = 4
-    probs = [_wide(args, i) for i in range(3)]
+    probs = [multistate_ocp(*args, i) for i in range(3)]
     assert plan_of(probs[0]).block_size == block
     hist, rec, live, dev_b = _against_host(probs, pol, lamb_init, iters, wide=True)
     assert dev_b.band_block == block
@@ -180,8 +163,8 @@ def test_wide_route_against_the_host_driven_controller(pgf, args, block, lamb_in
     assert np.array_equal(sol, live.sum(axis=0)), (sol, live)
     assert live.any()
     # split off: the second steps reduce again, nothing is lean, the trajectory is the same
-    off = [_wide(args, i, split=False) for i in range(3)]
-    off_b = _batch(off, pol, True, wide=True)
+    off = [multistate_ocp(*args, i, split=False) for i in range(3)]
+    off_b = _batch(off, pol, wide_band=True, band_ctl=True)
     dev = SC.DeviceResidentDistanceRatioController(off_b, Params(newton_type=pol, lamb_init=lamb_init),
                                                    rho=1.0, max_iterations=iters)
     dev.run(iters)
@@ -192,20 +175,8 @@ def test_wide_route_against_the_host_driven_controller(pgf, args, block, lamb_in
 
 
 # ------------------------------------------------------------------ 3: a singular instance
-def _decoupled(good, v):
-    """test_band_batch_gpu.py::_decoupled: variable v decoupled, H[v, v] = -1 (K[v, v] = 0 at
-    lambda = 1), on the same pattern."""
-    from pygradflow_amd import problems
-
-    H = sps.csr_matrix(good.hess_sparse(), copy=True)
-    rows = np.repeat(np.arange(H.shape[0]), np.diff(H.indptr))
-    H.data[(rows == v) | (H.indices == v)] = 0.0
-    H.data[(rows == v) & (H.indices == v)] = -1.0
-    return problems.LinearQuadraticProblem(H, good.q, good.jac_sparse(), good.b, good.var_lb, good.var_ub)
-
-
 def _ctl_run(probs, par, iters):
-    bd = _batch(probs, "Full", True)
+    bd = _batch(probs, "Full", band_ctl=True)
     dev = SC.DeviceResidentDistanceRatioController(bd, par, rho=1.0, max_iterations=iters)
     dev.run(iters)
     return bd, dev
@@ -220,9 +191,9 @@ SLOW_RED = Params(newton_type="Full", lamb_init=1.0, lamb_red=0.9)
 
 def test_one_singular_instance_is_rejected_and_goes_on(pgf):
     n, v, iters = 600, 333, 3
-    goods = [_forced(band_problem(n, 2.5 + np.random.default_rng(9 + i).uniform(0.0, 0.5, n), 3 + i, 5))
+    goods = [forced(band_problem(n, 2.5 + np.random.default_rng(9 + i).uniform(0.0, 0.5, n), 3 + i, 5))
              for i in range(3)]
-    bad = _forced(_decoupled(goods[1], v))
+    bad = forced(decoupled(goods[1], v))
     assert not (bad.hess_sparse().toarray() + np.eye(n))[v].any()
     bd, dev = _ctl_run([goods[0], bad, goods[2]], SLOW_RED, iters)
     two, dev2 = _ctl_run([goods[0], goods[2]], SLOW_RED, iters)
@@ -251,9 +222,9 @@ def _unstable(eps=1e-11):
     n, bw = 300, 5
     rng = np.random.default_rng(7)
     ds = [2.5 + rng.uniform(0.0, 0.5, n) for _ in range(3)]
-    v = head_of_first_eliminated(_forced(band_problem(n, ds[1], 1, bw)), 8)
+    v = head_of_first_eliminated(forced(band_problem(n, ds[1], 1, bw)), 8)
     ds[1][v] = -1.0 + eps
-    return [_forced(band_problem(n, ds[i], 1 + i, bw)) for i in range(3)]
+    return [forced(band_problem(n, ds[i], 1 + i, bw)) for i in range(3)]
 
 
 def test_a_miss_of_the_guard_is_a_rejected_step(pgf):
@@ -266,7 +237,7 @@ def test_a_miss_of_the_guard_is_a_rejected_step(pgf):
     assert list(dev.history[0, 1]) == [1.0, 2.0, 0.0]
     assert grd[1] >= 1 and grd[0] == 0 and grd[2] == 0 and not piv.any()
     # the host-driven twin, instance 1 starting at lambda = 2 (K[v, v] = 1 + eps: nothing to repair)
-    host_b = _batch(probs, "Full", False)
+    host_b = _batch(probs, "Full")
     host, rec, _ = _host_run(host_b, par, iters, lamb=[1.0, 2.0, 1.0])
     assert host_b.repaired() == 0
     _same_log(dev.history, rec, cols=[1], shift=1)
@@ -281,7 +252,7 @@ def test_no_guard_reject_when_the_handle_has_refinement_off(pgf):
     from pygradflow_amd import _lib
 
     probs = _unstable()
-    bd = _batch(probs, "Full", True)
+    bd = _batch(probs, "Full", band_ctl=True)
     lib, h = _lib.load(), bd.solvers[1]._hd.h
     _lib.check(lib.pgf_set_refinement(h, 0, 0.0, 0.0))  # (tolerances as they are)
     try:
@@ -299,14 +270,14 @@ def test_no_guard_reject_when_the_handle_has_refinement_off(pgf):
 def test_batch_of_one(pgf):
     from pygradflow_amd import problems
 
-    _against_host([_forced(problems.box_qp(264, seed=5))], "Full", 1.0, 3)[3].close()
+    _against_host([forced(problems.box_qp(264, seed=5))], "Full", 1.0, 3)[3].close()
 
 
 def test_seventy_tiny_instances(pgf):
     """Eighteen workgroups of kbb_step_final, the last with two instances; N = 40."""
     from pygradflow_amd import problems
 
-    probs = [_forced(problems.box_qp(40, seed=i, bound={3: 0.0, 5: np.inf}.get(i, 0.5))) for i in range(70)]
+    probs = [forced(problems.box_qp(40, seed=i, bound={3: 0.0, 5: np.inf}.get(i, 0.5))) for i in range(70)]
     _against_host(probs, "Full", 1.0, 3)[3].close()
 
 
@@ -315,10 +286,10 @@ def test_order_of_calls_and_mixing_with_host_driven_steps(pgf):
     from pygradflow_amd import _lib, problems
 
     lib = _lib.load()
-    probs = [_forced(problems.box_qp(264, seed=i)) for i in range(3)]
+    probs = [forced(problems.box_qp(264, seed=i)) for i in range(3)]
     par = Params(newton_type="Full", lamb_init=100.0)  # (a short step: converged after step one)
     nan = float("nan")
-    dev_b, host_b = _batch(probs, "Full", True), _batch(probs, "Full", False)
+    dev_b, host_b = _batch(probs, "Full", band_ctl=True), _batch(probs, "Full")
     assert lib.pgf_batch_ctl_iterate(dev_b._b, 3, nan, 1) == _lib.PGF_NOT_READY
     assert lib.pgf_batch_ctl_read(dev_b._b, None, None, None, 0) == _lib.PGF_NOT_READY
     dev = SC.DeviceResidentDistanceRatioController(dev_b, par, rho=1.0, max_iterations=2)

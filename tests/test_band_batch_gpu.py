@@ -1,11 +1,9 @@
 """Banded device batch (csrc/pgf_sparse.hip, csrc/pgf_api_band_batch.hip): many banded instances
 of one sparsity pattern advanced by one launch sequence per Newton step.
 
-Two references.  ``sequential=True`` drives the same instances one by one through their own handles:
-both routes run the same device functions in the same order, so masks, x and y are compared bit for
-bit (``np.array_equal``), the inertia exactly, and the step length within 1e-14 relative (its sum is
-taken in another order).  The CPU oracle: masks identical, x and y within ``band_util.TOL`` (1e-10),
-n_neg = m.  Shapes are the smallest that reach each kernel branch.
+Two references, with the bars of band_batch_util.py: ``sequential=True``, which drives the same
+instances one by one through their own handles (both routes run the same device functions in the
+same order), and the CPU oracle.  Shapes are the smallest that reach each kernel branch.
 """
 
 import ctypes as C
@@ -14,84 +12,24 @@ import numpy as np
 import pytest
 import scipy.sparse as sps
 
-from oracle import newton_oracle as O
 from tests import golden_util as G
-from tests.band_util import (TOL, band_problem, bordered_lq, head_of_first_eliminated, mask_changes,
-                             plan_of, refined_solve)
+from tests.band_batch_util import against_oracle, make_batch, same_as_sequential, same_step
+from tests.band_util import (TOL, band_problem, bordered_lq, decoupled, forced, head_of_first_eliminated,
+                             level_one_solve, mask_changes, multistate_ocp, normwise, plan_of, refined_solve)
 
 pytestmark = pytest.mark.gpu
 
 POLICIES = ("Simplified", "Full", "ActiveSet")
+ORACLE_STEPS = tuple((p, 3) for p in POLICIES)
 
-
-def _forced(prob):
-    prob.pgf_force_band = True
-    return prob
-
-
-def _batch(probs, pol, dt=1.0, rho=1.0, sequential=False):
-    from pygradflow_amd.batched import BatchedDeviceNewton
-
-    return BatchedDeviceNewton(lambda i: probs[i], len(probs), pol, dt, rho, sequential=sequential)
-
-
-def _same_step(bd, ref, tag):
-    """One step of the batch and of the sequential loop: the bars of the module docstring."""
-    st, nn, df = bd.step_local()
-    st2, nn2, df2 = ref.step_local()
-    assert not st.any() and not st2.any(), (tag, st, st2)
-    assert np.array_equal(bd.masks(), ref.masks()), tag
-    (x, y), (x2, y2) = bd.points(), ref.points()
-    assert np.array_equal(x, x2), (tag, G.rel_err(x, x2))
-    assert np.array_equal(y, y2), (tag, G.rel_err(y, y2))
-    assert np.array_equal(nn, nn2), (tag, nn, nn2)
-    assert np.all(np.abs(df - df2) <= 1e-14 * np.abs(df2)), (tag, df, df2)
-    return nn
-
-
-def _same_as_sequential(probs, policies=(("Full", 2), ("Simplified", 1))):
-    """Fresh instances per policy, batch against sequential=True."""
-    for pol, steps in policies:
-        bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
-        assert bd.band
-        for k in range(steps):
-            nn = _same_step(bd, ref, (pol, k))
-            assert np.all(nn == probs[0].num_cons), (pol, k, nn)
-        assert bd.band_stats()[0] == steps
-        bd.close()
-        ref.close()
-
-
-def _against_oracle(probs, policies=tuple((p, 3) for p in POLICIES), dt=1.0, rho=1.0):
-    """Every instance of the batch against NewtonOracle from zero; returns the number of steps whose
-    mask differs from the step before, summed over instances and policies."""
-    n, m = probs[0].num_vars, probs[0].num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    churn = 0
-    for pol, steps in policies:
-        recs = [O.NewtonOracle(p, pol, x0, y0, dt, rho).run(x0, y0, steps) for p in probs]
-        bd = _batch(probs, pol, dt, rho)
-        assert bd.band
-        for k in range(steps):
-            st, nn, _ = bd.step_local()
-            assert not st.any(), (pol, k, st)
-            mk = bd.masks()
-            x, y = bd.points()
-            for i, rec in enumerate(recs):
-                assert np.array_equal(mk[i], rec[k]["mask"]), (pol, k, i)
-                assert G.rel_err(x[i], rec[k]["xn"]) <= TOL, (pol, k, i)
-                assert G.rel_err(y[i], rec[k]["yn"]) <= TOL, (pol, k, i)
-                assert nn[i] == m, (pol, k, i, nn[i])
-        bd.close()
-        churn += sum(int(not np.array_equal(a["mask"], b["mask"])) for r in recs for a, b in zip(r, r[1:]))
-    return churn
+_batch = make_batch
 
 
 # ------------------------------------------------------------------ 1: the batch exists
 def test_banded_instances_form_a_device_batch_and_take_the_batched_route(pgf):
     from pygradflow_amd import problems
 
-    probs = [_forced(problems.box_qp(264, seed=i)) for i in range(3)]
+    probs = [forced(problems.box_qp(264, seed=i)) for i in range(3)]
     bd = _batch(probs, "Full")
     assert bd.band and bd._b is not None
     for _ in range(2):
@@ -108,7 +46,7 @@ def _sweep_problems(kind, size, B=3):
     from pygradflow_amd import problems
 
     make = problems.box_qp if kind == "box" else problems.sparse_ocp
-    return [_forced(make(size, seed=size + 7 * i)) for i in range(B)]
+    return [forced(make(size, seed=size + 7 * i)) for i in range(B)]
 
 
 @pytest.mark.parametrize("kind,size", [("box", n) for n in (7, 9, 256, 257, 513, 1033)]
@@ -120,14 +58,12 @@ def test_same_as_one_by_one_on_every_branch_of_the_launch_plan(pgf, kind, size):
     probs = _sweep_problems(kind, size)
     plan = plan_of(probs[0])
     assert plan.block_size == 8 and plan.bw <= 8
-    _same_as_sequential(probs)
+    same_as_sequential(_batch, probs)
 
 
 # ------------------------------------------------------------------ 3, 4: against the oracle
 def _ocp(i):
-    from pygradflow_amd import problems
-
-    return _forced(problems.multistate_ocp(60, 3, 1, seed=i))  # bw 7, N = 420, boxed controls
+    return multistate_ocp(60, 3, 1, i)  # bw 7, N = 420, boxed controls
 
 
 def test_against_the_oracle_constrained(pgf):
@@ -135,16 +71,16 @@ def test_against_the_oracle_constrained(pgf):
     assert plan_of(probs[0]).bw == 7 and probs[0].num_vars + probs[0].num_cons == 420
     for pol in ("Full", "ActiveSet"):  # (Simplified keeps its mask by definition)
         assert any(mask_changes(p, pol, 3) > 0 for p in probs)
-    assert _against_oracle(probs) > 0
+    assert against_oracle(_batch, probs, ORACLE_STEPS) > 0
 
 
 def test_against_the_oracle_box_qp(pgf):
     from pygradflow_amd import problems
 
-    probs = [_forced(problems.box_qp(600, seed=i)) for i in range(5)]
+    probs = [forced(problems.box_qp(600, seed=i)) for i in range(5)]
     for pol in ("Full", "ActiveSet"):
         assert any(mask_changes(p, pol, 3) > 0 for p in probs)
-    assert _against_oracle(probs) > 0
+    assert against_oracle(_batch, probs, ORACLE_STEPS) > 0
 
 
 def test_values_differ_per_instance_not_only_vectors(pgf):
@@ -153,10 +89,10 @@ def test_values_differ_per_instance_not_only_vectors(pgf):
 
     base = _ocp(0)
     H, J = base.hess_sparse(), base.jac_sparse()
-    probs = [_forced(problems.LinearQuadraticProblem(sps.csr_matrix(H * (1 + i / 4)), base.q,
+    probs = [forced(problems.LinearQuadraticProblem(sps.csr_matrix(H * (1 + i / 4)), base.q,
                                                      sps.csr_matrix(J * (1 - i / 8)), base.b,
                                                      base.var_lb, base.var_ub)) for i in range(4)]
-    assert _against_oracle(probs) > 0
+    assert against_oracle(_batch, probs, ORACLE_STEPS) > 0
 
 
 # ------------------------------------------------------------------ 5: bandwidths 1 .. 8
@@ -176,17 +112,17 @@ def _bandwidth_case(bw, k):
 
 @pytest.mark.parametrize("bw", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_every_bandwidth_up_to_8(pgf, bw):
-    probs = [_forced(_bandwidth_case(bw, k)) for k in range(2)]
+    probs = [forced(_bandwidth_case(bw, k)) for k in range(2)]
     plan = plan_of(probs[0])
     assert plan.bw == bw and plan.block_size == 8
-    _same_as_sequential(probs)
+    same_as_sequential(_batch, probs)
 
 
 # ------------------------------------------------------------------ 6: B edge cases
 def test_batch_of_one_equals_the_single_handle(pgf):
     from pygradflow_amd import problems
 
-    prob = _forced(problems.box_qp(264, seed=5))
+    prob = forced(problems.box_qp(264, seed=5))
     bd = _batch([prob], "Full")
     dn = pgf.DeviceNewton(prob, "Full", np.zeros(264), np.zeros(0), 1.0, 1.0)
     assert bd.band and dn.sparse
@@ -208,22 +144,22 @@ def test_seventy_tiny_instances_with_all_active_and_unbounded_ones(pgf):
     are ordinary."""
     from pygradflow_amd import problems
 
-    probs = [_forced(problems.box_qp(40, seed=i, bound={3: 0.0, 5: np.inf}.get(i, 0.5))) for i in range(70)]
+    probs = [forced(problems.box_qp(40, seed=i, bound={3: 0.0, 5: np.inf}.get(i, 0.5))) for i in range(70)]
     bd, ref = _batch(probs, "Full"), _batch(probs, "Full", sequential=True)
     for k in range(2):
-        _same_step(bd, ref, k)
+        same_step(bd, ref, k)
     mk = bd.masks()
     assert mk[3].all() and not mk[5].any() and mk[0].any() and not mk[0].all()
     bd.close()
     ref.close()
-    assert _against_oracle(probs[:8], (("Full", 2), ("Simplified", 1))) > 0
+    assert against_oracle(_batch, probs[:8], (("Full", 2), ("Simplified", 1))) > 0
 
 
 # ------------------------------------------------------------------ 7: per-instance outer steps
 def test_per_instance_outer_steps_rejection_and_freezing(pgf):
     from pygradflow_amd import problems
 
-    probs = [_forced(problems.box_qp(264, seed=20 + i)) for i in range(3)]
+    probs = [forced(problems.box_qp(264, seed=20 + i)) for i in range(3)]
     dt = np.array([0.5, 1.0, 2.0])
     bd, ref, free = _batch(probs, "Full"), _batch(probs, "Full", sequential=True), _batch(probs, "Full")
     for run in (bd, ref, free):
@@ -231,7 +167,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
         run.advance_outer_each(dt, 1.0)
     outer = bd.points()
     for k in range(2):
-        _same_step(bd, ref, ("dt", k))
+        same_step(bd, ref, ("dt", k))
         free.step_local()
     # instance 1 is rejected: back to its outer point, bit for bit; the others go on
     moved, m0 = bd.points(), bd.masks()
@@ -262,25 +198,13 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
 
 
 # ------------------------------------------------------------------ 8: one bad instance
-def _decoupled(good, v):
-    """``good`` with variable v decoupled and H[v, v] = -1 (K[v, v] = 0 at dt = 1) ON THE SAME
-    PATTERN: the entries of row and column v stay stored, as zeros."""
-    from pygradflow_amd import problems
-
-    H = sps.csr_matrix(good.hess_sparse(), copy=True)
-    rows = np.repeat(np.arange(H.shape[0]), np.diff(H.indptr))
-    H.data[(rows == v) | (H.indices == v)] = 0.0
-    H.data[(rows == v) & (H.indices == v)] = -1.0
-    return problems.LinearQuadraticProblem(H, good.q, good.jac_sparse(), good.b, good.var_lb, good.var_ub)
-
-
 def test_one_singular_instance_does_not_spoil_the_batch(pgf):
     from pygradflow_amd import _lib
 
     n, v = 600, 333
-    goods = [_forced(band_problem(n, 2.5 + np.random.default_rng(9 + i).uniform(0.0, 0.5, n), 3 + i, 5))
+    goods = [forced(band_problem(n, 2.5 + np.random.default_rng(9 + i).uniform(0.0, 0.5, n), 3 + i, 5))
              for i in range(3)]
-    bad = _forced(_decoupled(goods[1], v))
+    bad = forced(decoupled(goods[1], v))
     K = bad.hess_sparse().toarray() + np.eye(n)
     assert not K[v].any() and plan_of(bad).block_size == 8
     assert plan_of(bad).pattern_hash() == plan_of(goods[0]).pattern_hash()
@@ -311,42 +235,6 @@ def test_one_singular_instance_does_not_spoil_the_batch(pgf):
 
 
 # ------------------------------------------------------------------ 9: guard repair
-def _normwise(K, x, b):
-    """The guard's measure (band_residual_rel_of): max |b - K x| / max (|K| |x| + |b|)."""
-    return np.abs(b - K @ x).max() / (np.abs(K) @ np.abs(x) + np.abs(b)).max()
-
-
-def _gj_inverse(M):
-    """Unpivoted Gauss-Jordan inverse in float64 (gj_inverse8 of pgf_bcr_dev.h)."""
-    M = M.copy()
-    for k in range(M.shape[0]):
-        d = 1.0 / M[k, k]
-        row, col = M[k, :].copy(), M[:, k].copy()
-        M -= np.outer(col * d, row)
-        M[k, :] = row * d
-        M[:, k] = -col * d
-        M[k, k] = d
-    return M
-
-
-def _level_one_solve(Kp, f):
-    """The first level of the 8 x 8 cyclic reduction on the permuted matrix, in float64: the odd
-    blocks are inverted unpivoted as they stand and eliminated; what is left is solved by LAPACK."""
-    N = Kp.shape[0]
-    blk = np.arange(N) // 8
-    o, e = np.nonzero(blk % 2 == 1)[0], np.nonzero(blk % 2 == 0)[0]
-    Dinv = np.zeros((o.size, o.size))
-    for b in np.unique(blk[o]):
-        idx = np.nonzero(blk[o] == b)[0]
-        Dinv[np.ix_(idx, idx)] = _gj_inverse(Kp[np.ix_(o[idx], o[idx])])
-    Keo, Koe = Kp[np.ix_(e, o)], Kp[np.ix_(o, e)]
-    xe = np.linalg.solve(Kp[np.ix_(e, e)] - Keo @ Dinv @ Koe, f[e] - Keo @ (Dinv @ f[o]))
-    x = np.zeros(N)
-    x[e] = xe
-    x[o] = Dinv @ (f[o] - Koe @ xe)
-    return x
-
-
 def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     """The recipe of test_band_narrow_gpu.py::test_narrow_unstable_pivot_is_refined at bw 5 and block
     size 8: a tiny K[v, v] at the head of block 1, which level one inverts as it stands.  The pivot
@@ -356,9 +244,9 @@ def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     n, bw, eps = 300, 5, 1e-11
     rng = np.random.default_rng(7)
     ds = [2.5 + rng.uniform(0.0, 0.5, n) for _ in range(3)]
-    v = head_of_first_eliminated(_forced(band_problem(n, ds[1], 1, bw)), 8)
+    v = head_of_first_eliminated(forced(band_problem(n, ds[1], 1, bw)), 8)
     ds[1][v] = -1.0 + eps  # lambda = 1: K[v, v] = eps
-    probs = [_forced(band_problem(n, ds[i], 1 + i, bw)) for i in range(3)]
+    probs = [forced(band_problem(n, ds[i], 1 + i, bw)) for i in range(3)]
     plan = plan_of(probs[1])
     assert plan.bw == bw and plan.block_size == 8
     K = probs[1].hess_sparse().toarray() + np.eye(n)
@@ -368,10 +256,10 @@ def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     refine_tol = 1e-11
     perm = np.argsort(plan.pos)
     Kp, f = K[np.ix_(perm, perm)], probs[1].q[perm]
-    s0 = _level_one_solve(Kp, f)
-    assert _normwise(Kp, s0, f) > refine_tol
-    s1 = s0 + _level_one_solve(Kp, f - Kp @ s0)
-    assert _normwise(Kp, s1, f) <= refine_tol
+    s0 = level_one_solve(Kp, f)
+    assert normwise(Kp, s0, f) > refine_tol
+    s1 = s0 + level_one_solve(Kp, f - Kp @ s0)
+    assert normwise(Kp, s1, f) <= refine_tol
     ref, plain = refined_solve(K, probs[1].q)
     assert G.rel_err(plain, ref) < 1e-11
     bd = _batch(probs, "Full")
@@ -403,20 +291,20 @@ def test_what_a_band_batch_refuses(pgf):
     n = 300
     d = 2.5 + np.random.default_rng(3).uniform(0.0, 0.5, n)
     with pytest.raises(ValueError, match="dense and banded"):
-        _batch([_forced(problems.box_qp(n, seed=1)), problems.box_qp(n, seed=2, dense=True)], "Full")
+        _batch([forced(problems.box_qp(n, seed=1)), problems.box_qp(n, seed=2, dense=True)], "Full")
     with pytest.raises(ValueError, match="dense and banded"):
-        _batch([problems.box_qp(n, seed=2, dense=True), _forced(problems.box_qp(n, seed=1))], "Full")
+        _batch([problems.box_qp(n, seed=2, dense=True), forced(problems.box_qp(n, seed=1))], "Full")
     with pytest.raises(ValueError, match="one sparsity pattern"):
-        _batch([_forced(problems.box_qp(n, seed=1)), _forced(band_problem(n, d, 1, 3))], "Full")
-    wide = [_forced(problems.multistate_ocp(50, 8, 4, seed=i)) for i in range(2)]
+        _batch([forced(problems.box_qp(n, seed=1)), forced(band_problem(n, d, 1, 3))], "Full")
+    wide = [forced(problems.multistate_ocp(50, 8, 4, seed=i)) for i in range(2)]
     assert plan_of(wide[0]).block_size > 8
     with pytest.raises(ValueError, match="wide band"):
         _batch(wide, "Full")
     with pytest.raises(ValueError, match="bordered band"):
         _batch([bordered_lq(100, 3, 10, 1, 1, seed=i) for i in range(2)], "Full")
     with pytest.raises(ValueError, match=r"one \(n, m\)"):
-        _batch([_forced(problems.box_qp(n, seed=1)), _forced(problems.box_qp(n + 1, seed=1))], "Full")
-    bd = _batch([_forced(problems.box_qp(n, seed=i)) for i in range(2)], "Full")
+        _batch([forced(problems.box_qp(n, seed=1)), forced(problems.box_qp(n + 1, seed=1))], "Full")
+    bd = _batch([forced(problems.box_qp(n, seed=i)) for i in range(2)], "Full")
     with pytest.raises(NotImplementedError, match="dense batch only"):
         bd.ctl_init(pgf.Params())
     lib = _lib.load()
@@ -443,7 +331,7 @@ def test_measures_and_norms_as_one_by_one(pgf):
     for k in range(2):
         assert close(bd.residual_norms_local(), ref.residual_norms_local()), k
         assert close(bd.measures(), ref.measures()), k
-        _same_step(bd, ref, k)
+        same_step(bd, ref, k)
     assert close(bd.measures(), ref.measures()) and close(bd.residual_norms_local(), ref.residual_norms_local())
     assert bd.measures()[:, 3].max() > 0.0  # (multipliers have moved: the measures are not all zero)
     # the stream the launches went to is the batch's own

@@ -5,12 +5,10 @@ instance whose matrix changed factorises B once (the factor-only reduction that 
 multipliers) and forms Y = inv(B) C by one panel solve on the matrix pipes; every live instance
 solves against the kept factors every step.
 
-Two references, as in test_band_batch_border_gpu.py, with its bars.  ``sequential=True`` drives the
-same instances one by one through their own handles: both routes run the same device functions
-(pgf_band_wide_dev.h, pgf_border_dev.h) in the same order, so masks, x and y are compared bit for
-bit (``np.array_equal``), the inertia exactly, and the step length within 1e-14 relative (its sum
-is taken in another order).  The CPU oracle: masks identical, x and y within ``band_util.TOL``
-(1e-10) with cond(K) <= 1e4 asserted on the host first, n_neg = m.
+Two references, with the bars of band_batch_util.py: ``sequential=True``, which drives the same
+instances one by one through their own handles (both routes run the same device functions of
+pgf_band_wide_dev.h and pgf_border_dev.h in the same order), and the CPU oracle, with
+cond(K) <= 1e4 (band_util.COND_MAX) asserted on the host first.
 
 Shapes, each asserted on the host with ``plan_of`` before it is used, as (k, Nb, bw, block):
 
@@ -28,27 +26,24 @@ Shapes, each asserted on the host with ``plan_of`` before it is used, as (k, Nb,
 """
 
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
 from oracle import newton_oracle as O
 from tests import golden_util as G
-from tests.band_util import TOL, band_problem, bordered_lq, mask_changes, plan_of
-from tests.test_band_batch_border_gpu import _singular_schur
-from tests.test_border_edges_gpu import COND_MAX, case, guard_case, reduced_kkt
+from tests.band_batch_util import (against_oracle, churn_of, handle_stats, make_batch, phases, same_as_sequential,
+                                   same_step)
+from tests.band_util import (COND_MAX, bordered_lq, case, guard_case, mask_change_steps, plan_of, reduced_kkt,
+                             singular_schur_wide, wide_band_problem)
 
 pytestmark = pytest.mark.gpu
 
 POLICIES = ("Simplified", "Full", "ActiveSet")
 BLOCKS = (16, 32, 64)
 
-
-def _batch(probs, pol, dt=1.0, rho=1.0, sequential=False, wide_border=True, **kw):
-    from pygradflow_amd.batched import BatchedDeviceNewton
-
-    return BatchedDeviceNewton(lambda i: probs[i], len(probs), pol, dt, rho, sequential=sequential,
-                               wide_border=wide_border, **kw)
+_batch = functools.partial(make_batch, wide_border=True)
 
 
 def _wide(probs, k=None, Nb=None, bw=None, block=None):
@@ -63,53 +58,19 @@ def _wide(probs, k=None, Nb=None, bw=None, block=None):
     return p0
 
 
-def _same_step(bd, ref, tag, ok=True):
-    """One step of the batch and of the sequential loop: the bars of the module docstring."""
-    st, nn, df = bd.step_local()
-    st2, nn2, df2 = ref.step_local()
-    assert np.array_equal(st, st2), (tag, st, st2)
-    if ok:
-        assert not st.any(), (tag, st)
-    assert np.array_equal(bd.masks(), ref.masks()), tag
-    (x, y), (x2, y2) = bd.points(), ref.points()
-    assert np.array_equal(x, x2), (tag, G.rel_err(x, x2))
-    assert np.array_equal(y, y2), (tag, G.rel_err(y, y2))
-    good = st == 0
-    assert np.array_equal(nn[good], nn2[good]), (tag, nn, nn2)
-    assert np.all(np.abs(df - df2) <= 1e-14 * np.abs(df2)), (tag, df, df2)
-    return st, nn
-
-
-def _phases(bd):
-    """(factor phases, solve phases) per instance, which the border's and the wide band's counters
-    must both report."""
-    fac, sol = bd.border_stats()
-    red, kept, _ = bd.band_wide_stats()
-    assert np.array_equal(fac, red) and np.array_equal(sol, kept), (fac, red, sol, kept)
-    return fac, sol
-
-
-def _same_as_sequential(probs, policies=(("Full", 2), ("Simplified", 1))):
-    """Fresh instances per policy, batch against sequential=True: two Full steps and one Simplified."""
+def _as_one_by_one(probs):
+    """same_as_sequential with the flags the keyword derives, the plan's sizes and the phase counters."""
     plan = plan_of(probs[0])
-    for pol, steps in policies:
-        bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
-        assert bd.band and bd.wide_band and bd.border and bd.wide_border
+
+    def opened(bd):
+        assert bd.wide_band and bd.border and bd.wide_border
         assert bd.band_border == plan.k and bd.band_block == plan.block_size
-        for s in range(steps):
-            _, nn = _same_step(bd, ref, (pol, s))
-            assert np.all(nn == probs[0].num_cons), (pol, s, nn)
-        assert bd.band_stats()[0] == steps
-        fac, sol = _phases(bd)
+
+    def after(bd, pol, steps):
+        fac, sol = phases(bd)
         assert np.all(sol == steps) and np.all(fac == (steps if pol == "Full" else 1)), (pol, fac, sol)
-        bd.close()
-        ref.close()
 
-
-def _handle_stats(ref):
-    """(factor phases, solve phases) of the border and (reductions, solve phases) of the wide band on
-    the handles of a sequential run, one column per instance."""
-    return np.array([s.border_stats()[1:] + s.band_stats()[:2] for s in ref.solvers]).T
+    same_as_sequential(_batch, probs, opened=opened, after=after)
 
 
 # ------------------------------------------------------------------ 1: the batch exists
@@ -122,7 +83,7 @@ def test_wide_bordered_instances_form_a_device_batch(pgf):
     for _ in range(2):
         st, nn, _ = bd.step_local()
         assert not st.any() and np.all(nn == probs[0].num_cons)
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [2, 2, 2] and list(sol) == [2, 2, 2]
     assert bd.band_stats() == (2, 2)
     bd.close()
@@ -136,7 +97,7 @@ def test_border_widths_as_one_by_one(pgf, k, block):
     plan = _wide(probs, k=k, Nb=203, block=block)
     assert plan.kp == {1: 16, 16: 16, 17: 32, 64: 64}[k]
     assert (203 + block - 1) // block == {16: 13, 32: 7, 64: 4}[block]
-    _same_as_sequential(probs)
+    _as_one_by_one(probs)
 
 
 # ------------------------------------------------------------------ 3: row counts
@@ -148,7 +109,7 @@ def _row_counts(block):
 def test_row_counts_as_one_by_one(pgf, block, Nb):
     probs = [case(17, Nb, block=block, seed=17000 + Nb + block + i) for i in range(3)]
     _wide(probs, k=17, Nb=Nb, block=block)
-    _same_as_sequential(probs)
+    _as_one_by_one(probs)
 
 
 # ------------------------------------------------------------------ 4: automatic wide plans
@@ -175,34 +136,23 @@ def test_automatic_wide_plans_as_one_by_one(pgf, name):
     probs = [make(i) for i in range(3)]
     assert all(getattr(p, "pgf_band_block", None) is None for p in probs)
     _wide(probs, k=k, Nb=Nb, bw=bw, block=block)
-    _same_as_sequential(probs)
+    _as_one_by_one(probs)
 
 
 # ------------------------------------------------------------------ 5: against the oracle
-def _against_oracle(probs, steps=3, dt=1.0, rho=1.0):
-    n, m = probs[0].num_vars, probs[0].num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    for pol in POLICIES:
-        recs = [O.NewtonOracle(p, pol, x0, y0, dt, rho).run(x0, y0, steps) for p in probs]
+def _oracle_run(probs):
+    def check_recs(pol, recs):
         for p, r in zip(probs, recs):
             for rec in r:
                 cond = np.linalg.cond(reduced_kkt(p, rec["mask"]))
                 assert cond <= COND_MAX, (pol, cond)
         if pol != "Simplified":  # (which keeps its mask by definition)
-            assert all(mask_changes(p, pol, steps) > 0 for p in probs), pol
-        bd = _batch(probs, pol, dt, rho)
-        assert bd.band and bd.band_border and bd.band_block in BLOCKS
-        for k in range(steps):
-            st, nn, _ = bd.step_local()
-            assert not st.any(), (pol, k, st)
-            mk = bd.masks()
-            x, y = bd.points()
-            for i, rec in enumerate(recs):
-                assert np.array_equal(mk[i], rec[k]["mask"]), (pol, k, i)
-                assert G.rel_err(x[i], rec[k]["xn"]) <= TOL, (pol, k, i)
-                assert G.rel_err(y[i], rec[k]["yn"]) <= TOL, (pol, k, i)
-                assert nn[i] == m, (pol, k, i, nn[i])
-        bd.close()
+            assert all(churn_of([r]) > 0 for r in recs), pol
+
+    def opened(bd):
+        assert bd.band_border and bd.band_block in BLOCKS
+
+    against_oracle(_batch, probs, tuple((p, 3) for p in POLICIES), check_recs=check_recs, opened=opened)
 
 
 @pytest.mark.parametrize("name", ["lq100", "lq200", "ocp"])
@@ -212,35 +162,28 @@ def test_against_the_oracle(pgf, name):
     make, (k, Nb, bw, block) = AUTOMATIC[name]
     probs = [make(i) for i in range(3)]
     _wide(probs, k=k, Nb=Nb, bw=bw, block=block)
-    _against_oracle(probs)
+    _oracle_run(probs)
 
 
 # ------------------------------------------------------------------ 6: phases per instance
-def _mask_change_steps(prob, pol, steps):
-    n, m = prob.num_vars, prob.num_cons
-    x0, y0 = np.zeros(n), np.zeros(m)
-    recs = O.NewtonOracle(prob, pol, x0, y0, 1.0, 1.0).run(x0, y0, steps)
-    return [not np.array_equal(a["mask"], b["mask"]) for a, b in zip(recs, recs[1:])]
-
-
 def test_factor_phase_only_where_the_matrix_changed(pgf):
     """One pattern, three boxes: +-0.5 (the mask changes at every step), +-1.5 (at the second step
     only), +-5 (never active).  Under ActiveSet each instance factors where its own mask changed; the
     batch's counters are those of the handles in the sequential twin, step by step."""
     probs = [bordered_lq(200, 3, 40, 2, 2, seed=s, bound=b) for s, b in ((0, 0.5), (1, 1.5), (2, 5.0))]
     _wide(probs, k=4, Nb=240, bw=9, block=16)
-    ch = [_mask_change_steps(p, "ActiveSet", 4) for p in probs]
+    ch = [mask_change_steps(p, "ActiveSet", 4) for p in probs]
     assert ch == [[True, True, True], [True, False, False], [False, False, False]]
     want = [4, 2, 1]  # (the first step always factors)
     bd, ref = _batch(probs, "ActiveSet"), _batch(probs, "ActiveSet", sequential=True)
-    base = _handle_stats(ref)
+    base = handle_stats(ref, ("border", "band"))
     for k in range(4):
-        _same_step(bd, ref, k)
-        fac, sol = _phases(bd)
-        hf, hs, hred, hkept = _handle_stats(ref) - base
+        same_step(bd, ref, k)
+        fac, sol = phases(bd)
+        hf, hs, hred, hkept = handle_stats(ref, ("border", "band")) - base
         assert np.array_equal(fac, hf) and np.array_equal(sol, hs), (k, fac, hf, sol, hs)
         assert np.array_equal(fac, hred) and np.array_equal(sol, hkept), (k, fac, hred, sol, hkept)
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(sol) == [4, 4, 4] and list(fac) == want, (fac, want)
     assert bd.band_wide_stats()[2] == 0  # (the policy may change the mask: never lean)
     bd.close()
@@ -248,11 +191,11 @@ def test_factor_phase_only_where_the_matrix_changed(pgf):
     # Simplified: one factor phase, then two lean steps without a factor-phase launch, which leave the
     # factor counters alone
     bd, ref = _batch(probs, "Simplified"), _batch(probs, "Simplified", sequential=True)
-    _same_step(bd, ref, ("Simplified", 0))
-    fac1, _ = _phases(bd)
+    same_step(bd, ref, ("Simplified", 0))
+    fac1, _ = phases(bd)
     for k in (1, 2):
-        _same_step(bd, ref, ("Simplified", k))
-    fac, sol = _phases(bd)
+        same_step(bd, ref, ("Simplified", k))
+    fac, sol = phases(bd)
     assert list(fac1) == list(fac) == [1, 1, 1] and list(sol) == [3, 3, 3]
     assert bd.band_wide_stats()[2] == 2 and bd.band_stats() == (3, 1)
     bd.close()
@@ -270,7 +213,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
         run.advance_outer_each(dt, 1.0)
     outer = bd.points()
     for k in range(2):
-        _same_step(bd, ref, ("dt", k))
+        same_step(bd, ref, ("dt", k))
     # instance 1 is rejected: back to its outer point, bit for bit; the others go on
     moved, m0 = bd.points(), bd.masks()
     for run in (bd, ref):
@@ -280,7 +223,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
     assert np.array_equal(x[0], moved[0][0]) and np.array_equal(x[2], moved[0][2])
     assert not np.array_equal(x[1], moved[0][1])
     # instance 1 frozen: its point, its mask and all its counters stay
-    fac0, sol0 = _phases(bd)
+    fac0, sol0 = phases(bd)
     assert list(fac0) == [3, 3, 3] and list(sol0) == [3, 3, 3]
     bd.set_frozen([0, 1, 0])
     ref.set_frozen([0, 1, 0])
@@ -295,27 +238,20 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf):
         assert np.array_equal(bd.masks()[i], ref.solvers[i].mask()), i
     assert np.array_equal(x[1], outer[0][1]) and np.array_equal(y[1], outer[1][1])
     assert np.array_equal(bd.masks()[1], m0[1])
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac - fac0) == [2, 0, 2] and list(sol - sol0) == [2, 0, 2]
     # the next outer step thaws it
     for run in (bd, ref):
         run.advance_outer_each(dt, 1.0)
     ref.set_frozen(None)  # (the sequential loop keeps its own list until told otherwise)
-    _same_step(bd, ref, "thawed")
-    fac, sol = _phases(bd)
+    same_step(bd, ref, "thawed")
+    fac, sol = phases(bd)
     assert list(fac - fac0) == [3, 1, 3] and list(sol - sol0) == [3, 1, 3]
     bd.close()
     ref.close()
 
 
 # ------------------------------------------------------------------ 8: a bad pivot in one instance
-def _singular_schur_wide(base):
-    """_singular_schur of test_band_batch_border_gpu.py with the forced block size carried over."""
-    prob, v = _singular_schur(base)
-    prob.pgf_band_block = base.pgf_band_block
-    return prob, v
-
-
 @pytest.mark.parametrize("block", [16, 64])
 def test_a_singular_schur_complement_in_one_instance(pgf, block):
     """A decoupled border variable with H[v, v] = -lambda in the middle instance: B is as regular as
@@ -325,7 +261,7 @@ def test_a_singular_schur_complement_in_one_instance(pgf, block):
     from pygradflow_amd import _lib
 
     goods = [case(6, 203, block=block, seed=6203 + i) for i in range(3)]
-    bad, v = _singular_schur_wide(goods[1])
+    bad, v = singular_schur_wide(goods[1])
     probs = [goods[0], bad, goods[2]]
     plan = _wide(probs, k=6, Nb=203, block=block)
     assert plan.pos[v] == 203 + 1  # a border node
@@ -342,15 +278,15 @@ def test_a_singular_schur_complement_in_one_instance(pgf, block):
     for i in (0, 2):
         assert np.array_equal(x[i], x2[i]) and np.array_equal(y[i], y2[i]) and nn[i] == nn2[i] == m, i
         assert np.array_equal(bd.masks()[i], ref.solvers[i].mask()), i
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [1, 1, 1] and list(sol) == [1, 1, 1]
     for run in (bd, ref):
         run.advance_outer_each(np.array([1.0, 0.5, 1.0]), 1.0, accepted=[True, False, True])
-    st, nn = _same_step(bd, ref, "regular")
+    st, nn = same_step(bd, ref, "regular")
     assert np.all(nn == m)
     x, _ = bd.points()
     assert x[1].any()
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [2, 2, 2] and list(sol) == [2, 2, 2]
     bd.close()
     ref.close()
@@ -360,7 +296,7 @@ def test_a_singular_schur_complement_in_one_instance(pgf, block):
     for k in range(3):
         st, _, _ = bd.step_local()
         assert list(st) == [0, _lib.PGF_SINGULAR, 0], k
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [1, 3, 1] and list(sol) == [3, 3, 3]
     assert bd.band_wide_stats()[2] == 0  # (never lean while an instance is bad)
     bd.close()
@@ -373,7 +309,7 @@ def _guard_neighbours(block):
 
 @pytest.mark.parametrize("block", [16, 64])
 def test_a_zero_pivot_in_the_band_of_one_instance(pgf, block):
-    """guard_case(1, block, 0.0) of test_border_edges_gpu.py in the middle: K[v, v] = 0 at the head of
+    """band_util.guard_case(1, block, 0.0) in the middle: K[v, v] = 0 at the head of
     block 1 of B, which level one of the factor-only reduction inverts as it stands.  The flag is
     parked with those of S and comes back in front of the solve phase: PGF_SINGULAR, the point kept,
     a new factor phase before every further solve (Simplified keeps the mask), the neighbours bit for
@@ -395,7 +331,7 @@ def test_a_zero_pivot_in_the_band_of_one_instance(pgf, block):
         assert not x[1].any() and not y[1].any()
         for i in (0, 2):
             assert np.array_equal(x[i], x2[i]) and np.array_equal(y[i], y2[i]) and nn[i] == nn2[i], (k, i)
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [1, 2, 1] and list(sol) == [2, 2, 2]
     bd.close()
     ref.close()
@@ -435,7 +371,7 @@ def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf, block)
     assert G.rel_err(x[1], xr[1]) <= 1e-9 and G.rel_err(y[1], yr[1]) <= 1e-9
     # the corrections on the handle were solve phases: it never reduced B again
     assert h1[0] == h0[0] and h1[1] > h0[1], (h0, h1)
-    fac, sol = _phases(bd)
+    fac, sol = phases(bd)
     assert list(fac) == [1, 1, 1] and list(sol) == [1, 1, 1]
     for i in (0, 2):
         assert np.array_equal(x[i], xr[i]) and np.array_equal(y[i], yr[i]), i
@@ -469,8 +405,8 @@ def test_seventy_tiny_instances(pgf):
     _wide(probs, k=17, Nb=1, block=16)
     bd, ref = _batch(probs, "Full"), _batch(probs, "Full", sequential=True)
     for k in range(2):
-        _same_step(bd, ref, k)
-    fac, sol = _phases(bd)
+        same_step(bd, ref, k)
+    fac, sol = phases(bd)
     assert np.all(fac == 2) and np.all(sol == 2) and fac.size == 70
     bd.close()
     ref.close()
@@ -485,7 +421,7 @@ def test_the_flag_changes_nothing_for_narrow_borders_and_unbordered_wide_bands(p
     bd, old = _batch(narrow(), "Full"), _batch(narrow(), "Full", wide_border=False, border=True)
     assert bd.band_block == old.band_block == 8 and bd.band_border == old.band_border == 2
     for k in range(2):
-        _same_step(bd, old, ("narrow", k))
+        same_step(bd, old, ("narrow", k))
     assert bd.band_stats() == old.band_stats() == (2, 2)
     for a, b in zip(bd.border_stats() + bd.band_wide_stats(), old.border_stats() + old.band_wide_stats()):
         assert np.array_equal(a, b)
@@ -495,10 +431,7 @@ def test_the_flag_changes_nothing_for_narrow_borders_and_unbordered_wide_bands(p
     # a wide batch without a border: as under PGF_BATCH_WIDE_BAND alone
     def wide():
         rng = np.random.default_rng(8)
-        ps = [band_problem(300, 2.5 + rng.uniform(0.0, 0.5, 300), 1 + i, 12) for i in range(3)]
-        for p in ps:
-            p.pgf_force_band = True
-        return ps
+        return [wide_band_problem(300, 2.5 + rng.uniform(0.0, 0.5, 300), 1 + i) for i in range(3)]
 
     pl = plan_of(wide()[0])
     assert pl.block_size == 16 and pl.k == 0
@@ -506,7 +439,7 @@ def test_the_flag_changes_nothing_for_narrow_borders_and_unbordered_wide_bands(p
         bd, old = _batch(wide(), pol), _batch(wide(), pol, wide_border=False, wide_band=True)
         assert bd.band_block == old.band_block == 16 and bd.band_border == old.band_border == 0
         for k in range(steps):
-            _same_step(bd, old, ("wide", pol, k))
+            same_step(bd, old, ("wide", pol, k))
         assert bd.band_stats() == old.band_stats()
         for a, b in zip(bd.border_stats() + bd.band_wide_stats(), old.border_stats() + old.band_wide_stats()):
             assert np.array_equal(a, b)
@@ -522,7 +455,7 @@ def test_what_a_wide_bordered_batch_refuses(pgf):
     def steps_correctly():
         probs = [bordered_lq(100, 3, 10, 1, 1, seed=40 + i) for i in range(2)]
         bd, ref = _batch(probs, "Full"), _batch(probs, "Full", sequential=True)
-        _same_step(bd, ref, "after a refusal")
+        same_step(bd, ref, "after a refusal")
         bd.close()
         ref.close()
 

@@ -3,65 +3,29 @@ csrc/pgf_api_band_batch.hip): instances of one pattern on the wide route share e
 Newton step, each in the phase its own state asks for -- the reduction, or with the factor / solve
 split on the solve phase against the factors it kept.
 
-The bars are those of test_band_batch_gpu.py.  Against ``sequential=True`` (the same instances one by
-one through their own handles): masks, x and y bit for bit (``np.array_equal``), the inertia exactly,
-the step length within 1e-14 relative (its sum is taken in another order).  Against the CPU oracle:
-masks identical, x and y within ``band_util.TOL`` (1e-10), n_neg = m.  Every batch here is created
+The references are ``sequential=True`` (the same instances one by one through their own handles) and
+the CPU oracle, with the bars of band_batch_util.py.  Every batch here is created
 with ``wide_band=True`` (pgf_batch_create_ex with PGF_BATCH_WIDE_BAND).  The per-instance phase is read
 from ``band_wide_stats()``: (reductions, solve phases) each instance's workgroups ran, and the steps
 enqueued without inversion launches.
 """
 
+import functools
+
 import numpy as np
 import pytest
 
-from oracle import newton_oracle as O
 from tests import golden_util as G
-from tests.band_util import TOL, band_problem, head_of_first_eliminated, mask_changes, plan_of, refined_solve
+from tests.band_batch_util import against_oracle, handle_stats, make_batch, same_as_sequential, same_step
+from tests.band_util import (TOL, forced, head_of_first_eliminated, level_one_solve, mask_change_steps,
+                             mask_changes, multistate_ocp, normwise, plan_of, refined_solve, wide_band_problem)
 
 pytestmark = pytest.mark.gpu
 
 POLICIES = ("Simplified", "Full", "ActiveSet")
 NEW_REFUSAL = "must share the block size and the factor / solve split"
 
-
-def _ocp(T, nx, nu, seed, block=None, split=None):
-    from pygradflow_amd import problems
-
-    prob = problems.multistate_ocp(T, nx, nu, seed=seed)
-    prob.pgf_force_band = True
-    if block is not None:
-        prob.pgf_band_block = block
-    if split is not None:
-        prob.pgf_band_split = split
-    return prob
-
-
-def _batch(probs, pol, dt=1.0, rho=1.0, sequential=False, wide_band=True):
-    from pygradflow_amd.batched import BatchedDeviceNewton
-
-    return BatchedDeviceNewton(lambda i: probs[i], len(probs), pol, dt, rho, sequential=sequential,
-                               wide_band=wide_band)
-
-
-def _same_step(bd, ref, tag):
-    """One step of the batch and of the sequential loop: the bars of the module docstring."""
-    st, nn, df = bd.step_local()
-    st2, nn2, df2 = ref.step_local()
-    assert not st.any() and not st2.any(), (tag, st, st2)
-    assert np.array_equal(bd.masks(), ref.masks()), tag
-    (x, y), (x2, y2) = bd.points(), ref.points()
-    assert np.array_equal(x, x2), (tag, G.rel_err(x, x2))
-    assert np.array_equal(y, y2), (tag, G.rel_err(y, y2))
-    assert np.array_equal(nn, nn2), (tag, nn, nn2)
-    assert np.all(np.abs(df - df2) <= 1e-14 * np.abs(df2)), (tag, df, df2)
-    return nn
-
-
-def _handle_stats(ref):
-    """(reductions, solve phases, refinement steps) of every handle of a sequential run (pooled: use
-    differences)."""
-    return np.array([s.band_stats()[:2] + (s.refinement_stats()[0],) for s in ref.solvers])
+_batch = functools.partial(make_batch, wide_band=True)
 
 
 # ------------------------------------------------------------------ 1: block-count edges
@@ -76,50 +40,36 @@ def test_block_count_edges(pgf, args, block):
     instances with their own seeds.  Full for 2 steps, then fresh instances with Simplified for 3: one
     reduction, two solve phases per instance, and the last two steps enqueue no inversion."""
     T, nx, nu, seed = args
-    probs = [_ocp(T, nx, nu, seed + 7 * i, block) for i in range(3)]
-    m = probs[0].num_cons
+    probs = [multistate_ocp(T, nx, nu, seed + 7 * i, block) for i in range(3)]
     assert plan_of(probs[0]).block_size == block
-    for pol, steps in (("Full", 2), ("Simplified", 3)):
-        bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
-        assert bd.band and bd.band_block == block
-        for k in range(steps):
-            nn = _same_step(bd, ref, (pol, k))
-            assert np.all(nn == m), (pol, k, nn)
-        assert bd.band_stats()[0] == steps
+
+    def opened(bd):
+        assert bd.band_block == block
+
+    def after(bd, pol, steps):
         red, sol, lean = bd.band_wide_stats()
         if pol == "Full":
             assert list(red) == [2] * 3 and not sol.any() and lean == 0, (red, sol, lean)
         else:
             assert list(red) == [1] * 3 and list(sol) == [2] * 3 and lean == 2, (red, sol, lean)
-        bd.close()
-        ref.close()
+
+    same_as_sequential(_batch, probs, (("Full", 2), ("Simplified", 3)), opened, after)
 
 
 # ------------------------------------------------------------------ 2: the oracle
 def test_against_the_oracle(pgf):
     """5 instances of multistate_ocp(12, 8, 4): N = 240, half-bandwidth 22, block 32 by the plan."""
-    probs = [_ocp(12, 8, 4, i) for i in range(5)]
+    probs = [multistate_ocp(12, 8, 4, i) for i in range(5)]
     plan = plan_of(probs[0])
     n, m = probs[0].num_vars, probs[0].num_cons
     assert (plan.bw, plan.block_size, n + m) == (22, 32, 240)
     for pol in ("Full", "ActiveSet"):  # (Simplified keeps its mask by definition)
         assert any(mask_changes(p, pol, 3) > 0 for p in probs)
-    x0, y0 = np.zeros(n), np.zeros(m)
-    for pol in POLICIES:
-        recs = [O.NewtonOracle(p, pol, x0, y0, 1.0, 1.0).run(x0, y0, 3) for p in probs]
-        bd = _batch(probs, pol)
-        assert bd.band and bd.band_block == 32
-        for k in range(3):
-            st, nn, _ = bd.step_local()
-            assert not st.any(), (pol, k, st)
-            mk = bd.masks()
-            x, y = bd.points()
-            for i, rec in enumerate(recs):
-                assert np.array_equal(mk[i], rec[k]["mask"]), (pol, k, i)
-                assert G.rel_err(x[i], rec[k]["xn"]) <= TOL, (pol, k, i)
-                assert G.rel_err(y[i], rec[k]["yn"]) <= TOL, (pol, k, i)
-                assert nn[i] == m, (pol, k, i, nn[i])
-        bd.close()
+
+    def opened(bd):
+        assert bd.band_block == 32
+
+    against_oracle(_batch, probs, tuple((p, 3) for p in POLICIES), opened=opened)
 
 
 # ------------------------------------------------------------------ 3: per-instance phase
@@ -132,26 +82,21 @@ def test_each_instance_takes_its_own_phase(pgf):
     sequence.  After every step the batch's per-instance counters equal the difference of the single
     handles' band_stats() in the sequential run."""
     steps = 4
-    probs = [_ocp(12, 4, 2, s) for s in (0, 1, 2)]
-    n, m = probs[0].num_vars, probs[0].num_cons
+    probs = [multistate_ocp(12, 4, 2, s) for s in (0, 1, 2)]
     assert plan_of(probs[0]).block_size == 16
-    x0, y0 = np.zeros(n), np.zeros(m)
-    changed = []
-    for p in probs:
-        recs = O.NewtonOracle(p, "ActiveSet", x0, y0, 1.0, 1.0).run(x0, y0, steps)
-        changed.append([True] + [not np.array_equal(a["mask"], b["mask"]) for a, b in zip(recs, recs[1:])])
-    changed = np.array(changed)  # [instance][step]: the step reduces
+    # [instance][step]: the step reduces
+    changed = np.array([[True] + mask_change_steps(p, "ActiveSet", steps) for p in probs])
     assert any(changed[:, k].any() and not changed[:, k].all() for k in range(1, steps)), changed
     for pol in ("ActiveSet", "Full"):
         bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
-        h0 = _handle_stats(ref)
+        h0 = handle_stats(ref, ("band", "refined"))
         for k in range(steps):
-            _same_step(bd, ref, (pol, k))
+            same_step(bd, ref, (pol, k))
             red, sol, lean = bd.band_wide_stats()
-            dh = _handle_stats(ref) - h0
+            hred, hsol, hrefined = dh = handle_stats(ref, ("band", "refined")) - h0
             # (a refinement step of the guard is one more solve phase on the handle; the batch runs
             # its corrections on the handle too, outside its own counters)
-            assert np.array_equal(red, dh[:, 0]) and np.array_equal(sol, dh[:, 1] - dh[:, 2]), (pol, k, red, sol, dh)
+            assert np.array_equal(red, hred) and np.array_equal(sol, hsol - hrefined), (pol, k, red, sol, dh)
             want = changed[:, : k + 1].sum(axis=1) if pol == "ActiveSet" else np.full(3, k + 1)
             assert np.array_equal(red, want) and np.array_equal(red + sol, np.full(3, k + 1)), (pol, k, red, sol)
             assert lean == 0  # (a step that recomputes the mask may reduce: the inversions are enqueued)
@@ -164,10 +109,10 @@ def test_each_instance_takes_its_own_phase(pgf):
 def test_split_off_gives_the_same_bits_and_no_solve_phase(pgf, args, block):
     out = {}
     for split in (True, False):
-        probs = [_ocp(*args, 3 + i, block, split=split) for i in range(3)]
+        probs = [multistate_ocp(*args, 3 + i, block, split=split) for i in range(3)]
         bd, ref = _batch(probs, "Simplified"), _batch(probs, "Simplified", sequential=True)
         for k in range(3):
-            _same_step(bd, ref, (split, k))
+            same_step(bd, ref, (split, k))
         red, sol, lean = bd.band_wide_stats()
         if split:
             assert list(red) == [1] * 3 and list(sol) == [2] * 3 and lean == 2, (red, sol, lean)
@@ -181,19 +126,20 @@ def test_split_off_gives_the_same_bits_and_no_solve_phase(pgf, args, block):
 
 
 def test_mixed_split_or_block_size_is_refused(pgf):
-    on, off = _ocp(5, 4, 2, 0, 16, split=True), _ocp(5, 4, 2, 1, 16, split=False)
+    on, off = multistate_ocp(5, 4, 2, 0, 16, split=True), multistate_ocp(5, 4, 2, 1, 16, split=False)
     with pytest.raises(ValueError, match=NEW_REFUSAL):
         _batch([on, off], "Full")
     with pytest.raises(ValueError, match=NEW_REFUSAL):
         _batch([off, on], "Full")
-    b16, b32 = _ocp(5, 4, 2, 0, 16), _ocp(5, 4, 2, 1, 32)
+    b16, b32 = multistate_ocp(5, 4, 2, 0, 16), multistate_ocp(5, 4, 2, 1, 32)
     assert plan_of(b16).pattern_hash() == plan_of(b32).pattern_hash()
     assert (plan_of(b16).block_size, plan_of(b32).block_size) == (16, 32)
     with pytest.raises(ValueError, match=NEW_REFUSAL):
         _batch([b16, b32], "Full")
     # and the handles are none the worse for it
-    bd, ref = _batch([b16, _ocp(5, 4, 2, 1, 16)], "Full"), _batch([b16, _ocp(5, 4, 2, 1, 16)], "Full", sequential=True)
-    _same_step(bd, ref, "after the refusals")
+    pair = [b16, multistate_ocp(5, 4, 2, 1, 16)]
+    bd, ref = _batch(pair, "Full"), _batch(pair, "Full", sequential=True)
+    same_step(bd, ref, "after the refusals")
     bd.close()
     ref.close()
 
@@ -204,7 +150,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf, pol):
     """The scenario of test_band_batch_gpu.py's test of the same name on multistate_ocp(12, 4, 2).
     A frozen instance's counters do not move; after advance_outer_each (a new lambda: a new matrix)
     every instance reduces once, whatever the policy."""
-    probs = [_ocp(12, 4, 2, 20 + i) for i in range(3)]
+    probs = [multistate_ocp(12, 4, 2, 20 + i) for i in range(3)]
     dt = np.array([0.5, 1.0, 2.0])
     bd, ref, free = _batch(probs, pol), _batch(probs, pol, sequential=True), _batch(probs, pol)
     assert bd.band_block == 16
@@ -214,7 +160,7 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf, pol):
     outer = bd.points()
     c0 = bd.band_wide_stats()
     for k in range(2):
-        _same_step(bd, ref, ("dt", k))
+        same_step(bd, ref, ("dt", k))
         free.step_local()
         if k == 0:  # the first step behind the new outer step
             c1 = bd.band_wide_stats()
@@ -254,13 +200,6 @@ def test_per_instance_outer_steps_rejection_and_freezing(pgf, pol):
 
 
 # ------------------------------------------------------------------ 6: singular instance
-def _wide_band_problem(n, d, seed, block):
-    prob = band_problem(n, d, seed, 12)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
-    return prob
-
-
 @pytest.mark.parametrize("pol", ["Full", "Simplified"])
 @pytest.mark.parametrize("block", [16, 64])
 def test_one_singular_instance_does_not_spoil_the_batch(pgf, block, pol):
@@ -274,10 +213,10 @@ def test_one_singular_instance_does_not_spoil_the_batch(pgf, block, pol):
     n = 300
     rng = np.random.default_rng(8)
     ds = [2.5 + rng.uniform(0.0, 0.5, n) for _ in range(3)]
-    v = head_of_first_eliminated(_wide_band_problem(n, ds[1], 2, block), block)
-    good = _wide_band_problem(n, ds[1].copy(), 2, block)
+    v = head_of_first_eliminated(wide_band_problem(n, ds[1], 2, block), block)
+    good = wide_band_problem(n, ds[1].copy(), 2, block)
     ds[1][v] = -1.0  # lambda = 1: K[v, v] = 0
-    probs = [_wide_band_problem(n, ds[i], 1 + i, block) for i in range(3)]
+    probs = [wide_band_problem(n, ds[i], 1 + i, block) for i in range(3)]
     K = probs[1].hess_sparse().toarray() + np.eye(n)
     assert K[v, v] == 0.0 and np.linalg.cond(K) < 1e6
     assert plan_of(probs[1]).pattern_hash() == plan_of(good).pattern_hash() == plan_of(probs[0]).pattern_hash()
@@ -302,43 +241,6 @@ def test_one_singular_instance_does_not_spoil_the_batch(pgf, block, pol):
 
 
 # ------------------------------------------------------------------ 7: unstable pivot
-def _normwise(K, x, b):
-    """The guard's measure (band_residual_rel_of): max |b - K x| / max (|K| |x| + |b|)."""
-    return np.abs(b - K @ x).max() / (np.abs(K) @ np.abs(x) + np.abs(b)).max()
-
-
-def _gj_inverse(M):
-    """Unpivoted Gauss-Jordan inverse in float64 (bw_gj_inverse of pgf_band_wide_dev.h)."""
-    M = M.copy()
-    for k in range(M.shape[0]):
-        d = 1.0 / M[k, k]
-        row, col = M[k, :].copy(), M[:, k].copy()
-        M -= np.outer(col * d, row)
-        M[k, :] = row * d
-        M[:, k] = -col * d
-        M[k, k] = d
-    return M
-
-
-def _level_one_solve(Kp, f, block):
-    """The first level of the cyclic reduction with blocks of ``block`` rows on the permuted matrix,
-    in float64: the odd blocks are inverted unpivoted as they stand and eliminated; what is left is
-    solved by LAPACK (the level-one emulation of test_band_batch_gpu.py for any block size)."""
-    N = Kp.shape[0]
-    blk = np.arange(N) // block
-    o, e = np.nonzero(blk % 2 == 1)[0], np.nonzero(blk % 2 == 0)[0]
-    Dinv = np.zeros((o.size, o.size))
-    for b in np.unique(blk[o]):
-        idx = np.nonzero(blk[o] == b)[0]
-        Dinv[np.ix_(idx, idx)] = _gj_inverse(Kp[np.ix_(o[idx], o[idx])])
-    Keo, Koe = Kp[np.ix_(e, o)], Kp[np.ix_(o, e)]
-    xe = np.linalg.solve(Kp[np.ix_(e, e)] - Keo @ Dinv @ Koe, f[e] - Keo @ (Dinv @ f[o]))
-    x = np.zeros(N)
-    x[e] = xe
-    x[o] = Dinv @ (f[o] - Koe @ xe)
-    return x
-
-
 def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     """The construction of test_band_split_gpu.py::test_guard_refines_through_the_kept_factors in one
     instance of three at block size 16: a tiny K[v, v] at the head of block 1, which level one inverts
@@ -352,9 +254,9 @@ def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     n, bw, block, eps = 300, 12, 16, 1e-10
     rng = np.random.default_rng(7)
     ds = [2.5 + rng.uniform(0.0, 0.5, n) for _ in range(3)]
-    v = head_of_first_eliminated(_wide_band_problem(n, ds[1], 1, block), block)
+    v = head_of_first_eliminated(wide_band_problem(n, ds[1], 1, block), block)
     ds[1][v] = -1.0 + eps  # lambda = 1: K[v, v] = eps
-    probs = [_wide_band_problem(n, ds[i], 1 + i, block) for i in range(3)]
+    probs = [wide_band_problem(n, ds[i], 1 + i, block) for i in range(3)]
     plan = plan_of(probs[1])
     assert plan.bw == bw and plan.block_size == block
     K = probs[1].hess_sparse().toarray() + np.eye(n)
@@ -364,10 +266,10 @@ def test_an_unstable_pivot_in_one_instance_is_repaired_on_its_handle(pgf):
     refine_tol = 1e-11
     perm = np.argsort(plan.pos)
     Kp, f = K[np.ix_(perm, perm)], probs[1].q[perm]
-    s0 = _level_one_solve(Kp, f, block)
-    assert _normwise(Kp, s0, f) >= 10 * refine_tol
-    s1 = s0 + _level_one_solve(Kp, f - Kp @ s0, block)
-    assert _normwise(Kp, s1, f) <= refine_tol
+    s0 = level_one_solve(Kp, f, block)
+    assert normwise(Kp, s0, f) >= 10 * refine_tol
+    s1 = s0 + level_one_solve(Kp, f - Kp @ s0, block)
+    assert normwise(Kp, s1, f) <= refine_tol
     ref, plain = refined_solve(K, probs[1].q)
     assert G.rel_err(plain, ref) < 1e-11
     bd = _batch(probs, "Full")
@@ -402,11 +304,9 @@ def test_the_flag_changes_nothing_for_a_narrow_batch_and_wide_needs_it(pgf):
     from pygradflow_amd import problems
 
     def narrow():
-        return [problems.box_qp(264, seed=30 + i) for i in range(3)]
+        return [forced(problems.box_qp(264, seed=30 + i)) for i in range(3)]
 
     probs = narrow()
-    for p in probs:
-        p.pgf_force_band = True
     assert plan_of(probs[0]).block_size == 8
     for pol, steps in (("Full", 2), ("Simplified", 2)):
         a, b = _batch(probs, pol, wide_band=True), _batch(probs, pol, wide_band=False)
@@ -425,8 +325,6 @@ def test_the_flag_changes_nothing_for_a_narrow_batch_and_wide_needs_it(pgf):
             run.close()
     # the split is a matter of the wide route: narrow instances may differ in it, as before
     mixed = narrow()
-    for p in mixed:
-        p.pgf_force_band = True
     mixed[1].pgf_band_split = False
     for flag in (False, True):
         a, b = _batch(mixed, "Full", wide_band=flag), _batch(probs, "Full", wide_band=False)
@@ -435,7 +333,7 @@ def test_the_flag_changes_nothing_for_a_narrow_batch_and_wide_needs_it(pgf):
         assert not st.any() and np.array_equal(a.points()[0], b.points()[0]), flag
         a.close()
         b.close()
-    wide = [_ocp(12, 4, 2, i) for i in range(2)]
+    wide = [multistate_ocp(12, 4, 2, i) for i in range(2)]
     with pytest.raises(ValueError, match="wide band"):
         _batch(wide, "Full", wide_band=False)
 
@@ -443,7 +341,7 @@ def test_the_flag_changes_nothing_for_a_narrow_batch_and_wide_needs_it(pgf):
 # ------------------------------------------------------------------ 9: batch of one, and 70 instances
 @pytest.mark.parametrize("pol,steps", [("Full", 2), ("Simplified", 3)])
 def test_batch_of_one_equals_the_single_handle(pgf, pol, steps):
-    prob = _ocp(12, 4, 2, 5)
+    prob = multistate_ocp(12, 4, 2, 5)
     n, m = prob.num_vars, prob.num_cons
     bd = _batch([prob], pol)
     dn = pgf.DeviceNewton(prob, pol, np.zeros(n), np.zeros(m), 1.0, 1.0)
@@ -463,12 +361,12 @@ def test_batch_of_one_equals_the_single_handle(pgf, pol, steps):
 def test_seventy_tiny_instances(pgf):
     """More instances than any grid.x of the sequence, several per CU: multistate_ocp(3, 4, 2), N = 30,
     two blocks of 16."""
-    probs = [_ocp(3, 4, 2, i) for i in range(70)]
+    probs = [multistate_ocp(3, 4, 2, i) for i in range(70)]
     assert plan_of(probs[0]).block_size == 16
     for pol, steps in (("Full", 2), ("Simplified", 2)):
         bd, ref = _batch(probs, pol), _batch(probs, pol, sequential=True)
         for k in range(steps):
-            _same_step(bd, ref, (pol, k))
+            same_step(bd, ref, (pol, k))
         red, sol, _ = bd.band_wide_stats()
         assert np.all(red + sol == steps)
         bd.close()

@@ -17,23 +17,18 @@ import pytest
 import scipy.sparse as sps
 
 from tests import golden_util as G
-from tests.band_util import (SWEEP_BOX, SWEEP_OCP, TOL, _against_oracle, band_problem,
+from tests.band_util import (SWEEP_BOX, SWEEP_OCP, TOL, _against_oracle, band_problem, forced,
                              head_of_first_eliminated, mask_changes, plan_of, refined_solve,
                              simplified_mask_goes_stale)
 
 pytestmark = pytest.mark.gpu
 
 
-def _forced(prob):
-    prob.pgf_force_band = True
-    return prob
-
-
 def _rebound(prob, lb, ub):
     """The same linear-quadratic problem with other bounds."""
     from pygradflow_amd import problems
 
-    return _forced(problems.LinearQuadraticProblem(prob.hess_sparse(), prob.q, prob.jac_sparse(), prob.b,
+    return forced(problems.LinearQuadraticProblem(prob.hess_sparse(), prob.q, prob.jac_sparse(), prob.b,
                                                    lb, ub))
 
 
@@ -42,7 +37,7 @@ def _rebound(prob, lb, ub):
 def test_auto_route_unconstrained_churning_mask(pgf, W):
     from pygradflow_amd import problems
 
-    prob = _forced(problems.grid_box_qp(W, 60))
+    prob = forced(problems.grid_box_qp(W, 60))
     plan = plan_of(prob)
     assert plan.bw in (9, 10) and plan.block is None
     assert mask_changes(prob, "Full", 3) > 0 and mask_changes(prob, "ActiveSet", 3) > 0
@@ -55,7 +50,7 @@ def test_auto_route_unconstrained_churning_mask(pgf, W):
 def test_auto_route_constrained_indefinite(pgf, shape):
     from pygradflow_amd import problems
 
-    prob = _forced(problems.multistate_ocp(*shape))
+    prob = forced(problems.multistate_ocp(*shape))
     plan = plan_of(prob)
     assert plan.bw in (9, 10) and plan.block is None
     assert simplified_mask_goes_stale(prob)
@@ -70,7 +65,7 @@ def test_auto_route_around_the_walk_panel(pgf, W, L):
     1181 at ldb 12), the route these bandwidths once took."""
     from pygradflow_amd import problems
 
-    prob = _forced(problems.grid_box_qp(W, L, seed=L))
+    prob = forced(problems.grid_box_qp(W, L, seed=L))
     assert plan_of(prob).bw in (9, 10)
     churn = _against_oracle(pgf, prob, (("Full", 2), ("Simplified", 1)), n_neg=0)
     assert churn > 0
@@ -80,7 +75,7 @@ def test_auto_route_around_the_walk_panel(pgf, W, L):
 def test_auto_route_all_and_none_active(pgf, bound):
     from pygradflow_amd import problems
 
-    prob = _forced(problems.grid_box_qp(9, 60, seed=2, bound=bound))
+    prob = forced(problems.grid_box_qp(9, 60, seed=2, bound=bound))
     assert plan_of(prob).bw in (9, 10)
     _against_oracle(pgf, prob, (("Full", 2), ("Simplified", 1)), n_neg=0)
     dn = pgf.DeviceNewton(prob, "Full", np.zeros(540), np.zeros(0), 1.0, 1.0)
@@ -118,8 +113,8 @@ def _linear_solver_view(pgf, prob, seed, with_rcond):
 def test_auto_route_exposes_linear_solver_and_rcond(pgf):
     from pygradflow_amd import problems
 
-    _linear_solver_view(pgf, _forced(problems.grid_box_qp(9, 60, seed=3)), 1, True)  # m = 0
-    _linear_solver_view(pgf, _forced(problems.multistate_ocp(50, 4, 1, seed=3)), 2, True)
+    _linear_solver_view(pgf, forced(problems.grid_box_qp(9, 60, seed=3)), 1, True)  # m = 0
+    _linear_solver_view(pgf, forced(problems.multistate_ocp(50, 4, 1, seed=3)), 2, True)
 
 
 # ------------------------------------------------------------------ B: the guard at bw 9, 10
@@ -141,9 +136,9 @@ def test_narrow_unstable_pivot_is_refined(pgf, bw):
     eps = 1e-9
     rng = np.random.default_rng(7)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    v = _badly_placed(_forced(band_problem(n, d, 1, bw)))
+    v = _badly_placed(forced(band_problem(n, d, 1, bw)))
     d[v] = -1.0 + eps  # lambda = 1: K[v, v] = eps
-    prob = _forced(band_problem(n, d, 1, bw))
+    prob = forced(band_problem(n, d, 1, bw))
     block = _block_in_use(prob)
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert abs(K[v, v]) < 1e-8 and np.linalg.cond(K) < 1e5
@@ -183,9 +178,9 @@ def test_narrow_not_quasi_definite_is_a_step_solver_error(pgf, bw):
     n = 300
     rng = np.random.default_rng(8)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    v = _badly_placed(_forced(band_problem(n, d, 2, bw)))
+    v = _badly_placed(forced(band_problem(n, d, 2, bw)))
     d[v] = -1.0
-    prob = _forced(band_problem(n, d, 2, bw))
+    prob = forced(band_problem(n, d, 2, bw))
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert K[v, v] == 0.0 and np.linalg.cond(K) < 1e6
     params = pgf.Params(newton_type="Full")
@@ -205,7 +200,7 @@ def test_device_newton_after_the_plugin_solver_on_a_pooled_handle(pgf):
     [9].)"""
     n = 300
     d = 2.5 + np.random.default_rng(11).uniform(0.0, 0.5, n)
-    A, B = _forced(band_problem(n, d, 21, 9)), _forced(band_problem(n, d, 22, 9))
+    A, B = forced(band_problem(n, d, 21, 9)), forced(band_problem(n, d, 22, 9))
     x0, y0 = np.zeros(n), np.zeros(0)
     dn = pgf.DeviceNewton(A, "Full", x0, y0, 1.0, 1.0)
     dn.step()
@@ -233,7 +228,7 @@ def _sweep_problem(kind, size):
     from pygradflow_amd import problems
 
     prob = problems.box_qp(size, seed=size) if kind == "box" else problems.sparse_ocp(size, seed=size)
-    return _forced(prob)
+    return forced(prob)
 
 
 @pytest.mark.parametrize("kind,size", [("box", n) for n in SWEEP_BOX] + [("ocp", m) for m in SWEEP_OCP])
@@ -292,7 +287,7 @@ def _bandwidth_case(bw):
 
 @pytest.mark.parametrize("bw", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_every_bandwidth_up_to_8(pgf, bw):
-    prob = _forced(_bandwidth_case(bw))
+    prob = forced(_bandwidth_case(bw))
     plan = plan_of(prob)
     assert plan.bw == bw and plan.block_size == 8
     churn = _against_oracle(pgf, prob, (("Full", 2), ("Simplified", 1)), n_neg=prob.num_cons)
@@ -364,7 +359,7 @@ def test_singular_matrix_is_an_error_and_the_handle_survives(pgf):
     H[v, :] = 0.0
     H[:, v] = 0.0
     H[v, v] = -1.0
-    bad = _forced(problems.LinearQuadraticProblem(sps.csr_matrix(H), good.q, good.jac_sparse(), good.b,
+    bad = forced(problems.LinearQuadraticProblem(sps.csr_matrix(H), good.q, good.jac_sparse(), good.b,
                                                   good.var_lb, good.var_ub))
     K = bad.hess_sparse().toarray() + np.eye(n)
     assert not K[v].any() and plan_of(bad).block_size == 8
@@ -383,11 +378,11 @@ def test_singular_matrix_is_an_error_and_the_handle_survives(pgf):
     with pytest.raises(StepSolverError):
         dn.step()
     dn.close()
-    dn = pgf.DeviceNewton(_forced(good), "Full", np.zeros(n), np.zeros(0), 1.0, 1.0)
+    dn = pgf.DeviceNewton(forced(good), "Full", np.zeros(n), np.zeros(0), 1.0, 1.0)
     assert dn._hd is handle
     _, nn = dn.step()
     x, _ = dn.point()
     Kg = good.hess_sparse().toarray() + np.eye(n)
     assert nn == 0 and G.rel_err(x, -np.linalg.solve(Kg, good.q)) <= TOL
     dn.close()
-    _against_oracle(pgf, _forced(good), (("Full", 2), ("Simplified", 1)), n_neg=0)
+    _against_oracle(pgf, forced(good), (("Full", 2), ("Simplified", 1)), n_neg=0)

@@ -22,25 +22,14 @@ if __name__ == "__main__" and REPO not in sys.path:
 
 from oracle import newton_oracle as O  # noqa: E402
 from tests import golden_util as G  # noqa: E402
-from tests.band_util import (TOL, _against_oracle, _as_sparse_lq, band_problem, bordered_lq,  # noqa: E402
-                             head_of_first_eliminated, mask_changes, plan_of, refined_solve)
+from tests.band_util import (TOL, _against_oracle, _as_sparse_lq, bordered_lq, head_of_first_eliminated,  # noqa: E402
+                             mask_changes, multistate_ocp, plan_of, refined_solve, wide_band_problem)
 
 pytestmark = pytest.mark.gpu
 
 
 def _delta(after, before):
     return tuple(a - b for a, b in zip(after, before))
-
-
-def _ocp(T, nx, nu, seed, block, split=None):
-    from pygradflow_amd import problems
-
-    prob = problems.multistate_ocp(T, nx, nu, seed=seed)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
-    if split is not None:
-        prob.pgf_band_split = split
-    return prob
 
 
 def _step_solver(pgf, prob, mask=None, dt=1.0, rho=1.0, newton_type="Full"):
@@ -65,7 +54,7 @@ def test_block_count_edges(pgf, args, block):
     missing right neighbour at every level, powers of two on either side of 32; (2, 6, 3) and
     (30, 6, 3) at B = 32, 64.  Against the oracle, and the route of a Simplified trajectory: one
     reduction, then solve phases only."""
-    prob = _ocp(*args, block)
+    prob = multistate_ocp(*args, block)
     n, m = prob.num_vars, prob.num_cons
     _against_oracle(pgf, prob, (("Full", 1), ("Simplified", 3)), n_neg=m)
     x0, y0 = np.zeros(n), np.zeros(m)
@@ -94,7 +83,7 @@ def test_split_returns_the_same_bits(pgf, args, block):
     rng = np.random.default_rng(block)
     out = {}
     for split in (True, False):
-        prob = _ocp(*args, block, split=split)
+        prob = multistate_ocp(*args, block, split=split)
         sv, it = _step_solver(pgf, prob)
         b0 = sv.band_stats()
         res = sv.solve(it)
@@ -164,7 +153,7 @@ def test_active_set_changes_invalidate_the_kept_factors(pgf):
 
 
 def test_new_values_invalidate_the_kept_factors(pgf):
-    prob = _ocp(30, 6, 3, 3, 32)
+    prob = multistate_ocp(30, 6, 3, 3, 32)
     sv, it = _step_solver(pgf, prob)
     b0 = sv.band_stats()
     res = sv.solve(it)
@@ -207,7 +196,7 @@ def test_panel_solve(pgf, block):
     """(rows, nrhs) right-hand sides through _DeviceFactorView.solve: panels of at most 64 columns
     against the factors the step left; 1, 2 (one tile of 16 columns, mostly padding), 16, 17, 64,
     65 (a second panel of one column)."""
-    prob = _ocp(30, 6, 3, 3, block)
+    prob = multistate_ocp(30, 6, 3, 3, block)
     sv, it = _step_solver(pgf, prob)
     sv.solve(it)
     assert sv._hd.plan.block_size == block
@@ -342,10 +331,6 @@ def _child(out):
 
 
 # ------------------------------------------------------------------ 6: the guard through the kept factors
-def _hess_problem(n, d, seed):
-    return band_problem(n, d, seed, 12)
-
-
 @pytest.mark.parametrize("block", [16, 64])
 def test_guard_refines_through_the_kept_factors(pgf, block):
     """The construction of test_wide_unstable_pivot_is_refined: K[v, v] = 1e-9 at the head of
@@ -354,13 +339,9 @@ def test_guard_refines_through_the_kept_factors(pgf, block):
     n, eps = 300, 1e-9
     rng = np.random.default_rng(7)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    base = _hess_problem(n, d, 1)
-    base.pgf_band_block = block
-    v = head_of_first_eliminated(base, block)
+    v = head_of_first_eliminated(wide_band_problem(n, d, 1, block), block)
     d[v] = -1.0 + eps  # lambda = 1: K[v, v] = eps
-    prob = _hess_problem(n, d, 1)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
+    prob = wide_band_problem(n, d, 1, block)
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert abs(K[v, v]) < 1e-8 and np.linalg.cond(K) < 1e5
     sv, it = _step_solver(pgf, prob, mask=np.zeros(n, dtype=bool))
@@ -391,13 +372,9 @@ def test_zero_pivot_leaves_no_kept_factor(pgf, block):
     n = 300
     rng = np.random.default_rng(8)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    base = _hess_problem(n, d, 2)
-    base.pgf_band_block = block
-    v = head_of_first_eliminated(base, block)
+    v = head_of_first_eliminated(wide_band_problem(n, d, 2, block), block)
     d[v] = -1.0
-    prob = _hess_problem(n, d, 2)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
+    prob = wide_band_problem(n, d, 2, block)
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert K[v, v] == 0.0 and np.linalg.cond(K) < 1e6
     sv, it = _step_solver(pgf, prob, mask=np.zeros(n, dtype=bool))

@@ -6,11 +6,10 @@ Bars as in test_gpu_parity.py: masks bit-identical, x and y within 1e-10 relativ
 
 import numpy as np
 import pytest
-import scipy.sparse as sps
 
 from oracle import newton_oracle as O
 from tests import golden_util as G
-from tests.band_util import TOL, _against_oracle, _as_sparse_lq
+from tests.band_util import TOL, _against_oracle, _as_sparse_lq, head_of_first_eliminated, wide_band_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -167,39 +166,15 @@ def test_wide_factor_exposes_linear_solver_and_rcond(pgf, block):
 
 
 # ------------------------------------------------------------------ G: the guard
-def _wide_band_problem(n, d, seed):
-    """H = diag(d) + a symmetric band of half-width 12 with small entries, m = 0, no bounds."""
-    from pygradflow_amd import problems
-
-    rng = np.random.default_rng(seed)
-    offs = [k for k in range(-12, 13) if k != 0]
-    vals = {k: 0.04 * rng.uniform(0.5, 1.0, n - abs(k)) for k in range(1, 13)}
-    diags = [vals[abs(k)] for k in offs]
-    H = (sps.diags(diags, offs) + sps.diags(d)).tocsr()
-    return problems.LinearQuadraticProblem(H, rng.standard_normal(n), sps.csr_matrix((0, n)), np.zeros(0),
-                                           np.full(n, -np.inf), np.full(n, np.inf))
-
-
-def _head_of_first_eliminated(prob, block):
-    """Variable that the plan puts first in block 1 (inverted as it stands by level one)."""
-    from pygradflow_amd.sparse import BandPlan
-
-    plan = BandPlan(prob.hess_sparse(), prob.jac_sparse(), prob.num_vars, 0, block=block)
-    assert plan.bw <= block
-    return int(np.nonzero(plan.pos == block)[0][0])
-
-
 @pytest.mark.parametrize("block", [16, 64])
 def test_wide_unstable_pivot_is_refined(pgf, block):
     n = 300
     eps = 1e-9
     rng = np.random.default_rng(7)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    v = _head_of_first_eliminated(_wide_band_problem(n, d, 1), block)
+    v = head_of_first_eliminated(wide_band_problem(n, d, 1, block), block)
     d[v] = -1.0 + eps  # lambda = 1: K[v, v] = eps
-    prob = _wide_band_problem(n, d, 1)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
+    prob = wide_band_problem(n, d, 1, block)
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert abs(K[v, v]) < 1e-8 and np.linalg.cond(K) < 1e5
     params = pgf.Params(newton_type="Full")
@@ -236,11 +211,9 @@ def test_not_quasi_definite_is_a_step_solver_error(pgf, block):
     n = 300
     rng = np.random.default_rng(8)
     d = 2.5 + rng.uniform(0.0, 0.5, n)
-    v = _head_of_first_eliminated(_wide_band_problem(n, d, 2), block)
+    v = head_of_first_eliminated(wide_band_problem(n, d, 2, block), block)
     d[v] = -1.0
-    prob = _wide_band_problem(n, d, 2)
-    prob.pgf_force_band = True
-    prob.pgf_band_block = block
+    prob = wide_band_problem(n, d, 2, block)
     K = prob.hess_sparse().toarray() + np.eye(n)
     assert K[v, v] == 0.0 and np.linalg.cond(K) < 1e6
     params = pgf.Params(newton_type="Full")

@@ -42,34 +42,19 @@ if __name__ == "__main__" and REPO not in sys.path:
 
 from oracle import newton_oracle as O  # noqa: E402
 from tests import golden_util as G  # noqa: E402
-from tests.band_util import (TOL, _against_oracle, bordered_lq, head_of_first_eliminated, plan_of,  # noqa: E402
-                             refined_solve)
+from tests.band_util import (COND_MAX, TOL, _against_oracle, case, guard_case, plan_of,  # noqa: E402
+                             reduced_kkt, refined_solve)
 
 pytestmark = pytest.mark.gpu
 
-COND_MAX = 1e4
 WIDTHS = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64)
 ROWS = (1, 7, 8, 9, 16, 17, 24, 255, 256, 257, 511, 512, 513, 1023, 1025)
 ROUTE_SHAPES = ((1, 9), (33, 513), (64, 257))
 REPEATED_SHAPES = ((1, 9), (33, 513), (48, 203), (64, 257))
 
 
-def case(k, Nb, bw=2, block=None, mloc=None, seed=None, bound=0.5):
-    """bordered_lq with k border nodes (a third of them variables) and Nb band rows (a quarter of
-    them local constraints unless mloc is given)."""
-    mloc = Nb // 4 if mloc is None else mloc
-    kv = k // 3
-    return bordered_lq(Nb - mloc, bw, mloc, kv, k - kv, 1000 * k + Nb if seed is None else seed,
-                       block=block, bound=bound)
-
-
 def random_mask(prob, seed=0):
     return np.random.default_rng([seed, prob.num_vars, prob.num_cons]).uniform(size=prob.num_vars) < 0.4
-
-
-def reduced_kkt(prob, mask, lamb=1.0, rho=1.0):
-    return O.kkt_matrix(O.shifted_hess_rows(prob.hess_sparse(), lamb, mask), prob.jac_sparse().tocsc(), mask,
-                        lamb, rho).toarray()
 
 
 def right_hand_sides(K):
@@ -248,37 +233,6 @@ def test_masks(pgf, which):
 
 
 # ------------------------------------------------------------------ 5: the guard with a border
-def with_hess_diagonal(prob, v, value):
-    """The same problem with H[v, v] = value; border and block settings kept."""
-    from pygradflow_amd import problems
-
-    H = sps.lil_matrix(prob.hess_sparse())
-    H[v, v] = value
-    new = problems.LinearQuadraticProblem(sps.csr_matrix(H), prob.q, prob.jac_sparse(),
-                                          prob.b, prob.var_lb, prob.var_ub)
-    new.pgf_border = list(prob.pgf_border)
-    if getattr(prob, "pgf_band_block", None):
-        new.pgf_band_block = prob.pgf_band_block
-    return new
-
-
-def guard_case(k, block, pivot):
-    """Nb = 300 band variables with a full band of half-width 8 and no local constraints, the
-    layout of the narrow test one bandwidth down.  The variable v at the head of block 1 of B
-    (inverted as it stands by level one of either reduction) gets K[v, v] = pivot at lambda = 1;
-    the box is +-1e6, so no variable is active and v keeps its in-block couplings c = 0.04 U(0.5, 1).
-    With pivot = 1e-9 the unpivoted inverse of that block adds c^2 / pivot, about 1e6, to entries
-    of order one: a relative error near 1e6 u = 1e-10, ten times refine_tol, before the reduction
-    has done anything else."""
-    kv = k // 3
-    base = bordered_lq(300, 8, 0, kv, k - kv, 77 + k + block, block=None if block == 8 else block, bound=1e6)
-    v = head_of_first_eliminated(base, block)
-    assert v < 300  # a band variable
-    prob = with_hess_diagonal(base, v, -1.0 + pivot)
-    assert plan_of(prob).block_size == block and head_of_first_eliminated(prob, block) == v
-    return prob, v
-
-
 @pytest.mark.parametrize("block", [8, 16])
 @pytest.mark.parametrize("k", [1, 17])
 def test_bordered_unstable_pivot_is_refined(pgf, k, block):
