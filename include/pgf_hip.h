@@ -290,7 +290,8 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * finished per instance on the device (kernel kbb_step_final): step length, pivot flag, and the
  * guard's measure against the refine_tol the instance's handle had at pgf_batch_ctl_init (never
  * when its refine_mode is off).  An instance above its tolerance cannot be refined on its handle
- * inside a loop without host round trips: its step counts as FAILED, the controller rejects it with
+ * inside a loop without host round trips: without PGF_BATCH_CTL_REFINE (below, which refines it on
+ * the device) its step counts as FAILED, the controller rejects it with
  * 2 lambda and the instance goes back to its outer point at the next iteration -- the reference's
  * own recovery, a larger lambda makes K quasi-definite again (step_control.py:80-107).
  * pgf_batch_debug_ctl_stats counts such steps.  pgf_batch_ctl_read brings the device's frozen
@@ -312,9 +313,9 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * pgf_batch_debug_border_stats counts the phases per instance.  Refused under these flags: a border
  * on a wide remainder, with or without PGF_BATCH_WIDE_BAND ("batch: a bordered band joins a device
  * batch on the narrow route only (block size 8)"; PGF_BATCH_WIDE_BORDER, below, admits it), and
- * PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL on handles that have a border ("batch: the device-resident
- * controller does not drive a bordered band batch").  Handles without a border behave with the flag
- * as without it.
+ * PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL without PGF_BATCH_BORDER_CTL (below) on handles that have a
+ * border ("batch: the device-resident controller does not drive a bordered band batch").  Handles
+ * without a border behave with the flag as without it.
  *
  * PGF_BATCH_WIDE_BORDER, valid only as PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND | PGF_BATCH_WIDE_BORDER
  * (the bit without both of the others is PGF_INVALID), admits BORDERED instances whose remainder
@@ -328,13 +329,45 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * are, bit for bit, those of the single handles (PGF_BORDER_MULTI=0 stays a single-handle switch:
  * the batch always takes the panel route).  pgf_batch_debug_border_stats counts the phases, and
  * pgf_batch_debug_band_wide_stats the factor-only reductions and kept-factor solve phases of B,
- * which equal them.  A border under PGF_BATCH_BAND_CTL stays refused as above.  Narrow bordered
- * instances and instances without a border behave with the bit as under the other two alone. */
+ * which equal them.  A border under PGF_BATCH_BAND_CTL without PGF_BATCH_BORDER_CTL stays refused as
+ * above.  Narrow bordered instances and instances without a border behave with the bit as under the
+ * other two alone.
+ *
+ * PGF_BATCH_BORDER_CTL, valid only together with PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL (the bit
+ * without both is PGF_INVALID before any handle is read; on a wide remainder PGF_BATCH_WIDE_BAND |
+ * PGF_BATCH_WIDE_BORDER are needed as above), admits handles that have a border under
+ * PGF_BATCH_BAND_CTL: pgf_batch_ctl_init / _iterate / _read drive the bordered batch on the narrow
+ * route and on the wide route.  Step one of an iteration enqueues the factor phase and each
+ * instance decides from its control word; step two under a policy that keeps the mask is enqueued
+ * without factor-phase launches (a bad pivot in B or in S, or a miss of the guard, in step one has
+ * frozen the instance, so every live instance holds valid Y, factor of S and kept factors of B).
+ * The step is finished on the device as on an unbordered band batch: the pivot flag is that of B
+ * or S, the inertia that of B plus S.  Handles without a border behave with the bit as under
+ * PGF_BATCH_BAND_CTL alone.
+ *
+ * PGF_BATCH_CTL_REFINE, valid only with PGF_BATCH_BAND_CTL (PGF_INVALID otherwise; on a dense batch
+ * it changes nothing): a banded step inside pgf_batch_ctl_iterate whose guard measure misses the
+ * refine_tol its handle had at pgf_batch_ctl_init is REFINED on the device instead of rejected --
+ * what pgf_batch_sync does on the instance's handle, by the same device functions in the same
+ * order.  At most two rounds: a round runs while refine_tol < rel < 1 and stops when the measure
+ * does not fall; each round keeps the solution, solves for the residual with the guard off (the
+ * 8 x 8 reduction on the intact band; the solve phase against the kept factors on a wide band with
+ * the split on, the whole reduction with it off; with a border the solve phase against Y and the
+ * factor of S), adds the correction, takes the residual and the step again from the point the step
+ * started from.  Afterwards the step is a miss -- bit 2, counted by pgf_batch_debug_ctl_stats,
+ * rejected with 2 lambda -- if and only if the measure is still above the refine_fail the handle
+ * had at pgf_batch_ctl_init.  Both rounds are enqueued at every banded step of the loop; the
+ * workgroups of instances that do not refine return at once.  No factor is touched, so the lean
+ * second step stays lean.  pgf_batch_debug_ctl_refine_stats counts refined steps and rounds;
+ * pgf_batch_debug_band_wide_stats and pgf_batch_debug_border_stats count a round's solve phase as
+ * a solve phase (split off: its reduction as a reduction). */
 typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BAND 1u
 #define PGF_BATCH_BAND_CTL 2u
 #define PGF_BATCH_BORDER 4u
 #define PGF_BATCH_WIDE_BORDER 8u
+#define PGF_BATCH_BORDER_CTL 16u /* with PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL */
+#define PGF_BATCH_CTL_REFINE 32u /* with PGF_BATCH_BAND_CTL */
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
@@ -604,6 +637,11 @@ int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_pha
  * the instance's refine_tol, since the batch was created (arrays of `count` ints, synchronises).
  * Zeros on a dense batch and on a band batch without the flag.  Any pointer may be NULL. */
 int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *guard_rejects);
+/* per instance: steps of pgf_batch_ctl_iterate's loop that were refined on the device
+ * (PGF_BATCH_CTL_REFINE) and the refinement rounds they ran, since the batch was created (arrays of
+ * `count` ints, synchronises).  Zeros on a batch without the flag.  Any pointer may be NULL;
+ * b == NULL is PGF_INVALID and leaves the outputs alone. */
+int pgf_batch_debug_ctl_refine_stats(pgf_batch b, int *refined_steps, int *rounds);
 /* per instance: factor phases and solve phases of the bordered route the instance ran since the
  * batch was created (PGF_BATCH_BORDER; arrays of `count` ints, counted on the device, synchronises).
  * Zeros on a batch that is not bordered.  Any pointer may be NULL. */

@@ -28,6 +28,8 @@ BATCH_WIDE_BAND = 1
 BATCH_BAND_CTL = 2
 BATCH_BORDER = 4
 BATCH_WIDE_BORDER = 8
+BATCH_BORDER_CTL = 16
+BATCH_CTL_REFINE = 32
 FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
 FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 
@@ -127,6 +129,7 @@ SIGNATURES = {
     "pgf_batch_debug_band_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_debug_band_wide_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_debug_ctl_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_batch_debug_ctl_refine_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_debug_border_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_sparse_pattern_hash": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                           _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),

@@ -93,7 +93,8 @@ class BatchedDeviceNewton:
     bordered solve only where its matrix changed, the solve phase every step; the results are those
     of the single handles bit for bit.  ``self.band_border`` is k for a band batch (0 without a
     border, ``None`` on a dense batch), ``border_stats()`` counts the phases per instance.  A border
-    on a wide remainder (without ``wide_border``) and a border under ``band_ctl`` are refused.
+    on a wide remainder (without ``wide_border``) and a border under ``band_ctl`` (without
+    ``border_ctl``) are refused.
 
     ``wide_border=True`` (``PGF_BATCH_WIDE_BORDER``; it sets ``wide_band`` and ``border`` too, the
     three bits go together) admits bordered instances whose remainder is on the wide route: one
@@ -102,7 +103,8 @@ class BatchedDeviceNewton:
     the kept factors; every step solves against them.  ``band_block`` is 16, 32 or 64 and
     ``band_border`` is k; ``border_stats()`` counts the phases and ``band_wide_stats()`` the
     factor-only reductions and kept-factor solves of the band, which equal them.  Host-driven steps
-    only (``band_ctl`` refuses a border); no effect with ``sequential=True``.
+    unless ``border_ctl`` is given (``band_ctl`` without it refuses a border); no effect with
+    ``sequential=True``.
 
     ``band_ctl=True`` (``PGF_BATCH_BAND_CTL``, alone or with ``wide_band``) opens the device-resident
     step controller (``ctl_init / ctl_iterate / ctl_read``) to a band batch; without it a band batch
@@ -110,11 +112,23 @@ class BatchedDeviceNewton:
     an instance whose solve misses its handle's ``refine_tol`` is not repaired on its handle (that
     needs the host): its step is rejected with 2 lambda, like a failed factorisation.
     ``ctl_stats()`` counts such steps.
+
+    ``border_ctl=True`` (``PGF_BATCH_BORDER_CTL``; the library takes it only with ``border`` and
+    ``band_ctl``, which are the caller's to give) lets the device-resident controller drive a bordered
+    band batch, on the narrow route and, with ``wide_border``, on the wide one.  Without it the
+    refusal stays; instances without a border take no notice of it.
+
+    ``ctl_refine=True`` (``PGF_BATCH_CTL_REFINE``, only with ``band_ctl``) refines such an instance
+    inside ``ctl_iterate`` on the device, as the host-driven batch repairs it on its handle: at most
+    two rounds by the handle's rule, the same device functions in the same order.  The step is
+    rejected only when the measure stays above the handle's ``refine_fail``.  Every banded step of
+    the loop then carries the launches of two rounds, whose workgroups return at once for instances
+    that do not refine.  ``ctl_refine_stats()`` counts refined steps and rounds.
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
                  world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False,
-                 border=False, wide_border=False):
+                 border=False, wide_border=False, border_ctl=False, ctl_refine=False):
         import ctypes as C
         import math
 
@@ -150,6 +164,8 @@ class BatchedDeviceNewton:
         self.wide_band = bool(wide_band) or self.wide_border
         self.band_ctl = bool(band_ctl)
         self.border = bool(border) or self.wide_border
+        self.border_ctl = bool(border_ctl)
+        self.ctl_refine = bool(ctl_refine)
         self.band_border = None
         self._frozen = None
         self._outer_points = [s.point() for s in self.solvers] if self.sequential else []
@@ -169,14 +185,18 @@ class BatchedDeviceNewton:
 
     def _create(self, lib, handles, out):
         """The device batch over ``handles``: through ``pgf_batch_create_ex`` with
-        ``PGF_BATCH_WIDE_BAND``, ``PGF_BATCH_BAND_CTL``, ``PGF_BATCH_BORDER`` and / or
-        ``PGF_BATCH_WIDE_BORDER`` when ``wide_band`` / ``band_ctl`` / ``border`` / ``wide_border`` was
-        asked for (``wide_border`` has set the first and the third as well: the library takes its bit
-        only with both), ``pgf_batch_create`` otherwise."""
+        ``PGF_BATCH_WIDE_BAND``, ``PGF_BATCH_BAND_CTL``, ``PGF_BATCH_BORDER``,
+        ``PGF_BATCH_WIDE_BORDER``, ``PGF_BATCH_BORDER_CTL`` and / or ``PGF_BATCH_CTL_REFINE`` when
+        ``wide_band`` / ``band_ctl`` / ``border`` / ``wide_border`` / ``border_ctl`` / ``ctl_refine``
+        was asked for (``wide_border`` has set the first and the third as well: the library takes its
+        bit only with both; the last two are passed as given, and the library refuses them without
+        their companions), ``pgf_batch_create`` otherwise."""
         flags = (self._lib.BATCH_WIDE_BAND if self.wide_band else 0) | \
             (self._lib.BATCH_BAND_CTL if getattr(self, "band_ctl", False) else 0) | \
             (self._lib.BATCH_BORDER if getattr(self, "border", False) else 0) | \
-            (self._lib.BATCH_WIDE_BORDER if getattr(self, "wide_border", False) else 0)
+            (self._lib.BATCH_WIDE_BORDER if getattr(self, "wide_border", False) else 0) | \
+            (self._lib.BATCH_BORDER_CTL if getattr(self, "border_ctl", False) else 0) | \
+            (self._lib.BATCH_CTL_REFINE if getattr(self, "ctl_refine", False) else 0)
         if flags:
             return lib.pgf_batch_create_ex(handles, self.count, flags, out)
         return lib.pgf_batch_create(handles, self.count, out)
@@ -416,6 +436,20 @@ class BatchedDeviceNewton:
         self._lib.check(self._lib.load().pgf_batch_debug_ctl_stats(
             self._b, piv.ctypes.data_as(ip), grd.ctypes.data_as(ip)), batch=self._b)
         return piv, grd
+
+    def ctl_refine_stats(self):
+        """(refined_steps[count], rounds[count]) of a ``ctl_refine`` batch
+        (``pgf_batch_debug_ctl_refine_stats``): per instance the Newton steps ``ctl_iterate`` refined
+        on the device and the refinement rounds they ran.  Zeros on any other batch.  Device batch
+        only."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        ref = np.zeros(self.count, dtype=np.int32)
+        rnd = np.zeros(self.count, dtype=np.int32)
+        ip = self._C.POINTER(self._C.c_int)
+        self._lib.check(self._lib.load().pgf_batch_debug_ctl_refine_stats(
+            self._b, ref.ctypes.data_as(ip), rnd.ctypes.data_as(ip)), batch=self._b)
+        return ref, rnd
 
     def factor_kind(self):
         """Pivot order of the factors the batch's instances hold: 0 none yet, 1 the natural

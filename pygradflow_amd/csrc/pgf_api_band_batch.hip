@@ -45,7 +45,8 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     if (sp.bk && sp.B != 8 && !wide_border_ok)
       return fail(h, PGF_INVALID,
                   "batch: a bordered band joins a device batch on the narrow route only (block size 8)");
-    if (sp.bk && (flags & PGF_BATCH_BAND_CTL))
+    // (pgf_batch_create_ex has seen to it that PGF_BATCH_BORDER_CTL comes with the other two)
+    if (sp.bk && (flags & PGF_BATCH_BAND_CTL) && !(flags & PGF_BATCH_BORDER_CTL))
       return fail(h, PGF_INVALID, "batch: the device-resident controller does not drive a bordered band batch");
     // (the wide border's phases are those of the handle under wide_kept, pgf_border.hip: B factorised
     // once, every solve against the kept factors)
@@ -69,6 +70,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   if (!b) return PGF_INVALID;
   b->band = true;
   b->band_ctl = (flags & PGF_BATCH_BAND_CTL) != 0;
+  b->ctl_refine = b->band_ctl && (flags & PGF_BATCH_CTL_REFINE) != 0;
   b->hs.assign(handles, handles + count);
   b->B = count;
   b->n = h0->n;
@@ -115,12 +117,25 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   if (b->band_ctl &&
       ((e = hipMalloc((void **)&b->flags_out, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
        (e = hipMalloc((void **)&b->diff_out, cnt * sizeof(double))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->band_guard, cnt * 2 * sizeof(double))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->band_guard, cnt * BG_STRIDE * sizeof(double))) != hipSuccess ||
        (e = hipMalloc((void **)&b->band_rejects, cnt * 2 * sizeof(int))) != hipSuccess ||
        (e = hipMemset(b->flags_out, 0, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
        (e = hipMemset(b->diff_out, 0, cnt * sizeof(double))) != hipSuccess ||
-       (e = hipMemset(b->band_guard, 0, cnt * 2 * sizeof(double))) != hipSuccess ||
+       (e = hipMemset(b->band_guard, 0, cnt * BG_STRIDE * sizeof(double))) != hipSuccess ||
        (e = hipMemset(b->band_rejects, 0, cnt * 2 * sizeof(int))) != hipSuccess)) {
+    pgf_batch_destroy(b);
+    return PGF_HIP_ERROR + (int)e;
+  }
+  // the refinement rounds' table, control words (written by each round's decision kernel before
+  // anything reads them), measure and counters
+  if (b->ctl_refine &&
+      ((e = hipMalloc((void **)&b->rtab, cnt * sizeof(BandInst))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->rctl, cnt * 4 * sizeof(int))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->rcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
+       (e = hipMalloc((void **)&b->rrel, cnt * sizeof(double))) != hipSuccess ||
+       (e = hipMemset(b->rctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
+       (e = hipMemset(b->rcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
+       (e = hipMemset(b->rrel, 0, cnt * sizeof(double))) != hipSuccess)) {
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
   }
@@ -209,6 +224,13 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
   }
+  if (b->ctl_refine) {
+    for (int i = 0; i < count; ++i) btab[i].ctl = b->rctl + 4 * i;
+    if ((e = hipMemcpy(b->rtab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess) {
+      pgf_batch_destroy(b);
+      return PGF_HIP_ERROR + (int)e;
+    }
+  }
   *out = b;
   return PGF_OK;
 }
@@ -221,6 +243,10 @@ void band_batch_free(pgf_batch b) {
   if (b->h_bstat) (void)hipHostFree(b->h_bstat);
   if (b->band_guard) (void)hipFree(b->band_guard);
   if (b->band_rejects) (void)hipFree(b->band_rejects);
+  if (b->rtab) (void)hipFree(b->rtab);
+  if (b->rctl) (void)hipFree(b->rctl);
+  if (b->rcnt) (void)hipFree(b->rcnt);
+  if (b->rrel) (void)hipFree(b->rrel);
 }
 
 // c = A x - b ; w = rho c + y ; g = Q x + (q + A' w) at every instance's point
@@ -403,15 +429,55 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
 // where band_batch_sync would finish the step on the host, kbb_step_final on the device.
 void band_batch_enqueue_final(pgf_batch b) {
   bandb_launch_step_final(b->stream, b->btab, b->B, b->bsh, b->band_guard, b->diff_out, b->flags_out,
-                          b->band_rejects);
+                          b->band_rejects, b->ctl_refine ? b->rctl : nullptr);
+}
+
+// PGF_BATCH_CTL_REFINE, between the step update and kbb_step_final: band_batch_sync ->
+// band_batch_repair -> band_refine on the device, for the instances whose measure asks for it.  The
+// host cannot know which: both rounds are enqueued, every launch of a round on the refinement table,
+// whose ctl[3] the round's decision kernel has set for every instance that does not refine -- its
+// workgroups return at once.  ctl[0] is 0 there: nothing assembles, a wide band with the split on
+// solves against its kept factors (the step left them clean, or the instance would not refine), and
+// the step update writes no ctl[1].  A round, per route, is band_refine's loop body: the copies,
+// sp_cyclic_solve(guard = false), the axpy, sp_cyclic_residual, and the step taken again from the
+// point it started from (which the load kernel has put back).  No factor phase is touched, so a
+// lean second step stays lean; the round's solve counts as a solve phase in wcnt / bcnt (split off:
+// as a reduction).
+void band_batch_enqueue_refine(pgf_batch b) {
+  hipStream_t s = b->stream;
+  const BandShape &sh = b->bsh;
+  const BandInst *rt = b->rtab;
+  for (int round = 0; round < 2; ++round) {
+    bandb_launch_refine_decide(s, b->btab, b->B, sh, b->band_guard, b->rctl, b->rrel, b->rcnt, round);
+    bandb_launch_refine_load(s, rt, b->B, sh);
+    if (sh.bk) {
+      borderb_launch_solve(s, rt, b->B, sh, /*guard=*/false);
+      bandb_launch_refine_axpy(s, rt, b->B, sh);
+      borderb_launch_residual(s, rt, b->B, sh);
+    } else if (sh.B > 8) {
+      if (sh.split)
+        bandb_launch_wide_kept_solve(s, rt, b->B, sh);
+      else
+        bandb_launch_wide_solve(s, rt, b->B, sh, /*lean=*/false, /*guard=*/false);
+      bandb_launch_refine_axpy(s, rt, b->B, sh);
+      bandb_launch_wide_residual(s, rt, b->B, sh);
+    } else {
+      bandb_launch_solve(s, rt, b->B, sh, /*residual=*/false, /*save_rhs=*/false);
+      bandb_launch_refine_axpy(s, rt, b->B, sh);
+      bandb_launch_residual(s, rt, b->B, sh);
+    }
+    bandb_launch_step_update(s, rt, b->B, sh);
+  }
 }
 
 // the guard's setting of every handle, as it stands now (pgf_set_refinement), for kbb_step_final
+// and the refinement rounds
 int band_batch_ctl_init(pgf_batch b) {
-  std::vector<double> g((size_t)2 * b->B);
+  std::vector<double> g((size_t)BG_STRIDE * b->B);
   for (int i = 0; i < b->B; ++i) {
-    g[2 * (size_t)i] = b->hs[i]->refine_mode ? 1.0 : 0.0;
-    g[2 * (size_t)i + 1] = b->hs[i]->refine_tol;
+    g[BG_STRIDE * (size_t)i] = b->hs[i]->refine_mode ? 1.0 : 0.0;
+    g[BG_STRIDE * (size_t)i + 1] = b->hs[i]->refine_tol;
+    g[BG_STRIDE * (size_t)i + 2] = b->hs[i]->refine_fail;
   }
   BHIPCHK(b, hipMemcpyAsync(b->band_guard, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice,
                             b->stream));
@@ -447,6 +513,22 @@ extern "C" int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *g
   for (int i = 0; i < b->B; ++i) {
     if (pivot_rejects) pivot_rejects[i] = cnt[2 * (size_t)i];
     if (guard_rejects) guard_rejects[i] = cnt[2 * (size_t)i + 1];
+  }
+  return PGF_OK;
+}
+
+extern "C" int pgf_batch_debug_ctl_refine_stats(pgf_batch b, int *refined_steps, int *rounds) {
+  if (!b) return PGF_INVALID;
+  if (!refined_steps && !rounds) return PGF_OK;
+  std::vector<int> cnt((size_t)2 * b->B, 0);
+  if (b->rcnt) {
+    (void)hipSetDevice(b->device);
+    BHIPCHK(b, hipStreamSynchronize(b->stream));
+    BHIPCHK(b, hipMemcpy(cnt.data(), b->rcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < b->B; ++i) {
+    if (refined_steps) refined_steps[i] = cnt[2 * (size_t)i];
+    if (rounds) rounds[i] = cnt[2 * (size_t)i + 1];
   }
   return PGF_OK;
 }

@@ -38,12 +38,18 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
 
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
-  if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER | PGF_BATCH_WIDE_BORDER))
+  if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER | PGF_BATCH_WIDE_BORDER |
+                PGF_BATCH_BORDER_CTL | PGF_BATCH_CTL_REFINE))
     return PGF_INVALID;
   // (a border on a wide remainder: only together with the two flags it combines)
   if ((flags & PGF_BATCH_WIDE_BORDER) &&
       (flags & (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND)) != (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND))
     return PGF_INVALID;
+  // (a border under the device-resident controller, refinement inside its loop: likewise)
+  if ((flags & PGF_BATCH_BORDER_CTL) &&
+      (flags & (PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL)) != (PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL))
+    return PGF_INVALID;
+  if ((flags & PGF_BATCH_CTL_REFINE) && !(flags & PGF_BATCH_BAND_CTL)) return PGF_INVALID;
   const pgf_handle h0 = handles[0];
   if (!h0) return PGF_INVALID;
   for (int i = 0; i < count; ++i)  // any banded handle: a band batch, or its refusal
@@ -452,6 +458,8 @@ int pgf_batch_ctl_init(pgf_batch b, double lamb_init, double rho, const double *
 static void ctl_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean) {
   if (b->band) {
     band_batch_enqueue_step(b, policy, tau, lean);
+    // (PGF_BATCH_CTL_REFINE: the host cannot know which instances refine, so both rounds go in)
+    if (b->ctl_refine) band_batch_enqueue_refine(b);
     band_batch_enqueue_final(b);
   } else {
     batch_enqueue_step(b, policy, tau, false);

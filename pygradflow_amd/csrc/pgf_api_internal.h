@@ -322,6 +322,16 @@ struct pgf_batch_s {
   bool band_ctl = false;
   double *band_guard = nullptr;
   int *band_rejects = nullptr;
+  // created with PGF_BATCH_CTL_REFINE besides: band_guard has a third double per instance
+  // (refine_fail), and every banded step of the loop enqueues two refinement rounds on rtab -- btab
+  // over again, except that ctl points at the instance's refinement words in rctl ([0] stays 0: no
+  // assembly, kept factors, no write of ctl[1]; [1] a round ran in this step; [2] the step missed
+  // refine_tol as it came out of the solve; [3] sits this round out) -- rrel: the measure the next
+  // round has to beat; rcnt: per instance (steps refined, rounds run)
+  bool ctl_refine = false;
+  BandInst *rtab = nullptr;
+  int *rctl = nullptr, *rcnt = nullptr;
+  double *rrel = nullptr;
   PgfProfile prof;
   std::string err = "";
 };
@@ -350,6 +360,7 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff);      //
 // the launches of one banded step, without the evaluation made ahead and the status copy;
 // lean_allowed: the caller knows that every instance still live holds a clean factor of its band
 void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed);  // pgf_batch_ctl_iterate
+void band_batch_enqueue_refine(pgf_batch b);                                  // pgf_batch_ctl_iterate
 void band_batch_enqueue_final(pgf_batch b);                                   // pgf_batch_ctl_iterate
 int band_batch_ctl_init(pgf_batch b);                                         // pgf_batch_ctl_init
 int band_batch_ctl_read(pgf_batch b);                                         // pgf_batch_ctl_read

@@ -671,9 +671,13 @@ __device__ __forceinline__ void b_band_residual(const double *__restrict__ band,
 // kb_dctl_mid / kb_dctl_end reject it with 2 lambda and kb_advance puts the instance back on its
 // outer point, over the inaccurate point the step update swapped in -- the reference's own recovery,
 // a larger lambda makes K quasi-definite again (step_control.py:80-107).
+// rw != nullptr (PGF_BATCH_CTL_REFINE, behind the refinement rounds): the instance's refinement words,
+// and bit 2 is band_refine's verdict instead -- the step missed tol as it came out of the solve
+// (rw[2], b_band_refine_decide) and the measure is above fail now.
 __device__ __forceinline__ void b_band_step_final(const double *__restrict__ stat, int nred, int n_inner,
                                                   bool guard_on, double tol, double *__restrict__ diff_out,
-                                                  int *__restrict__ flags_out, int *__restrict__ rejects) {
+                                                  int *__restrict__ flags_out, int *__restrict__ rejects,
+                                                  const int *__restrict__ rw = nullptr, double fail = 0.0) {
   const int lane = threadIdx.x & 63;
   double r = 0.0, den = 0.0;
   int broken = 0;
@@ -696,11 +700,63 @@ __device__ __forceinline__ void b_band_step_final(const double *__restrict__ sta
   const int bad = stat[3 * nred] != 0.0 ? 1 : 0;
   double sum = 0.0;
   for (int k = 0; k < nred; ++k) sum += stat[2 * nred + k];
-  const int miss = (!bad && guard_on && !(rel <= tol)) ? 4 : 0;
+  const bool above = rw ? (rw[2] != 0 && !(rel <= fail)) : !(rel <= tol);
+  const int miss = (!bad && guard_on && above) ? 4 : 0;
   *diff_out = bad ? 0.0 : sqrt(sum);
   flags_out[0] = bad | miss;
   flags_out[1] = (int)stat[3 * nred + 1];
   flags_out[2] = n_inner;
   if (bad) ++rejects[0];
   if (miss) ++rejects[1];
+}
+
+// ---------------------------------------------------------------- refinement inside the loop
+// band_refine's rule (pgf_api_band.hip) for one instance and one round, ONE wavefront per instance;
+// stat as above.  The measure is band_residual_rel_of of the pairs as they stand: the step's in
+// round 0, the last round's behind it.  w: the instance's refinement words, which the round's
+// launches read as their ctl -- [0] stays 0 (no assembly, kept factors, no write of ctl[1]), [1] a
+// round ran, [2] the step missed tol as it came out of the solve (for b_band_step_final), [3] sits
+// this round out.  A round runs for an instance that is live, has a clean pivot and the guard on,
+// while tol < rel < 1; a second one only behind a first that made the measure fall (*prev).
+// cnt: [0] steps refined, [1] rounds run -- the instance's own words, no atomics.
+__device__ __forceinline__ void b_band_refine_decide(const double *__restrict__ stat, int nred, bool frozen,
+                                                     bool guard_on, double tol, int round,
+                                                     int *__restrict__ w, double *__restrict__ prev,
+                                                     int *__restrict__ cnt) {
+  const int lane = threadIdx.x & 63;
+  double r = 0.0, den = 0.0;
+  int broken = 0;
+  for (int k = lane; k < nred; k += 64) {
+    const double rk = stat[2 * k];
+    if (!(rk == rk) || !(rk <= 1.79e308))
+      broken = 1;
+    else
+      r = fmax(r, rk);
+    den = fmax(den, stat[2 * k + 1]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    r = fmax(r, __shfl_xor(r, off));
+    den = fmax(den, __shfl_xor(den, off));
+    broken |= __shfl_xor(broken, off);
+  }
+  if (lane != 0) return;
+  const double rel = broken ? __builtin_huge_val() : r / (den > 0.0 ? den : 1.0);
+  const bool live = !frozen && guard_on && stat[3 * nred] == 0.0;
+  bool go;
+  if (round == 0) {
+    const bool missed = live && !(rel <= tol);
+    w[2] = missed ? 1 : 0;
+    go = missed && rel > tol && rel < 1.0;
+    if (go) ++cnt[0];
+  } else {
+    go = live && w[1] != 0 && rel < *prev && rel > tol && rel < 1.0;
+  }
+  w[0] = 0;
+  w[1] = go ? 1 : 0;
+  w[3] = go ? 0 : 1;
+  if (go) {
+    *prev = rel;
+    ++cnt[1];
+  }
 }

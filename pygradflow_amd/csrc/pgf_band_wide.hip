@@ -392,7 +392,10 @@ void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double 
 // reduction of B for the instances with ctl[0] != 0 (BW_FACTOR) and, later in the SAME step, while
 // ctl[0] is still set, the solve phase against the kept factors for every live instance (BW_SOLVE).
 // The BW_BY_CTL instantiations are the kernels the unbordered batch has always launched.
-enum { BW_BY_CTL = 0, BW_FACTOR = 1, BW_SOLVE = 2 };
+// BW_NO_GUARD: BW_BY_CTL's extraction without the guard's copy of the right-hand side, for a
+// refinement round with the split off (sp_launch_bw_solve with guard == false); the other twins of
+// such a round are the BW_BY_CTL ones.
+enum { BW_BY_CTL = 0, BW_FACTOR = 1, BW_SOLVE = 2, BW_NO_GUARD = 3 };
 
 // true: this instance reduces in this step; false: it solves against the factors it kept
 __device__ __forceinline__ bool bw_reduces(const BandInst &I, const BandShape &sh) {
@@ -421,7 +424,7 @@ __global__ __launch_bounds__(BW_THREADS) void kbw_extract(const BandInst *__rest
   const bool red = bw_reduces(I, sh);
   if (i == 0 && threadIdx.x == 0) ++I.wcnt[red ? 0 : 1];
   if (red) bw_extract_matrix<B>(I.band, sh.ldb, sh.bw, sh.N, sh.nb, I.bD, I.bL, I.bU, I.flags, i);
-  bw_extract_rhs<B>(I.brhs, sh.N, I.bF, I.brhs0, i);
+  bw_extract_rhs<B>(I.brhs, sh.N, I.bF, PHASE == BW_NO_GUARD ? nullptr : I.brhs0, i);
 }
 
 template <int B, int PHASE>
@@ -517,11 +520,15 @@ __global__ __launch_bounds__(BW_THREADS) void kbw_back_panel(const BandInst *__r
 // the walk of bw_solve / bw_backsolve (pgf_band_wide.hip), every launch with the instances in grid.y;
 // lean: no instance reduces (the host knows), so the inversion launches are left out
 template <int B>
-static void bandb_wide_solve(hipStream_t s, const BandInst *tab, int Bi, const BandShape &sh, bool lean) {
+static void bandb_wide_solve(hipStream_t s, const BandInst *tab, int Bi, const BandShape &sh, bool lean,
+                             bool guard) {
   const int nb = sh.nb;
   const unsigned Bu = (unsigned)Bi;
   const dim3 blk(BW_THREADS);
-  hipLaunchKernelGGL((kbw_extract<B, BW_BY_CTL>), dim3(nb, Bu), blk, 0, s, tab, sh);
+  if (guard)
+    hipLaunchKernelGGL((kbw_extract<B, BW_BY_CTL>), dim3(nb, Bu), blk, 0, s, tab, sh);
+  else
+    hipLaunchKernelGGL((kbw_extract<B, BW_NO_GUARD>), dim3(nb, Bu), blk, 0, s, tab, sh);
   int levels[32], nlev = 0;
   for (int st = 1; st < nb; st *= 2) {
     const int ne = bcr_eliminated(nb, st), nk = bcr_kept(nb, st);
@@ -534,16 +541,21 @@ static void bandb_wide_solve(hipStream_t s, const BandInst *tab, int Bi, const B
     const int st = levels[q];
     hipLaunchKernelGGL(kbw_back<B>, dim3(bcr_eliminated(nb, st), Bu), blk, 0, s, tab, sh, st);
   }
-  hipLaunchKernelGGL(kbw_residual, dim3((sh.N + 255) / 256, Bu), dim3(256), 0, s, tab, sh);
+  if (guard) hipLaunchKernelGGL(kbw_residual, dim3((sh.N + 255) / 256, Bu), dim3(256), 0, s, tab, sh);
 }
 
-void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean) {
+void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean,
+                             bool guard) {
   if (!sh.N) return;
   switch (sh.B) {
-    case 16: bandb_wide_solve<16>(s, tab, B, sh, lean); break;
-    case 32: bandb_wide_solve<32>(s, tab, B, sh, lean); break;
-    default: bandb_wide_solve<64>(s, tab, B, sh, lean); break;
+    case 16: bandb_wide_solve<16>(s, tab, B, sh, lean, guard); break;
+    case 32: bandb_wide_solve<32>(s, tab, B, sh, lean, guard); break;
+    default: bandb_wide_solve<64>(s, tab, B, sh, lean, guard); break;
   }
+}
+
+void bandb_launch_wide_residual(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
+  if (sh.N) hipLaunchKernelGGL(kbw_residual, dim3((sh.N + 255) / 256, (unsigned)B), dim3(256), 0, s, tab, sh);
 }
 
 // ---- bordered wide route: the band part of pgf_border.hip's two batch phases -----------------------

@@ -389,6 +389,26 @@ __global__ void kbd_border_save_wide(const BandInst *__restrict__ tab, BandShape
   if (i >= sh.Nb) I.brb[i - sh.Nb] = v;
 }
 
+// Both with the guard off (sp_border_solve(guard = false): a refinement round inside the
+// device-resident controller's loop, whose brhs0 still holds the step's right-hand side): brb alone
+__global__ void kbd_border_save_ng(const BandInst *__restrict__ tab, BandShape sh) {
+  SINST(I);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < sh.bk) I.brb[i] = I.brhs[sh.Nb + i];
+}
+
+__global__ void kbd_border_save_wide_ng(const BandInst *__restrict__ tab, BandShape sh) {
+  SINST(I);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    I.flags[0] = I.bsflags[2];
+    I.flags[1] = I.bsflags[3];
+    I.flags[2] = 0;
+    I.flags[3] = 0;
+  }
+  if (i < sh.bk) I.brb[i] = I.brhs[sh.Nb + i];
+}
+
 __global__ __launch_bounds__(256) void kbd_border_ctv(const BandInst *__restrict__ tab, BandShape sh) {
   SINST(I);
   b_border_ctv(I.bC, I.brhs, sh.Nb, sh.bkp, I.bpartv);
@@ -455,23 +475,35 @@ void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const Band
   hipLaunchKernelGGL(kbd_border_factor_S, dim3(1, Bu), dim3(256), 0, s, tab, sh);
 }
 
-// sp_border_solve with the guard on
-void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
+// sp_border_solve, with the guard on or (a refinement round) off
+void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool guard) {
   const unsigned Bu = (unsigned)B;
   BandShape shB = sh;  // v = inv(B) ra over the Nb band rows
   shB.N = sh.Nb;
   if (sh.B > 8) {  // against the factors the instance kept, with the flags of B as parked
-    hipLaunchKernelGGL(kbd_border_save_wide, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    if (guard)
+      hipLaunchKernelGGL(kbd_border_save_wide, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    else
+      hipLaunchKernelGGL(kbd_border_save_wide_ng, gy(sh.bk, 64, B), dim3(64), 0, s, tab, sh);
     shB.nb = (sh.Nb + sh.B - 1) / sh.B;
     bandb_launch_wide_kept_solve(s, tab, B, shB);
   } else {  // the plain band's reduction
-    hipLaunchKernelGGL(kbd_border_save, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    if (guard)
+      hipLaunchKernelGGL(kbd_border_save, gy(sh.Nb + sh.bk, 256, B), dim3(256), 0, s, tab, sh);
+    else
+      hipLaunchKernelGGL(kbd_border_save_ng, gy(sh.bk, 64, B), dim3(64), 0, s, tab, sh);
     shB.nb = (sh.Nb + 7) / 8;
-    bandb_launch_solve(s, tab, B, shB, /*residual=*/false);
+    bandb_launch_solve(s, tab, B, shB, /*residual=*/false, /*save_rhs=*/guard);
   }
   hipLaunchKernelGGL(kbd_border_ctv, dim3(sh.bnchunk, Bu), dim3(256), 0, s, tab, sh);
   hipLaunchKernelGGL(kbd_border_small_solve, dim3(1, Bu), dim3(64), 0, s, tab, sh);
   hipLaunchKernelGGL(kbd_border_update, gy(sh.Nb, 256, B), dim3(256), 0, s, tab, sh);
+  if (guard) borderb_launch_residual(s, tab, B, sh);
+}
+
+// sp_border_residual
+void borderb_launch_residual(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
+  const unsigned Bu = (unsigned)B;
   hipLaunchKernelGGL(kbd_border_ctv, dim3(sh.bnchunk, Bu), dim3(256), 0, s, tab, sh);
   hipLaunchKernelGGL(kbd_border_residual, dim3(sh.nred, Bu), dim3(256), 0, s, tab, sh);
 }

@@ -292,6 +292,7 @@ struct BatchScalars {
 struct BandInst {
   const double *Hval, *Jval;
   double *band, *brhs, *brhs0, *bres;
+  double *bsol;  // the solution a refinement round keeps (PGF_BATCH_CTL_REFINE; SparseDev::bsol)
   double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev; wide: one)
   double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
@@ -332,6 +333,7 @@ inline BandInst band_inst_of(const SparseDev &sp, int *flags, double *stat) {
   u.brhs = sp.brhs;  // (SparseDev::bX is brhs: the back-substitution writes the solution there)
   u.brhs0 = sp.brhs0;
   u.bres = sp.bres;
+  u.bsol = sp.bsol;
   u.bD = sp.bD;
   u.bL = sp.bL;
   u.bU = sp.bU;
@@ -395,7 +397,10 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 // cyclic reduction of every instance that is not frozen (one launch plan: it depends on N only),
 // then the residual of the solution into the status block (residual == false: left out; the
 // bordered route reduces over sh.N = Nb rows and has a residual of its own)
-void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual = true);
+// save_rhs == false: the extraction leaves brhs0 alone (sp_launch_bcr_solve with the guard off: a
+// refinement round, whose brhs0 still holds the step's right-hand side)
+void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual = true,
+                        bool save_rhs = true);
 // bordered routes (pgf_border.hip; both wrappers branch on sh.B > 8).  Factor phase of the
 // instances with ctl[0] != 0: band, C and D cleared and assembled, Y = inv(B) C by the panel reduction
 // (wide: B factorised once, Y by one panel solve against the kept factors), S and its factor.
@@ -403,10 +408,17 @@ void borderb_launch_factor(hipStream_t s, const BandInst *tab, int B, const Band
 // solve phase of every instance that is not frozen, guard included: the border part of the
 // right-hand side and the whole of it saved, the 8 x 8 reduction of B (wide: the solve against the
 // kept factors), z, x_a, the residual
-void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// guard == false (a refinement round): brhs0 is not saved and the residual is left out
+// (borderb_launch_residual is sp_border_residual's twin)
+void borderb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool guard = true);
+void borderb_launch_residual(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // the same on the wide route (sh.B > 8): per instance the reduction, or with the split on and
 // ctl[0] == 0 the solve phase against its kept factors; lean: the host knows that no instance reduces
-void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean);
+// guard == false (a refinement round with the split off): no copy to brhs0, no residual
+// (bandb_launch_wide_residual is sp_launch_bw_residual's twin)
+void bandb_launch_wide_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool lean,
+                             bool guard = true);
+void bandb_launch_wide_residual(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // The band part of a bordered batch on the wide route (sh: the copy with N = Nb, nb = ceil(Nb / B)),
 // each phase fixed by the caller instead of read from ctl[0] alone.  For the instances with ctl[0]
 // != 0: the factor-only KEEP reduction of B (flags, inertia, kept multipliers; brhs survives), and
@@ -421,10 +433,27 @@ void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const B
 // The step finished per instance on the device, behind the step update (the device-resident
 // controller; what band_batch_sync does on the host): diff_out[i] the step length; flags_out[3 i]
 // bit 0 a zero or non-finite pivot, bit 2 the guard's measure above the instance's tolerance
-// (guard[2 i] != 0: the guard is on, guard[2 i + 1]: refine_tol), [3 i + 1] negative pivots,
-// [3 i + 2] |I|; rejects[2 i], [2 i + 1]: steps that set bit 0 / bit 2, counted
+// (guard[BG_STRIDE i] != 0: the guard is on, [+ 1]: refine_tol, [+ 2]: refine_fail), [3 i + 1]
+// negative pivots, [3 i + 2] |I|; rejects[2 i], [2 i + 1]: steps that set bit 0 / bit 2, counted.
+// rctl != nullptr (PGF_BATCH_CTL_REFINE): the refinement rounds have run, and bit 2 is band_refine's
+// verdict -- the step missed refine_tol as it came out of the solve (rctl[4 i + 2]) and the measure
+// is above refine_fail now.
+#define BG_STRIDE 3
 void bandb_launch_step_final(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
-                             const double *guard, double *diff_out, int *flags_out, int *rejects);
+                             const double *guard, double *diff_out, int *flags_out, int *rejects,
+                             const int *rctl = nullptr);
+// Refinement inside the device-resident controller's loop (PGF_BATCH_CTL_REFINE): what band_refine
+// does on an instance's handle, one round.  decide: tab is the batch's OWN table (whose ctl[3] and
+// status block it reads); per instance it sets rctl[4 i + 3] = 1 (sits the round out) unless the
+// instance refines in this round, by band_refine's rule, and counts in rcnt.  The other launches
+// take the refinement table (ctl -> rctl): load is bsol <- brhs, brhs <- bres and the point the step
+// started from back in (x, y); the route's solve with the guard off follows (the launchers above),
+// then axpy brhs += bsol, the route's residual and bandb_launch_step_update.
+void bandb_launch_refine_decide(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
+                                const double *guard, int *rctl, double *rrel, int *rcnt, int round);
+void bandb_launch_refine_load(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh);
+void bandb_launch_refine_axpy(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh);
+void bandb_launch_residual(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh);
 // c = J x - b and F[0:n] = H x + q + J' y for the termination measures
 void bandb_launch_measures_eval(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 

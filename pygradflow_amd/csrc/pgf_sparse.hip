@@ -487,6 +487,12 @@ __global__ __launch_bounds__(64) void kbb_bcr_extract(const BandInst *__restrict
   b_bcr_extract(I.band, sh.ldb, sh.bw, I.brhs, sh.N, sh.nb, I.bD, I.bL, I.bU, I.bF, I.brhs0, I.flags);
 }
 
+// the same with the guard off (a refinement round): brhs0 keeps the step's right-hand side
+__global__ __launch_bounds__(64) void kbb_bcr_extract_ng(const BandInst *__restrict__ tab, BandShape sh) {
+  INST(I);
+  b_bcr_extract(I.band, sh.ldb, sh.bw, I.brhs, sh.N, sh.nb, I.bD, I.bL, I.bU, I.bF, nullptr, I.flags);
+}
+
 __global__ __launch_bounds__(64) void kbb_bcr_invert(const BandInst *__restrict__ tab, BandShape sh,
                                                      int set, int s, int first, int stride) {
   INST(I);
@@ -588,13 +594,52 @@ __global__ __launch_bounds__(256) void kbb_band_step_update(const BandInst *__re
 __global__ __launch_bounds__(256) void kbb_step_final(const BandInst *__restrict__ tab, int B, BandShape sh,
                                                       const double *__restrict__ guard,
                                                       double *__restrict__ diff_out,
-                                                      int *__restrict__ flags_out, int *__restrict__ rejects) {
+                                                      int *__restrict__ flags_out, int *__restrict__ rejects,
+                                                      const int *__restrict__ rctl) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= B) return;
   const BandInst &I = tab[i];
   if (I.ctl[3]) return;
-  b_band_step_final(I.stat, sh.nred, I.counts[0], guard[2 * i] != 0.0, guard[2 * i + 1], diff_out + i,
-                    flags_out + 3 * i, rejects + 2 * i);
+  const double *g = guard + (size_t)BG_STRIDE * i;
+  b_band_step_final(I.stat, sh.nred, I.counts[0], g[0] != 0.0, g[1], diff_out + i, flags_out + 3 * i,
+                    rejects + 2 * i, rctl ? rctl + 4 * i : nullptr, g[2]);
+}
+
+// ---------------------------------------------------------------- refinement inside the loop
+// (PGF_BATCH_CTL_REFINE) band_refine's round for the instances that refine.  kbb_refine_decide has
+// kbb_step_final's grid and reads the batch's own table; the others take the refinement table, whose
+// ctl is the instance's refinement words: INST returns for an instance that sits the round out.
+__global__ __launch_bounds__(256) void kbb_refine_decide(const BandInst *__restrict__ tab, int B, BandShape sh,
+                                                         const double *__restrict__ guard,
+                                                         int *__restrict__ rctl, double *__restrict__ rrel,
+                                                         int *__restrict__ rcnt, int round) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= B) return;
+  const BandInst &I = tab[i];
+  const double *g = guard + (size_t)BG_STRIDE * i;
+  b_band_refine_decide(I.stat, sh.nred, I.ctl[3] != 0, g[0] != 0.0, g[1], round, rctl + 4 * i, rrel + i,
+                       rcnt + 2 * i);
+}
+
+// bsol <- brhs, brhs <- bres (band_refine's two copies) over the n + m entries, and the point the
+// step started from back in (x, y) (band_batch_repair's two): kbb_band_step_update swapped it out
+__global__ void kbb_refine_load(const BandInst *__restrict__ tab, BandShape sh) {
+  INST(I);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sh.n + sh.m) return;
+  I.bsol[i] = I.brhs[i];
+  I.brhs[i] = I.bres[i];
+  if (i < sh.n)
+    I.x[i] = I.xn[i];
+  else
+    I.y[i - sh.n] = I.yn[i - sh.n];
+}
+
+// twin of k_band_axpy: solution = saved + correction
+__global__ void kbb_refine_axpy(const BandInst *__restrict__ tab, BandShape sh) {
+  INST(I);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < sh.n + sh.m) I.brhs[i] += I.bsol[i];
 }
 
 // ---------------------------------------------------------------- launch wrappers
@@ -627,11 +672,15 @@ void bandb_launch_assemble(hipStream_t s, const BandInst *tab, int B, const Band
 
 // the walk of sp_launch_bcr_solve over the same plan, every launch with the instances in grid.y
 // (a bordered batch passes a shape whose N, nb are those of the band rows, and residual == false)
-void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual) {
+void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool residual,
+                        bool save_rhs) {
   if (!sh.N) return;
   const int nb = sh.nb;
   const unsigned Bu = (unsigned)B;
-  hipLaunchKernelGGL(kbb_bcr_extract, dim3(nb, Bu), dim3(64), 0, s, tab, sh);
+  if (save_rhs)
+    hipLaunchKernelGGL(kbb_bcr_extract, dim3(nb, Bu), dim3(64), 0, s, tab, sh);
+  else
+    hipLaunchKernelGGL(kbb_bcr_extract_ng, dim3(nb, Bu), dim3(64), 0, s, tab, sh);
   const BcrPlan plan = sp_bcr_plan(nb);
   for (int q = 0; q < plan.nlev; ++q) {
     const int st = plan.lev[q].s, cur = plan.lev[q].set;
@@ -670,8 +719,28 @@ void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const B
 }
 
 void bandb_launch_step_final(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
-                             const double *guard, double *diff_out, int *flags_out, int *rejects) {
+                             const double *guard, double *diff_out, int *flags_out, int *rejects,
+                             const int *rctl) {
   if (sh.N)
     hipLaunchKernelGGL(kbb_step_final, dim3((B + 3) / 4), dim3(256), 0, s, tab, B, sh, guard, diff_out,
-                       flags_out, rejects);
+                       flags_out, rejects, rctl);
+}
+
+void bandb_launch_refine_decide(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
+                                const double *guard, int *rctl, double *rrel, int *rcnt, int round) {
+  if (sh.N)
+    hipLaunchKernelGGL(kbb_refine_decide, dim3((B + 3) / 4), dim3(256), 0, s, tab, B, sh, guard, rctl, rrel,
+                       rcnt, round);
+}
+
+void bandb_launch_refine_load(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh) {
+  if (sh.N) hipLaunchKernelGGL(kbb_refine_load, gy(sh.n + sh.m, 256, B), dim3(256), 0, s, rtab, sh);
+}
+
+void bandb_launch_refine_axpy(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh) {
+  if (sh.N) hipLaunchKernelGGL(kbb_refine_axpy, gy(sh.n + sh.m, 256, B), dim3(256), 0, s, rtab, sh);
+}
+
+void bandb_launch_residual(hipStream_t s, const BandInst *rtab, int B, const BandShape &sh) {
+  if (sh.N) hipLaunchKernelGGL(kbb_band_residual, gy(sh.N, 256, B), dim3(256), 0, s, rtab, sh);
 }

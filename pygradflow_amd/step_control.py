@@ -286,8 +286,11 @@ class DeviceResidentDistanceRatioController:
     ``history`` then holds (lambda used, lambda next, accepted) per iteration and instance.
 
     Works unchanged on a band batch made with ``BatchedDeviceNewton(..., band_ctl=True)``, narrow or
-    wide.  There a solve that misses the accuracy guard's tolerance is a rejected step (2 lambda)
-    where the host-driven controller's batch would repair the instance on its handle."""
+    wide, and with ``border_ctl=True`` on a bordered one.  There a solve that misses the accuracy
+    guard's tolerance is a rejected step (2 lambda) where the host-driven controller's batch would
+    repair the instance on its handle -- unless the batch was made with ``ctl_refine=True``: then the
+    instance is refined inside the loop by the handle's own rule, and the trajectory is the
+    host-driven one."""
 
     def __init__(self, batch, params, rho=None, max_iterations=64):
         self.bd = batch

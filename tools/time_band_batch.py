@@ -9,7 +9,7 @@ session.
                                     [--policy Full|Simplified] [--routes batch,sequential]
     python tools/time_band_batch.py --controller [--iterations 20] [--warmup 3] [--reps 5]
                                     [--batches 1,8,64,256] [--workloads sparse_ocp,multistate_ocp_w32]
-                                    [--policies Full,Simplified] [--lamb-min 1e-3] [--out FILE]
+                                    [--policies Full,Simplified] [--lamb-min 1e-3] [--refine] [--out FILE]
 
 The workloads ``multistate_ocp_w16``, ``_w32``, ``_w64`` are on the wide route (block sizes 16, 32,
 64): their batch is created with ``wide_band=True`` and their rows go to
@@ -53,6 +53,16 @@ the floor; left to the default it falls to where the accuracy guard fires (from 
 then the host route repairs instances on their handles where the device route rejects the step: the
 two routes no longer do the same work, which the ratio line shows (``host_repaired``,
 ``device_guard_rejects``, ``accept_flags_equal``).
+
+--controller takes the bordered workloads too (narrow and wide): the device route's batch is then
+created with ``border_ctl=True`` beside the route's own flags, and the rows go to
+profiles/band_batch_ctl_border_timing.jsonl unless --out says otherwise.  --refine adds a third
+route, ``device_refine``: a second device-resident twin created with ``ctl_refine=True``, which
+refines an instance above ``refine_tol`` inside the loop as the host route repairs it on its handle.
+Its row carries the refined steps and rounds; the ratio line has ``refine_over_device`` (the price
+of the two rounds of launches per step when nothing refines, what the flag buys when the plain
+device route rejects), whether its accept flags equal the host route's and its largest relative
+difference of lambda from the host route.  Rows go to profiles/band_batch_ctl_refine_timing.jsonl.
 """
 import argparse
 import json
@@ -130,11 +140,19 @@ def controller_rows(a, emit):
                     p.pgf_force_band = True
                     probs.append(p)
                 par = Params(newton_type=pol, lamb_init=1.0, lamb_min=a.lamb_min)
-                host_b, dev_b = (BatchedDeviceNewton(lambda i: probs[i], B, pol, 1.0, 1.0, wide_band=key in WIDE,
-                                                     band_ctl=ctl) for ctl in (False, True))
-                assert host_b.band and dev_b.band
+                bordered = key in BORDERED + WIDE_BORDERED
+                route_flags = dict(wide_band=key in WIDE, border=key in BORDERED, wide_border=key in WIDE_BORDERED)
+                host_b, dev_b = (BatchedDeviceNewton(lambda i: probs[i], B, pol, 1.0, 1.0, band_ctl=ctl,
+                                                     border_ctl=ctl and bordered, **route_flags)
+                                 for ctl in (False, True))
+                assert host_b.band and dev_b.band and (dev_b.band_border > 0) == bordered
                 host = SC.BatchedDistanceRatioController(host_b, par, rho=1.0)
                 dev = SC.DeviceResidentDistanceRatioController(dev_b, par, rho=1.0, max_iterations=total)
+                ref_b = ref = None
+                if a.refine:
+                    ref_b = BatchedDeviceNewton(lambda i: probs[i], B, pol, 1.0, 1.0, band_ctl=True,
+                                                border_ctl=bordered, ctl_refine=True, **route_flags)
+                    ref = SC.DeviceResidentDistanceRatioController(ref_b, par, rho=1.0, max_iterations=total)
                 rec = []
 
                 def host_iters(k):
@@ -148,7 +166,14 @@ def controller_rows(a, emit):
                     dev.run(k)  # (ends in ctl_read: the one host synchronisation)
                     return (time.perf_counter() - t0) / k
 
+                def ref_iters(k):
+                    t0 = time.perf_counter()
+                    ref.run(k)
+                    return (time.perf_counter() - t0) / k
+
                 routes = {"host_driven": host_iters, "device_resident": dev_iters}
+                if a.refine:
+                    routes["device_refine"] = ref_iters
                 for run in routes.values():
                     run(a.warmup)
                 times = {r: [] for r in routes}
@@ -169,10 +194,25 @@ def controller_rows(a, emit):
                     rows[r] = {"workload": name, "N": N, "B": B, "route": r, "policy": pol, "lamb_min": a.lamb_min,
                                "iterations": a.iterations, "warmup": a.warmup, "reps": a.reps,
                                "median_ms": 1e3 * med, "min_ms": 1e3 * min(ts), "max_ms": 1e3 * max(ts)}
+                    if r == "device_refine":
+                        steps, rounds = ref_b.ctl_refine_stats()
+                        rows[r].update(refined_steps=int(steps.sum()), rounds=int(rounds.sum()),
+                                       guard_rejects=int(ref_b.ctl_stats()[1].sum()))
                     emit(rows[r])
                 d, s = rows["device_resident"], rows["host_driven"]
                 spreads = (d["max_ms"] - d["min_ms"]) + (s["max_ms"] - s["min_ms"])
-                emit({"workload": name, "N": N, "B": B, "route": "ratio", "policy": pol,
+                extra = {}
+                if a.refine:
+                    f, hr = rows["device_refine"], ref.history
+                    both = (d["max_ms"] - d["min_ms"]) + (f["max_ms"] - f["min_ms"])
+                    extra = {"refine_over_device": f["median_ms"] / d["median_ms"],
+                             "refine_differs_from_device_by_more_than_both_spreads":
+                                 bool(abs(f["median_ms"] - d["median_ms"]) > both),
+                             "host_over_refine": s["median_ms"] / f["median_ms"],
+                             "refine_accept_flags_equal": bool(np.array_equal(hr[:, :, 2] != 0.0, acc)),
+                             "refine_max_rel_lambda_diff": float(max(np.max(np.abs(hr[:, :, 0] - used) / used),
+                                                                     np.max(np.abs(hr[:, :, 1] - nxt) / nxt)))}
+                emit({"workload": name, "N": N, "B": B, "route": "ratio", "policy": pol, **extra,
                       "host_over_device": s["median_ms"] / d["median_ms"],
                       "device_below_host_by_more_than_both_spreads": bool(s["median_ms"] - d["median_ms"] > spreads),
                       "accept_flags_equal": flags_equal, "max_rel_lambda_diff": lamb_diff,
@@ -180,6 +220,8 @@ def controller_rows(a, emit):
                       "device_pivot_rejects": int(piv.sum()), "device_guard_rejects": int(grd.sum())})
                 host_b.close()
                 dev_b.close()
+                if ref_b is not None:
+                    ref_b.close()
 
 
 def main():
@@ -188,6 +230,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--policies", default="Full,Simplified")
     ap.add_argument("--lamb-min", type=float, default=1e-3)
+    ap.add_argument("--refine", action="store_true")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--reps", type=int, default=None)
@@ -215,6 +258,10 @@ def main():
             name = "band_batch_wide_border_timing.jsonl"
         if a.controller:
             name = "band_batch_ctl_timing.jsonl"
+            if all(k in BORDERED + WIDE_BORDERED for k in keys):
+                name = "band_batch_ctl_border_timing.jsonl"
+            if a.refine:
+                name = "band_batch_ctl_refine_timing.jsonl"
         a.out = os.path.join(REPO, "profiles", name)
     out = open(a.out, "a")
 
