@@ -560,7 +560,7 @@ int pgf_batch_debug_fail_next_helper(pgf_batch b);
 int pgf_debug_chain_helpers(int on);
 /* Which factorisation the handle's current dense factor is (tests, tools/check_condensed.py):
  * 0 none / stale, 1 LDL^T of the reduced KKT matrix in its natural order, 2 LDL^T of the
- * condensed system (constraint block eliminated first: condensed_wanted in csrc/pgf_api.hip), 3 the
+ * condensed system (constraint block eliminated first: condensed_wanted in csrc/pgf_api_factor.hip), 3 the
  * pivoted LU that took over after a failed residual check. */
 int pgf_debug_factor_kind(pgf_handle h);
 /* The pivot order of the factors a device batch's instances hold (tests): 0 none (no step yet),

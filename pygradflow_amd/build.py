@@ -25,6 +25,9 @@ SOURCES = [
     ("pgf_lu.hip", []),
     ("pgf_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api.hip", ["-ffp-contract=off"]),
+    ("pgf_api_factor.hip", ["-ffp-contract=off"]),
+    ("pgf_api_guard.hip", ["-ffp-contract=off"]),
+    ("pgf_api_step.hip", ["-ffp-contract=off"]),
     ("pgf_api_band.hip", ["-ffp-contract=off"]),
     ("pgf_api_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api_batch.hip", ["-ffp-contract=off"]),

@@ -1,8 +1,14 @@
 // Entry points of the C ABI that need nothing of the dense step: the handle's stream, the
-// profiling read-out, the stand-alone linear solver pgf_ls_* and pgf_bench_update.
+// profiling read-out, the stand-alone linear solver pgf_ls_* and pgf_bench_update; and the
+// pgf_debug_* hooks of the dense handle: test injections, counters (pgf_solver::dbg) and the host
+// walks of the head and update plans.
+#include <algorithm>
+#include <cstring>
 #include <new>
 
 #include "pgf_api_internal.h"
+#include "pgf_kernels.h"
+#include "pgf_update_plan.h"
 
 int pgf_stream(pgf_handle h, void **stream_out) {
   if (!h || !stream_out) return PGF_INVALID;
@@ -107,10 +113,10 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count) {
     out[PGF_PROF_TRSMUD_MS] = p.acc_trsmud_ms;
   }
   if (count >= PGF_PROF_COUNT3) {
-    out[PGF_PROF_UNSYM_ASM_MS] = h->acc_unsym_asm_ms;
-    out[PGF_PROF_UNSYM_ASM_LAUNCHES] = (double)h->acc_unsym_asm_launches;
-    h->acc_unsym_asm_ms = 0;
-    h->acc_unsym_asm_launches = 0;
+    out[PGF_PROF_UNSYM_ASM_MS] = h->unsym.acc_unsym_asm_ms;
+    out[PGF_PROF_UNSYM_ASM_LAUNCHES] = (double)h->unsym.acc_unsym_asm_launches;
+    h->unsym.acc_unsym_asm_ms = 0;
+    h->unsym.acc_unsym_asm_launches = 0;
   }
   profile_reset(p);
   return PGF_OK;
@@ -257,4 +263,139 @@ int pgf_bench_update(int N, int KB, int variant, int reps, int device, double *m
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = ldlt_bench_update(N, KB, variant, reps, ms_out, flops_out);
   return e == hipSuccess ? PGF_OK : PGF_HIP_ERROR + (int)e;
+}
+
+int pgf_debug_fail_next_chain(pgf_handle h) {
+  if (!h) return PGF_INVALID;
+  h->fac.inject_chain_failure = 1;
+  return PGF_OK;
+}
+
+int pgf_debug_chain_enable(int on) {
+  ldlt_chain_set_enabled(on != 0);
+  return PGF_OK;
+}
+
+int pgf_debug_fail_next_helper(pgf_handle h) {
+  if (!h) return PGF_INVALID;
+  h->fac.inject_helper_failure = 1;
+  return PGF_OK;
+}
+
+int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps) {
+  if (!h) return PGF_INVALID;
+  if (host_syncs) *host_syncs = h->dbg.stat_host_syncs;
+  if (redone_steps) *redone_steps = h->dbg.stat_redone;
+  return PGF_OK;
+}
+
+int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram) {
+  if (!h) return PGF_INVALID;
+  if (builds) *builds = h->dbg.stat_gram_builds;
+  if (factorisations_with_gram) *factorisations_with_gram = h->dbg.stat_gram_factors;
+  return PGF_OK;
+}
+
+int pgf_debug_tail_stats(pgf_handle h, int *fused_steps, int *plain_steps) {
+  if (!h) return PGF_INVALID;
+  if (fused_steps) *fused_steps = h->dbg.stat_tail_fused;
+  if (plain_steps) *plain_steps = h->dbg.stat_tail_plain;
+  return PGF_OK;
+}
+
+int pgf_debug_head_stats(pgf_handle h, int *fused, int *plain) {
+  if (!h) return PGF_INVALID;
+  if (fused) *fused = h->dbg.stat_head_fused;
+  if (plain) *plain = h->dbg.stat_head_plain;
+  return PGF_OK;
+}
+
+// The head workers' unit list, walked on the host (no GPU): k_units[i * N + j] counts the units
+// that write entry (i, j) of K, k_head the same for the head launch's row groups, v_units the
+// units per entry of V ((nI + 1) x mp: the tail row last) -- N = nI in the condensed layout
+// (V: m columns padded to mp = a multiple of 32), nI + m in the natural one (no V).  The entry
+// tests are those of b_assemble_kkt and the panel's tile body.
+int pgf_debug_head_plan(int nI, int m, int condensed, int *k_units, int *k_head, int *v_units, int *n_units) {
+  if (nI < 0 || m < 0) return PGF_INVALID;
+  const int N = condensed ? nI : nI + m, mp = condensed ? round_up32(m) : 0;
+  // (the list as head_unit defines it; ldlt_head_wanted fuses nothing for N <= 256, whose list is
+  // the panel's tiles alone)
+  const int total = head_asm_units(N) + head_panel_units(nI, mp);
+  if (n_units) *n_units = total;
+  auto rows = [&](int *cnt, int cb, int rg) {
+    if (cb * 256 >= N || cb * 256 > rg * HEAD_ASM_ROWS + HEAD_ASM_ROWS - 1) return;
+    for (int i = rg * HEAD_ASM_ROWS; i < (rg + 1) * HEAD_ASM_ROWS; ++i)
+      for (int j = cb * 256; j < cb * 256 + 256; ++j)
+        if (i < N && j <= i && j < N) ++cnt[(size_t)i * N + j];
+  };
+  if (k_head)
+    for (int rg = 0; rg < (std::min(N, LDLT_OB) + HEAD_ASM_ROWS - 1) / HEAD_ASM_ROWS; ++rg) rows(k_head, 0, rg);
+  for (int u = 0; u < total; ++u) {
+    const HeadUnit hu = head_unit(u, N, nI, mp);
+    if (hu.kind == 0 && k_units) rows(k_units, hu.a, hu.b);
+    if (hu.kind == 1 && v_units) {
+      for (int i = hu.a * 32; i < hu.a * 32 + 32; ++i)
+        for (int r = hu.b * 32; r < hu.b * 32 + 32; ++r)
+          if (i < nI && r < mp) ++v_units[(size_t)i * mp + r];
+      if (hu.a == 0)
+        for (int r = hu.b * 32; r < hu.b * 32 + 32; ++r)
+          if (r < mp) ++v_units[(size_t)nI * mp + r];
+    }
+    if (hu.kind < 0) return PGF_INVALID;
+  }
+  return PGF_OK;
+}
+
+// The lazy update plan of a dense factorisation, walked on the host (no GPU, no handle): the
+// jobs of every stage, and on request every tile of them as upd_tile -- the mapping the device
+// workers run -- numbers it.
+int pgf_debug_update_plan(int N, int nrows, int vdepth, int budget, int cap, int *jobs, int jobs_cap,
+                          int *n_jobs, int *tiles, int tiles_cap, int *n_tiles, int *stage_jobs,
+                          int *budget_out) {
+  if (N < 1 || nrows < N || nrows > N + 1 || vdepth < 0 || vdepth % 32 || (budget >= 0 && cap < 1))
+    return PGF_INVALID;
+  UpdPlan made;
+  if (budget >= 0) plan_updates(made, N, nrows, LDLT_OB, budget ? budget : UPD_NO_LIMIT, cap, vdepth);
+  const UpdPlan &pl = budget >= 0 ? made : update_plan_for(N, nrows, vdepth, false);
+  if (budget_out) *budget_out = pl.budget == UPD_NO_LIMIT ? 0 : pl.budget;
+  const int nblk = (N + LDLT_OB - 1) / LDLT_OB;
+  int nj = 0, nt = 0;
+  for (int st = -1; st < nblk - 1; ++st) {
+    UpdJobs none;
+    none.njobs = 0;
+    none.tile_begin[0] = 0;
+    const UpdJobs &js = st >= 0 ? pl.launch[st] : (vdepth > 0 ? pl.first : none);
+    if (stage_jobs) stage_jobs[st + 1] = js.njobs;
+    for (int q = 0; q < js.njobs; ++q, ++nj) {
+      if (!jobs || nj >= jobs_cap) continue;
+      const int rec[PGF_UPDATE_PLAN_JOB_INTS] = {st,         js.col0[q], js.ntc[q], js.rowstart[q],     js.kc0v[q],
+                                                 js.KBv[q],  js.kc0[q],  js.KB[q],  js.tile_begin[q],
+                                                 js.tile_begin[q + 1]};
+      std::memcpy(jobs + (size_t)PGF_UPDATE_PLAN_JOB_INTS * nj, rec, sizeof rec);
+    }
+    if (!tiles || tiles_cap <= 0) continue;
+    for (int t = 0;; ++t, ++nt) {  // until the mapping itself says "past the end"
+      int q, i0, j0;
+      if (!upd_tile(js, t, N, nrows, q, i0, j0)) break;
+      if (nt >= tiles_cap) continue;
+      const int rec[4] = {st, q, i0, j0};
+      std::memcpy(tiles + (size_t)4 * nt, rec, sizeof rec);
+    }
+  }
+  if (n_jobs) *n_jobs = nj;
+  if (n_tiles) *n_tiles = nt;
+  return PGF_OK;
+}
+
+int pgf_debug_factor_kind(pgf_handle h) {
+  if (!h || h->sparse) return 0;
+  if (h->guard.lu_active) return 3;
+  if (!h->fac.factored) return 0;
+  return h->cond.condensed ? 2 : 1;
+}
+
+int pgf_debug_chain_helpers(int on) {
+  const int was = ldlt_chain_helpers_enabled() ? 1 : 0;
+  if (on == 0 || on == 1) ldlt_chain_helpers_set(on == 1);
+  return was;
 }

@@ -1,5 +1,5 @@
 // The banded driver behind the C ABI: the pgf_sparse_* entry points and the banded halves of the
-// step, factor, refinement and linear-solve functions of pgf_api.hip (pgf_api_internal.h lists
+// step, factor, refinement and linear-solve functions of the dense handle's files (pgf_api_internal.h lists
 // them).  The system keeps its full size n + m (an active variable is an identity row) and is
 // solved by block cyclic reduction: B = 8 (pgf_sparse.hip), B = 16, 32, 64 (pgf_band_wide.hip),
 // or the bordered band on top of either (pgf_border.hip).  The reduction leaves the assembled band
@@ -114,16 +114,16 @@ double band_residual_rel_of(const double *pairs, int nred) {
 static double sparse_residual_rel(pgf_handle h) { return band_residual_rel_of(h->sp.h_bred, h->sp.nred); }
 
 int band_refine(pgf_handle h, bool swapped, bool with_step) {
-  if (!h->refine_mode || !h->sp.guarded) return PGF_OK;
+  if (!h->guard.refine_mode || !h->sp.guarded) return PGF_OK;
   const int Nf = h->n + h->m;
   if (Nf == 0) return PGF_OK;
   double rel = sparse_residual_rel(h);
-  h->stat_last_rel = rel;
-  if (rel <= h->refine_tol) return PGF_OK;
+  h->guard.stat_last_rel = rel;
+  if (rel <= h->guard.refine_tol) return PGF_OK;
   hipStream_t s = h->stream;
   SparseDev &sp = h->sp;
   auto unswap = [&]() { if (swapped) swap_point(h); };
-  for (int it = 0; it < 2 && rel > h->refine_tol && rel < 1.0; ++it) {
+  for (int it = 0; it < 2 && rel > h->guard.refine_tol && rel < 1.0; ++it) {
     HIPCHK(h, hipMemcpyAsync(sp.bsol, sp.brhs, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, hipMemcpyAsync(sp.brhs, sp.bres, (size_t)Nf * sizeof(double), hipMemcpyDeviceToDevice, s));
     sp_cyclic_solve(s, sp, Nf, h->fac.flags, /*guard=*/false);
@@ -139,7 +139,7 @@ int band_refine(pgf_handle h, bool swapped, bool with_step) {
       HIPCHK(h, hipMemcpyAsync(h->h_scal, h->scal, sizeof(double), hipMemcpyDeviceToHost, s));
     }
     HIPCHK(h, hipStreamSynchronize(s));
-    ++h->stat_refined;
+    ++h->guard.stat_refined;
     const double now = sparse_residual_rel(h);
     if (!(now < rel)) {
       rel = now;
@@ -147,8 +147,8 @@ int band_refine(pgf_handle h, bool swapped, bool with_step) {
     }
     rel = now;
   }
-  h->stat_last_rel = rel;
-  if (!(rel <= h->refine_fail))
+  h->guard.stat_last_rel = rel;
+  if (!(rel <= h->guard.refine_fail))
     return fail(h, PGF_SINGULAR,
                 "banded KKT system could not be solved to a small residual (unpivoted block cyclic reduction)");
   return PGF_OK;
@@ -176,9 +176,9 @@ int band_step_async(pgf_handle h, bool *did_factor) {
     (void)hipEventRecord(e0, s);
   }
   const bool solve_phase = !sp.bk && sp.kept == 2;
-  sp_cyclic_solve(s, sp, Nf, h->fac.flags, h->refine_mode != 0);
+  sp_cyclic_solve(s, sp, Nf, h->fac.flags, h->guard.refine_mode != 0);
   const bool keep_red = sp.kept == 1;
-  sp.guarded = h->refine_mode != 0;
+  sp.guarded = h->guard.refine_mode != 0;
   if (p) {
     (void)hipEventRecord(e1, s);
     p->update_spans.emplace_back(e0, e1);
@@ -222,8 +222,8 @@ int band_linear_solve(pgf_handle h, const double *rhs, double *sol) {
   sp_launch_permute(h->stream, sp, Nf, h->rhs, sp.brhs, 0);
   // cyclic reduction keeps the assembled band intact: (re)assemble only when stale
   if (!h->fac.factored) sp_assemble(h);
-  sp_cyclic_solve(h->stream, sp, Nf, h->fac.flags, h->refine_mode != 0);
-  sp.guarded = h->refine_mode != 0;
+  sp_cyclic_solve(h->stream, sp, Nf, h->fac.flags, h->guard.refine_mode != 0);
+  sp.guarded = h->guard.refine_mode != 0;
   if (sp.guarded)
     HIPCHK(h, hipMemcpyAsync(sp.h_bred, sp.bred, (size_t)2 * sp.nred * sizeof(double),
                              hipMemcpyDeviceToHost, h->stream));
@@ -282,7 +282,7 @@ int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t l
     h->fac.n_neg = h->fac.h_flags[1];
     h->fac.factored = true;
   }
-  const bool guard = h->refine_mode != 0;
+  const bool guard = h->guard.refine_mode != 0;
   const int nb = (Nf + sp.B - 1) / sp.B;
   int rc;
   double worst = 0.0;
@@ -310,15 +310,15 @@ int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t l
     if (!guard) continue;
     for (int j = 0; j < nc; ++j) {
       const double rel = band_residual_rel_of(sp.h_bredm + (size_t)j * pairs, sp.nred);
-      if (rel > h->refine_tol) {  // this column once more, guarded and refined
+      if (rel > h->guard.refine_tol) {  // this column once more, guarded and refined
         if ((rc = band_linear_solve(h, rhs + (int64_t)(c0 + j) * ld, sol + (int64_t)(c0 + j) * ld))) return rc;
-        worst = std::max(worst, h->stat_last_rel);
+        worst = std::max(worst, h->guard.stat_last_rel);
       } else {
         worst = std::max(worst, rel);
       }
     }
   }
-  if (guard) h->stat_last_rel = worst;
+  if (guard) h->guard.stat_last_rel = worst;
   return PGF_OK;
 }
 

@@ -36,7 +36,7 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       return fail(h, PGF_INVALID, "batch: dense and banded handles cannot share a batch");
     if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
       return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
-    if (h->form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
+    if (h->unsym.form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
     const SparseDev &sp = h->sp;
     if (!sp.active || !sp.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
@@ -406,8 +406,8 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
         for (int k = 0; k < nred; ++k) sum += st[2 * nred + k];
         d = std::sqrt(sum);
         const double rel = band_residual_rel_of(st, nred);
-        h->stat_last_rel = rel;
-        if (h->refine_mode && !(rel <= h->refine_tol)) {
+        h->guard.stat_last_rel = rel;
+        if (h->guard.refine_mode && !(rel <= h->guard.refine_tol)) {
           rc = band_batch_repair(b, i, st, &d);
           b->eval_fresh = false;  // the instance moved after the evaluation made ahead
           if (rc == PGF_OK) ++b->repaired;
@@ -475,9 +475,9 @@ void band_batch_enqueue_refine(pgf_batch b) {
 int band_batch_ctl_init(pgf_batch b) {
   std::vector<double> g((size_t)BG_STRIDE * b->B);
   for (int i = 0; i < b->B; ++i) {
-    g[BG_STRIDE * (size_t)i] = b->hs[i]->refine_mode ? 1.0 : 0.0;
-    g[BG_STRIDE * (size_t)i + 1] = b->hs[i]->refine_tol;
-    g[BG_STRIDE * (size_t)i + 2] = b->hs[i]->refine_fail;
+    g[BG_STRIDE * (size_t)i] = b->hs[i]->guard.refine_mode ? 1.0 : 0.0;
+    g[BG_STRIDE * (size_t)i + 1] = b->hs[i]->guard.refine_tol;
+    g[BG_STRIDE * (size_t)i + 2] = b->hs[i]->guard.refine_fail;
   }
   BHIPCHK(b, hipMemcpyAsync(b->band_guard, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice,
                             b->stream));

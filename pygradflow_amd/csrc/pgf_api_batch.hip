@@ -25,9 +25,9 @@ static int batch_store_norms(pgf_batch b) {
     int rc = residual_norms(h);
     if (rc) return rc;
     double *p = b->h_ps + (size_t)BPS_STRIDE * i;
-    p[BPS_NORM_H] = h->h_rs[4];
-    p[BPS_NORM_J1] = h->h_rs[6];
-    p[BPS_NORM_JINF] = h->h_rs[5];
+    p[BPS_NORM_H] = h->guard.h_rs[4];
+    p[BPS_NORM_J1] = h->guard.h_rs[6];
+    p[BPS_NORM_JINF] = h->guard.h_rs[5];
   }
   return PGF_OK;
 }
@@ -60,7 +60,7 @@ int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pg
     if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
       return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
     if (h->sparse) return fail(h, PGF_INVALID, "batch: dense handles only");
-    if (h->form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
+    if (h->unsym.form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
     if (!h->qp_mode || !h->bounds_set || !h->point_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_problem, pgf_qp_set_point first");
     if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
@@ -571,22 +571,9 @@ int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log
 // instance's step is good now (its point, step length and factor state are in place).
 static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
   pgf_handle h = b->hs[i];
-  if (h->sparse || !h->refine_mode) return PGF_SINGULAR;
-  const int nI = b->h_flags[3 * i + 2];
-  h->nI = nI;
-  h->nA = h->n - nI;
-  h->N = nI + h->m;
-  h->mask_set = true;
-  h->condensed = b->cond_last;
-  h->lu_active = false;
-  h->last_solve = 2;
+  if (h->sparse || !h->guard.refine_mode) return PGF_SINGULAR;
+  adopt_batch_factor(h, b->h_flags[3 * i + 2], b->h_flags[3 * i + 1], b->cond_last, b->cond_mp);
   DenseLdlt &f = h->fac;
-  f.N = h->condensed ? nI : h->N;
-  f.vdepth = h->condensed ? b->cond_mp : 0;
-  f.ldv = condensed_ldv(h->m);
-  f.vneg = h->condensed ? h->m : 0;
-  f.factored = true;
-  f.n_neg = b->h_flags[3 * i + 1] + (h->condensed ? h->m : 0);
   enqueue_residual(h);
   hipError_t e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) return hip_fail(h, e, "batched repair");

@@ -1,7 +1,10 @@
-// What the translation units behind the C ABI share -- pgf_api.hip: the dense Symmetric handle and
-// the LQ step; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the unsymmetric formulations;
-// pgf_api_batch.hip: the batch driver; pgf_api_aux.hip: profiling read-out and the stand-alone
-// linear solver -- the handles, the error helpers and the small interfaces between the files.
+// What the translation units behind the C ABI share -- pgf_api.hip: the dense Symmetric handle's
+// lifecycle, uploads, index sets and linear solves; pgf_api_factor.hip: its factorisation (condensed
+// order, Gram matrix); pgf_api_guard.hip: its accuracy guard; pgf_api_step.hip: the Newton step and
+// the device-resident LQ mode; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the
+// unsymmetric formulations; pgf_api_batch.hip: the batch driver; pgf_api_aux.hip: profiling read-out,
+// the stand-alone linear solver and the pgf_debug_* hooks -- the handles, the error helpers and
+// the small interfaces between the files.
 #pragma once
 
 #include <cstdio>
@@ -62,80 +65,108 @@ struct pgf_solver {
   bool sparse = false;
   PgfProfile prof;
   bool step_pending = false;
-  int last_solve = 0;  // what newton_core_async enqueued: 1 back-solve of row N, 2 full solve
-  // residual check of the reduced system (dense mode): scratch vectors, r = rhs - K s, the
-  // correction, [max |r|, max |rhs|, max |s|] on device and pinned host; the pivoted LU that
-  // takes over when refinement does not converge (allocated on first use)
-  double *rs_v = nullptr, *rs_lv = nullptr, *rs_u = nullptr, *rs_wy = nullptr, *rs_r = nullptr,
-         *rs_d = nullptr, *rs_red = nullptr, *h_rs = nullptr;
-  DenseLu lu;
-  bool lu_active = false;       // the current factor is the LU (until the next factorisation)
-  int refine_mode = 1;          // 0 off, 1 check + refine on demand (default)
-  double refine_tol = 1e-11, refine_fail = 1e-7;
-  // ||H||_inf, ||J||_inf, ||J||_1 of the matrices in HBM (h_rs[4..6]); computed the first time a
-  // residual misses refine_tol against max |rhs| alone
-  bool norms_valid = false;
-  int stat_refined = 0, stat_lu = 0;
-  double stat_last_rel = 0.0;
-  // the factorisation step's own residual was far below the tolerance: the back-solve steps
-  // with the same factor (same backward error, other right-hand sides) skip the check
-  bool factor_clean = false;
-  bool rs_skipped = false;
   // status block (STAT_COPY above) and its pinned mirror
   double *stat = nullptr, *h_stat = nullptr;
   unsigned *ticket = nullptr;
-  int stat_bits = 0;  // DenseLdlt::status_words gathered into the block by the step update
   // speculative index-set sizes (pgf_qp_step_async): the step is enqueued with the last known
   // |I|, |A|; the compaction flags a mismatch in counts[3], and pgf_qp_sync redoes the step
-  bool counts_known = false, spec_pending = false;
-  bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
-  int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
-  // PGF_STEP_FUSED: the forced mask refresh of the step being enqueued has also written F, b0full
-  // and the reduced rhs (consumed by newton_core_async); steps enqueued with the residual check and
-  // the evaluation ahead in the fused / the separate launches (pgf_debug_tail_stats)
-  bool front_done = false;
-  int stat_tail_fused = 0, stat_tail_plain = 0;
+  // (flight.spec_pending)
+  bool counts_known = false;
   uint8_t *h_mask_stage = nullptr;  // pinned staging of pgf_set_active_set's mask
   hipEvent_t mask_ev = nullptr;
-  // the current dense factor is that of the condensed system (constraint block eliminated
-  // first, condensed_wanted below); cd_t: its right-hand side
-  bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
-  bool condensed = false;
-  bool condensed_veto = false;  // it met a zero pivot: natural order until the matrix changes
-  double *cd_t = nullptr;
-  // The condensed system's rank-m term from a resident Gram matrix (gram_prepare below): G = J^T J,
-  // n x n with row stride ldg, lower triangle; gram_aux: the identity index list of the build
-  // (n ints) and, behind it, the build's tile counter.  Valid until the next pgf_set_derivs_*
-  // (as norms_valid); gram_off: the allocation failed once, the handle keeps the virtual blocks.
-  double *G = nullptr;
-  int64_t ldg = 0;
-  int *gram_aux = nullptr;
-  bool gram_valid = false, gram_off = false;
-  int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
-  // what the factorisation in flight added to the counters (taken back when it is discarded)
-  bool fac_counted = false, fac_used_gram = false;
-  int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
-  // the factorisation in flight took the step's head beside its first chain (1) or not (2);
-  // pgf_debug_head_stats counts both kinds
-  int fac_head = 0;
-  int stat_head_fused = 0, stat_head_plain = 0;
-  // The unsymmetric formulations (pgf_set_formulation, pgf_api_unsym.hip): form --
+
+  // ---- the accuracy guard (pgf_api_guard.hip) ----
+  struct {
+    // residual check of the reduced system (dense mode): scratch vectors, r = rhs - K s, the
+    // correction, [max |r|, max |rhs|, max |s|] on device and pinned host; the pivoted LU that
+    // takes over when refinement does not converge (allocated on first use)
+    double *rs_v = nullptr, *rs_lv = nullptr, *rs_u = nullptr, *rs_wy = nullptr, *rs_r = nullptr,
+           *rs_d = nullptr, *rs_red = nullptr, *h_rs = nullptr;
+    DenseLu lu;
+    bool lu_active = false;       // the current factor is the LU (until the next factorisation)
+    int refine_mode = 1;          // 0 off, 1 check + refine on demand (default)
+    double refine_tol = 1e-11, refine_fail = 1e-7;
+    // ||H||_inf, ||J||_inf, ||J||_1 of the matrices in HBM (h_rs[4..6]); computed the first time a
+    // residual misses refine_tol against max |rhs| alone
+    bool norms_valid = false;
+    int stat_refined = 0, stat_lu = 0;
+    double stat_last_rel = 0.0;
+    // the factorisation step's own residual was far below the tolerance: the back-solve steps
+    // with the same factor (same backward error, other right-hand sides) skip the check
+    bool factor_clean = false;
+    bool rs_skipped = false;
+  } guard;
+
+  // ---- the condensed order and its resident Gram matrix (pgf_api_factor.hip) ----
+  struct {
+    // the current dense factor is that of the condensed system (constraint block eliminated
+    // first, condensed_wanted); cd_t: its right-hand side
+    bool condensed = false;
+    bool condensed_veto = false;  // it met a zero pivot: natural order until the matrix changes
+    double *cd_t = nullptr;
+    // The condensed system's rank-m term from a resident Gram matrix (gram_prepare): G = J^T J,
+    // n x n with row stride ldg, lower triangle; gram_aux: the identity index list of the build
+    // (n ints) and, behind it, the build's tile counter.  Valid until the next pgf_set_derivs_*
+    // (as norms_valid); gram_off: the allocation failed once, the handle keeps the virtual blocks.
+    double *G = nullptr;
+    int64_t ldg = 0;
+    int *gram_aux = nullptr;
+    bool gram_valid = false, gram_off = false;
+    int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
+  } cond;
+
+  // ---- what the step or factorisation in flight took: valid until it is settled (pgf_qp_sync,
+  // factor_finish) ----
+  struct {
+    int last_solve = 0;  // what newton_core_async enqueued: 1 back-solve of row N, 2 full solve
+    int stat_bits = 0;   // DenseLdlt::status_words gathered into the block by the step update
+    bool spec_pending = false;      // it was enqueued with speculative index-set sizes (counts_known)
+    bool step_took_inject = false;  // the step in flight consumed pgf_debug_fail_next_helper
+    // PGF_STEP_FUSED: the forced mask refresh of the step being enqueued has also written F, b0full
+    // and the reduced rhs (consumed by newton_core_async)
+    bool front_done = false;
+    bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
+    // what the factorisation in flight added to the counters (taken back when it is discarded)
+    bool fac_counted = false, fac_used_gram = false;
+    // the factorisation in flight took the step's head beside its first chain (1) or not (2);
+    // pgf_debug_head_stats counts both kinds
+    int fac_head = 0;
+    // forget what the last factorisation counted
+    void forget_factor() {
+      fac_counted = fac_used_gram = false;
+      fac_head = 0;
+    }
+  } flight;
+
+  // ---- counters read only by the pgf_debug_* hooks (pgf_api_aux.hip, pgf_api_unsym.hip) ----
+  struct {
+    int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
+    // steps enqueued with the residual check and the evaluation ahead in the fused / the separate
+    // launches (pgf_debug_tail_stats)
+    int stat_tail_fused = 0, stat_tail_plain = 0;
+    int stat_gram_builds = 0, stat_gram_factors = 0;  // pgf_debug_gram_stats
+    int stat_head_fused = 0, stat_head_plain = 0;     // pgf_debug_head_stats
+    int stat_unsym_asm = 0, stat_unsym_lu = 0;        // pgf_debug_unsym_stats
+    int64_t stat_unsym_bytes = 0;
+  } dbg;
+
+  // ---- The unsymmetric formulations (pgf_set_formulation, pgf_api_unsym.hip): form --
   // PGF_FORM_*; ulu -- the pivoted LU of the (n + m) x (n + m) Newton matrix, assembled on the
-  // device into ulu.A (its own factor: `lu' above belongs to the accuracy guard of the Symmetric
+  // device into ulu.A (its own factor: guard.lu belongs to the accuracy guard of the Symmetric
   // path and is never touched here); ulu_ok -- it holds the factor of the current matrix;
   // h_has_lag_only -- H in HBM is the plain Lagrangian Hessian (pgf_qp_set_problem), so Standard
   // adds rho J^T J from the resident Gram matrix; a caller of pgf_set_derivs_* uploads
   // aug_lag_deriv_xx(rho) itself.
-  int form = PGF_FORM_SYMMETRIC;
-  DenseLu ulu;
-  bool ulu_ok = false;
-  bool h_has_lag_only = false;
-  int stat_unsym_asm = 0, stat_unsym_lu = 0;  // pgf_debug_unsym_stats
-  int64_t stat_unsym_bytes = 0;
-  // while profiling is enabled: device time of the assembly launches of unsym_factor since the
-  // last pgf_profile_read_ex, and their count
-  double acc_unsym_asm_ms = 0;
-  int64_t acc_unsym_asm_launches = 0;
+  struct {
+    int form = PGF_FORM_SYMMETRIC;
+    DenseLu ulu;
+    bool ulu_ok = false;
+    bool h_has_lag_only = false;
+    // while profiling is enabled: device time of the assembly launches of unsym_factor since the
+    // last pgf_profile_read_ex, and their count
+    double acc_unsym_asm_ms = 0;
+    int64_t acc_unsym_asm_launches = 0;
+  } unsym;
 };
 
 struct pgf_linsolver {
@@ -150,6 +181,13 @@ struct pgf_linsolver {
 static const char *const k_no_handle = "null handle";
 static const char *const k_chain_msg = "chained triangular solve failed its placement / timeout check "
                                        "and so did the per-block solve that replaced it";
+static const char *const k_helper_msg =
+    "the dense factorisation failed its hand-over checks with and without helper workgroups";
+// internal: the factorisation just awaited must be repeated (its chain helpers failed their
+// hand-over checks and are switched off now, ldlt_finish -- or the condensed pivot order met a
+// zero pivot the natural order may not have: S = A + J^T J / delta can cancel exactly where no
+// pivot of K does); never leaves the library
+#define PGF_RETRY_FACTOR (-2)
 
 static inline int fail(pgf_handle h, int code, const char *msg) {
   if (h) h->err = msg;
@@ -216,10 +254,10 @@ static inline int round_up32(int m) { return (m + 31) / 32 * 32; }
 
 static inline void invalidate_factor(pgf_handle h) {
   h->fac.factored = false;
-  h->condensed_veto = false;
-  h->lu_active = false;
-  h->factor_clean = false;
-  h->ulu_ok = false;
+  h->cond.condensed_veto = false;
+  h->guard.lu_active = false;
+  h->guard.factor_clean = false;
+  h->unsym.ulu_ok = false;
 }
 
 // ---- the banded driver (pgf_api_band.hip), for handles created with PGF_CREATE_SPARSE ----------
@@ -239,7 +277,7 @@ bool band_split_default();                                     // pgf_create (PG
 void band_eval(pgf_handle h);                                  // qp_eval
 void band_measures_eval(pgf_handle h);                         // pgf_qp_measures
 
-// ---- the unsymmetric formulations (pgf_api_unsym.hip), for handles with h->form != 0 -------------
+// ---- the unsymmetric formulations (pgf_api_unsym.hip), for handles with h->unsym.form != 0 -------------
 // Each is the unsymmetric half of the dense function named beside it, which hands over in one line.
 int unsym_factor(pgf_handle h);                                           // pgf_factor, pgf_linear_solve
 int unsym_step_core(pgf_handle h);                                        // pgf_newton_solve
@@ -247,24 +285,49 @@ void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint
 int unsym_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, bool wait_counts);  // pgf_qp_update_active_set
 int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau);       // pgf_qp_step_async
 int unsym_qp_sync(pgf_handle h, int *n_neg, double *diff);                // pgf_qp_sync
-// what they take from pgf_api.hip
-void tau_factors(pgf_handle h, double tau, int *use_tau, double *f_x, double *f_x0, double *f_d);  // unsym_mask
-void qp_eval(pgf_handle h);                                               // unsym_qp_step_async
-bool gram_build(pgf_handle h);                                            // unsym_gram (Standard: H + rho J^T J)
-int check_ready(pgf_handle h);                                            // pgf_get_newton_matrix
+// what they take from the dense handle's files
+void tau_factors(pgf_handle h, double tau, int *use_tau, double *f_x, double *f_x0, double *f_d);  // unsym_mask (pgf_api.hip)
+void qp_eval(pgf_handle h);                                               // unsym_qp_step_async (pgf_api_step.hip)
+bool gram_build(pgf_handle h);                                            // unsym_gram (Standard: H + rho J^T J; pgf_api_factor.hip)
+int check_ready(pgf_handle h);                                            // pgf_get_newton_matrix (pgf_api.hip)
 
-// ---- what the batch driver (pgf_api_batch.hip) takes from pgf_api.hip --------------------------
-int residual_norms(pgf_handle h);           // batch_store_norms, pgf_batch_advance_outer_each
+// ---- what the batch driver (pgf_api_batch.hip) takes from the dense handle's files -------------
+int residual_norms(pgf_handle h);           // batch_store_norms, pgf_batch_advance_outer_each (pgf_api_guard.hip)
+// (pgf_api_factor.hip)
 int condensed_mode();                       // pgf_batch_create
 hipError_t condensed_reserve(pgf_handle h); // pgf_batch_create (and unsym_gram)
-int64_t condensed_ldv(int m);               // pgf_batch_create, batch_repair_instance
+int64_t condensed_ldv(int m);               // pgf_batch_create, adopt_batch_factor
 bool condensed_growth_ok(pgf_handle h);     // pgf_batch_advance_outer_each
-bool eval_ahead();                          // pgf_batch_step_async
+bool eval_ahead();                          // pgf_batch_step_async (pgf_api_step.hip)
 // batch_repair_instance: the single-instance accuracy guard on an instance's own handle
 struct StepCondY;
-void enqueue_residual(pgf_handle h, bool may_skip = false);
-int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true);
-void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr);
+void enqueue_residual(pgf_handle h, bool may_skip = false);                                  // (pgf_api_guard.hip)
+int refine_if_needed(pgf_handle h, bool swapped, bool with_step = true);                     // (pgf_api_guard.hip)
+void enqueue_step_update(pgf_handle h, bool expand = false, const StepCondY *cy = nullptr);  // (pgf_api_step.hip)
+
+// ---- between the dense handle's own files ------------------------------------------------------
+// One group per providing file, each beside its users.  (Hidden: these cross files, not the
+// library's boundary -- its dynamic symbol table stays as it was.)
+#pragma GCC visibility push(hidden)
+// pgf_api.hip
+int adopt_index_sets(pgf_handle h, bool spec);      // qp_refresh_mask
+int refresh_index_sets(pgf_handle h, bool in_step); // qp_refresh_mask
+void assemble(pgf_handle h, double *K, int64_t ldk);  // refine_if_needed (the LU's matrix)
+// pgf_api_factor.hip
+hipError_t kkt_solve_async(pgf_handle h, const double *rhs, double *sol);  // newton_core_async, refine_if_needed, chain_recover, pgf_linear_solve
+hipError_t kkt_backsolve_async(pgf_handle h, double *sol, StepCondY *cy = nullptr);  // newton_core_async, chain_recover
+int factor_async(pgf_handle h, bool with_rhs);      // newton_core_async
+int finish_factor_state(pgf_handle h, hipError_t *e);  // pgf_qp_sync
+int factor_finish(pgf_handle h);                    // pgf_newton_solve
+int factor_sync(pgf_handle h);                      // pgf_linear_solve
+void gram_uncount(pgf_handle h);                    // settle_spec
+// the batch's factor of an instance becomes the handle's own, for refine_if_needed
+void adopt_batch_factor(pgf_handle h, int nI, int n_neg_reported, bool condensed, int cond_mp);  // batch_repair_instance
+// pgf_api_guard.hip
+int chain_recover(pgf_handle h, bool swapped);      // pgf_newton_solve, pgf_qp_sync
+// pgf_api_step.hip
+bool step_spec();                                   // refresh_index_sets
+#pragma GCC visibility pop
 
 // ---- the batch (pgf_api_batch.hip: the dense half and the dispatch; pgf_api_band_batch.hip: the
 // banded half) ----------------------------------------------------------------------------------

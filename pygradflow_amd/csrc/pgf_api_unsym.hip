@@ -1,5 +1,5 @@
 // The unsymmetric formulations behind the C ABI: their entry points and the halves of the step,
-// factor and mask functions of pgf_api.hip that run when pgf_set_formulation chose one
+// factor and mask functions of the dense handle's files that run when pgf_set_formulation chose one
 // (pgf_api_internal.h lists them).
 #include <cmath>
 #include <utility>
@@ -16,20 +16,20 @@
 // |A| on the device, so a step needs no host synchronisation for the index sets -- the one wait
 // inside a factorising step is lu_factor's own (it reads its pivots).  No LDL^T, no inertia
 // (n_neg = -1, LUSolver.num_neg_eigvals() is None), no accuracy guard: the LU pivots.
-static const double *unsym_lo(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->lb : h->slb; }
-static const double *unsym_hi(pgf_handle h) { return h->form == PGF_FORM_STANDARD ? h->ub : h->sub; }
+static const double *unsym_lo(pgf_handle h) { return h->unsym.form == PGF_FORM_STANDARD ? h->lb : h->slb; }
+static const double *unsym_hi(pgf_handle h) { return h->unsym.form == PGF_FORM_STANDARD ? h->ub : h->sub; }
 
 // Device-resident Standard linearises with aug_lag_deriv_xx(rho) = H + rho J^T J: the Gram matrix
 // the condensed LDL^T keeps per derivative upload (gram_build) -- never rebuilt per step.
 static int unsym_gram(pgf_handle h, const double **G) {
   *G = nullptr;
-  if (h->form != PGF_FORM_STANDARD || !h->h_has_lag_only || h->m == 0 || h->n == 0) return PGF_OK;
-  if (!h->gram_valid) {
+  if (h->unsym.form != PGF_FORM_STANDARD || !h->unsym.h_has_lag_only || h->m == 0 || h->n == 0) return PGF_OK;
+  if (!h->cond.gram_valid) {
     HIPCHK(h, condensed_reserve(h));
-    if (h->gram_off || !gram_build(h))
+    if (h->cond.gram_off || !gram_build(h))
       return fail(h, PGF_HIP_ERROR, "Standard formulation: the Gram matrix J^T J could not be built");
   }
-  *G = h->G;
+  *G = h->cond.G;
   return PGF_OK;
 }
 
@@ -37,7 +37,7 @@ static int unsym_assemble(pgf_handle h, double *M, int64_t ld) {
   const double *G;
   int rc;
   if ((rc = unsym_gram(h, &G))) return rc;
-  launch_assemble_unsym(h->stream, h->form, M, ld, h->n, h->m, h->H, h->ldh, h->J, h->ldj, G, h->ldg,
+  launch_assemble_unsym(h->stream, h->unsym.form, M, ld, h->n, h->m, h->H, h->ldh, h->J, h->ldj, G, h->cond.ldg,
                         h->rho, h->mask, h->idxI, h->idxA, h->counts, h->dt, h->lamb, h->delta);
   return PGF_OK;
 }
@@ -45,14 +45,14 @@ static int unsym_assemble(pgf_handle h, double *M, int64_t ld) {
 // assemble + factorise (waits: lu_factor reads its pivots)
 int unsym_factor(pgf_handle h) {
   const int Nf = h->n + h->m;
-  if (!h->ulu.A) {
-    const hipError_t ea = lu_alloc(h->ulu, Nf, h->stream);
+  if (!h->unsym.ulu.A) {
+    const hipError_t ea = lu_alloc(h->unsym.ulu, Nf, h->stream);
     if (ea != hipSuccess) {
-      lu_free(h->ulu);  // (nothing half allocated stays behind)
+      lu_free(h->unsym.ulu);  // (nothing half allocated stays behind)
       return hip_fail(h, ea, "lu_alloc");
     }
   }
-  h->ulu_ok = false;
+  h->unsym.ulu_ok = false;
   int rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->prof.enabled) {
@@ -60,25 +60,25 @@ int unsym_factor(pgf_handle h) {
     e1 = prof_event(&h->prof);
     (void)hipEventRecord(e0, h->stream);
   }
-  rc = unsym_assemble(h, h->ulu.A, h->ulu.ld);
+  rc = unsym_assemble(h, h->unsym.ulu.A, h->unsym.ulu.ld);
   if (e0) (void)hipEventRecord(e1, h->stream);
   hipError_t e = hipSuccess;
-  const int st = rc ? 0 : lu_factor(h->ulu, &e);  // (waits for the stream)
+  const int st = rc ? 0 : lu_factor(h->unsym.ulu, &e);  // (waits for the stream)
   if (e0) {
     float ms = 0.f;
     if (!rc && st >= 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) {
-      h->acc_unsym_asm_ms += ms;
-      ++h->acc_unsym_asm_launches;
+      h->unsym.acc_unsym_asm_ms += ms;
+      ++h->unsym.acc_unsym_asm_launches;
     }
     h->prof.pool.push_back(e0);
     h->prof.pool.push_back(e1);
   }
   if (rc) return rc;
-  ++h->stat_unsym_asm;
+  ++h->dbg.stat_unsym_asm;
   if (st < 0) return hip_fail(h, e, "LU of the Newton matrix");
-  ++h->stat_unsym_lu;
+  ++h->dbg.stat_unsym_lu;
   if (st == 1) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in the LU of the Newton matrix");
-  h->ulu_ok = true;
+  h->unsym.ulu_ok = true;
   return PGF_OK;
 }
 
@@ -87,7 +87,7 @@ void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint
   int use_tau;
   double f_x, f_x0, f_d;
   tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
-  if (h->form == PGF_FORM_STANDARD)
+  if (h->unsym.form == PGF_FORM_STANDARD)
     launch_unscaled_active_set(h->stream, h->n, use_tau, h->dt, use_tau ? 1.0 - tau * h->lamb : 0.0,
                                use_tau ? tau * h->lamb : 0.0, use_tau ? tau : 0.0, h->xhat, x, g, h->lb,
                                h->ub, out);
@@ -99,13 +99,13 @@ void unsym_mask(pgf_handle h, double tau, const double *x, const double *g, uint
 // (h->x, h->y, h->g, h->c); scal[0] <- the step length.  Enqueued, except for lu_factor's wait.
 int unsym_step_core(pgf_handle h) {
   hipStream_t s = h->stream;
-  h->fused_eval_done = false;
-  launch_unsym_residual_rhs(s, h->form, h->n, h->m, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y,
+  h->flight.fused_eval_done = false;
+  launch_unsym_residual_rhs(s, h->unsym.form, h->n, h->m, h->lamb, h->dt, h->fact, h->xhat, h->yhat, h->x, h->y,
                             h->g, h->c, unsym_lo(h), unsym_hi(h), h->mask, h->pos, h->counts, h->F, h->rhs);
   int rc;
-  if (!h->ulu_ok && (rc = unsym_factor(h))) return rc;
-  HIPCHK(h, lu_solve_async(h->ulu, h->rhs, h->sol, 0));
-  launch_unsym_step_update(s, h->form, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F, h->sol,
+  if (!h->unsym.ulu_ok && (rc = unsym_factor(h))) return rc;
+  HIPCHK(h, lu_solve_async(h->unsym.ulu, h->rhs, h->sol, 0));
+  launch_unsym_step_update(s, h->unsym.form, h->n, h->m, h->fact, h->rho, h->x, h->y, h->lb, h->ub, h->F, h->sol,
                            h->dx, h->dy, h->xn, h->yn, h->red);
   launch_final_reduce(s, h->red, (h->n + h->m + 255) / 256, h->scal, 1);
   return PGF_OK;
@@ -124,7 +124,7 @@ int unsym_refresh_mask(pgf_handle h, double tau, bool force, int *changed_out, b
     launch_mask_diff(s, h->n, h->mask, h->mask_new, h->counts + 2);
     if ((rc = down(h, h->h_counts + 2, h->counts + 2, sizeof(int)))) return rc;
     HIPCHK(h, hipStreamSynchronize(s));
-    if (!wait_counts) ++h->stat_host_syncs;
+    if (!wait_counts) ++h->dbg.stat_host_syncs;
     changed = h->h_counts[2] != 0;
   }
   if (changed_out) *changed_out = changed;
@@ -162,7 +162,7 @@ int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau) {
 
 int unsym_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  ++h->stat_host_syncs;
+  ++h->dbg.stat_host_syncs;
   adopt_counts(h);
   if (n_neg) *n_neg = -1;
   if (diff) *diff = h->h_scal[0];
@@ -175,20 +175,20 @@ int pgf_set_formulation(pgf_handle h, int form) {
   if (form < PGF_FORM_SYMMETRIC || form > PGF_FORM_ASYMMETRIC)
     return fail(h, PGF_INVALID, "pgf_set_formulation: unknown formulation");
   if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the step in flight first");
-  h->form = form;
+  h->unsym.form = form;
   invalidate_factor(h);
   // a handle that goes back to Symmetric gives the (n + m) x ld array of its LU back
-  if (form == PGF_FORM_SYMMETRIC && h->ulu.A) {
+  if (form == PGF_FORM_SYMMETRIC && h->unsym.ulu.A) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    lu_free(h->ulu);
+    lu_free(h->unsym.ulu);
   }
   return PGF_OK;
 }
 
 int pgf_get_newton_matrix(pgf_handle h, double *M_out, int64_t ld) {
   if (!h) return PGF_INVALID;
-  if (!h->form) return fail(h, PGF_INVALID, "pgf_get_newton_matrix: pgf_set_formulation first");
+  if (!h->unsym.form) return fail(h, PGF_INVALID, "pgf_get_newton_matrix: pgf_set_formulation first");
   int rc;
   if ((rc = check_ready(h))) return rc;
   const int Nf = h->n + h->m;
@@ -215,14 +215,14 @@ int pgf_get_newton_matrix(pgf_handle h, double *M_out, int64_t ld) {
 int pgf_debug_unsym_stats(pgf_handle h, int *assemblies, int *lu_factorisations,
                           int64_t *matrix_bytes_from_host) {
   if (!h) return PGF_INVALID;
-  if (assemblies) *assemblies = h->stat_unsym_asm;
-  if (lu_factorisations) *lu_factorisations = h->stat_unsym_lu;
-  if (matrix_bytes_from_host) *matrix_bytes_from_host = h->stat_unsym_bytes;
+  if (assemblies) *assemblies = h->dbg.stat_unsym_asm;
+  if (lu_factorisations) *lu_factorisations = h->dbg.stat_unsym_lu;
+  if (matrix_bytes_from_host) *matrix_bytes_from_host = h->dbg.stat_unsym_bytes;
   return PGF_OK;
 }
 
 int pgf_debug_unsym_note_upload(pgf_handle h, int64_t bytes) {
   if (!h || bytes < 0) return PGF_INVALID;
-  h->stat_unsym_bytes += bytes;
+  h->dbg.stat_unsym_bytes += bytes;
   return PGF_OK;
 }

@@ -1217,7 +1217,7 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *hea
 // G <- V V^T, lower triangle (declared in pgf_internal.h): the update role alone (k_update_jobs)
 // with one job over every 128-wide tile column, its K-range the panel V only (KB = 0: no column of
 // G itself is read as an operand).  With vd = -1 the tile's C -= V diag(vd) V^T adds V V^T to the
-// zeroed G.  n^2 depth flops once per derivative upload (pgf_api.hip, gram_prepare).
+// zeroed G.  n^2 depth flops once per derivative upload (pgf_api_factor.hip, gram_prepare).
 hipError_t ldlt_gram_async(hipStream_t s, double *G, int64_t ldg, int n, const double *V, int64_t ldv,
                            const double *vd, int depth, int *ctr) {
   if (n <= 0 || depth <= 0 || depth % 32) return hipErrorInvalidValue;

@@ -84,12 +84,12 @@ struct DenseLdlt {
   bool factored = false;
   int n_neg = 0;
   PgfProfile *prof = nullptr;
-  // A pre-eliminated diagonal block (the condensed KKT system, pgf_api.hip): when vdepth > 0 the
+  // A pre-eliminated diagonal block (the condensed KKT system, pgf_api_factor.hip): when vdepth > 0 the
   // matrix to factorise is K - V diag(vd) V^T, V = (N + 1) x vdepth row-major (row N rides along
   // like row N of K); the look-ahead schedule applies it as `virtual' column blocks that are
   // already factorised, lazily, like any other pending block.  vneg = the negative pivots of the
   // block eliminated beforehand; ldlt_finish adds them whatever vdepth is: a caller that has put
-  // the block's Schur term into K itself (the resident Gram matrix, pgf_api.hip) factorises with
+  // the block's Schur term into K itself (the resident Gram matrix, pgf_api_factor.hip) factorises with
   // vdepth = 0 and still owes them to the inertia.  Whoever sets vdepth sets vneg with it.
   double *V = nullptr;
   int64_t ldv = 0;
@@ -99,7 +99,7 @@ struct DenseLdlt {
   size_t vcap = 0, vdcap = 0;  // allocated doubles
   int inject_chain_failure = 0;  // test hook: the next chained solve reports a failure
   int inject_helper_failure = 0;  // test hook: the next factorisation reports failed helpers
-  // Status words of a dense Newton step (pgf_api.hip): flags_zeroed -- the caller's assembly
+  // Status words of a dense Newton step (pgf_api_step.hip): flags_zeroed -- the caller's assembly
   // launch has already cleared flags [0, 4 + LDLT_UPD_COUNTERS), so the next factorisation skips
   // its memset (consumed by it); defer_status -- the factorisation's flags and the chained solve's
   // status word are NOT copied to h_flags here: status_words records what is pending (bit 0: flags
@@ -110,7 +110,7 @@ struct DenseLdlt {
   int status_words = 0;
 };
 
-// Head work of a dense Newton step (pgf_api.hip, factor_async): what the step writes in front of
+// Head work of a dense Newton step (pgf_api_factor.hip, factor_async): what the step writes in front of
 // a factorisation whose first diagonal chain reads nothing but K[0:256, 0:256].  Given to
 // ldlt_factor_async, the rows below 256 of the assembly and the panel V = J_I^T are written by
 // the idle workgroups of the first chain's launch (k_chain_head, pgf_factor2.hip) instead of by

@@ -99,7 +99,7 @@ void launch_symmetrize(hipStream_t s, double *A, int64_t ld, int N);
 // ||H||_inf, ||J||_inf, ||J||_1 -> norms3 (device), for the normwise backward error of the guard
 void launch_matrix_norms(hipStream_t s, int n, int m, const double *H, int64_t ldh, const double *J,
                          int64_t ldj, double *norms3);
-// condensed KKT system (constraint block eliminated first; pgf_kernels.hip, pgf_api.hip):
+// condensed KKT system (constraint block eliminated first; pgf_kernels.hip, pgf_api_factor.hip):
 // V <- J[:, I]^T zero-padded to mp columns, row nI <- rhs_y (or 0), vd <- -1 / delta
 void launch_cond_panel(hipStream_t s, double *V, int64_t ldv, int mp, double *vd, const double *J,
                        int64_t ldj, const int *idxI, int nI, int m, double delta, const double *rhs_y);

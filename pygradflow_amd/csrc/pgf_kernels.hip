@@ -1236,7 +1236,7 @@ void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, 
                        reinterpret_cast<unsigned long long *>(red3));
 }
 
-// ---- the same in three launches (PGF_STEP_FUSED, pgf_api.hip): every value is computed by the
+// ---- the same in three launches (PGF_STEP_FUSED, pgf_api_step.hip): every value is computed by the
 // expressions above in the same order, only the launch it is computed in changes.
 // The row passes over J and H in one launch: the first jb workgroups are k_gemv_rows2 over J
 // (c = J xn - b, wy = J v - delta s_y, complete), the others row_dot2 of H with (xn, v), stored raw
@@ -1358,7 +1358,7 @@ void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double 
                        g, u, lv, mask, pos, rhs, sol, wy, r, reinterpret_cast<unsigned long long *>(red3));
 }
 
-// ---- matrix norms for the normwise backward error of the residual guard (pgf_api.hip)
+// ---- matrix norms for the normwise backward error of the residual guard (pgf_api_guard.hip)
 // out[0] = max_i sum_j |A_ij| (rows x cols, row-major): one workgroup per row; non-negative
 // doubles order like their bit patterns, so atomicMax on the 64-bit words does the reduction
 __global__ __launch_bounds__(256) void k_abs_rowsum_max(int cols, const double *__restrict__ A, int64_t ld,

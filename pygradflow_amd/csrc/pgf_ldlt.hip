@@ -723,7 +723,7 @@ int ldlt_chain_check(DenseLdlt &f) {
   return bad;
 }
 
-// a chained solve of a step that is discarded (pgf_api.hip, speculative index-set sizes) reported
+// a chained solve of a step that is discarded (pgf_api_step.hip, speculative index-set sizes) reported
 // a failure: the state it may have left half published is reset, but the chain stays on -- the
 // repeated step's own solve decides that
 void ldlt_chain_discard(DenseLdlt &f, int word) {

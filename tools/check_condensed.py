@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The condensed KKT factorisation (constraint block eliminated first, csrc/pgf_api.hip
+"""The condensed KKT factorisation (constraint block eliminated first, csrc/pgf_api_factor.hip
 ``condensed_wanted``) against the CPU oracle (GPU): boxed dense QPs whose reduced sizes put the
 constraint block across zero, one and several 256-column blocks, Full and Simplified steps
 (factorisation with the right-hand side riding along, then back-solve steps with the same
@@ -66,7 +66,7 @@ if len(sys.argv) == 1:
     # The condensed pivot order can meet an exactly zero pivot where the natural order does not:
     # A = diag(-2, 3, 2, 5), J = (1, 1, 0, 0), delta = 1/2 gives S[0][0] = -2 + 1 / delta = 0.  The
     # library then repeats the factorisation in the natural order inside the same call
-    # (finish_factor_state, csrc/pgf_api.hip) -- the caller sees the reference's behaviour: the
+    # (finish_factor_state, csrc/pgf_api_factor.hip) -- the caller sees the reference's behaviour: the
     # step goes through with inertia m + 1.
     Q = np.diag([-3.0, 2.0, 1.0, 4.0])
     A = np.array([[1.0, 1.0, 0.0, 0.0]])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The resident Gram matrix of the condensed factorisation (G = J^T J, csrc/pgf_api.hip
+"""The resident Gram matrix of the condensed factorisation (G = J^T J, csrc/pgf_api_factor.hip
 ``gram_prepare``) against the CPU oracle (GPU).  Run under PGF_CONDENSED=2 with
 PGF_CONDENSED_GRAM = 0 (never: the virtual column blocks), 1 (default: G is built at the second
 condensed factorisation since the last derivative upload) and 2 (at the first); the switches are
