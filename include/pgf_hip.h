@@ -37,6 +37,9 @@ extern "C" {
 #define PGF_INERTIA 2
 #define PGF_INVALID 3
 #define PGF_NOT_READY 4
+/* PGF_STEP_LINE_SEARCH: none of the 30 trial step lengths was accepted (newton.py:291-292, the
+ * reference's bare Exception("Line search failed to converge")); the device point has not moved */
+#define PGF_LINE_SEARCH 5
 #define PGF_HIP_ERROR 100
 
 #define PGF_HOST 0
@@ -49,6 +52,13 @@ extern "C" {
 #define PGF_STEP_RECOMPUTE_MASK 1u  /* Full, ActiveSet: mask from the current point  */
 #define PGF_STEP_REFACTOR 2u        /* Full: assemble + factor every step             */
 #define PGF_STEP_REFACTOR_ON_CHANGE 4u /* ActiveSet: refactor iff the mask changed     */
+/* Globalized (GlobalizedNewtonMethod, newton.py:218-304): with PGF_STEP_RECOMPUTE_MASK |
+ * PGF_STEP_REFACTOR only, on a dense Symmetric or a banded handle (anything else: PGF_INVALID).
+ * The Newton direction is solved at the OUTER point with the device point's mask (:244-248), then
+ * the Armijo line search on 1/2 ||F||^2 over alpha = 2^-k, k < 30 (:250-292), runs in one launch;
+ * the new point is measured from the outer point (:296).  pgf_qp_sync waits twice, whatever the
+ * number of trials; PGF_LINE_SEARCH when no trial is accepted. */
+#define PGF_STEP_LINE_SEARCH 8u
 
 typedef struct pgf_solver *pgf_handle;
 typedef struct pgf_linsolver *pgf_ls_handle;
@@ -201,6 +211,20 @@ int pgf_qp_step(pgf_handle h, unsigned policy, double tau, int inertia_check, in
 /* enqueue-only variant for timing loops: no host sync, status checked by pgf_qp_sync */
 int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau);
 int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff);
+/* The line search of steps with PGF_STEP_LINE_SEARCH.  newton_tol: Params.newton_tol (params.py,
+ * default 1e-8, the handle's default too): a merit at or below it ends the search (newton.py:254,
+ * 281).  pgf_qp_line_search_stats: the last such step's accepted alpha (1 without a trial), the
+ * number of trials evaluated (0: merit0 <= newton_tol, newton.py:254-255; 30 on PGF_LINE_SEARCH),
+ * merit0 = 1/2 ||F(x, y)||^2 (:251-252), the slope F . dF d (:260-268) and all 30 trial merits of
+ * the ladder (:273-279; trial_merits may be NULL, as any other pointer).  PGF_NOT_READY before the
+ * first such step. */
+int pgf_qp_set_line_search(pgf_handle h, double newton_tol);
+/* (dx, dy) as the last settled step's update left them (dx rewritten where x - dx was clipped,
+ * step_solver.py:25-48).  After a step with PGF_STEP_LINE_SEARCH: the FULL direction, measured from
+ * the outer point (newton.py:248), which the search scaled by alpha.  Either pointer may be NULL. */
+int pgf_qp_get_direction(pgf_handle h, double *dx, double *dy);
+int pgf_qp_line_search_stats(pgf_handle h, double *alpha, int *trials, double *merit0, double *slope,
+                             double *trial_merits);
 /* ||F(z)||_2 of the UNSCALED residual (ImplicitFunc.value_at, implicit_func.py:150-161)
  * at the device point; host result, and optionally a device slot (RCCL all-gather input) */
 int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev);
@@ -572,6 +596,10 @@ int pgf_batch_debug_factor_kind(pgf_batch b);
  * enqueued); redone_steps -- steps enqueued with the previous |I|, |A| that were discarded and
  * enqueued again by pgf_qp_sync because the sizes had changed.  Either pointer may be NULL. */
 int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
+/* Device time (ms) of the last line-search stage -- the direction's images, k_ls_ladder,
+ * k_ls_finish -- of a step with PGF_STEP_LINE_SEARCH made while profiling was enabled
+ * (pgf_profile_enable); 0 before. */
+int pgf_debug_line_search_ms(pgf_handle h, double *ms);
 /* Counters of the resident Gram matrix G = J^T J of the condensed dense factorisation (tests;
  * DESIGN.md 4.0, PGF_CONDENSED_GRAM): builds -- how often G was formed for this handle (at most
  * once per derivative upload); factorisations_with_gram -- condensed factorisations that took

@@ -8,7 +8,7 @@ reference's default step controller on top of either.  All arithmetic is in ``li
 there is no CPU fallback.
 """
 
-from .errors import EvalError, LinearSolverError, StepSolverError  # noqa: F401
+from .errors import EvalError, LinearSolverError, LineSearchError, StepSolverError  # noqa: F401
 from .params import (  # noqa: F401
     ActiveSetType,
     LinearSolverType,

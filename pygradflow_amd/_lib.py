@@ -15,14 +15,17 @@ import sys
 
 import numpy as np
 
-from .errors import LinearSolverError
+from .errors import LinearSolverError, LineSearchError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpgf_hip.so")
 
 PGF_OK, PGF_SINGULAR, PGF_INERTIA, PGF_INVALID, PGF_NOT_READY, PGF_HIP_ERROR = 0, 1, 2, 3, 4, 100
+PGF_LINE_SEARCH = 5
 PGF_HOST, PGF_DEVICE = 0, 1
 STEP_RECOMPUTE_MASK, STEP_REFACTOR, STEP_REFACTOR_ON_CHANGE = 1, 2, 4
+STEP_LINE_SEARCH = 8
+LS_TRIALS = 30
 CREATE_SPARSE = 1
 BATCH_WIDE_BAND = 1
 BATCH_BAND_CTL = 2
@@ -75,6 +78,10 @@ SIGNATURES = {
     "pgf_qp_step": (C.c_int, [_h, C.c_uint, C.c_double, C.c_int, _ip, _dp]),
     "pgf_qp_step_async": (C.c_int, [_h, C.c_uint, C.c_double]),
     "pgf_qp_sync": (C.c_int, [_h, _ip, _dp]),
+    "pgf_qp_set_line_search": (C.c_int, [_h, C.c_double]),
+    "pgf_qp_get_direction": (C.c_int, [_h, _dp, _dp]),
+    "pgf_qp_line_search_stats": (C.c_int, [_h, _dp, _ip, _dp, _dp, _dp]),
+    "pgf_debug_line_search_ms": (C.c_int, [_h, _dp]),
     "pgf_qp_residual_norm": (C.c_int, [_h, _dp, C.c_void_p]),
     "pgf_qp_measures": (C.c_int, [_h, C.c_double, _dp]),
     "pgf_stream": (C.c_int, [_h, C.POINTER(C.c_void_p)]),
@@ -218,6 +225,8 @@ def check(rc, handle=None, what="", batch=None):
     text = f"{what}: {msg}" if what else msg
     if rc in (PGF_SINGULAR, PGF_INERTIA):
         raise LinearSolverError(text or ("singular matrix" if rc == PGF_SINGULAR else "Invalid matrix inertia"))
+    if rc == PGF_LINE_SEARCH:
+        raise LineSearchError("Line search failed to converge")
     if rc == PGF_INVALID:
         raise ValueError(text or "invalid argument")
     raise RuntimeError(f"{text} (status {rc})")

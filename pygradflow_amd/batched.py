@@ -143,6 +143,10 @@ class BatchedDeviceNewton:
         self.lo, self.hi = shard_range(num_instances, world, rank)
         self.count = self.hi - self.lo
         self.kind = enum_name(newton_type) if not isinstance(newton_type, str) else newton_type
+        if self.kind == "Globalized" and not sequential:
+            raise NotImplementedError(
+                "Globalized: not in the device batch (its line search is per handle); "
+                "sequential=True runs the instances through their own handles")
         self.policy = _POLICY_BITS[self.kind]
         self.tau = math.nan if tau is None else float(tau)
         self.dt, self.rho = float(dt), float(rho)

@@ -17,6 +17,7 @@ ARCH = "gfx950"
 SOURCES = [
     ("pgf_kernels.hip", ["-ffp-contract=off"]),
     ("pgf_sparse.hip", ["-ffp-contract=off"]),
+    ("pgf_line_search.hip", ["-ffp-contract=off"]),
     ("pgf_band_wide.hip", []),
     ("pgf_border.hip", ["-ffp-contract=off"]),
     ("pgf_ldlt.hip", ["-DPGF_RECIP_ONE_STEP"] if os.environ.get("PGF_BUILD_RECIP1") else []),
@@ -29,6 +30,7 @@ SOURCES = [
     ("pgf_api_guard.hip", ["-ffp-contract=off"]),
     ("pgf_api_step.hip", ["-ffp-contract=off"]),
     ("pgf_api_band.hip", ["-ffp-contract=off"]),
+    ("pgf_api_line_search.hip", ["-ffp-contract=off"]),
     ("pgf_api_unsym.hip", ["-ffp-contract=off"]),
     ("pgf_api_batch.hip", ["-ffp-contract=off"]),
     ("pgf_api_band_batch.hip", ["-ffp-contract=off"]),

@@ -119,6 +119,7 @@ int pgf_destroy(pgf_handle h) {
   lu_free(h->unsym.ulu);
   if (h->h_meas) (void)hipHostFree(h->h_meas);
   band_free(h);
+  ls_free(h);
   ldlt_free(h->fac);
   for (hipEvent_t e : h->prof.pool) (void)hipEventDestroy(e);
   for (auto &sp : h->prof.update_spans) {
@@ -137,6 +138,7 @@ int pgf_destroy(pgf_handle h) {
 // new derivatives: what was computed from the matrices in HBM goes (their norms, the Gram matrix)
 static void invalidate_derivs(pgf_handle h) {
   h->guard.norms_valid = false;
+  h->ls.hat_fresh = false;
   h->cond.gram_valid = false;
   h->cond.cond_since_upload = 0;
 }
@@ -172,6 +174,7 @@ int pgf_set_outer(pgf_handle h, const double *xhat, const double *yhat, double d
   launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   h->outer_set = true;
   h->mask_set = false;
+  h->ls.hat_fresh = false;
   invalidate_factor(h);
   return PGF_OK;
 }

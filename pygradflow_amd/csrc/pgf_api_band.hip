@@ -624,6 +624,7 @@ int pgf_sparse_set_values(pgf_handle h, const double *Hval, const double *Jval) 
   if ((rc = up(h, h->sp.Jval, Jval, (size_t)h->sp.nnzJ * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->sp.values_set = true;
+  h->ls.hat_fresh = false;
   h->derivs_set = true;
   invalidate_factor(h);
   return PGF_OK;

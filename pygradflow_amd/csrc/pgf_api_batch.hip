@@ -388,6 +388,8 @@ int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   if (!b) return PGF_INVALID;
   if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
+  if (policy & PGF_STEP_LINE_SEARCH)
+    return bfail(b, PGF_INVALID, "batch: PGF_STEP_LINE_SEARCH is served by single handles only");
   (void)hipSetDevice(b->device);
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;

@@ -1,7 +1,8 @@
 // What the translation units behind the C ABI share -- pgf_api.hip: the dense Symmetric handle's
 // lifecycle, uploads, index sets and linear solves; pgf_api_factor.hip: its factorisation (condensed
 // order, Gram matrix); pgf_api_guard.hip: its accuracy guard; pgf_api_step.hip: the Newton step and
-// the device-resident LQ mode; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the
+// the device-resident LQ mode; pgf_api_line_search.hip: the Globalized policy's line search around that
+// step; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the
 // unsymmetric formulations; pgf_api_batch.hip: the batch driver; pgf_api_aux.hip: profiling read-out,
 // the stand-alone linear solver and the pgf_debug_* hooks -- the handles, the error helpers and
 // the small interfaces between the files.
@@ -137,6 +138,26 @@ struct pgf_solver {
       fac_head = 0;
     }
   } flight;
+
+  // ---- the Globalized policy's line search (pgf_api_line_search.hip; allocated by the first step
+  // that carries PGF_STEP_LINE_SEARCH) ----
+  struct {
+    double newton_tol = 1e-8;  // Params().newton_tol (pgf_qp_set_line_search)
+    // g, c at the outer point (hat_fresh: current for the outer step, the matrices and rho as they
+    // are); the direction's images u = A dx, v = Q dx + A'(rho u + dy); zeros in place of q and b;
+    // the ladder's partial sums; the block the host reads (pgf_line_search.h) and its pinned mirror
+    double *ghat = nullptr, *chat = nullptr, *u = nullptr, *v = nullptr, *zero = nullptr, *red = nullptr,
+           *blk = nullptr, *h_blk = nullptr;
+    bool hat_fresh = false;
+    bool want = false;    // the step being enqueued or in flight carries the bit
+    // the handle's (x, y, g, c) name the outer point's vectors, (ox, oy, og, oc) the device
+    // point's, until the step in flight is settled (ls_enter / ls_leave)
+    bool active = false;
+    double *ox = nullptr, *oy = nullptr, *og = nullptr, *oc = nullptr;
+    bool have_stats = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the stage while profiling is enabled
+    double stage_ms = 0.0;
+  } ls;
 
   // ---- counters read only by the pgf_debug_* hooks (pgf_api_aux.hip, pgf_api_unsym.hip) ----
   struct {
@@ -276,6 +297,12 @@ void band_kept_resolve(pgf_handle h);                          // finish_factor_
 bool band_split_default();                                     // pgf_create (PGF_BW_SPLIT)
 void band_eval(pgf_handle h);                                  // qp_eval
 void band_measures_eval(pgf_handle h);                         // pgf_qp_measures
+
+// ---- the Globalized policy's line search (pgf_api_line_search.hip) -------------------------------
+void ls_free(pgf_handle h);                 // pgf_destroy
+int ls_enter(pgf_handle h);                 // pgf_qp_step_async, in front of enqueue_qp_step
+void ls_leave(pgf_handle h);                // pgf_qp_step_async (on an error), pgf_qp_sync
+int ls_search(pgf_handle h, double *diff);  // pgf_qp_sync, behind the settled step
 
 // ---- the unsymmetric formulations (pgf_api_unsym.hip), for handles with h->unsym.form != 0 -------------
 // Each is the unsymmetric half of the dense function named beside it, which hands over in one line.

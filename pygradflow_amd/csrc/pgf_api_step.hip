@@ -72,7 +72,8 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   h->guard.rs_skipped = h->fac.factored && h->guard.factor_clean;  // (a step that factorises is always checked)
   // the tail of a qp step in fewer launches (same values): s_y in the step update, the row passes
   // over J and H in one launch, the sums, the H pass's epilogue and the residual in another
-  const bool ahead = eval_ahead() && h->qp_mode && h->guard.refine_mode && !h->guard.rs_skipped;
+  // (a step with PGF_STEP_LINE_SEARCH: the point after it is not x - d, nothing is evaluated ahead)
+  const bool ahead = eval_ahead() && h->qp_mode && h->guard.refine_mode && !h->guard.rs_skipped && !h->ls.want;
   const bool fused_tail = ahead && step_fused();
   StepCondY cy{nullptr, nullptr, nullptr, 0.0, 0};
   if (!h->fac.factored) {
@@ -215,6 +216,7 @@ int pgf_qp_set_vectors(pgf_handle h, const double *q, const double *b) {
   if ((rc = up(h, h->b, b, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
+  h->ls.hat_fresh = false;
   h->unsym.h_has_lag_only = true;
   return PGF_OK;
 }
@@ -236,6 +238,7 @@ int pgf_qp_set_problem(pgf_handle h, const double *Q, int64_t ldq, const double 
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
+  h->ls.hat_fresh = false;
   h->unsym.h_has_lag_only = true;
   return PGF_OK;
 }
@@ -243,6 +246,7 @@ int pgf_qp_set_problem(pgf_handle h, const double *Q, int64_t ldq, const double 
 int pgf_qp_set_point(pgf_handle h, const double *x, const double *y) {
   if (!h) return PGF_INVALID;
   if ((h->n && !x) || (h->m && !y)) return fail(h, PGF_INVALID, "null argument");
+  if (h->step_pending && h->ls.active) return fail(h, PGF_NOT_READY, "pgf_qp_sync the line-search step first");
   (void)hipSetDevice(h->device);
   int rc;
   if ((rc = up(h, h->x, x, h->n * sizeof(double)))) return rc;
@@ -257,6 +261,8 @@ int pgf_qp_set_point(pgf_handle h, const double *x, const double *y) {
 // off the production path), so that the point read is never that of a discarded step
 static int settle_spec(pgf_handle h, bool *redone);
 static int settle_before_read(pgf_handle h) {
+  // (a step with PGF_STEP_LINE_SEARCH in flight: the handle's vectors name the outer point's)
+  if (h->step_pending && h->ls.active) return fail(h, PGF_NOT_READY, "pgf_qp_sync the line-search step first");
   if (!h->step_pending || !h->flight.spec_pending) return PGF_OK;  // (never speculative on a banded handle)
   HIPCHK(h, hipStreamSynchronize(h->stream));
   bool redone;
@@ -281,6 +287,18 @@ int pgf_qp_get_mask(pgf_handle h, uint8_t *mask) {
   (void)hipSetDevice(h->device);
   int rc;
   if ((rc = down(h, mask, h->mask, h->n))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PGF_OK;
+}
+
+int pgf_qp_get_direction(pgf_handle h, double *dx, double *dy) {
+  if (!h) return PGF_INVALID;
+  if (!h->point_set) return fail(h, PGF_NOT_READY, "pgf_qp_set_point first");
+  if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the step first");
+  (void)hipSetDevice(h->device);
+  int rc;
+  if (dx && (rc = down(h, dx, h->dx, h->n * sizeof(double)))) return rc;
+  if (dy && (rc = down(h, dy, h->dy, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return PGF_OK;
 }
@@ -317,7 +335,7 @@ static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_ou
     if (changed_out) *changed_out = 1;
     // a step enqueued with |A| = 0: its residual and reduced rhs in the same launch (newton_core_async
     // then enqueues neither; a step that is discarded and redone takes the launches of its own)
-    h->flight.front_done = spec && h->nA == 0 && step_fused();
+    h->flight.front_done = spec && h->nA == 0 && step_fused() && !h->ls.want;  // (its rhs reads the outer point)
     if (h->flight.front_done)
       launch_mask_compact_rhs(s, h->n, h->m, h->nI, use_tau, h->lamb, f_x, f_x0, f_d, h->dt, h->fact, h->xhat,
                               h->yhat, h->x, h->y, h->g, h->c, h->slb, h->sub, h->mask, h->idxI, h->idxA, h->pos,
@@ -367,6 +385,7 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
   int rc;
   if ((rc = qp_ready(h))) return rc;
   if (!(dt > 0.0) || !(rho > 0.0)) return fail(h, PGF_INVALID, "dt and rho must be positive");
+  if (h->step_pending && h->ls.active) return fail(h, PGF_NOT_READY, "pgf_qp_sync the line-search step first");
   (void)hipSetDevice(h->device);
   const bool one = step_fused() && !h->sparse;  // the copies and the scaling in one launch
   if (!one) {
@@ -385,6 +404,7 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
   else
     launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   h->mask_set = false;
+  h->ls.hat_fresh = false;
   invalidate_factor(h);
   return PGF_OK;
 }
@@ -401,6 +421,8 @@ static int enqueue_qp_step(pgf_handle h) {
   h->fac.defer_status = false;
   h->flight.step_took_inject = armed && !h->fac.inject_helper_failure;
   if (rc) return rc;
+  // (PGF_STEP_LINE_SEARCH: the point moves behind the line search, ls_search; g, c stay current)
+  if (h->ls.want) return h->sparse ? PGF_OK : down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double));
   swap_point(h);  // (x, y) <- (xn, yn)
   h->eval_fresh = false;
   // g and c at the new point, enqueued NOW: the next step needs them first thing, and behind the
@@ -421,7 +443,7 @@ static int enqueue_qp_step(pgf_handle h) {
 // helpers failed their hand-over): the step in flight is discarded and enqueued again from the
 // point it started at.  Each path does the bookkeeping of its own in front of this.
 static int redo_step(pgf_handle h) {
-  swap_point(h);
+  if (!h->ls.want) swap_point(h);
   h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
   return enqueue_qp_step(h);
 }
@@ -461,23 +483,38 @@ int pgf_qp_step_async(pgf_handle h, unsigned policy, double tau) {
   if ((rc = qp_ready(h))) return rc;
   if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the previous step first");
   (void)hipSetDevice(h->device);
+  const bool ls = (policy & PGF_STEP_LINE_SEARCH) != 0;
+  if (ls && (policy & ~PGF_STEP_LINE_SEARCH) != (PGF_STEP_RECOMPUTE_MASK | PGF_STEP_REFACTOR))
+    return fail(h, PGF_INVALID,
+                "PGF_STEP_LINE_SEARCH goes with PGF_STEP_RECOMPUTE_MASK | PGF_STEP_REFACTOR only");
+  if (ls && h->unsym.form)
+    return fail(h, PGF_INVALID, "PGF_STEP_LINE_SEARCH: the Symmetric formulation only");
   if (h->unsym.form) return unsym_qp_step_async(h, policy, tau);
+  // an error on the way: the handle's vectors are its own again, no step carries the bit
+  auto drop = [h](int code) {
+    ls_leave(h);
+    h->ls.want = false;
+    return code;
+  };
+  h->ls.want = ls;
   h->flight.front_done = false;
   qp_eval(h);
   if (policy & PGF_STEP_RECOMPUTE_MASK) {
-    // Full (newton.py:83-89): the mask is always re-set, which drops the factor;
-    // ActiveSet (:203-215): only when it differs elementwise.
+    // Full (newton.py:83-89), Globalized (:239-242): the mask is always re-set, which drops the
+    // factor; ActiveSet (:203-215): only when it differs elementwise.
     const bool force = (policy & PGF_STEP_REFACTOR) != 0;
-    if ((rc = qp_refresh_mask(h, tau, force, nullptr, true))) return rc;
+    if ((rc = qp_refresh_mask(h, tau, force, nullptr, true))) return drop(rc);
   }
-  if (!h->mask_set) return fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first");
+  if (!h->mask_set) return drop(fail(h, PGF_NOT_READY, "no active set: pgf_qp_update_active_set first"));
   if (policy & PGF_STEP_REFACTOR) invalidate_factor(h);
-  if ((rc = enqueue_qp_step(h))) return rc;
+  if (ls && (rc = ls_enter(h))) return drop(rc);
+  if ((rc = enqueue_qp_step(h))) return drop(rc);
   h->step_pending = true;
   return PGF_OK;
 }
 
-int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
+// the Newton step in flight, settled: its status, the redo paths, the accuracy guard
+static int qp_sync_step(pgf_handle h, int *n_neg, double *diff) {
   if (!h) return PGF_INVALID;
   if (!h->step_pending) return fail(h, PGF_NOT_READY, "no step pending");
   h->step_pending = false;
@@ -513,11 +550,24 @@ int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
   }
   if (st < 0) return hip_fail(h, e, "step");
   if (st == 1) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in LDL^T of the KKT matrix");
-  if ((rc = chain_recover(h, true))) return rc;
-  if ((rc = refine_if_needed(h, true))) return rc;
+  // (swapped: (x, y) is already the new point -- not with PGF_STEP_LINE_SEARCH, whose point moves later)
+  if ((rc = chain_recover(h, !h->ls.want))) return rc;
+  if ((rc = refine_if_needed(h, !h->ls.want))) return rc;
   if (n_neg) *n_neg = h->fac.n_neg;
   if (diff) *diff = h->h_scal[0];
   return PGF_OK;
+}
+
+// With PGF_STEP_LINE_SEARCH the settled step is the direction: the line-search launches follow it
+// and one further wait brings their block -- a fixed number of waits whatever the trial count.
+int pgf_qp_sync(pgf_handle h, int *n_neg, double *diff) {
+  const bool ls = h && h->step_pending && h->ls.want;
+  int rc = qp_sync_step(h, n_neg, diff);
+  if (!ls) return rc;
+  ls_leave(h);
+  h->ls.want = false;
+  if (rc) return rc;
+  return ls_search(h, diff);
 }
 
 int pgf_qp_step(pgf_handle h, unsigned policy, double tau, int inertia_check, int *n_neg,
@@ -536,6 +586,7 @@ int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev) {
   if (!h) return PGF_INVALID;
   int rc;
   if ((rc = qp_ready(h))) return rc;
+  if (h->step_pending && h->ls.active) return fail(h, PGF_NOT_READY, "pgf_qp_sync the line-search step first");
   (void)hipSetDevice(h->device);
   qp_eval(h);
   // (the norm also reaches norm_out_dev from the launch itself).  Between pgf_qp_step_async and

@@ -29,6 +29,16 @@ class StepSolverError(_RefStepSolverError):
     """The step solver failed, e.g. because the Newton matrix is (near) singular."""
 
 
+class LineSearchError(Exception):
+    """No trial step length of the Globalized policy's Armijo line search was accepted.  The
+    reference raises a bare ``Exception("Line search failed to converge")``
+    (``pygradflow/newton.py:291-292``), which no step controller catches as a failed step: this is
+    NOT a ``StepSolverError``."""
+
+    def __init__(self, msg="Line search failed to converge"):
+        super().__init__(msg)
+
+
 class EvalError(_RefEvalError):
     """A problem callback failed or returned non-finite values at ``x`` (reference
     ``pygradflow/eval.py:18-21``); step controllers reject the step and halve ``dt``

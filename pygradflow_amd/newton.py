@@ -20,7 +20,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .errors import LinearSolverError, StepSolverError
+from .errors import LinearSolverError, LineSearchError, StepSolverError  # noqa: F401
 from .params import enum_name
 from .sparse import MAX_BANDWIDTH, BandPlan, apply_band_split, border_key
 from .step_solver import DENSE_LIMIT, POOL, HipStepSolver, residency_key, same_key
@@ -172,6 +172,8 @@ _POLICY_BITS = {
     "Simplified": 0,
     "Full": _lib.STEP_RECOMPUTE_MASK | _lib.STEP_REFACTOR,
     "ActiveSet": _lib.STEP_RECOMPUTE_MASK | _lib.STEP_REFACTOR_ON_CHANGE,
+    # the Full step solved at the outer point, then the Armijo line search in one launch
+    "Globalized": _lib.STEP_RECOMPUTE_MASK | _lib.STEP_REFACTOR | _lib.STEP_LINE_SEARCH,
 }
 
 
@@ -181,10 +183,15 @@ class DeviceNewton:
     ``DeviceNewton(problem, newton_type, x_hat, y_hat, dt, rho, tau)`` mirrors
     ``newton_method(...)``; ``step()`` advances the device-resident point and returns
     ``(diff, n_neg)``; ``point()`` / ``mask()`` copy results out for checking.
+
+    ``"Globalized"`` (dense Symmetric and banded handles): ``step()`` raises ``LineSearchError``
+    when no trial step length is accepted -- the point has not moved and the handle stays usable;
+    ``newton_tol`` is ``Params.newton_tol`` (None: 1e-8, its default); ``line_search()`` reports
+    the last step's search.
     """
 
     def __init__(self, problem, newton_type, x_hat, y_hat, dt, rho, tau=None, device=0,
-                 start=None, step_solver_type="Symmetric"):
+                 start=None, step_solver_type="Symmetric", newton_tol=None):
         _lib.require_gpu()
         self._lib = _lib.load()
         self.problem = problem
@@ -213,6 +220,9 @@ class DeviceNewton:
         # on every dense handle, also to Symmetric: whatever its last user left does not matter
         if not self.sparse:
             _lib.check(lib.pgf_set_formulation(h, self.formulation), h, "pgf_set_formulation")
+        # (on every handle: whatever its last user left does not matter)
+        self.newton_tol = 1e-8 if newton_tol is None else float(newton_tol)
+        _lib.check(lib.pgf_qp_set_line_search(h, self.newton_tol), h, "pgf_qp_set_line_search")
         lb, ub = _lib.as_f64(problem.var_lb), _lib.as_f64(problem.var_ub)
         _lib.check(lib.pgf_set_bounds(h, _lib.dptr(lb), _lib.dptr(ub)), h, "pgf_set_bounds")
         key = residency_key(problem)
@@ -303,6 +313,38 @@ class DeviceNewton:
         _lib.check(self._lib.pgf_qp_sync(self._hd.h, C.byref(n_neg), C.byref(diff)), self._hd.h,
                    "pgf_qp_sync")
         return diff.value, n_neg.value
+
+    def line_search(self):
+        """The last Globalized step's line search: dict(alpha, trials, merit0, slope, trial_merits)
+        -- ``trials`` 0: merit0 was within ``newton_tol``, the full step without a trial; 30 and a
+        ``LineSearchError`` from ``step()``: none accepted (``pgf_qp_line_search_stats``)."""
+        a, k, m0, sl = C.c_double(0.0), C.c_int(0), C.c_double(0.0), C.c_double(0.0)
+        tm = np.empty(_lib.LS_TRIALS)
+        _lib.check(self._lib.pgf_qp_line_search_stats(self._hd.h, C.byref(a), C.byref(k), C.byref(m0),
+                                                      C.byref(sl), _lib.dptr(tm)),
+                   self._hd.h, "pgf_qp_line_search_stats")
+        return dict(alpha=a.value, trials=k.value, merit0=m0.value, slope=sl.value, trial_merits=tm)
+
+    def direction(self):
+        """``(dx, dy)`` of the last step as its update left them; after a Globalized step the full
+        direction the line search scaled (``pgf_qp_get_direction``)."""
+        dx, dy = np.empty(self.n), np.empty(self.m)
+        _lib.check(self._lib.pgf_qp_get_direction(self._hd.h, _lib.dptr(dx), _lib.dptr(dy)),
+                   self._hd.h, "pgf_qp_get_direction")
+        return dx, dy
+
+    def line_search_ms(self):
+        """Device time of the last line-search stage, measured while ``profile(...)`` is on
+        (``pgf_debug_line_search_ms``)."""
+        ms = C.c_double(0.0)
+        _lib.check(self._lib.pgf_debug_line_search_ms(self._hd.h, C.byref(ms)), self._hd.h)
+        return ms.value
+
+    def step_stats(self):
+        """(host_syncs, redone_steps) of the handle's qp steps (``pgf_debug_step_stats``)."""
+        a, b = C.c_int(0), C.c_int(0)
+        _lib.check(self._lib.pgf_debug_step_stats(self._hd.h, C.byref(a), C.byref(b)), self._hd.h)
+        return a.value, b.value
 
     def point(self):
         x, y = np.empty(self.n), np.empty(self.m)
