@@ -281,50 +281,77 @@ __device__ __forceinline__ double ld_agent(const double *p) {
 }
 
 // inverse of the unit-lower 64 x 64 diagonal tile g of the block (rows / columns from b0), by
-// the four wavefronts [4 slot, 4 slot + 4) of the workgroup; every thread of the workgroup
-// calls this (barriers), `live` says whether its wavefront group has a tile.  Blocked by 16:
+// the four wavefronts [4 slot, 4 slot + 4) of the workgroup.  Blocked by 16:
 // wavefront v inverts the 16 x 16 diagonal sub-tile v by substitution (lane c <-> column c),
 // then wavefront q < 3 builds block column q of the inverse top down,
 //   X_pq = -D_p sum_{r = q}^{p-1} L_pr X_rq   (D_p = inv(L_pp), X_qq = D_q),
 // with MFMA: a 16 x 16 accumulator (row (l >> 4) + 4 reg, column l & 15) IS the B operand
 // of the next four k-steps, so the X_rq stay in registers.  Stored as inv and as its
 // transpose, [tile][row][64]: forward and backward solves both read coalesced rows.
-__device__ __forceinline__ void invert_tile(unsigned char *smem, const double *K, int64_t ldk,
-                                            int b0, int nbw, bool live, double *__restrict__ Linv,
-                                            double *__restrict__ LinvT) {
-  // wave: uniform per wavefront -> scalar register, role tests and tile numbers on the SALU
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, l4 = lane >> 4, v = wave & 3;
-  double(*Lg)[C_LD] = reinterpret_cast<double(*)[C_LD]>(smem + (size_t)(wave >> 2) * 64 * C_LD * 8);
-  if (live) {
-    for (int idx = tid & 255; idx < 64 * 32; idx += 256) {
-      const int row = idx >> 5, c2 = (idx & 31) * 2;
-      double2_t t = (double2_t){0.0, 0.0};
-      if (row < nbw) {
-        const double *src = K + (int64_t)(b0 + row) * ldk + b0 + c2;
-        if (c2 + 1 < row) t = *reinterpret_cast<const double2_t *>(src);
-        else if (c2 < row) t.x = *src;
-      }
-      if (c2 == row) t.x = 1.0;
-      if (c2 + 1 == row) t.y = 1.0;
-      *reinterpret_cast<double2_t *>(&Lg[row][c2]) = t;
+// Three pieces: the unit-lower copy Lg in LDS, the inversion in place, the two stores.  (The
+// chain's own last tile takes the same sums in another order of time: tail_column_step.)
+
+// Lg <- the tile's unit-lower part from K (zeros above the diagonal, ones on it, identity
+// beyond nbw columns); thread t of nt
+__device__ __forceinline__ void inv_fill_global(double (*Lg)[C_LD], const double *K, int64_t ldk,
+                                                int b0, int nbw, int t, int nt) {
+  for (int idx = t; idx < 64 * 32; idx += nt) {
+    const int row = idx >> 5, c2 = (idx & 31) * 2;
+    double2_t v = (double2_t){0.0, 0.0};
+    if (row < nbw) {
+      const double *src = K + (int64_t)(b0 + row) * ldk + b0 + c2;
+      if (c2 + 1 < row) v = *reinterpret_cast<const double2_t *>(src);
+      else if (c2 < row) v.x = *src;
     }
+    if (c2 == row) v.x = 1.0;
+    if (c2 + 1 == row) v.y = 1.0;
+    *reinterpret_cast<double2_t *>(&Lg[row][c2]) = v;
   }
-  __syncthreads();
-  if (live && lane < 16) {
-    double y[16];
+}
+
+// D_t = inverse of the unit-lower 16 x 16 diagonal sub-tile t of the tile in Ls (only its entries
+// below the diagonal are read), by substitution: lane c < 16 <-> column c; written to the same
+// place of Dd (which may be Ls itself: a row is stored once no later step reads it, see below).
+// Fifteen dependent steps of a few FMAs each, each behind the LDS reads of its column: from step
+// INV_PF on, column c + 1 is fetched while column c is applied (the kernels have no registers
+// for two whole columns beside y in the first steps).  Row c is final after step c - 1 and stored
+// at once: no later step reads it.
+#define INV_PF 5
+__device__ __forceinline__ void inv_diag16(const double (*Ls)[C_LD], double (*Dd)[C_LD], int t, int lane) {
+  if (lane < 16) {
+    double y[16], cur[16], nxt[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) y[j] = (j == lane) ? 1.0 : 0.0;
 #pragma unroll
-    for (int t = 0; t < 15; ++t) {
-      const double yt = y[t];
+    for (int c = 0; c < 15; ++c) {
+      if (c <= INV_PF) {
 #pragma unroll
-      for (int j = t + 1; j < 16; ++j) y[j] = fma(-yt, Lg[16 * v + j][16 * v + t], y[j]);
+        for (int j = c + 1; j < 16; ++j) cur[j] = Ls[16 * t + j][16 * t + c];
+      }
+      if (c >= INV_PF) {
+#pragma unroll
+        for (int j = c + 2; j < 16; ++j) nxt[j] = Ls[16 * t + j][16 * t + c + 1];
+      }
+      const double yc = y[c];
+      Dd[16 * t + c][16 * t + lane] = yc;
+#pragma unroll
+      for (int j = c + 1; j < 16; ++j) y[j] = fma(-yc, cur[j], y[j]);
       __builtin_amdgcn_sched_barrier(0);
-    }
+      if (c >= INV_PF) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) Lg[16 * v + j][16 * v + lane] = y[j];
+        for (int j = c + 2; j < 16; ++j) cur[j] = nxt[j];
+      }
+    }
+    Dd[16 * t + 15][16 * t + lane] = y[15];
   }
+}
+
+// Lg (complete, behind a barrier) <- its inverse, in place.  Every thread of the workgroup calls
+// this (three barriers, the last one behind the inverse's last LDS store); `live` says whether
+// the thread's wavefront is one of the tile's four, v = its number among them.
+__device__ __forceinline__ void inv_lds(double (*Lg)[C_LD], bool live, int v, int lane) {
+  const int l15 = lane & 15, l4 = lane >> 4;
+  if (live) inv_diag16(Lg, Lg, v, lane);
   __syncthreads();
   double4_t Xo[3];
   if (live) {
@@ -344,14 +371,95 @@ __device__ __forceinline__ void invert_tile(unsigned char *smem, const double *K
     }
   }
   __syncthreads();
-  if (live) {
-    double *o = Linv + (size_t)(b0 / 64) * 4096;
-    double *ot = LinvT + (size_t)(b0 / 64) * 4096;
-    for (int idx = tid & 255; idx < 64 * 64; idx += 256) {
-      const int row = idx >> 6, col = idx & 63;
-      o[idx] = Lg[row][col];
-      ot[idx] = Lg[col][row];
+}
+
+// the inverse in Lg -> Linv and LinvT of tile b0 / 64; thread t of nt
+__device__ __forceinline__ void inv_store(const double (*Lg)[C_LD], int b0, double *__restrict__ Linv,
+                                          double *__restrict__ LinvT, int t, int nt) {
+  double *o = Linv + (size_t)(b0 / 64) * 4096;
+  double *ot = LinvT + (size_t)(b0 / 64) * 4096;
+  for (int idx = t; idx < 64 * 64; idx += nt) {
+    const int row = idx >> 6, col = idx & 63;
+    o[idx] = Lg[row][col];
+    ot[idx] = Lg[col][row];
+  }
+}
+
+// ---- the chain's own inverse of its block's LAST tile (chain_body, PGF_CHAIN_TAIL), pipelined
+// with the tile's elimination.  Column block t of the factored tile in M[0..63] is final once
+// chain_a_plus has eliminated it, so the same sums as above can be taken apart by the column block
+// they read: wavefront q + 1 (q < 3; never wavefront 0's SIMD) owns block column q of the inverse
+// and, as soon as column block t >= q is final, forms
+//   D_t by substitution (each of the three for itself: no hand-over between wavefronts),
+//   X_tq = D_q (t == q) or -D_t S_t (S_t is complete: its last term came with column block t - 1),
+//   S_p += L_pt X_tq for every p > t       (S_p = sum_{r = q}^{p-1} L_pr X_rq, r ascending)
+// -- per entry invert_tile's operations in invert_tile's order.  Between two calls everything
+// lives in the wavefront's own 64 rows of M (rows 64 (q + 1) ..: free, nothing lies below a last
+// tile), laid out like the tile: D_t at block (t, t), X_tq and the unfinished S_p at block (., q).
+// After the call for t = 3 those rows hold block column q of the inverse (and D_3 at (3, 3)).
+__device__ __forceinline__ void tail_column_step(double (*M)[C_LD], int t, int q, int lane) {
+  if (t < q) return;
+  // (laundered here: no address of this function is formed ahead of the call and kept alive
+  // across the eliminations of the sub-panels in front, cf. chain_body)
+  asm volatile("" : "+v"(lane));
+  double(*P)[C_LD] = M + 64 * (q + 1);
+  const int l15 = lane & 15, l4 = lane >> 4;
+  inv_diag16(M, P, t, lane);
+  __builtin_amdgcn_wave_barrier();  // (LDS serves a wavefront's accesses in order)
+  double4_t X;
+  if (t == q) {
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) X[rr] = P[16 * q + 4 * rr + l4][16 * q + l15];
+  } else {
+    double4_t S;
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) S[rr] = P[16 * t + l4 + 4 * rr][16 * q + l15];
+    X = (double4_t){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      X = __builtin_amdgcn_mfma_f64_16x16x4f64(-P[16 * t + l15][16 * t + 4 * rr + l4], S[rr], X, 0, 0, 0);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) P[16 * t + l4 + 4 * rr][16 * q + l15] = X[rr];
+  }
+#pragma unroll
+  for (int pp = 1; pp < 4; ++pp) {  // (unrolled: the three sums are independent)
+    const int p = t + pp;
+    if (p >= 4) break;
+    double4_t S = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (t > q) {
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) S[rr] = P[16 * p + l4 + 4 * rr][16 * q + l15];
     }
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      S = __builtin_amdgcn_mfma_f64_16x16x4f64(M[16 * p + l15][16 * t + 4 * rr + l4], X[rr], S, 0, 0, 0);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) P[16 * p + l4 + 4 * rr][16 * q + l15] = S[rr];
+  }
+}
+// entry (row, col) of the inverse the three wavefronts have left behind
+__device__ __forceinline__ double tail_entry(const double (*M)[C_LD], int row, int col) {
+  const int bc = col >> 4;
+  return (row >> 4) < bc ? 0.0 : M[64 * (min(bc, 2) + 1) + row][col];
+}
+
+// fill from global memory, invert, store: every thread of the workgroup calls this (barriers),
+// `live` says whether its wavefront group has a tile.  st (PGF_CHAIN_TIMING, else null): thread 0
+// stamps "tile in LDS" into st[1] and "inverse stored" (its own stores drained) into st[2].
+__device__ __forceinline__ void invert_tile(unsigned char *smem, const double *K, int64_t ldk,
+                                            int b0, int nbw, bool live, double *__restrict__ Linv,
+                                            double *__restrict__ LinvT, long long *st = nullptr) {
+  // wave: uniform per wavefront -> scalar register, role tests and tile numbers on the SALU
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double(*Lg)[C_LD] = reinterpret_cast<double(*)[C_LD]>(smem + (size_t)(wave >> 2) * 64 * C_LD * 8);
+  if (live) inv_fill_global(Lg, K, ldk, b0, nbw, tid & 255, 256);
+  __syncthreads();
+  if (st && tid == 0) st[1] = wall_clock64();
+  inv_lds(Lg, live, wave & 3, lane);
+  if (live) inv_store(Lg, b0, Linv, LinvT, tid & 255, 256);
+  if (st && tid == 0) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    st[2] = wall_clock64();
   }
   __syncthreads();  // Lg is refilled by the next pass
 }
@@ -437,19 +545,38 @@ __device__ __forceinline__ void helper_tiles(unsigned char *smem, double *K, int
   }
 }
 
+// The chain inverts its block's LAST diagonal tile itself (PGF_CHAIN_TAIL, `tail`) when that tile
+// is a full one: it still holds the tile in LDS when helper I could only begin to fetch it.  A
+// ragged last tile stays with helper I.  Chain and helper decide with this one test.
+__device__ __forceinline__ bool chain_takes_last_tile(int tail, int nb) {
+  return tail && nb > 0 && (nb & 63) == 0;
+}
+
+// PGF_CHAIN_TIMING: helper I's stamps live behind the chain's in the same buffer, three per
+// sub-panel: released from help_wait, tile in LDS, inverse stored
+#define CH_DBG_CHAIN 32
+#define CH_DBG_WORDS (CH_DBG_CHAIN + 12)
+
 // helper I (workgroup 16): the inverse of every sub-panel's diagonal tile as soon as it is final
+// (but for the one the chain takes itself)
 __device__ __forceinline__ void helper_inverses(unsigned char *smem, const double *K, int64_t ldk,
                                                 int c0, int nb, int *hc, int epoch, int *flags,
                                                 double *__restrict__ Linv,
-                                                double *__restrict__ LinvT) {
+                                                double *__restrict__ LinvT, int tail,
+                                                long long *__restrict__ dbg = nullptr) {
   const int tid = threadIdx.x, wave = tid >> 6;
   const int bend = c0 + nb, ns = (nb + 63) / 64;
+  const int mine = chain_takes_last_tile(tail, nb) ? ns - 1 : ns;
   if (tid == 0) help_check_xcc(hc, epoch, flags);
-  for (int s = 0; s < ns; ++s) {
+  for (int s = 0; s < mine; ++s) {
     const int b0 = c0 + 64 * s;
-    if (tid == 0) help_wait(hc + HC_STAMP + s, epoch, flags);
+    long long *st = (dbg && s < 4) ? dbg + CH_DBG_CHAIN + 3 * s : nullptr;
+    if (tid == 0) {
+      help_wait(hc + HC_STAMP + s, epoch, flags);
+      if (st) st[0] = wall_clock64();
+    }
     __syncthreads();
-    invert_tile(smem, K, ldk, b0, min(64, bend - b0), wave < 4, Linv, LinvT);
+    invert_tile(smem, K, ldk, b0, min(64, bend - b0), wave < 4, Linv, LinvT, st);
   }
 }
 
@@ -458,7 +585,8 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
                                            int nb, double *__restrict__ dvec,
                                            double *__restrict__ dinv, int *__restrict__ flags,
                                            double *__restrict__ Linv, double *__restrict__ LinvT,
-                                           long long *__restrict__ dbg, int *hc, int epoch) {
+                                           long long *__restrict__ dbg, int *hc, int epoch,
+                                           int tail) {
   double(*M)[C_LD] = reinterpret_cast<double(*)[C_LD]>(smem);
   double(*Wt)[C_WLD] = reinterpret_cast<double(*)[C_WLD]>(smem + CH_ROWS * C_LD * 8);
   double *dD = reinterpret_cast<double *>(smem + CH_ROWS * C_LD * 8 + 2 * 64 * C_WLD * 8);
@@ -469,11 +597,12 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int bend = c0 + nb;
   const int ns = (nb + 63) / 64;
+  const bool own_last = HELP && chain_takes_last_tile(tail, nb);  // (see "the last tile" below)
   // PGF_CHAIN_TIMING: phase stamps of the first sub-panel (100 MHz wall clock), thread 0
   int dbi = 0;
-#define CH_STAMP()                                               \
-  do {                                                           \
-    if (dbg && tid == 0 && dbi < 32) dbg[dbi++] = wall_clock64(); \
+#define CH_STAMP()                                                         \
+  do {                                                                     \
+    if (dbg && tid == 0 && dbi < CH_DBG_CHAIN) dbg[dbi++] = wall_clock64(); \
   } while (0)
   CH_STAMP();
   if (HELP && tid == 0) help_check_xcc(hc, epoch, flags);
@@ -556,6 +685,8 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
         if (!(early0 && sb == 0)) chain_a_plus(M, Wt + (sb & 1) * 64, dD, dI, s_bad, lane, sb, ncol);
       } else if (wave <= 3) {
         if (sb > 0 && 64 * (wave - 1) < own) chain_b_own(M, 64 * wave + lane, sb - 1, lane, dD, dI);
+        // the block's last tile: its inverse follows the elimination one step behind
+        if (own_last && s == ns - 1 && sb > 0) tail_column_step(M, sb - 1, wave - 1, lane);
       } else {
         // deferred tiles: diagonal (ti, tj), tj in [sb + 1, 3], of step sb - 1; lower (ti, tj),
         // tj in [sb, 3], of step sb - 2
@@ -596,6 +727,9 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
       __syncthreads();
     }
     if (s == 0) CH_STAMP();  // four steps done
+    // the block's last tile, full, with helpers: written back behind the loop, where its
+    // inverse is finished
+    if (own_last && s == ns - 1) break;
     // ---- trailing update inside the block (rows / columns below the tile, K-depth 64, A = -X
     // from M, B = X D^-1): the C tiles live in global memory; ALL of a wavefront's tiles are
     // fetched in one burst here, so that their latency (they were last written by another
@@ -854,8 +988,52 @@ __device__ __forceinline__ void chain_body(unsigned char *smem, double *K, int64
     CH_STAMP();  // in-block update done
   }
 
+  // ---- the last tile (own_last): factored in M[0..63]; wavefronts 1-3 have brought their block
+  // columns of its inverse as far as column block 2 allows (tail_column_step, rows 64.. of M).
+  // They finish them -- D_3 and one product -- while the other thirteen write the tile, D, 1/D
+  // and the flags back; then all sixteen store the inverse.  No stamp, no drained stores, no
+  // read from global memory: helper I could only begin all of that once this workgroup had
+  // ended.  Linv and LinvT are the same bits as invert_tile's.
+  if (own_last) {
+    int tl_ = threadIdx.x;
+    asm volatile("" : "+v"(tl_));
+    const int tid = tl_, lane = tid & 63;
+    const int cb = c0 + 64 * (ns - 1);
+    CH_STAMP();  // panel factored
+    if (wave >= 1 && wave <= 3) {
+      tail_column_step(M, 3, wave - 1, lane);
+    } else {
+      for (int p = wave == 0 ? tid : tid - 192; p < 64 * 64; p += NT - 192) {
+        const int row = p >> 6, c = p & 63;
+        if (c <= row) K[(int64_t)(cb + row) * ldk + cb + c] = M[row][c];
+      }
+      if (tid < 64) {
+        dvec[cb + tid] = dD[tid];
+        dinv[cb + tid] = dI[tid];
+      }
+      if (wave == 0) {
+        const unsigned long long negs = __ballot(dD[lane] < 0.0);
+        if (lane == 0) {
+          if (s_bad) atomicOr(&flags[0], 1);
+          const int neg = __popcll(negs);
+          if (neg) atomicAdd(&flags[1], neg);
+        }
+      }
+    }
+    __syncthreads();
+    CH_STAMP();  // inverted
+    double *o = Linv + (size_t)(cb / 64) * 4096;
+    double *ot = LinvT + (size_t)(cb / 64) * 4096;
+    for (int idx = tid; idx < 64 * 64; idx += NT) {
+      const int row = idx >> 6, col = idx & 63;
+      o[idx] = tail_entry(M, row, col);
+      ot[idx] = tail_entry(M, col, row);
+    }
+    if (dbg && tid == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (as helper I's last stamp)
+  }
+
   // ---- inverses of the block's unit-lower diagonal tiles (invert_tile), four wavefronts per
-  // tile; with helpers this is helper I's work
+  // tile; with helpers this is helper I's work (and, for the last tile, the code above)
   if (!HELP) {
     for (int g0 = 0; g0 < ns; g0 += CH_WAVES / 4) {
       const int g = g0 + (wave >> 2);

@@ -505,14 +505,14 @@ __global__ __launch_bounds__(64 * CH_WAVES) void k_diag_chain(double *K, int64_t
                                                            double *__restrict__ Linv,
                                                            double *__restrict__ LinvT,
                                                            long long *__restrict__ dbg, int *hc,
-                                                           int epoch) {
+                                                           int epoch, int tail) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   if (blockIdx.x == 0) {
-    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch);
+    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch, tail);
   } else if (HELP && blockIdx.x == 8) {
     helper_tiles(smem, K, ldk, c0, nb, dvec, hc, epoch, flags);
   } else if (HELP && blockIdx.x == 16) {
-    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
+    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT, tail, dbg);
   }
 }
 
@@ -573,11 +573,12 @@ __global__ __launch_bounds__(1024) void k_chain_update(double *K, int64_t ldk, i
                                                        double *__restrict__ Linv,
                                                        double *__restrict__ LinvT, int *hc,
                                                        int epoch, int N, int nrows,
-                                                       const UpdJobs jobs, const UpdVirt uv, int *ctr) {
+                                                       const UpdJobs jobs, const UpdVirt uv, int *ctr,
+                                                       int tail) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   const int b = (int)blockIdx.x;
   if (b == 0) {
-    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, nullptr, hc, epoch);
+    chain_body<HELP>(smem, K, ldk, c0, nb, dvec, dinv, flags, Linv, LinvT, nullptr, hc, epoch, tail);
     return;
   }
   if (HELP && b == 8) {
@@ -585,7 +586,7 @@ __global__ __launch_bounds__(1024) void k_chain_update(double *K, int64_t ldk, i
     return;
   }
   if (HELP && b == 16) {
-    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT);
+    helper_inverses(smem, K, ldk, c0, nb, hc, epoch, flags, Linv, LinvT, tail);
     return;
   }
   update_worker(smem, K, ldk, dvec, N, nrows, jobs, uv, ctr);
@@ -640,11 +641,11 @@ __global__ __launch_bounds__(1024) void k_chain_head(double *K, int64_t ldk, int
                                                      double *__restrict__ Linv,
                                                      double *__restrict__ LinvT,
                                                      long long *__restrict__ dbg, int *hc, int epoch,
-                                                     const LdltHead hw) {
+                                                     const LdltHead hw, int tail) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   const int b = (int)blockIdx.x;
   if (b == 0) {
-    chain_body<HELP>(smem, K, ldk, 0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch);
+    chain_body<HELP>(smem, K, ldk, 0, nb, dvec, dinv, flags, Linv, LinvT, dbg, hc, epoch, tail);
     return;
   }
   if (HELP && b == 8) {
@@ -652,7 +653,7 @@ __global__ __launch_bounds__(1024) void k_chain_head(double *K, int64_t ldk, int
     return;
   }
   if (HELP && b == 16) {
-    helper_inverses(smem, K, ldk, 0, nb, hc, epoch, flags, Linv, LinvT);
+    helper_inverses(smem, K, ldk, 0, nb, hc, epoch, flags, Linv, LinvT, tail, dbg);
     return;
   }
   if (HELP)
@@ -794,7 +795,7 @@ __global__ __launch_bounds__(256) void kb_virtual_diag(const BInst *__restrict__
 // chain per CU and a spinning helper could wait for a CU its own chain occupies.
 template <bool HELP>
 __global__ __launch_bounds__(1024) void kb_diag_chain(const BInst *__restrict__ tab, int B, int Bp, int m,
-                                                      int c0, int epoch) {
+                                                      int c0, int epoch, int tail) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   // roles: [0, Bp) chains, [Bp, 2 Bp) helpers T, [2 Bp, 3 Bp) helpers I; Bp = B rounded up to 8,
   // so that the three workgroups of an instance land on one XCD (ids equal modulo 8)
@@ -807,11 +808,11 @@ __global__ __launch_bounds__(1024) void kb_diag_chain(const BInst *__restrict__ 
   const int nb = min(256, N - c0);
   if (role == 0)
     chain_body<HELP>(smem, I.K, I.ldk, c0, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
-                     I.hctl, epoch);
+                     I.hctl, epoch, tail);
   else if (HELP && role == 1)
     helper_tiles(smem, I.K, I.ldk, c0, nb, I.dvec, I.hctl, epoch, I.flags);
   else if (HELP && role == 2)
-    helper_inverses(smem, I.K, I.ldk, c0, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
+    helper_inverses(smem, I.K, I.ldk, c0, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT, tail);
 }
 
 // chains of the outer block at c1 beside the previous block's trailing update (everything below
@@ -822,7 +823,7 @@ __global__ __launch_bounds__(1024) void kb_diag_chain(const BInst *__restrict__ 
 template <bool HELP>
 __global__ __launch_bounds__(1024) void kb_chain_update(const BInst *__restrict__ tab, int B, int Bp,
                                                         int per, int m, int wbuf, int c1, int epoch,
-                                                        int vdepth) {
+                                                        int vdepth, int tail) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[CH_SMEM];
   const int id = (int)blockIdx.x;
   constexpr int NR = HELP ? 3 : 1;  // roles of the chain: chain, helper T, helper I
@@ -836,11 +837,11 @@ __global__ __launch_bounds__(1024) void kb_chain_update(const BInst *__restrict_
     const int nb = min(256, N - c1);
     if (role == 0)
       chain_body<HELP>(smem, I.K, I.ldk, c1, nb, I.dvec, I.dinv, I.flags, I.Linv, I.LinvT, nullptr,
-                       I.hctl, epoch);
+                       I.hctl, epoch, tail);
     else if (role == 1)
       helper_tiles(smem, I.K, I.ldk, c1, nb, I.dvec, I.hctl, epoch, I.flags);
     else
-      helper_inverses(smem, I.K, I.ldk, c1, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT);
+      helper_inverses(smem, I.K, I.ldk, c1, nb, I.hctl, epoch, I.flags, I.Linv, I.LinvT, tail);
     return;
   }
   int inst, t;
@@ -890,6 +891,7 @@ static int next_help_epoch() {
   return e;
 }
 static bool chain_helpers();  // (below: PGF_CHAIN_HELP and the process-wide switch-off)
+static int chain_tail();      // (below: PGF_CHAIN_TAIL)
 // compute units of the current device, asked once per process (256 if it cannot be asked)
 static int device_cus() {
   static const int ncu = []() {
@@ -919,10 +921,10 @@ void ldlt_batch_launch_chain_update(hipStream_t s, const BInst *tab, int B, int 
   if (helpers && 2 * B * per > 3 * std::max(1, ncu - B)) helpers = false;
   if (helpers && chain_helpers())
     hipLaunchKernelGGL(kb_chain_update<true>, dim3(3 * Bp + tiles), dim3(1024), 0, s, tab, B, Bp,
-                       std::max(per, 1), m, wbuf, c1, next_help_epoch(), vdepth);
+                       std::max(per, 1), m, wbuf, c1, next_help_epoch(), vdepth, chain_tail());
   else
     hipLaunchKernelGGL(kb_chain_update<false>, dim3(Bp + tiles), dim3(1024), 0, s, tab, B, Bp,
-                       std::max(per, 1), m, wbuf, c1, 0, vdepth);
+                       std::max(per, 1), m, wbuf, c1, 0, vdepth, 0);
 }
 void ldlt_batch_launch_virtual_diag(hipStream_t s, const BInst *tab, int B, int vdepth) {
   hipLaunchKernelGGL(kb_virtual_diag, dim3(34, 1, B), dim3(256), 0, s, tab, vdepth);
@@ -931,9 +933,9 @@ void ldlt_batch_launch_chain(hipStream_t s, const BInst *tab, int B, int m, int 
   const int Bp = 8 * ((B + 7) / 8);
   if (helpers && chain_helpers())
     hipLaunchKernelGGL(kb_diag_chain<true>, dim3(3 * Bp), dim3(1024), 0, s, tab, B, Bp, m, c0,
-                       next_help_epoch());
+                       next_help_epoch(), chain_tail());
   else
-    hipLaunchKernelGGL(kb_diag_chain<false>, dim3(Bp), dim3(1024), 0, s, tab, B, Bp, m, c0, 0);
+    hipLaunchKernelGGL(kb_diag_chain<false>, dim3(Bp), dim3(1024), 0, s, tab, B, Bp, m, c0, 0, 0);
 }
 // per: 16-row groups of the largest possible instance below the block
 void ldlt_batch_launch_trsm(hipStream_t s, const BInst *tab, int B, int per, int m, int wbuf, int c0) {
@@ -956,6 +958,12 @@ void ldlt_chain_helpers_off() {
   g_fused_ud_off = true;
 }
 bool ldlt_chain_helpers_enabled() { return chain_helpers(); }
+// the chain inverts its block's last full diagonal tile itself, straight from its LDS
+// (PGF_CHAIN_TAIL=0: helper I does, behind the chain's last stamp)
+static int chain_tail() {
+  static const bool on = env_on("PGF_CHAIN_TAIL");
+  return on ? 1 : 0;
+}
 void ldlt_chain_helpers_set(bool on) {
   g_help_off = !on;
   g_fused_ud_off = !on;
@@ -991,25 +999,39 @@ bool ldlt_head_wanted(const DenseLdlt &f, int N) {
   return head_fused() && fused() && !per_kernel && N > LDLT_OB && f.vdepth == 0;
 }
 
-// PGF_CHAIN_TIMING=1 (diagnostic): the chain kernel of the FIRST block of every factorisation
-// stamps its phases into this buffer; ldlt_chain_timing_dump prints the last set
+// PGF_CHAIN_TIMING=k (diagnostic): the chain of outer block k - 1 of every factorisation (k = 1:
+// the first block; later blocks only where the chain is a launch of its own, PGF_FUSED=0) stamps
+// its phases into this buffer, helper I its own behind them (CH_DBG_CHAIN);
+// ldlt_chain_timing_dump prints the last set
 static long long *g_chain_dbg = nullptr;
+static int chain_dbg_block() {
+  static const int blk = []() {
+    const char *v = getenv("PGF_CHAIN_TIMING");
+    return v ? std::max(0, atoi(v) - 1) : -1;
+  }();
+  return blk;
+}
 static long long *chain_dbg_buffer() {
-  static const bool on = getenv("PGF_CHAIN_TIMING") != nullptr;
-  if (!on) return nullptr;
+  if (chain_dbg_block() < 0) return nullptr;
   if (!g_chain_dbg) {
-    if (hipMalloc((void **)&g_chain_dbg, 32 * sizeof(long long)) != hipSuccess) return nullptr;
-    (void)hipMemset(g_chain_dbg, 0, 32 * sizeof(long long));
+    if (hipMalloc((void **)&g_chain_dbg, CH_DBG_WORDS * sizeof(long long)) != hipSuccess) return nullptr;
+    (void)hipMemset(g_chain_dbg, 0, CH_DBG_WORDS * sizeof(long long));
   }
   return g_chain_dbg;
 }
 void ldlt_chain_timing_dump() {
   if (!g_chain_dbg) return;
-  long long h[32];
+  long long h[CH_DBG_WORDS];
   if (hipMemcpy(h, g_chain_dbg, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
+  if (!h[0]) return;  // (no stamped chain since the last dump)
   fprintf(stderr, "k_diag_chain phase stamps (us since kernel start):");
-  for (int i = 1; i < 32 && h[i]; ++i) fprintf(stderr, " %.2f", (double)(h[i] - h[0]) * 0.01);
+  for (int i = 1; i < CH_DBG_CHAIN && h[i]; ++i) fprintf(stderr, " %.2f", (double)(h[i] - h[0]) * 0.01);
+  fprintf(stderr, "\nhelper I (released, tile in LDS, inverse stored) per sub-panel:");
+  for (int i = CH_DBG_CHAIN; i < CH_DBG_WORDS; ++i)
+    if (h[i]) fprintf(stderr, " %.2f", (double)(h[i] - h[0]) * 0.01);
+    else fprintf(stderr, " -");
   fprintf(stderr, "\n");
+  (void)hipMemset(g_chain_dbg, 0, sizeof(h));
 }
 
 hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *head) {
@@ -1046,15 +1068,15 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *hea
   const UpdVirt uv{f.V, f.ldv, f.vd};
   auto launch_d = [&](int c0) {
     span_begin(pr.chain_spans);
-    long long *dbg = (c0 == 0) ? chain_dbg_buffer() : nullptr;
+    long long *dbg = (c0 == OB * chain_dbg_block()) ? chain_dbg_buffer() : nullptr;
     const int nb = std::min(OB, N - c0);
     const int ep = next_help_epoch();
     if (help)
       hipLaunchKernelGGL(k_diag_chain<true>, dim3(17), dim3(1024), 0, s, f.K, f.ldk, c0, nb, f.dvec,
-                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
+                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep, chain_tail());
     else
       hipLaunchKernelGGL(k_diag_chain<false>, dim3(1), dim3(1024), 0, s, f.K, f.ldk, c0, nb, f.dvec,
-                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep);
+                         f.dinv, f.flags, f.Linv, f.LinvT, dbg, f.hctl, ep, chain_tail());
     span_end(pr.chain_spans);
   };
   // T(c0) -- with the update of the next diagonal block in the same launch (k_trsm_ud) unless
@@ -1118,10 +1140,11 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *hea
     const int workers = std::min(ntiles, ncu - 3);  // one workgroup per CU: persistent tile loops
     if (help)
       hipLaunchKernelGGL(k_chain_update<true>, dim3(std::max(17, workers + 3)), dim3(1024), 0, s, f.K, f.ldk,
-                         c1, nb1, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, f.hctl, ep, N, nrows, js, uv, ctr);
+                         c1, nb1, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, f.hctl, ep, N, nrows, js, uv, ctr,
+                         chain_tail());
     else
       hipLaunchKernelGGL(k_chain_update<false>, dim3(1 + workers), dim3(1024), 0, s, f.K, f.ldk, c1, nb1,
-                         f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, f.hctl, ep, N, nrows, js, uv, ctr);
+                         f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, f.hctl, ep, N, nrows, js, uv, ctr, 0);
     if (prod) span_end(pr.fused_spans);
   };
   // update jobs alone
@@ -1161,13 +1184,14 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *hea
       const int units = head_asm_units(N) + head_panel_units(head->nI, head->V ? head->mp : 0);
       const int workers = std::min((units + 3) / 4, ncu - 3);
       const int ep = next_help_epoch();
+      long long *head_dbg = chain_dbg_block() == 0 ? chain_dbg_buffer() : nullptr;
       span_begin(pr.chain_spans);
       if (help)
         hipLaunchKernelGGL(k_chain_head<true>, dim3(std::max(17, workers + 3)), dim3(1024), 0, s, f.K, f.ldk,
-                           OB, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, chain_dbg_buffer(), f.hctl, ep, *head);
+                           OB, f.dvec, f.dinv, f.flags, f.Linv, f.LinvT, head_dbg, f.hctl, ep, *head, chain_tail());
       else
         hipLaunchKernelGGL(k_chain_head<false>, dim3(1 + workers), dim3(1024), 0, s, f.K, f.ldk, OB, f.dvec,
-                           f.dinv, f.flags, f.Linv, f.LinvT, chain_dbg_buffer(), f.hctl, ep, *head);
+                           f.dinv, f.flags, f.Linv, f.LinvT, head_dbg, f.hctl, ep, *head, 0);
       span_end(pr.chain_spans);
       if (head->crhs)
         launch_cond_rhs(s, head->nI, head->pm, head->V, head->ldv, head->crhs, head->delta, head->crhs_out);
