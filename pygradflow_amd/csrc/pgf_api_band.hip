@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "pgf_api_internal.h"
+#include "pgf_env.h"
 #include "pgf_kernels.h"
 
 // PGF_BW_SPLIT=0: new handles start with the wide band's factor / solve split off

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pgf_api_internal.h"
+#include "pgf_env.h"
 #include "pgf_kernels.h"
 
 // ---- the condensed system ------------------------------------------------------------------

@@ -14,7 +14,10 @@
 #include <vector>
 
 #include "../../include/pgf_hip.h"
-#include "pgf_internal.h"
+#include "pgf_band_batch.h"
+#include "pgf_batch.h"
+#include "pgf_ldlt.h"
+#include "pgf_lu.h"
 #include "pgf_sparse.h"
 
 // The status block of a dense step (doubles): every word the host reads after the step, read

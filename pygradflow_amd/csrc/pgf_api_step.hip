@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "pgf_api_internal.h"
+#include "pgf_env.h"
 #include "pgf_kernels.h"
 #include "pgf_unsym.h"
 

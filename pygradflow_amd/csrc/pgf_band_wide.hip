@@ -380,7 +380,7 @@ void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double 
 //
 // The twins see the contraction rules of the kernels they mirror: this file is compiled WITHOUT
 // -ffp-contract=off.
-#include "pgf_internal.h"
+#include "pgf_band_batch.h"
 
 #define INST(I)                        \
   const BandInst &I = tab[blockIdx.y]; \

@@ -19,7 +19,9 @@
 
 #include "pgf_band_dev.h"
 #include "pgf_border_dev.h"
-#include "pgf_internal.h"
+#include "pgf_band_batch.h"
+#include "pgf_batch.h"
+#include "pgf_env.h"
 #include "pgf_sparse.h"
 
 static inline dim3 g1(int n, int b = 256) { return dim3((n + b - 1) / b); }

@@ -41,10 +41,12 @@
 // of its job tables: pgf_update_plan.h, pgf_update_plan.hip (host only).
 #include <hip/hip_ext.h>
 
+#include "pgf_batch.h"
 #include "pgf_chain_dev.h"
+#include "pgf_env.h"
 #include "pgf_head_dev.h"
-#include "pgf_internal.h"
 #include "pgf_kernels.h"
+#include "pgf_ldlt.h"
 #include "pgf_ldlt_dev.h"
 #include "pgf_update_plan.h"
 
@@ -593,7 +595,7 @@ __global__ __launch_bounds__(1024) void k_chain_update(double *K, int64_t ldk, i
 }
 
 // ------------------------------------------------------------------ D(0) beside the step's head
-// The first chain's launch of a step (LdltHead, pgf_internal.h): the same grid and roles as
+// The first chain's launch of a step (LdltHead, pgf_ldlt.h): the same grid and roles as
 // k_chain_update, but the workgroups beside the chain and its helpers write what the step has
 // not assembled yet -- K's rows below the first diagonal block and the panel V -- instead of
 // update tiles: D(0) reads K[0:256, 0:256] alone, which the launch in front (k_assemble_kkt_head)
@@ -1238,7 +1240,7 @@ hipError_t ldlt_factor_async(DenseLdlt &f, int N, int nrows, const LdltHead *hea
   return hipGetLastError();
 }
 
-// G <- V V^T, lower triangle (declared in pgf_internal.h): the update role alone (k_update_jobs)
+// G <- V V^T, lower triangle (declared in pgf_ldlt.h): the update role alone (k_update_jobs)
 // with one job over every 128-wide tile column, its K-range the panel V only (KB = 0: no column of
 // G itself is read as an operand).  With vd = -1 the tile's C -= V diag(vd) V^T adds V V^T to the
 // zeroed G.  n^2 depth flops once per derivative upload (pgf_api_factor.hip, gram_prepare).

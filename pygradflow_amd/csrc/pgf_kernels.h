@@ -1,9 +1,13 @@
-// Launch wrappers of pgf_kernels.hip (all asynchronous on the given stream).
+// Launch wrappers of the single-handle step kernels (all asynchronous on the given stream).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// 1-D grid of ceil(n / b) workgroups
+static inline dim3 g1(int n, int b = 256) { return dim3((n + b - 1) / b); }
+
+// ---- pgf_kernels.hip: the step ----------------------------------------------
 void launch_scale_bounds(hipStream_t s, int n, double lamb, const double *lb, const double *ub,
                          double *slb, double *sub);
 void launch_active_set(hipStream_t s, int n, int use_tau, double lamb, double f_x, double f_x0,
@@ -45,7 +49,7 @@ void launch_assemble_kkt(hipStream_t s, double *K, int64_t ldk, const double *H,
                          double lamb, double delta, int *zero = nullptr, int nzero = 0,
                          const double *row_src = nullptr, double *row_dst = nullptr, int row_n = 0,
                          const double *G = nullptr, int64_t ldg = 0);
-// the first diagonal block's rows of the assembly described by hw (pgf_internal.h), the zeroing of
+// the first diagonal block's rows of the assembly described by hw (pgf_ldlt.h), the zeroing of
 // `zero' and the rhs row: the launch in front of a first chain that carries the rest (k_chain_head)
 struct LdltHead;
 void launch_assemble_kkt_head(hipStream_t s, double *K, int64_t ldk, const LdltHead &hw, int *zero, int nzero);
@@ -86,19 +90,6 @@ void launch_measures(hipStream_t s, int n, int m, double active_tol, const doubl
                      const double *ub, double *red, double *out);
 void launch_csr_to_dense(hipStream_t s, int rows, const int *ptr, const int *idx, const double *val,
                          double *dst, int64_t ld);
-// r = rhs - K s of the reduced KKT system, K applied from H, J and the mask (never assembled);
-// red3 <- max |r|, max |rhs|, max |s|.  v, lv, u: n-vectors of scratch, wy: m, r: nI + m.
-void launch_kkt_residual(hipStream_t s, int n, int m, int nI, double lamb, double delta,
-                         const double *H, int64_t ldh, const double *J, int64_t ldj,
-                         const int *idxI, const int *pos, const uint8_t *mask, const double *rhs,
-                         const double *sol, double *v, double *lv, double *u, double *wy,
-                         double *partial, int nparts, double *r, double *red3,
-                         bool prepared = false);
-void launch_axpy1(hipStream_t s, int N, const double *d, double *x);
-void launch_symmetrize(hipStream_t s, double *A, int64_t ld, int N);
-// ||H||_inf, ||J||_inf, ||J||_1 -> norms3 (device), for the normwise backward error of the guard
-void launch_matrix_norms(hipStream_t s, int n, int m, const double *H, int64_t ldh, const double *J,
-                         int64_t ldj, double *norms3);
 // condensed KKT system (constraint block eliminated first; pgf_kernels.hip, pgf_api_factor.hip):
 // V <- J[:, I]^T zero-padded to mp columns, row nI <- rhs_y (or 0), vd <- -1 / delta
 void launch_cond_panel(hipStream_t s, double *V, int64_t ldv, int mp, double *vd, const double *J,
@@ -113,6 +104,21 @@ void launch_cond_y(hipStream_t s, int nI, int m, const double *V, int64_t ldv, c
 // for StepCondY::nparts
 int launch_cond_y_partial(hipStream_t s, int nI, int m, const double *V, int64_t ldv, const double *solx,
                           double *partial, size_t partial_cap);
+
+// ---- pgf_guard_kernels.hip: residual guard and evaluation ahead --------------
+// r = rhs - K s of the reduced KKT system, K applied from H, J and the mask (never assembled);
+// red3 <- max |r|, max |rhs|, max |s|.  v, lv, u: n-vectors of scratch, wy: m, r: nI + m.
+void launch_kkt_residual(hipStream_t s, int n, int m, int nI, double lamb, double delta,
+                         const double *H, int64_t ldh, const double *J, int64_t ldj,
+                         const int *idxI, const int *pos, const uint8_t *mask, const double *rhs,
+                         const double *sol, double *v, double *lv, double *u, double *wy,
+                         double *partial, int nparts, double *r, double *red3,
+                         bool prepared = false);
+void launch_axpy1(hipStream_t s, int N, const double *d, double *x);
+void launch_symmetrize(hipStream_t s, double *A, int64_t ld, int N);
+// ||H||_inf, ||J||_inf, ||J||_1 -> norms3 (device), for the normwise backward error of the guard
+void launch_matrix_norms(hipStream_t s, int n, int m, const double *H, int64_t ldh, const double *J,
+                         int64_t ldj, double *norms3);
 // launch_residual_and_eval(..., prepared = true) with the row passes over J and H in one launch and
 // the sums, the H pass's epilogue and the residual in another: at most three launches, same values
 void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double delta, const double *H, int64_t ldh,

@@ -17,7 +17,9 @@
 //   kb_*                batched variants, one instance per blockIdx.z or batch_decode
 #include <hip/hip_ext.h>
 
-#include "pgf_internal.h"
+#include "pgf_batch.h"
+#include "pgf_env.h"
+#include "pgf_ldlt.h"
 
 #include <algorithm>
 #include <cmath>
@@ -515,7 +517,7 @@ __global__ __launch_bounds__(256, 3) void k_trsv_fwd_chain(const double *__restr
 }
 
 // ------------------------------------------------------------------ batched variants
-// One instance per blockIdx.z (BInst, pgf_internal.h).  Every instance has its own reduced
+// One instance per blockIdx.z (BInst, pgf_batch.h).  Every instance has its own reduced
 // size N = counts[0] + m, known only on the device: the host walks the panel / update
 // schedule of the largest possible system (n + m) and workgroups beyond an instance's own
 // N return at once.  ctl[0] == 0 (factor still valid) skips the factorisation kernels.
@@ -707,7 +709,6 @@ static bool use_chain() {
 }
 
 void ldlt_chain_set_enabled(bool on) { g_chain_off = !on; }
-bool ldlt_chain_enabled() { return use_chain(); }
 
 // after a host synchronisation of f.stream: did a chained solve since the last check fail its
 // own checks?  (bit 0: a wait timed out, bit 1: workers on different XCDs)

@@ -7,13 +7,9 @@
 // summed in a fixed order by the last workgroup to arrive (the ticket of k_unscaled_res_norm).
 #include "pgf_line_search.h"
 
-#define ACTIVE_EPS 1e-8  // reference implicit_func.py:44
+#include "pgf_reduce_dev.h"
 
-__device__ __forceinline__ double ls_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  return v;
-}
+#define ACTIVE_EPS 1e-8  // reference implicit_func.py:44
 
 // lamb x - P(p), p = lamb xhat - g clipped where it leaves [slb - eps, sub + eps]: an x row of
 // ScaledImplicitFunc.value_at with the mask of its own point (implicit_func.py:219-231, 246)
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(256) void k_ls_ladder(int n, int m, double lamb, do
   }
 #pragma unroll
   for (int k = 0; k < LS_TERMS; ++k) {
-    const double s = ls_wave_sum(t[k]);
+    const double s = wave_sum(t[k]);
     if ((tid & 63) == 0) part[tid >> 6][k] = s;
   }
   __syncthreads();
@@ -166,14 +162,14 @@ __global__ __launch_bounds__(256) void k_ls_finish(int n, int m, const double *_
     yn[r] = yhat[r] - d;
     sq = d * d;
   }
-  sq = ls_wave_sum(sq);
+  sq = wave_sum(sq);
   if ((tid & 63) == 0) part[tid >> 6] = sq;
   __syncthreads();
   if (tid == 0) red[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
   if (!ls_last_block(ticket)) return;
   double s = 0.0;
   for (unsigned b = tid; b < gridDim.x; b += 256) s += red[b];
-  s = ls_wave_sum(s);
+  s = wave_sum(s);
   __syncthreads();  // (part is read above by lane 0 of this same workgroup)
   if ((tid & 63) == 0) part[tid >> 6] = s;
   __syncthreads();

@@ -22,7 +22,8 @@
 // linear_solver/linear_solver.py:23-25, used by step/cond_estimate.py:82).
 // A zero or non-finite pivot sets flags[0] -> PGF_SINGULAR -> LinearSolverError, like the
 // RuntimeError of splu (lu_solver.py:13-17).
-#include "pgf_internal.h"
+#include "pgf_env.h"
+#include "pgf_lu.h"
 #include "pgf_ldlt_dev.h"
 
 #include <algorithm>

@@ -16,7 +16,9 @@
 // Compiled with -ffp-contract=off like pgf_kernels.hip (explicit fma() only).
 #include "pgf_sparse.h"
 #include "pgf_band_dev.h"
-#include "pgf_internal.h"
+#include "pgf_band_batch.h"
+#include "pgf_batch.h"
+#include "pgf_env.h"
 
 #define ACTIVE_EPS 1e-8
 
@@ -78,14 +80,6 @@ __global__ void k_band_scatter_J(int nnz, const int *__restrict__ col,
                                  const uint8_t *__restrict__ mask, double *__restrict__ band) {
   b_band_scatter_J(nnz, col, val, slot, mask, band);
 }
-
-__global__ void k_band_rhs(int n, int m, const uint8_t *__restrict__ mask,
-                           const double *__restrict__ F, const double *__restrict__ b0full,
-                           const double *__restrict__ Hb0, const double *__restrict__ Jb0,
-                           double fact, const int *__restrict__ pos, double *__restrict__ brhs) {
-  b_band_rhs(n, m, mask, F, b0full, Hb0, Jb0, fact, pos, brhs);
-}
-
 
 // full-length vector <-> permuted band order (LinearSolver.solve against the banded factor)
 __global__ void k_band_permute(int N, const int *__restrict__ pos, const double *__restrict__ in,
@@ -269,11 +263,6 @@ __global__ __launch_bounds__(1024) void k_bcr_tail(const double *__restrict__ D,
   b_bcr_tail(D, L, U, F, X, nb, s0, flags, negcnt);
 }
 
-
-__global__ void k_bcr_scatter(const double *__restrict__ X, double *__restrict__ out, int N) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) out[i] = X[i];
-}
 
 // accuracy guard: residual of the solution against the intact band (b_band_residual)
 __global__ __launch_bounds__(256) void k_band_residual(const double *__restrict__ band, int ldb, int bw,

@@ -15,6 +15,7 @@
 #include "pgf_unsym.h"
 
 #include "../../include/pgf_hip.h"
+#include "pgf_reduce_dev.h"
 
 #define ACTIVE_EPS 1e-8  // reference implicit_func.py:44
 #define UT 64            // tile edge of the assembly
@@ -293,8 +294,7 @@ __global__ __launch_bounds__(256) void k_unsym_step_update(
     yn[r] = y[r] - d;
     sq = d * d;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sq += __shfl_down(sq, off);
+  sq = wave_sum(sq);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sq;
   __syncthreads();
   if (threadIdx.x == 0) red[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);

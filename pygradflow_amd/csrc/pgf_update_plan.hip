@@ -3,7 +3,8 @@
 // call: pgf_debug_update_plan walks the same plans without a GPU.
 #include "pgf_update_plan.h"
 
-#include "pgf_internal.h"
+#include "pgf_env.h"
+#include "pgf_ldlt.h"
 
 #include <algorithm>
 #include <cmath>
