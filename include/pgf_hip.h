@@ -596,6 +596,20 @@ int pgf_batch_debug_factor_kind(pgf_batch b);
  * enqueued); redone_steps -- steps enqueued with the previous |I|, |A| that were discarded and
  * enqueued again by pgf_qp_sync because the sizes had changed.  Either pointer may be NULL. */
 int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps);
+/* Counters of the waits of the dense qp steps that end in the hand-back launch (tests; DESIGN.md
+ * 4d, PGF_STEP_HANDBACK): by_word -- waits satisfied by the sequence word the step's last launch
+ * stores into host memory, without a runtime call; fell_back -- waits whose spin bound expired (or
+ * was zero) and that ended in hipStreamSynchronize.  A wait already taken for the same step (pgf_qp_sync
+ * behind pgf_qp_residual_norm) counts in neither.  Either pointer may be NULL. */
+int pgf_debug_handback_stats(pgf_handle h, int *by_word, int *fell_back);
+/* Test hook: the wall-clock bound of that spin in seconds; 0: no spin, every wait falls back;
+ * negative: the bound derived from the previous step's duration again. */
+int pgf_debug_handback_spin_bound(pgf_handle h, double seconds);
+/* Counters of the mask refreshes of the dense qp steps and of pgf_qp_update_active_set (tests;
+ * DESIGN.md 4d, PGF_UNBOUNDED_FRONT): general -- those that evaluated the mask (and compacted it or
+ * waited for its difference); unbounded -- those of a handle without a finite bound, which launch
+ * nothing once the empty mask and the identity lists are on the device.  Either pointer may be NULL. */
+int pgf_debug_front_stats(pgf_handle h, int *general, int *unbounded);
 /* Device time (ms) of the last line-search stage -- the direction's images, k_ls_ladder,
  * k_ls_finish -- of a step with PGF_STEP_LINE_SEARCH made while profiling was enabled
  * (pgf_profile_enable); 0 before. */

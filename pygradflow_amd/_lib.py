@@ -124,6 +124,9 @@ SIGNATURES = {
     "pgf_debug_chain_helpers": (C.c_int, [C.c_int]),
     "pgf_debug_factor_kind": (C.c_int, [_h]),
     "pgf_debug_step_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_debug_handback_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_debug_handback_spin_bound": (C.c_int, [_h, C.c_double]),
+    "pgf_debug_front_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_gram_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_head_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_debug_tail_stats": (C.c_int, [_h, _ip, _ip]),

@@ -66,8 +66,14 @@ int pgf_create(int n, int m, int device, unsigned flags, pgf_handle *out) {
       (n && (e = hipMemset(h->idxI, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
       (n && (e = hipMemset(h->idxA, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
       (n && (e = hipMemset(h->pos, 0, (size_t)n * sizeof(int))) != hipSuccess) ||
-      (e = hipHostMalloc((void **)&h->h_stat, STAT_COPY * sizeof(double))) != hipSuccess ||
+      // (coherent: the hand-back's last launch stores into it while the host spins on the word behind it)
+      (e = hipHostMalloc((void **)&h->h_stat, (STAT_COPY + 1) * sizeof(double),
+                         hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
       (e = hipHostMalloc((void **)&h->h_meas, 4 * sizeof(double))) != hipSuccess) {
+    pgf_destroy(h);
+    return PGF_HIP_ERROR + (int)e;
+  }
+  if ((e = hipHostGetDevicePointer((void **)&h->hb.dev, h->h_stat, 0)) != hipSuccess) {
     pgf_destroy(h);
     return PGF_HIP_ERROR + (int)e;
   }
@@ -75,7 +81,7 @@ int pgf_create(int n, int m, int device, unsigned flags, pgf_handle *out) {
   h->scal = h->stat + 8;
   h->counts = reinterpret_cast<int *>(h->stat + 12);
   h->ticket = reinterpret_cast<unsigned *>(h->stat + 16);
-  for (int i = 0; i < STAT_COPY; ++i) h->h_stat[i] = 0.0;
+  for (int i = 0; i <= STAT_COPY; ++i) h->h_stat[i] = 0.0;  // (the sequence word: 0, as hb.issued)
   h->guard.h_rs = h->h_stat;
   h->h_scal = h->h_stat + 8;
   h->h_counts = reinterpret_cast<int *>(h->h_stat + 12);
@@ -152,6 +158,12 @@ int pgf_set_bounds(pgf_handle h, const double *lb, const double *ub) {
   if ((rc = up(h, h->ub, ub, h->n * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->bounds_set = true;
+  // no finite bound anywhere: the active set is empty at every point (pgf_solver::unb)
+  bool none = true;
+  for (int i = 0; i < h->n && none; ++i) none = lb[i] == -HUGE_VAL && ub[i] == HUGE_VAL;
+  h->unb.no_finite_bound = none;
+  h->unb.lists_ready = false;
+  drop_norm(h);
   if (h->outer_set) launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   return PGF_OK;
 }
@@ -175,6 +187,7 @@ int pgf_set_outer(pgf_handle h, const double *xhat, const double *yhat, double d
   h->outer_set = true;
   h->mask_set = false;
   h->ls.hat_fresh = false;
+  drop_norm(h);
   invalidate_factor(h);
   return PGF_OK;
 }
@@ -318,6 +331,7 @@ int pgf_active_set(pgf_handle h, const double *x, const double *g, double tau, u
   if ((rc = down(h, mask_out, h->mask_new, h->n))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->eval_fresh = false;
+  drop_norm(h);
   return PGF_OK;
 }
 
@@ -342,6 +356,7 @@ int adopt_index_sets(pgf_handle h, bool spec) {
 }
 int refresh_index_sets(pgf_handle h, bool in_step) {
   const bool spec = in_step && h->counts_known && step_spec();
+  h->unb.lists_ready = false;
   launch_compact(h->stream, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, spec ? h->nI : -1);
   return adopt_index_sets(h, spec);
 }
@@ -376,6 +391,8 @@ int pgf_set_active_set(pgf_handle h, const uint8_t *mask) {
   h->counts_known = true;
   h->mask_set = true;
   invalidate_factor(h);
+  // (an empty mask compacts to what a handle without finite bounds keeps: zero, the identity, (n, 0, ., 0))
+  h->unb.lists_ready = !h->sparse && na == 0;
   if (!h->sparse)
     launch_compact(h->stream, h->n, h->mask, h->idxI, h->idxA, h->pos, h->counts, h->nI);
   return PGF_OK;

@@ -289,6 +289,26 @@ int pgf_debug_step_stats(pgf_handle h, int *host_syncs, int *redone_steps) {
   return PGF_OK;
 }
 
+int pgf_debug_handback_stats(pgf_handle h, int *by_word, int *fell_back) {
+  if (!h) return PGF_INVALID;
+  if (by_word) *by_word = h->dbg.stat_hb_word;
+  if (fell_back) *fell_back = h->dbg.stat_hb_fallback;
+  return PGF_OK;
+}
+
+int pgf_debug_handback_spin_bound(pgf_handle h, double seconds) {
+  if (!h) return PGF_INVALID;
+  h->hb.bound_override = seconds;
+  return PGF_OK;
+}
+
+int pgf_debug_front_stats(pgf_handle h, int *general, int *unbounded) {
+  if (!h) return PGF_INVALID;
+  if (general) *general = h->dbg.stat_compactions;
+  if (unbounded) *unbounded = h->dbg.stat_unb_fronts;
+  return PGF_OK;
+}
+
 int pgf_debug_gram_stats(pgf_handle h, int *builds, int *factorisations_with_gram) {
   if (!h) return PGF_INVALID;
   if (builds) *builds = h->dbg.stat_gram_builds;

@@ -174,6 +174,8 @@ int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pg
     // the batch owns the device-side state of the handle from here on
     h->mask_set = false;
     h->eval_fresh = false;
+    h->unb.lists_ready = false;
+    drop_norm(h);
     invalidate_factor(h);
   }
   if ((e = hipMemcpy(b->tab, tab.data(), count * sizeof(BInst), hipMemcpyHostToDevice)) !=

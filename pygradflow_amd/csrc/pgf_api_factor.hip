@@ -273,8 +273,8 @@ int factor_async(pgf_handle h, bool with_rhs) {
   return PGF_OK;
 }
 
-int finish_factor_state(pgf_handle h, hipError_t *e) {
-  const int st = ldlt_finish(h->fac, e);
+int finish_factor_state(pgf_handle h, hipError_t *e, bool awaited) {
+  const int st = ldlt_finish(h->fac, e, awaited && !h->sparse);
   if (h->sparse && st >= 0) band_kept_resolve(h);
   if (st == 1 && h->cond.condensed && !h->cond.condensed_veto) {
     h->cond.condensed_veto = true;

@@ -75,6 +75,7 @@ int refine_if_needed(pgf_handle h, bool swapped, bool with_step) {
   auto finish_round = [&]() -> int {
     enqueue_residual(h);
     h->eval_fresh = false;  // the point moves: what pgf_qp_step_async evaluated ahead is stale
+    drop_norm(h);
     if (with_step) {
       unswap();
       enqueue_step_update(h);
@@ -132,6 +133,7 @@ int refine_if_needed(pgf_handle h, bool swapped, bool with_step) {
 int chain_recover(pgf_handle h, bool swapped) {
   if (!ldlt_chain_check(h->fac)) return PGF_OK;  // (0 on a banded handle: it has no chain)
   h->eval_fresh = false;  // the point is computed again
+  drop_norm(h);
   if (swapped) swap_point(h);
   if (h->flight.last_solve == 1)
     HIPCHK(h, kkt_backsolve_async(h, h->sol));

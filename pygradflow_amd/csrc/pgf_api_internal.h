@@ -27,8 +27,11 @@
 //   [12, 14) counts (int): |I|, |A|, mask difference, size mismatch of a speculative step
 //   [14, 16) status (int): factor flags [0, 3), chained-solve status [3] (DenseLdlt::h_flags)
 //   [16, 17) two tickets of the last-workgroup reductions (never copied)
+// With the hand-back (pgf_solver::hb) the step's last launch stores the STAT_COPY doubles into
+// h_stat itself; h_stat[STAT_COPY] is the sequence word it writes behind them.
 #define STAT_COPY 16
 #define STAT_ALLOC 17
+#define STAT_NORM 9  // scal[1] inside the block
 
 #define PGF_GEMVT_PARTS 32  // row chunks of the J^T products' partial sums (pgf_solver::partial)
 
@@ -119,6 +122,31 @@ struct pgf_solver {
     int cond_since_upload = 0;  // condensed factorisations enqueued since the last derivative upload
   } cond;
 
+  // ---- the hand-back of a dense qp step to the host (pgf_api_step.hip; PGF_STEP_HANDBACK) ----
+  // h_stat is coherent host memory: the last launch of a step with the fused tail stores the status
+  // block into it and then the sequence word h_stat[STAT_COPY] (issued: the value of the last such
+  // launch enqueued), and the step's one wait spins on that word (hb_wait) instead of calling the
+  // runtime.  armed: the step in flight ends in such a launch (else: the copy and
+  // hipStreamSynchronize).  seen: the last value a wait has observed -- a wait for a value already
+  // seen returns at once.  norm_fresh: scal[1] of the block is the residual norm of the current
+  // device point under the current outer point (written by the tail's last launch); cleared by
+  // whatever moves either (drop_norm).
+  struct {
+    double *dev = nullptr;  // h_stat as the device addresses it
+    unsigned long long issued = 0, seen = 0;
+    bool armed = false, norm_fresh = false;
+    double t_enqueued = 0.0, last_step_s = -1.0;  // seconds: when the step was enqueued, how long the last one took
+    double bound_override = -1.0;                 // pgf_debug_handback_spin_bound (< 0: the derived bound)
+  } hb;
+
+  // ---- a handle without a finite bound (pgf_set_bounds; PGF_UNBOUNDED_FRONT) ----
+  // every lb is -inf and every ub +inf: the active set is empty at every point, so the mask (zero),
+  // the index lists (the identity) and the counts (n, 0, ., 0) are written once (lists_ready; cleared by
+  // whatever else writes them) and a step takes neither the compaction nor the mask difference
+  struct {
+    bool no_finite_bound = false, lists_ready = false;
+  } unb;
+
   // ---- what the step or factorisation in flight took: valid until it is settled (pgf_qp_sync,
   // factor_finish) ----
   struct {
@@ -130,6 +158,7 @@ struct pgf_solver {
     // and the reduced rhs (consumed by newton_core_async)
     bool front_done = false;
     bool fused_eval_done = false;  // newton_core_async evaluated g, c at (xn, yn) beside the residual check
+    bool fused_norm_done = false;  // ... and the tail's last launch left that point's residual norm and the hand-back
     // what the factorisation in flight added to the counters (taken back when it is discarded)
     bool fac_counted = false, fac_used_gram = false;
     // the factorisation in flight took the step's head beside its first chain (1) or not (2);
@@ -165,6 +194,8 @@ struct pgf_solver {
   // ---- counters read only by the pgf_debug_* hooks (pgf_api_aux.hip, pgf_api_unsym.hip) ----
   struct {
     int stat_host_syncs = 0, stat_redone = 0;  // pgf_debug_step_stats
+    int stat_hb_word = 0, stat_hb_fallback = 0;    // pgf_debug_handback_stats
+    int stat_compactions = 0, stat_unb_fronts = 0;  // pgf_debug_front_stats
     // steps enqueued with the residual check and the evaluation ahead in the fused / the separate
     // launches (pgf_debug_tail_stats)
     int stat_tail_fused = 0, stat_tail_plain = 0;
@@ -276,6 +307,10 @@ static inline void adopt_counts(pgf_handle h) {
 // the depth of the panel V: the constraint count in whole 32-column tiles
 static inline int round_up32(int m) { return (m + 31) / 32 * 32; }
 
+// the device point, the outer point, dt, the bounds or the problem's vectors change: the block's
+// residual norm is no longer that of the current point
+static inline void drop_norm(pgf_handle h) { h->hb.norm_fresh = false; }
+
 static inline void invalidate_factor(pgf_handle h) {
   h->fac.factored = false;
   h->cond.condensed_veto = false;
@@ -347,7 +382,7 @@ void assemble(pgf_handle h, double *K, int64_t ldk);  // refine_if_needed (the L
 hipError_t kkt_solve_async(pgf_handle h, const double *rhs, double *sol);  // newton_core_async, refine_if_needed, chain_recover, pgf_linear_solve
 hipError_t kkt_backsolve_async(pgf_handle h, double *sol, StepCondY *cy = nullptr);  // newton_core_async, chain_recover
 int factor_async(pgf_handle h, bool with_rhs);      // newton_core_async
-int finish_factor_state(pgf_handle h, hipError_t *e);  // pgf_qp_sync
+int finish_factor_state(pgf_handle h, hipError_t *e, bool awaited = false);  // pgf_qp_sync (awaited: hb_wait saw the step's word)
 int factor_finish(pgf_handle h);                    // pgf_newton_solve
 int factor_sync(pgf_handle h);                      // pgf_linear_solve
 void gram_uncount(pgf_handle h);                    // settle_spec

@@ -64,6 +64,7 @@ int ls_enter(pgf_handle h) {
   ls.active = true;
   if (!ls.hat_fresh) {
     h->eval_fresh = false;
+    drop_norm(h);
     qp_eval(h);
     ls.hat_fresh = true;
   }
@@ -119,6 +120,7 @@ int ls_search(pgf_handle h, double *diff) {
   if (ls.h_blk[34] != 0.0) return fail(h, PGF_LINE_SEARCH, "Line search failed to converge");
   swap_point(h);
   h->eval_fresh = false;
+  drop_norm(h);
   h->h_scal[0] = ls.h_blk[35];
   if (diff) *diff = ls.h_blk[35];
   return PGF_OK;

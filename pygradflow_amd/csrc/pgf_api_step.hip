@@ -1,9 +1,12 @@
 // The Newton step of the dense Symmetric handle (newton_core_async, pgf_newton_solve,
 // pgf_residual) and the device-resident LQ mode: pgf_qp_set_* ... pgf_qp_sync with the speculative
 // step and its two redo paths, pgf_qp_step, pgf_qp_residual_norm, pgf_qp_measures.  The switches
-// of the step (eval_ahead, step_fused, step_spec) are here too.  Host code only.
+// of the step (eval_ahead, step_fused, step_spec, step_handback, unbounded_front) and the wait of the
+// hand-back (hb_wait) are here too.  Host code only.
+#include <chrono>
 #include <cmath>
 #include <cstring>
+#include <thread>
 
 #include "pgf_api_internal.h"
 #include "pgf_env.h"
@@ -22,6 +25,73 @@ static bool step_fused() { static const bool on = env_on("PGF_STEP_FUSED"); retu
 // PGF_STEP_SPEC=0: a step waits for the sizes of its index sets (one more host synchronisation
 // per step) instead of running with the last known ones
 bool step_spec() { static const bool on = env_on("PGF_STEP_SPEC"); return on; }
+
+// PGF_STEP_HANDBACK=0: the tail's last launch leaves neither the new point's residual norm nor the
+// status block in host memory -- k_unscaled_res_norm, the two copies and hipStreamSynchronize as before
+static bool step_handback() { static const bool on = env_on("PGF_STEP_HANDBACK"); return on; }
+
+// PGF_UNBOUNDED_FRONT=0: a handle without a finite bound takes the mask, the compaction and the mask
+// difference like any other
+static bool unbounded_front() { static const bool on = env_on("PGF_UNBOUNDED_FRONT"); return on; }
+
+// ---------------------------------------------------------------- the hand-back's wait
+static double now_s() {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+static inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+  __builtin_ia32_pause();
+#else
+  std::this_thread::yield();
+#endif
+}
+// The spin is bounded by wall-clock time: HB_SPIN_FACTOR times what the handle's previous step
+// took from its enqueueing to its word plus HB_SPIN_FLOOR_S (a step after a change of sizes or a
+// first Gram build is longer than its predecessor), never more than HB_SPIN_CAP_S, which is also the
+// bound of a handle's first step.  pgf_debug_handback_spin_bound overrides it (0: no spin at all).
+static const double HB_SPIN_FACTOR = 16.0, HB_SPIN_FLOOR_S = 0.02, HB_SPIN_CAP_S = 2.0;
+
+// The one wait of a dense qp step (the only user): for the sequence word the step's last launch
+// stores behind the status block in h_stat -- no runtime call -- or, for a step that does not end in
+// such a launch, when the bound expires or after a fault (the word never comes; the error surfaces
+// here), hipStreamSynchronize.  A wait already taken for the same word returns at once.  *by_word
+// (may be null): everything enqueued was seen complete without the runtime.
+static int hb_wait(pgf_handle h, bool *by_word = nullptr) {
+  if (by_word) *by_word = false;
+  if (!h->hb.armed) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return PGF_OK;
+  }
+  const unsigned long long want = h->hb.issued;
+  if (h->hb.seen == want) {
+    if (by_word) *by_word = true;
+    return PGF_OK;
+  }
+  const unsigned long long *word = reinterpret_cast<const unsigned long long *>(h->h_stat + STAT_COPY);
+  double bound = HB_SPIN_CAP_S;
+  if (h->hb.last_step_s >= 0.0) bound = std::fmin(bound, HB_SPIN_FLOOR_S + HB_SPIN_FACTOR * h->hb.last_step_s);
+  if (h->hb.bound_override >= 0.0) bound = h->hb.bound_override;
+  bool got = false;
+  if (bound > 0.0) {
+    const double t0 = now_s();
+    do {
+      for (int k = 0; k < 64 && !got; ++k) {
+        got = __atomic_load_n(word, __ATOMIC_ACQUIRE) >= want;
+        if (!got) cpu_relax();
+      }
+    } while (!got && now_s() - t0 < bound);
+  }
+  if (got) {
+    ++h->dbg.stat_hb_word;
+    h->hb.last_step_s = now_s() - h->hb.t_enqueued;
+  } else {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ++h->dbg.stat_hb_fallback;
+  }
+  h->hb.seen = want;
+  if (by_word) *by_word = got;
+  return PGF_OK;
+}
 
 // (expand: also the residual check's expansion of the solution into rs_v, rs_lv and the zeroing of
 // its maxima, launch_residual_and_eval(..., prepared = true))
@@ -54,6 +124,7 @@ static void absorb_status(pgf_handle h) {
 static int newton_core_async(pgf_handle h, bool *did_factor) {
   hipStream_t s = h->stream;
   h->flight.fused_eval_done = false;
+  h->flight.fused_norm_done = false;
   h->flight.forget_factor();  // (set by factor_async, if this step factorises)
   if (h->sparse) return band_step_async(h, did_factor);
   const bool front_done = h->flight.front_done;
@@ -99,12 +170,18 @@ static int newton_core_async(pgf_handle h, bool *did_factor) {
   if (ahead) {
     enqueue_step_update(h, /*expand=*/true, &cy);
     ++(fused_tail ? h->dbg.stat_tail_fused : h->dbg.stat_tail_plain);
-    if (fused_tail)
+    if (fused_tail) {
+      // a qp step (enqueue_qp_step; it swaps the point right behind): the combine launch besides leaves
+      // the new point's residual norm in the status block and the block in h_stat (pgf_solver::hb)
+      const bool hand = step_handback() && h->fac.defer_status && h->n + h->m > 0;
+      const TailHandback th{h->dt, h->xhat, h->yhat, h->xn, h->yn, h->c, h->lb, h->ub, h->red, h->scal + 1,
+                            h->ticket + 1, h->stat, STAT_COPY, h->hb.dev, hand ? ++h->hb.issued : 0ull};
       launch_residual_and_eval_fused(s, h->n, h->m, h->nI, h->delta, h->H, h->ldh, h->J, h->ldj, h->pos, h->mask,
                                      h->rhs, h->sol, h->guard.rs_v, h->guard.rs_lv, h->guard.rs_u, h->guard.rs_wy, h->partial,
                                      PGF_GEMVT_PARTS, h->guard.rs_r, h->guard.rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c,
-                                     h->w, h->tmpn, h->g);
-    else
+                                     h->w, h->tmpn, h->g, hand ? &th : nullptr);
+      h->flight.fused_norm_done = hand;
+    } else
       launch_residual_and_eval(s, h->n, h->m, h->nI, h->lamb, h->delta, h->H, h->ldh, h->J, h->ldj, h->idxI,
                                h->pos, h->mask, h->rhs, h->sol, h->guard.rs_v, h->guard.rs_lv, h->guard.rs_u, h->guard.rs_wy, h->partial,
                                PGF_GEMVT_PARTS, h->guard.rs_r, h->guard.rs_red, h->xn, h->yn, h->b, h->q, h->rho, h->c, h->w,
@@ -133,6 +210,7 @@ int pgf_newton_solve(pgf_handle h, const double *x, const double *y, const doubl
   if ((rc = up(h, h->g, g, h->n * sizeof(double)))) return rc;
   if ((rc = up(h, h->c, c, h->m * sizeof(double)))) return rc;
   h->eval_fresh = false;
+  drop_norm(h);
   if (h->unsym.form) {
     if (inertia_check) return fail(h, PGF_INVALID, "no inertia with an unsymmetric formulation (LU)");
     if ((rc = unsym_step_core(h))) return rc;
@@ -218,6 +296,7 @@ int pgf_qp_set_vectors(pgf_handle h, const double *q, const double *b) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
   h->ls.hat_fresh = false;
+  drop_norm(h);
   h->unsym.h_has_lag_only = true;
   return PGF_OK;
 }
@@ -240,6 +319,7 @@ int pgf_qp_set_problem(pgf_handle h, const double *Q, int64_t ldq, const double 
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->qp_mode = true;
   h->ls.hat_fresh = false;
+  drop_norm(h);
   h->unsym.h_has_lag_only = true;
   return PGF_OK;
 }
@@ -255,6 +335,7 @@ int pgf_qp_set_point(pgf_handle h, const double *x, const double *y) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->point_set = true;
   h->eval_fresh = false;
+  drop_norm(h);
   return PGF_OK;
 }
 
@@ -330,6 +411,30 @@ static int qp_refresh_mask(pgf_handle h, double tau, bool force, int *changed_ou
   double f_x, f_x0, f_d;
   tau_factors(h, tau, &use_tau, &f_x, &f_x0, &f_d);
   hipStream_t s = h->stream;
+  if (!h->sparse && h->unb.no_finite_bound && unbounded_front()) {
+    // No finite bound: the mask at ANY point is empty (active_flag compares with -inf and +inf; a
+    // NaN compares false).  It, the identity lists and the counts are on the device from the first
+    // such call on; the sizes are exact, so the step is never speculative and never redone for them,
+    // and its residual and reduced rhs take the multi-workgroup launch (newton_core_async, |A| = 0).
+    const bool same = h->mask_set && h->unb.lists_ready;
+    if (!h->unb.lists_ready) {
+      launch_unbounded_sets(s, h->n, h->mask, h->idxI, h->pos, h->counts);
+      h->unb.lists_ready = true;
+      h->nI = h->n;
+      h->nA = 0;
+      h->N = h->n + h->m;
+      h->counts_known = true;
+    }
+    if (changed_out) *changed_out = (force || !same) ? 1 : 0;
+    ++h->dbg.stat_unb_fronts;
+    if (force || !same) {  // (what adopt_index_sets does for a mask that was re-set)
+      h->mask_set = true;
+      invalidate_factor(h);
+    }
+    return PGF_OK;
+  }
+  ++h->dbg.stat_compactions;
+  h->unb.lists_ready = false;
   if (force && !h->sparse) {
     // the mask, straight into h->mask, and its compaction in one launch
     const bool spec = in_step && h->counts_known && step_spec();
@@ -394,6 +499,7 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
     launch_copy(h->stream, h->yhat, h->y, h->m);
   }
   if (rho != h->rho) h->eval_fresh = false;  // g depends on rho
+  drop_norm(h);                              // (the norm on the outer point and dt besides)
   h->dt = dt;
   h->lamb = 1.0 / dt;
   h->rho = rho;
@@ -414,6 +520,9 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
 // dense, ONE copy of the status block (the factorisation's and the chained solve's status words
 // are gathered into it by the step update, DenseLdlt::defer_status).
 static int enqueue_qp_step(pgf_handle h) {
+  h->hb.armed = false;
+  drop_norm(h);
+  h->hb.t_enqueued = now_s();
   qp_eval(h);
   bool did_factor;
   const bool armed = h->fac.inject_helper_failure != 0;
@@ -437,6 +546,11 @@ static int enqueue_qp_step(pgf_handle h) {
   } else if (eval_ahead()) {
     qp_eval(h);
   }
+  if (h->flight.fused_norm_done) {  // (the combine launch hands the block back: no copy, hb_wait spins)
+    h->flight.fused_norm_done = false;
+    h->hb.armed = h->hb.norm_fresh = true;
+    return PGF_OK;
+  }
   return down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double));
 }
 
@@ -446,6 +560,7 @@ static int enqueue_qp_step(pgf_handle h) {
 static int redo_step(pgf_handle h) {
   if (!h->ls.want) swap_point(h);
   h->eval_fresh = false;  // (g, c were evaluated ahead at the point that is discarded)
+  drop_norm(h);
   return enqueue_qp_step(h);
 }
 
@@ -523,30 +638,31 @@ static int qp_sync_step(pgf_handle h, int *n_neg, double *diff) {
   if (h->unsym.form) return unsym_qp_sync(h, n_neg, diff);
   hipError_t e;
   int rc;
+  bool awaited = false;
   if ((rc = band_status_sync(h))) return rc;
   if (!h->sparse) {
-    // the step's one wait: its status block
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // the step's one wait: its status block (hb_wait: none, if pgf_qp_residual_norm has taken it)
+    if ((rc = hb_wait(h, &awaited))) return rc;
     ++h->dbg.stat_host_syncs;
     bool redone;
     if ((rc = settle_spec(h, &redone))) return rc;
     if (redone) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if ((rc = hb_wait(h, &awaited))) return rc;
       ++h->dbg.stat_host_syncs;
     }
     absorb_status(h);
   }
-  int st = finish_factor_state(h, &e);  // flags are only rewritten by a factor launch
+  int st = finish_factor_state(h, &e, awaited);  // flags are only rewritten by a factor launch
   if (st == 2) {
     // the chain's helper workgroups failed their checks (off now): the step is computed again
     // from the point it started at
     if ((rc = redo_step(h))) return rc;
     if (!h->sparse) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if ((rc = hb_wait(h, &awaited))) return rc;
       ++h->dbg.stat_host_syncs;
       absorb_status(h);
     }
-    st = finish_factor_state(h, &e);
+    st = finish_factor_state(h, &e, awaited);
     if (st == 2) return fail(h, PGF_HIP_ERROR, k_helper_msg);
   }
   if (st < 0) return hip_fail(h, e, "step");
@@ -594,6 +710,20 @@ int pgf_qp_residual_norm(pgf_handle h, double *norm_out, double *norm_out_dev) {
   // pgf_qp_sync the point is that of the step in flight; if that step turns out to have run with
   // stale index-set sizes (settle_spec), it is redone and the norm taken again at its new point.
   for (int pass = 0; pass < 2; ++pass) {
+    if (h->hb.norm_fresh) {
+      // The tail's last launch left this point's norm in the status block (bit for bit what the
+      // launch below gives) and the block in h_stat.  A device slot: one workgroup stores the norm
+      // there and hands the block back again behind it -- the slot is written before the word the
+      // host waits for, so another stream may read it as soon as this returns.
+      if (norm_out_dev)
+        launch_handback_store(h->stream, h->stat, STAT_COPY, STAT_NORM, h->hb.dev, ++h->hb.issued, norm_out_dev);
+      if ((rc = hb_wait(h))) return rc;
+      bool redone = false;
+      if (h->step_pending && (rc = settle_spec(h, &redone))) return rc;
+      if (!redone) break;
+      qp_eval(h);
+      continue;
+    }
     launch_unscaled_res_norm(h->stream, h->n, h->m, h->dt, h->xhat, h->yhat, h->x, h->y, h->g, h->c,
                              h->lb, h->ub, h->red, h->scal + 1, norm_out_dev, h->ticket + 1);
     if ((rc = down(h, h->h_scal + 1, h->scal + 1, sizeof(double)))) return rc;

@@ -155,6 +155,7 @@ int unsym_qp_step_async(pgf_handle h, unsigned policy, double tau) {
   if ((rc = unsym_step_core(h))) return rc;
   swap_point(h);
   h->eval_fresh = false;
+  drop_norm(h);
   if ((rc = down(h, h->h_stat, h->stat, STAT_COPY * sizeof(double)))) return rc;
   h->step_pending = true;
   return PGF_OK;
@@ -177,6 +178,8 @@ int pgf_set_formulation(pgf_handle h, int form) {
   if (h->step_pending) return fail(h, PGF_NOT_READY, "pgf_qp_sync the step in flight first");
   h->unsym.form = form;
   invalidate_factor(h);
+  h->unb.lists_ready = false;  // (the unsymmetric steps write the mask and the lists their own way)
+  drop_norm(h);
   // a handle that goes back to Symmetric gives the (n + m) x ld array of its LU back
   if (form == PGF_FORM_SYMMETRIC && h->unsym.ulu.A) {
     (void)hipSetDevice(h->device);

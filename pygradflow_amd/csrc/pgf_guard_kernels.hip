@@ -6,6 +6,7 @@
 // shares dot products with (pgf_reduce_dev.h).
 #include "pgf_kernels.h"
 #include "pgf_reduce_dev.h"
+#include "pgf_step_dev.h"
 
 // ---------------------------------------------------------------- residual of the reduced system
 // v <- the reduced solution's variable part scattered to the full index set (zero on the
@@ -250,7 +251,44 @@ __global__ __launch_bounds__(256) void k_rows_jh(int m, int n, int jb, const dou
 // (dot1 arrives in g, dot2 in u; nparts == 0: the plain copies of the m == 0 branch), and
 // r[pos[t]] = rhs[pos[t]] - lv[t] where the variable is inactive; lane n + k takes the constraint row
 // k from wy.  The maxima: atomicMax on bit patterns (red zeroed by k_step_update).
-__global__ __launch_bounds__(64) void k_tail_combine(int n, int m, int nI, int nparts,
+//
+// The hand-back of a dense qp step (TailHandback, pgf_solver::hb): the `nstat' doubles of the status
+// block go to coherent host memory, the norm besides to `slot' (device memory, may be null), and
+// behind a system-scope fence the sequence word h_stat[nstat] -- plain vector stores by one
+// workgroup; the host spins on the word.  (Agent-scope loads: the maxima were written by atomics
+// of other workgroups of the same launch when k_tail_combine's last workgroup gets here.)
+__device__ __forceinline__ void handback_store(const double *stat, int nstat, int norm_at, double *h_stat,
+                                               unsigned long long seq, double *slot) {
+  if ((int)threadIdx.x < nstat) {
+    const unsigned long long w = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(stat) + threadIdx.x,
+                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    reinterpret_cast<unsigned long long *>(h_stat)[threadIdx.x] = w;
+    if (slot && (int)threadIdx.x == norm_at) slot[0] = __longlong_as_double((long long)w);
+    __threadfence_system();
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(h_stat) + nstat, seq, __ATOMIC_RELEASE,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// the step's last launch when pgf_qp_residual_norm was given a device slot: one workgroup
+__global__ __launch_bounds__(64) void k_handback_store(const double *stat, int nstat, int norm_at, double *h_stat,
+                                                       unsigned long long seq, double *slot) {
+  handback_store(stat, nstat, norm_at, h_stat, seq, slot);
+}
+void launch_handback_store(hipStream_t s, const double *stat, int nstat, int norm_at, double *h_stat,
+                           unsigned long long seq, double *slot) {
+  hipLaunchKernelGGL(k_handback_store, dim3(1), dim3(64), 0, s, stat, nstat, norm_at, h_stat, seq, slot);
+}
+
+// NORM (256 lanes: workgroup b owns the entries [256 b, 256 b + 256) of the n + m concatenation,
+// k_unscaled_res_norm's partition): each workgroup besides forms its partial of the unscaled
+// residual's squares at the new point -- b_unscaled_res_sq's expressions and in-block order, with the
+// g its lanes have just stored and the c k_rows_jh left complete -- and the last one to finish sums
+// the partials (last_block_reduce, a ticket of its own) into th.norm_out, the value
+// k_unscaled_res_norm gives at that point bit for bit, and hands the status block back.
+template <int LANES, bool NORM>
+__global__ __launch_bounds__(LANES) void k_tail_combine(int n, int m, int nI, int nparts,
                                                      const double *__restrict__ partial1,
                                                      const double *__restrict__ partial2,
                                                      const double *__restrict__ q, double *__restrict__ tmpn,
@@ -259,11 +297,12 @@ __global__ __launch_bounds__(64) void k_tail_combine(int n, int m, int nI, int n
                                                      const int *__restrict__ pos, const double *rhs,  // may alias r
                                                      const double *__restrict__ sol,
                                                      const double *__restrict__ wy, double *r,
-                                                     unsigned long long *__restrict__ red) {
-  const int t = blockIdx.x * 64 + threadIdx.x;
+                                                     unsigned long long *red,  // (inside th.stat)
+                                                     TailHandback th) {
+  const int t = blockIdx.x * LANES + threadIdx.x;
   double ar = 0.0, ab = 0.0, as = 0.0;
   int i = -1;
-  double ks = 0.0;
+  double ks = 0.0, gnew = 0.0;
   if (t < n) {
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll 8
@@ -277,7 +316,8 @@ __global__ __launch_bounds__(64) void k_tail_combine(int n, int m, int nI, int n
     const double d1 = g[t], d2 = u[t];
     tmpn[t] = tv;
     u[t] = uv;
-    g[t] = d1 + sgn * tv;
+    gnew = d1 + sgn * tv;
+    g[t] = gnew;
     ks = d2 + sgn * uv;
     lv[t] = ks;
     if (!mask[t]) i = pos[t];
@@ -300,10 +340,22 @@ __global__ __launch_bounds__(64) void k_tail_combine(int n, int m, int nI, int n
     ab = fmax(ab, __shfl_down(ab, off));
     as = fmax(as, __shfl_down(as, off));
   }
-  if (threadIdx.x == 0) {
+  if ((threadIdx.x & 63) == 0) {
     atomicMax(&red[0], (unsigned long long)__double_as_longlong(ar));
     atomicMax(&red[1], (unsigned long long)__double_as_longlong(ab));
     atomicMax(&red[2], (unsigned long long)__double_as_longlong(as));
+    if (NORM) __threadfence();  // (performed before this workgroup's ticket: the last one reads them)
+  }
+  if constexpr (NORM) {
+    double sq = 0.0;
+    if (t < n)
+      sq = unscaled_sq_x(th.dt, th.xhat[t], th.x[t], gnew, th.lb[t], th.ub[t]);
+    else if (t < n + m)
+      sq = unscaled_sq_y(th.dt, th.yhat[t - n], th.y[t - n], th.c[t - n]);
+    block_sq_partial(sq, th.red);
+    if (!last_block_reduce(th.red, gridDim.x, th.norm_out, th.ticket)) return;
+    __syncthreads();  // (lane 0 has just stored the norm into the block)
+    handback_store(th.stat, th.nstat, -1, th.h_stat, th.seq, nullptr);
   }
 }
 
@@ -313,7 +365,8 @@ void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double 
                                     const double *rhs, const double *sol, const double *v, double *lv, double *u,
                                     double *wy, double *partial, int nparts, double *r, double *red3,
                                     const double *xn, const double *yn, const double *b, const double *q,
-                                    double rho, double *c, double *w, double *tmpn, double *g) {
+                                    double rho, double *c, double *w, double *tmpn, double *g,
+                                    const TailHandback *th) {
   const int N = nI + m;
   const int jb = (m + 3) / 4, hb = (n + 3) / 4;
   if (jb + hb)
@@ -328,9 +381,14 @@ void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double 
     hipLaunchKernelGGL(k_gemvT_partial2, dim3((n + 255) / 256, used), dim3(256), 0, s, m, n, J, ldj, rho, c, yn, w,
                        sol + nI, chunk, partial, p2);
   }
-  if (n || N)
-    hipLaunchKernelGGL(k_tail_combine, dim3((n + m + 63) / 64), dim3(64), 0, s, n, m, nI, used, partial, p2, q, tmpn,
-                       g, u, lv, mask, pos, rhs, sol, wy, r, reinterpret_cast<unsigned long long *>(red3));
+  if (th && (n || N))
+    hipLaunchKernelGGL((k_tail_combine<256, true>), dim3((n + m + 255) / 256), dim3(256), 0, s, n, m, nI, used,
+                       partial, p2, q, tmpn, g, u, lv, mask, pos, rhs, sol, wy, r,
+                       reinterpret_cast<unsigned long long *>(red3), *th);
+  else if (n || N)
+    hipLaunchKernelGGL((k_tail_combine<64, false>), dim3((n + m + 63) / 64), dim3(64), 0, s, n, m, nI, used, partial,
+                       p2, q, tmpn, g, u, lv, mask, pos, rhs, sol, wy, r,
+                       reinterpret_cast<unsigned long long *>(red3), TailHandback{});
 }
 
 // ---- matrix norms for the normwise backward error of the residual guard (pgf_api_guard.hip)

@@ -28,6 +28,8 @@ void launch_mask_compact_rhs(hipStream_t s, int n, int m, int nI, int use_tau, d
                              const double *c, const double *slb, const double *sub, uint8_t *mask, int *idxI,
                              int *idxA, int *pos, int *counts, int expect, double *F, double *b0full,
                              double *rhs);
+// mask <- 0, idxI = pos <- the identity, counts <- (n, 0, ., 0): a handle without a finite bound
+void launch_unbounded_sets(hipStream_t s, int n, uint8_t *mask, int *idxI, int *pos, int *counts);
 // xhat <- x, yhat <- y, (slb, sub) <- lamb (lb, ub) in one launch
 void launch_advance_outer(hipStream_t s, int n, int m, double lamb, const double *x, const double *y,
                           const double *lb, const double *ub, double *xhat, double *yhat, double *slb,
@@ -119,6 +121,20 @@ void launch_symmetrize(hipStream_t s, double *A, int64_t ld, int N);
 // ||H||_inf, ||J||_inf, ||J||_1 -> norms3 (device), for the normwise backward error of the guard
 void launch_matrix_norms(hipStream_t s, int n, int m, const double *H, int64_t ldh, const double *J,
                          int64_t ldj, double *norms3);
+// What k_tail_combine takes to leave the new point's unscaled residual norm and hand the step's
+// status block back to the host (launch_residual_and_eval_fused; x, y: the NEW point): red --
+// (n + m + 255) / 256 partials; norm_out -- inside the block stat[0, nstat); h_stat -- coherent host
+// memory, nstat doubles and the sequence word behind them, which receives seq
+struct TailHandback {
+  double dt;
+  const double *xhat, *yhat, *x, *y, *c, *lb, *ub;
+  double *red, *norm_out;
+  unsigned *ticket;
+  const double *stat;
+  int nstat;
+  double *h_stat;
+  unsigned long long seq;
+};
 // launch_residual_and_eval(..., prepared = true) with the row passes over J and H in one launch and
 // the sums, the H pass's epilogue and the residual in another: at most three launches, same values
 void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double delta, const double *H, int64_t ldh,
@@ -126,7 +142,12 @@ void launch_residual_and_eval_fused(hipStream_t s, int n, int m, int nI, double 
                                     const double *rhs, const double *sol, const double *v, double *lv, double *u,
                                     double *wy, double *partial, int nparts, double *r, double *red3,
                                     const double *xn, const double *yn, const double *b, const double *q,
-                                    double rho, double *c, double *w, double *tmpn, double *g);
+                                    double rho, double *c, double *w, double *tmpn, double *g,
+                                    const TailHandback *th = nullptr);
+// the status block (nstat doubles, the norm at norm_at) to coherent host memory, the norm to slot
+// (device, may be null), then the sequence word h_stat[nstat] <- seq: one workgroup
+void launch_handback_store(hipStream_t s, const double *stat, int nstat, int norm_at, double *h_stat,
+                           unsigned long long seq, double *slot);
 // launch_kkt_residual of the solve just made AND the evaluation of g, c at the new point (xn, yn)
 // in one pass over H and two over J (the separate kernels: two and four); partial: 2 * nparts * n
 void launch_residual_and_eval(hipStream_t s, int n, int m, int nI, double lamb, double delta, const double *H,

@@ -166,24 +166,23 @@ __global__ void k_mask_diff(int n, const uint8_t *__restrict__ a, const uint8_t 
   b_mask_diff(n, a, b, out);
 }
 
-// The last workgroup to finish (atomic ticket) sums the per-block partials of red[0, nb) in
-// b_final_reduce's fixed order, every workgroup's partial having been published by a release
-// fence before its ticket; the ticket word is reset for the next launch.  Returns true in the
-// workgroup that did it.
-__device__ __forceinline__ bool last_block_reduce(const double *red, int nb, double *out,
-                                                  unsigned *ticket) {
-  __shared__ bool last;
-  __syncthreads();  // (red[blockIdx.x] is stored by lane 0 after the block's own barrier)
-  if (threadIdx.x == 0) {
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == (unsigned)(nb - 1);
+// (last_block_reduce: pgf_step_dev.h)
+
+// A handle without a finite bound (pgf_solver::unb): what k_mask_compact writes for an empty active
+// set, whatever the point -- mask 0, idxI = pos = the identity, counts (n, 0, ., 0) -- written once
+__global__ __launch_bounds__(256) void k_unbounded_sets(int n, uint8_t *__restrict__ mask,
+    int *__restrict__ idxI, int *__restrict__ pos, int *__restrict__ counts) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j < n) {
+    mask[j] = 0;
+    idxI[j] = j;
+    pos[j] = j;
   }
-  __syncthreads();
-  if (!last) return false;
-  __threadfence();
-  b_final_reduce(red, nb, out, 1);
-  if (threadIdx.x == 0) *ticket = 0u;
-  return true;
+  if (j == 0) {
+    counts[0] = n;
+    counts[1] = 0;
+    counts[3] = 0;
+  }
 }
 
 // Optional extras of the step-update launch (StepExtras, nullptr members are skipped):
@@ -328,6 +327,10 @@ void launch_mask_compact_rhs(hipStream_t s, int n, int m, int nI, int use_tau, d
   const ActiveArgs a{use_tau, lamb, f_x, f_x0, f_d, xhat, x, g, slb, sub};
   hipLaunchKernelGGL(k_mask_compact_rhs, dim3(1), dim3(1024), 0, s, n, a, mask, idxI, idxA, pos, counts, expect,
                      m, nI, dt, fact, yhat, y, c, F, b0full, rhs);
+}
+
+void launch_unbounded_sets(hipStream_t s, int n, uint8_t *mask, int *idxI, int *pos, int *counts) {
+  hipLaunchKernelGGL(k_unbounded_sets, dim3(n ? (n + 255) / 256 : 1), dim3(256), 0, s, n, mask, idxI, pos, counts);
 }
 
 void launch_advance_outer(hipStream_t s, int n, int m, double lamb, const double *x, const double *y,

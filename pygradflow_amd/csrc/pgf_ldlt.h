@@ -160,7 +160,8 @@ void ldlt_chain_discard(DenseLdlt &f, int word);
 // wait and read flags: returns 0 ok / 1 singular / 2 the diagonal chain's helper workgroups
 // failed their checks (they are switched off, factorise again); sets f.n_neg.  (A chained solve that failed
 // its own checks is reported by ldlt_chain_check after any host synchronisation.)
-int ldlt_finish(DenseLdlt &f, hipError_t *err);
+// (awaited: the caller has already seen everything enqueued on f.stream complete -- no runtime call)
+int ldlt_finish(DenseLdlt &f, hipError_t *err, bool awaited = false);
 // sol <- K^{-1} rhs on device vectors of length N (rhs preserved if rhs != sol)
 hipError_t ldlt_solve_async(DenseLdlt &f, const double *rhs, double *sol);
 // backward half only: sol <- L^{-T} w, w already equals D^{-1} L^{-1} rhs (row N trick)

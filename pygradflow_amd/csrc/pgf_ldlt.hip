@@ -683,8 +683,8 @@ hipEvent_t prof_event(PgfProfile *p) {
   return e;
 }
 
-int ldlt_finish(DenseLdlt &f, hipError_t *err) {
-  hipError_t e = hipStreamSynchronize(f.stream);
+int ldlt_finish(DenseLdlt &f, hipError_t *err, bool awaited) {
+  hipError_t e = awaited ? hipSuccess : hipStreamSynchronize(f.stream);
   if (err) *err = e;
   if (e != hipSuccess) return -1;
   ldlt_chain_timing_dump();  // no-op unless PGF_CHAIN_TIMING is set

@@ -320,6 +320,26 @@ __device__ __forceinline__ void b_final_reduce(const double *__restrict__ red, i
   }
 }
 
+// The last workgroup to finish (atomic ticket) sums the per-block partials of red[0, nb) in
+// b_final_reduce's fixed order, every workgroup's partial having been published by a release
+// fence before its ticket; the ticket word is reset for the next launch.  Returns true in the
+// workgroup that did it.
+__device__ __forceinline__ bool last_block_reduce(const double *red, int nb, double *out,
+                                                  unsigned *ticket) {
+  __shared__ bool last;
+  __syncthreads();  // (red[blockIdx.x] is stored by lane 0 after the block's own barrier)
+  if (threadIdx.x == 0) {
+    __threadfence();
+    last = atomicAdd(ticket, 1u) == (unsigned)(nb - 1);
+  }
+  __syncthreads();
+  if (!last) return false;
+  __threadfence();
+  b_final_reduce(red, nb, out, 1);
+  if (threadIdx.x == 0) *ticket = 0u;
+  return true;
+}
+
 // ---------------------------------------------------------------- linear-quadratic evaluation
 // out[r] = M[r, :] . v + sgn * add[r]     (c = A x - b ;  g = Q x + (q + A'(rho c + y)))
 __device__ __forceinline__ void b_gemv_rows(int rows, int cols,
@@ -367,30 +387,41 @@ __device__ __forceinline__ void b_mult_vec(int m, double rho, const double *__re
 }
 
 // squared entries of the UNSCALED residual with its own mask (ImplicitFunc.value_at,
-// implicit_func.py:131-161): per-block partial sums -> red
+// implicit_func.py:131-161): per-block partial sums -> red.  (The entry expressions and the block's
+// sum on their own: k_tail_combine forms the same partials from the g it has just computed.)
+__device__ __forceinline__ double unscaled_sq_x(double dt, double xhat, double x, double g, double lb,
+                                                double ub) {
+  double p = xhat - dt * g;
+  const bool act = (p < lb - ACTIVE_EPS) || (p > ub + ACTIVE_EPS);
+  if (act) p = fmin(fmax(p, lb), ub);
+  const double f = x - p;
+  return f * f;
+}
+__device__ __forceinline__ double unscaled_sq_y(double dt, double yhat, double y, double c) {
+  const double f = y - (yhat + dt * c);
+  return f * f;
+}
+__device__ __forceinline__ void block_sq_partial(double sq, double *__restrict__ red) {  // 256 lanes
+  __shared__ double part[4];
+  sq = wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) red[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+}
 __device__ __forceinline__ void b_unscaled_res_sq(
     int n, int m, double dt, const double *__restrict__ xhat, const double *__restrict__ yhat,
     const double *__restrict__ x, const double *__restrict__ y, const double *__restrict__ g,
     const double *__restrict__ c, const double *__restrict__ lb, const double *__restrict__ ub,
     double *__restrict__ red) {
-  __shared__ double part[4];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double sq = 0.0;
   if (i < n) {
-    double p = xhat[i] - dt * g[i];
-    const bool act = (p < lb[i] - ACTIVE_EPS) || (p > ub[i] + ACTIVE_EPS);
-    if (act) p = fmin(fmax(p, lb[i]), ub[i]);
-    const double f = x[i] - p;
-    sq = f * f;
+    sq = unscaled_sq_x(dt, xhat[i], x[i], g[i], lb[i], ub[i]);
   } else if (i < n + m) {
     const int r = i - n;
-    const double f = y[r] - (yhat[r] + dt * c[r]);
-    sq = f * f;
+    sq = unscaled_sq_y(dt, yhat[r], y[r], c[r]);
   }
-  sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0) red[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
+  block_sq_partial(sq, red);
 }
 
 // ---------------------------------------------------------------- termination measures
