@@ -384,7 +384,33 @@ int pgf_profile_read_ex(pgf_handle h, double *out, int count);
  * workgroups of instances that do not refine return at once.  No factor is touched, so the lean
  * second step stays lean.  pgf_batch_debug_ctl_refine_stats counts refined steps and rounds;
  * pgf_batch_debug_band_wide_stats and pgf_batch_debug_border_stats count a round's solve phase as
- * a solve phase (split off: its reduction as a reduction). */
+ * a solve phase (split off: its reduction as a reduction).
+ *
+ * PGF_BATCH_LINE_SEARCH opens the Globalized policy (GlobalizedNewtonMethod.step, newton.py:218-304)
+ * to a device batch: dense instances, banded ones on the narrow route and, with PGF_BATCH_WIDE_BAND,
+ * on the wide route.  Together with any of PGF_BATCH_BORDER, PGF_BATCH_WIDE_BORDER,
+ * PGF_BATCH_BAND_CTL, PGF_BATCH_BORDER_CTL, PGF_BATCH_CTL_REFINE it is PGF_INVALID with a message on
+ * the first handle, before any handle is read further; an unsymmetric formulation is refused as for
+ * every batch.  Creation reserves each handle's line-search vectors and the batch's blocks.  On
+ * such a batch pgf_batch_step_async takes PGF_STEP_RECOMPUTE_MASK | PGF_STEP_REFACTOR |
+ * PGF_STEP_LINE_SEARCH (the bit without both companions: PGF_INVALID, as on the handle) besides
+ * the other policies; pgf_batch_ctl_iterate refuses the bit.  Per instance, as on the single handle
+ * (pgf_qp_step above): the mask from the instance's current point with the caller's tau
+ * (newton.py:244), the direction solved at its OUTER point (:248), the merits with the tau-less
+ * mask of their own point (:251, :277), the Armijo term with the reference's sign and 1e-4 (:281-285),
+ * the ladder alpha = 2^-k with 30 trials (:270-289), no trial when merit0 <= newton_tol (:254), the
+ * new point measured from the outer point and clipped (:296, step_solver.py:25-48).  Every
+ * instance's search runs in the same launches behind the step update: the step takes ONE stream
+ * wait, in pgf_batch_sync, whatever the batch size and the trial counts.  pgf_batch_sync reports
+ * status[i] = PGF_LINE_SEARCH when no trial was accepted (newton.py:291-292): the instance's point
+ * has not moved, bit for bit, and diff[i] = 0; PGF_SINGULAR as for the other policies (no search is
+ * applied, the point stays); a frozen instance sits the step out, and keeps its statistics.  An
+ * instance the accuracy guard repairs on its handle runs its search there (extra waits).  Without
+ * the flag the bit is refused as before ("served by single handles only").
+ * pgf_batch_set_line_search: newton_tol (Params.newton_tol, default 1e-8) for the batch and its
+ * handles; negative or NaN, or a batch without the flag: PGF_INVALID.
+ * pgf_batch_line_search_stats: pgf_qp_line_search_stats per instance for the last such step --
+ * arrays of B, trial_merits B x 30; any pointer may be NULL; PGF_NOT_READY before the first one. */
 typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BAND 1u
 #define PGF_BATCH_BAND_CTL 2u
@@ -392,6 +418,10 @@ typedef struct pgf_batch_s *pgf_batch;
 #define PGF_BATCH_WIDE_BORDER 8u
 #define PGF_BATCH_BORDER_CTL 16u /* with PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL */
 #define PGF_BATCH_CTL_REFINE 32u /* with PGF_BATCH_BAND_CTL */
+#define PGF_BATCH_LINE_SEARCH 64u /* alone or with PGF_BATCH_WIDE_BAND */
+int pgf_batch_set_line_search(pgf_batch b, double newton_tol);
+int pgf_batch_line_search_stats(pgf_batch b, double *alpha, int *trials, double *merit0, double *slope,
+                                double *trial_merits);
 int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out);
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);
 int pgf_batch_destroy(pgf_batch b);
@@ -688,6 +718,13 @@ int pgf_batch_debug_ctl_refine_stats(pgf_batch b, int *refined_steps, int *round
  * batch was created (PGF_BATCH_BORDER; arrays of `count` ints, counted on the device, synchronises).
  * Zeros on a batch that is not bordered.  Any pointer may be NULL. */
 int pgf_batch_debug_border_stats(pgf_batch b, int *factor_phases, int *solve_phases);
+/* The last step with PGF_STEP_LINE_SEARCH of a batch (PGF_BATCH_LINE_SEARCH): *stage_launches -- the
+ * launches its line-search stage enqueued for the whole batch (the direction's images u = A dx,
+ * v = Q dx + A'(rho u + dy), the ladder, the finish; newton.py:259-296 in one pass), which depend
+ * neither on the batch size nor on any trial count; *host_waits -- the stream waits from
+ * pgf_batch_step_async to the end of pgf_batch_sync, 1 unless an instance was repaired on its
+ * handle.  Zeros before the first such step.  Either pointer may be NULL. */
+int pgf_batch_debug_line_search_stats(pgf_batch b, int *stage_launches, int *host_waits);
 /* The 64-bit hash a banded handle keeps of its pattern (host only, no device needed): FNV-1a over
  * n, m, bw, the entry counts and every index array as pgf_sparse_set_pattern receives them. */
 int pgf_sparse_pattern_hash(int n, int m, int bw, const int *pos, int nnzH, const int *Hptr,

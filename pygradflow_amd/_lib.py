@@ -33,6 +33,7 @@ BATCH_BORDER = 4
 BATCH_WIDE_BORDER = 8
 BATCH_BORDER_CTL = 16
 BATCH_CTL_REFINE = 32
+BATCH_LINE_SEARCH = 64
 FORM_SYMMETRIC, FORM_STANDARD, FORM_EXTENDED, FORM_ASYMMETRIC = 0, 1, 2, 3
 FORMULATIONS = {"Symmetric": 0, "Standard": 1, "Extended": 2, "Asymmetric": 3}
 
@@ -141,6 +142,9 @@ SIGNATURES = {
     "pgf_batch_debug_ctl_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_debug_ctl_refine_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_batch_debug_border_stats": (C.c_int, [_h, _ip, _ip]),
+    "pgf_batch_set_line_search": (C.c_int, [_h, C.c_double]),
+    "pgf_batch_line_search_stats": (C.c_int, [_h, _dp, _ip, _dp, _dp, _dp]),
+    "pgf_batch_debug_line_search_stats": (C.c_int, [_h, _ip, _ip]),
     "pgf_sparse_pattern_hash": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, _ip, _ip, _ip, C.c_int,
                                           _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_uint64)]),
     "pgf_comm_unique_id": (C.c_int, [C.c_void_p]),

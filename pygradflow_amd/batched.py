@@ -124,11 +124,24 @@ class BatchedDeviceNewton:
     rejected only when the measure stays above the handle's ``refine_fail``.  Every banded step of
     the loop then carries the launches of two rounds, whose workgroups return at once for instances
     that do not refine.  ``ctl_refine_stats()`` counts refined steps and rounds.
+
+    ``"Globalized", line_search=True`` (``PGF_BATCH_LINE_SEARCH``, alone or with ``wide_band``) runs
+    the reference's ``GlobalizedNewtonMethod.step`` for every instance of a dense or band batch, each
+    instance's Armijo line search in the same launches behind the step update: one host wait per
+    step.  ``newton_tol`` is ``Params.newton_tol`` for the handles and the batch.  ``step_local()``
+    reports an instance whose search accepted no trial as ``PGF_LINE_SEARCH`` in ``status`` -- its
+    point has not moved and its ``diff`` is 0 -- and raises nothing; ``line_search()`` returns the
+    last step's searches.  With another ``newton_type``, or with ``border`` / ``wide_border`` /
+    ``band_ctl`` / ``border_ctl`` / ``ctl_refine``, ``line_search=True`` is a ``ValueError``, as is a
+    negative ``newton_tol``, before any handle is built.  Without ``line_search`` a Globalized device
+    batch is refused as before; ``sequential=True, line_search=True`` is the loop of single handles
+    with the same surface (a handle's ``LineSearchError`` becomes the status).
     """
 
     def __init__(self, make_problem, num_instances, newton_type, dt, rho, device=0, rank=0,
                  world=1, group=None, tau=None, sequential=False, wide_band=False, band_ctl=False,
-                 border=False, wide_border=False, border_ctl=False, ctl_refine=False):
+                 border=False, wide_border=False, border_ctl=False, ctl_refine=False,
+                 line_search=False, newton_tol=1e-8):
         import ctypes as C
         import math
 
@@ -143,7 +156,19 @@ class BatchedDeviceNewton:
         self.lo, self.hi = shard_range(num_instances, world, rank)
         self.count = self.hi - self.lo
         self.kind = enum_name(newton_type) if not isinstance(newton_type, str) else newton_type
-        if self.kind == "Globalized" and not sequential:
+        self.line_search_on = bool(line_search)
+        self.newton_tol = float(newton_tol)
+        if self.line_search_on:
+            if self.kind != "Globalized":
+                raise ValueError(f"line_search=True is the Globalized policy's, not {self.kind}'s")
+            given = [name for name, on in (("border", border), ("wide_border", wide_border),
+                                           ("band_ctl", band_ctl), ("border_ctl", border_ctl),
+                                           ("ctl_refine", ctl_refine)) if on]
+            if given:
+                raise ValueError("line_search=True goes alone or with wide_band, not with " + ", ".join(given))
+        if not self.newton_tol >= 0.0:
+            raise ValueError("newton_tol must not be negative")
+        if self.kind == "Globalized" and not sequential and not self.line_search_on:
             raise NotImplementedError(
                 "Globalized: not in the device batch (its line search is per handle); "
                 "sequential=True runs the instances through their own handles")
@@ -156,7 +181,7 @@ class BatchedDeviceNewton:
             prob = make_problem(i)
             x0, y0 = np.zeros(prob.num_vars), np.zeros(prob.num_cons)
             self.solvers.append(DeviceNewton(prob, newton_type, x0, y0, dt, rho, tau=tau,
-                                             device=device))
+                                             device=device, newton_tol=self.newton_tol))
         self._torch = torch
         self._lib, self._C = _lib, C
         self.device = torch.device("cuda", device)
@@ -182,6 +207,9 @@ class BatchedDeviceNewton:
             rc = self._create(lib, arr, C.byref(b))
             _lib.check(rc, self.solvers[0]._hd.h, "pgf_batch_create")
             self._b = b
+            if self.line_search_on:
+                _lib.check(lib.pgf_batch_set_line_search(b, self.newton_tol), batch=b,
+                           what="pgf_batch_set_line_search")
             if self.band:
                 self.band_block = int(self.solvers[0]._hd.plan.block_size)
                 self.band_border = int(self.solvers[0]._hd.plan.k)
@@ -200,7 +228,8 @@ class BatchedDeviceNewton:
             (self._lib.BATCH_BORDER if getattr(self, "border", False) else 0) | \
             (self._lib.BATCH_WIDE_BORDER if getattr(self, "wide_border", False) else 0) | \
             (self._lib.BATCH_BORDER_CTL if getattr(self, "border_ctl", False) else 0) | \
-            (self._lib.BATCH_CTL_REFINE if getattr(self, "ctl_refine", False) else 0)
+            (self._lib.BATCH_CTL_REFINE if getattr(self, "ctl_refine", False) else 0) | \
+            (self._lib.BATCH_LINE_SEARCH if getattr(self, "line_search_on", False) else 0)
         if flags:
             return lib.pgf_batch_create_ex(handles, self.count, flags, out)
         return lib.pgf_batch_create(handles, self.count, out)
@@ -280,7 +309,7 @@ class BatchedDeviceNewton:
         if cnt == 0:
             return status, n_neg, diff
         if self._b is None:
-            from .errors import StepSolverError
+            from .errors import LineSearchError, StepSolverError
 
             base = self.norms.data_ptr()
             frozen = getattr(self, "_frozen", None)
@@ -292,6 +321,10 @@ class BatchedDeviceNewton:
                 except StepSolverError:
                     status[k] = self._lib.PGF_SINGULAR
                     continue
+                except LineSearchError:
+                    if not self.line_search_on:
+                        raise
+                    status[k] = self._lib.PGF_LINE_SEARCH  # (the point has not moved)
                 s.residual_norm(base + 8 * k)
             return status, n_neg, diff
         lib, b = self._lib.load(), self._b
@@ -307,6 +340,36 @@ class BatchedDeviceNewton:
     def step(self):
         self.step_local()
         return gather_residual_norms(self.norms[: self.count], self.num_instances, self.group)
+
+    def line_search(self):
+        """The last Globalized step's line searches: dict(alpha[count], trials[count],
+        merit0[count], slope[count], trial_merits[count, 30]) (``pgf_batch_line_search_stats``; with
+        ``sequential=True`` the handles' own).  A frozen instance keeps what its last search left."""
+        cnt = self.count
+        out = dict(alpha=np.zeros(cnt), trials=np.zeros(cnt, dtype=np.int32), merit0=np.zeros(cnt),
+                   slope=np.zeros(cnt), trial_merits=np.zeros((cnt, self._lib.LS_TRIALS)))
+        if self._b is None:
+            for k, s in enumerate(self.solvers):
+                one = s.line_search()
+                for key in out:
+                    out[key][k] = one[key]
+            return out
+        self._lib.check(self._lib.load().pgf_batch_line_search_stats(
+            self._b, self._lib.dptr(out["alpha"]), out["trials"].ctypes.data_as(self._C.POINTER(self._C.c_int)),
+            self._lib.dptr(out["merit0"]), self._lib.dptr(out["slope"]), self._lib.dptr(out["trial_merits"])),
+            batch=self._b, what="pgf_batch_line_search_stats")
+        return out
+
+    def line_search_stats(self):
+        """(stage_launches, host_waits) of the last Globalized step of a device batch
+        (``pgf_batch_debug_line_search_stats``): the launches its line-search stage enqueued for the
+        whole batch and the stream waits the step took."""
+        if self._b is None:
+            raise NotImplementedError("device batch only")
+        a, w = self._C.c_int(0), self._C.c_int(0)
+        self._lib.check(self._lib.load().pgf_batch_debug_line_search_stats(
+            self._b, self._C.byref(a), self._C.byref(w)), batch=self._b)
+        return a.value, w.value
 
     def points(self):
         """(x[count][n], y[count][m]) of the local instances (host copies)."""

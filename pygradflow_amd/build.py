@@ -22,6 +22,7 @@ NO_CONTRACT = [
     "pgf_batch_kernels.hip",
     "pgf_sparse.hip",
     "pgf_line_search.hip",
+    "pgf_batch_line_search.hip",
     "pgf_border.hip",
     "pgf_unsym.hip",
     "pgf_api.hip",
@@ -33,6 +34,7 @@ NO_CONTRACT = [
     "pgf_api_unsym.hip",
     "pgf_api_batch.hip",
     "pgf_api_band_batch.hip",
+    "pgf_api_batch_line_search.hip",
     "pgf_api_aux.hip",
 ]
 # The factorisations and the wide band contract freely; what must be bit-exact inside them switches

@@ -273,15 +273,20 @@ void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->strea
 void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed) {
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+  // PGF_STEP_LINE_SEARCH (PGF_BATCH_LINE_SEARCH, no border): as in batch_enqueue_step -- g, c at the
+  // outer points behind the evaluation, the mask from the current points, the residual and the step
+  // update on the tables that name the outer points, nothing moved
+  const bool search = (policy & PGF_STEP_LINE_SEARCH) != 0;
   hipStream_t s = b->stream;
   if (!b->eval_fresh) {
     band_batch_eval(b);
     b->eval_fresh = true;
   }
+  if (search) batch_ls_eval_outer(b);
   batch_launch_mask(s, b->tab, b->B, b->sc, recompute ? (force ? 2 : 1) : 0, tau);
   b->have_mask = true;
   b->stepped = true;
-  batch_launch_residual(s, b->tab, b->B, b->sc);
+  batch_launch_residual(s, search ? b->ls.otab : b->tab, b->B, b->sc);
   bandb_launch_rhs(s, b->btab, b->B, b->bsh);
   // instances whose band is still valid return at once (ctl[0] == 0); when the host knows that
   // none assembles (a Simplified step behind a good one), the launches are skipped
@@ -316,13 +321,16 @@ void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean
     bandb_launch_solve(s, b->btab, b->B, b->bsh);
   }
   ++b->stat_band_reductions;
-  bandb_launch_step_update(s, b->btab, b->B, b->bsh);
+  bandb_launch_step_update(s, search ? b->ls.obtab : b->btab, b->B, b->bsh, /*move=*/!search);
   b->eval_fresh = false;
 }
 
 int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   hipStream_t s = b->stream;
   band_batch_enqueue_step(b, policy, tau, b->all_factored);
+  // (the Globalized policy: every instance's line search directly behind the step update)
+  if (policy & PGF_STEP_LINE_SEARCH)
+    if (int rc = batch_ls_enqueue_stage(b)) return rc;
   // g and c at the new points, ahead of the host synchronisation (as pgf_batch_step_async)
   if (eval_ahead()) {
     band_batch_eval(b);
@@ -354,24 +362,42 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 // is called from sp_border_factor alone, which only sp_assemble reaches, and band_refine never
 // assembles).  All of these are the instance's arrays as the batch's factor phase left them.
 // Returns 0 when the instance's step is good now.
-static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out) {
+//
+// search (the step carried PGF_STEP_LINE_SEARCH): the step update moved nothing and the stage sat
+// the instance out (kb_ls_ladder takes the same measure against the same tolerance), so the point is
+// where the step found it and nothing goes back.  band_refine's corrections read the band, brhs and
+// bres only; its step update reads the point, so the handle is in its entered state around it --
+// (x, y) name the outer point's vectors, as while a single handle's Globalized step is in flight,
+// where pgf_qp_sync calls the same band_refine -- and leaves the repaired clipped direction.  Then
+// the handle's own ls_search, what pgf_qp_sync runs behind a settled step: PGF_LINE_SEARCH when it
+// finds no trial.
+static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_out, bool search) {
   pgf_handle h = b->hs[i];
   SparseDev &sp = h->sp;
   hipStream_t s = h->stream;
   const size_t S = (size_t)3 * sp.nred + 4;
-  launch_copy(s, h->x, h->xn, h->n);
-  launch_copy(s, h->y, h->yn, h->m);
+  if (!search) {
+    launch_copy(s, h->x, h->xn, h->n);
+    launch_copy(s, h->y, h->yn, h->m);
+  }
   std::memcpy(sp.h_bred, st, S * sizeof(double));
   sp.guarded = true;
   h->mask_set = true;
   sp.kept = b->bsh.split ? 2 : 0;
+  if (search) batch_ls_handle_enter(b, i);
+  const int refined = h->guard.stat_refined;
   int rc = band_refine(h, /*swapped=*/false, /*with_step=*/true);
+  if (search) {
+    ls_leave(h);
+    b->ls.host_waits += h->guard.stat_refined - refined;  // (one wait per round)
+  }
   sp.kept = 0;  // (outside a repair the handle's own view stays: no factors of its making)
   h->mask_set = false;
   if (rc) {
     (void)hipStreamSynchronize(s);  // (the point the step started from is back in place)
     return rc;
   }
+  if (search) return batch_ls_handle_search(b, i, diff_out);
   launch_copy(s, h->x, h->xn, h->n);
   launch_copy(s, h->y, h->yn, h->m);
   HIPCHK(h, hipStreamSynchronize(s));
@@ -381,6 +407,12 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
 
 int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
   BHIPCHK(b, hipStreamSynchronize(b->stream));
+  const bool search = b->ls.pending;
+  b->ls.pending = false;
+  if (search) {
+    ++b->ls.host_waits;
+    b->ls.have_stats = true;
+  }
   const int nred = b->bsh.nred;
   const size_t S = (size_t)3 * nred + 4;
   bool all_ok = true;
@@ -408,8 +440,9 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
         const double rel = band_residual_rel_of(st, nred);
         h->guard.stat_last_rel = rel;
         if (h->guard.refine_mode && !(rel <= h->guard.refine_tol)) {
-          rc = band_batch_repair(b, i, st, &d);
+          rc = band_batch_repair(b, i, st, &d, search);
           b->eval_fresh = false;  // the instance moved after the evaluation made ahead
+          if (search && rc == PGF_LINE_SEARCH) rc = PGF_OK;  // (repaired; its block says the rest)
           if (rc == PGF_OK) ++b->repaired;
           else if (rc != PGF_SINGULAR) return bfail(b, rc, pgf_last_error(h));
         }
@@ -419,6 +452,8 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
     if (status) status[i] = rc ? PGF_SINGULAR : PGF_OK;
     if (n_neg) n_neg[i] = b->last_neg[i];
     if (diff) diff[i] = rc ? 0.0 : d;
+    // (the Globalized policy: the instance's search decides its status and the length of its step)
+    if (search && !rc) batch_ls_report(b, i, status, diff);
   }
   b->all_factored = all_ok;
   return PGF_OK;

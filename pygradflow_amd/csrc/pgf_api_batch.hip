@@ -39,8 +39,25 @@ int pgf_batch_create(const pgf_handle *handles, int count, pgf_batch *out) {
 int pgf_batch_create_ex(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   if (!out || !handles || count <= 0 || count > 65535) return PGF_INVALID;
   if (flags & ~(PGF_BATCH_WIDE_BAND | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER | PGF_BATCH_WIDE_BORDER |
-                PGF_BATCH_BORDER_CTL | PGF_BATCH_CTL_REFINE))
+                PGF_BATCH_BORDER_CTL | PGF_BATCH_CTL_REFINE | PGF_BATCH_LINE_SEARCH))
     return PGF_INVALID;
+  // The Globalized policy: dense, narrow and wide band batches, host-driven steps.  The flag is
+  // taken off before the batch is built and the line search attached behind it.
+  if (flags & PGF_BATCH_LINE_SEARCH) {
+    if (flags & (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BORDER | PGF_BATCH_BAND_CTL | PGF_BATCH_BORDER_CTL |
+                 PGF_BATCH_CTL_REFINE))
+      return fail(handles[0], PGF_INVALID,
+                  "batch: PGF_BATCH_LINE_SEARCH goes alone or with PGF_BATCH_WIDE_BAND (no border, no "
+                  "device-resident controller)");
+    int rc = pgf_batch_create_ex(handles, count, flags & ~PGF_BATCH_LINE_SEARCH, out);
+    if (rc) return rc;
+    if ((rc = batch_ls_attach(*out))) {
+      if (handles[0]) handles[0]->err = (*out)->err;
+      pgf_batch_destroy(*out);
+      *out = nullptr;
+    }
+    return rc;
+  }
   // (a border on a wide remainder: only together with the two flags it combines)
   if ((flags & PGF_BATCH_WIDE_BORDER) &&
       (flags & (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND)) != (PGF_BATCH_BORDER | PGF_BATCH_WIDE_BAND))
@@ -206,6 +223,7 @@ int pgf_batch_destroy(pgf_batch b) {
   (void)hipSetDevice(b->device);
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   band_batch_free(b);
+  batch_ls_free(b);
   for (void *p : {(void *)b->tab, (void *)b->ctl, (void *)b->flags_out, (void *)b->diff_out,
                   (void *)b->norm_out, (void *)b->red4, (void *)b->meas_out, (void *)b->ps,
                   (void *)b->bytes, (void *)b->dctl_cs, (void *)b->dctl_cp, (void *)b->dctl_log})
@@ -293,6 +311,7 @@ int pgf_batch_advance_outer_each(pgf_batch b, const double *dt, const double *rh
   BHIPCHK(b, hipMemcpyAsync(b->bytes, b->h_bytes, (size_t)b->B, hipMemcpyHostToDevice, b->stream));
   batch_launch_advance(b->stream, b->tab, b->B, b->sc, b->bytes);
   b->eval_fresh = eval_stays;  // g depends on rho, and rejected instances moved
+  b->ls.hat_fresh = false;     // (g, c at the outer points: evaluated by the next Globalized step)
   b->outer_set = true;
   b->have_mask = false;
   b->all_factored = false;
@@ -346,10 +365,19 @@ int pgf_batch_update_active_set(pgf_batch b, double tau) {
 
 // everything of one batched Newton step, enqueued; host_knows_factored: the host's view that
 // every instance holds a valid factor (lets a Simplified step skip the factor launches)
+//
+// PGF_STEP_LINE_SEARCH (a batch created with PGF_BATCH_LINE_SEARCH): the mask comes from the current
+// points as always, but the residual, the right-hand side and the step update read the table that
+// names the OUTER points (step_solver.solve(self.orig_iterate), newton.py:248), whose g, c are
+// evaluated between the evaluation at the current points and the mask, as ls_enter orders them on
+// the handle; the step update leaves the clipped direction and moves nothing.
 static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool host_knows_factored) {
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+  const bool search = (policy & PGF_STEP_LINE_SEARCH) != 0;
+  const BInst *st = search ? b->ls.otab : b->tab;
   batch_eval(b);
+  if (search) batch_ls_eval_outer(b);
   batch_launch_mask(b->stream, b->tab, b->B, b->sc, recompute ? (force ? 2 : 1) : 0, tau);
   b->have_mask = true;
   // pivot order: free to choose when every instance refactorises (Full, or the first step of an
@@ -358,7 +386,7 @@ static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool ho
   b->cond_last = cond;
   b->cond_free = false;
   b->stepped = true;
-  batch_launch_rhs_assemble(b->stream, b->tab, b->B, b->sc, cond ? b->cond_mp : 0);
+  batch_launch_rhs_assemble(b->stream, st, b->B, b->sc, cond ? b->cond_mp : 0);
   // (condensed: the factor and solve kernels see nI rows -- their `m' is 0)
   const int Nmax = cond ? b->n : b->n + b->m, mf = cond ? 0 : b->m;
   // kernels of instances whose factor is still valid return at once (ctl[0] == 0); when the
@@ -375,7 +403,7 @@ static void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool ho
   if (cond && !force) batch_launch_cond_prep_fwd(b->stream, b->tab, b->B, b->sc);
   ldlt_batch_solve_async(b->stream, b->tab, b->B, Nmax, mf, !force, cond);
   if (cond) batch_launch_cond_y(b->stream, b->tab, b->B, b->sc);
-  batch_launch_step_update(b->stream, b->tab, b->B, b->sc, b->diff_out, b->flags_out);
+  batch_launch_step_update(b->stream, st, b->B, b->sc, b->diff_out, b->flags_out, /*move=*/!search);
   b->eval_fresh = false;
 }
 
@@ -390,17 +418,24 @@ int pgf_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   if (!b) return PGF_INVALID;
   if (!b->outer_set) return bfail(b, PGF_NOT_READY, "pgf_batch_advance_outer first");
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
-  if (policy & PGF_STEP_LINE_SEARCH)
+  const bool search = (policy & PGF_STEP_LINE_SEARCH) != 0;
+  if (search && !b->ls.on)
     return bfail(b, PGF_INVALID, "batch: PGF_STEP_LINE_SEARCH is served by single handles only");
   (void)hipSetDevice(b->device);
   const bool recompute = (policy & PGF_STEP_RECOMPUTE_MASK) != 0;
   const bool force = (policy & PGF_STEP_REFACTOR) != 0;
+  if (search && !(recompute && force))
+    return bfail(b, PGF_INVALID,
+                 "PGF_STEP_LINE_SEARCH needs PGF_STEP_RECOMPUTE_MASK | PGF_STEP_REFACTOR (the Globalized policy)");
   if (!recompute && !b->have_mask)
     return bfail(b, PGF_NOT_READY, "no active set: pgf_batch_update_active_set first");
   if (!recompute && force)
     return bfail(b, PGF_INVALID, "batch: PGF_STEP_REFACTOR needs PGF_STEP_RECOMPUTE_MASK");
   if (b->band) return band_batch_step_async(b, policy, tau);
   batch_enqueue_step(b, policy, tau, b->all_factored);
+  // (the Globalized policy: every instance's line search directly behind the step update)
+  if (search)
+    if (int rc = batch_ls_enqueue_stage(b)) return rc;
   // g and c at the new points, enqueued ahead of the host synchronisation (as pgf_qp_step_async):
   // behind it the five small launches would wait for the host one by one
   if (eval_ahead()) batch_eval(b);
@@ -472,6 +507,8 @@ static void ctl_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean
 
 int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iterations) {
   if (!b || iterations < 0) return PGF_INVALID;
+  if (policy & PGF_STEP_LINE_SEARCH)
+    return bfail(b, PGF_INVALID, "batch: PGF_STEP_LINE_SEARCH is for host-driven steps (pgf_batch_step_async)");
   if (b->band && !b->band_ctl) return bfail(b, PGF_INVALID, k_band_ctl);
   if (!b->dctl_cs) return bfail(b, PGF_NOT_READY, "pgf_batch_ctl_init first");
   if (b->step_pending) return bfail(b, PGF_NOT_READY, "pgf_batch_sync the previous step first");
@@ -482,6 +519,7 @@ int pgf_batch_ctl_iterate(pgf_batch b, unsigned policy, double tau, int iteratio
     return bfail(b, PGF_INVALID, "batch: PGF_STEP_REFACTOR needs PGF_STEP_RECOMPUTE_MASK");
   (void)hipSetDevice(b->device);
   hipStream_t s = b->stream;
+  b->ls.hat_fresh = false;  // (the loop moves the outer points)
   for (int it = 0; it < iterations; ++it) {
     // outer step of every instance at its own lambda; rejected instances go back first
     batch_launch_dctl_begin(s, b->B, b->dctl_cs, b->dctl_cp, b->ps, b->bytes);
@@ -573,7 +611,14 @@ int pgf_batch_ctl_read(pgf_batch b, double *lamb, uint8_t *accepted, double *log
 // not contract (refine_if_needed) -- then the step update from the repaired solution.  The batch's
 // stream is idle (pgf_batch_sync); the handle's buffers ARE the instance's.  Returns 0 when the
 // instance's step is good now (its point, step length and factor state are in place).
-static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
+//
+// search (the step carried PGF_STEP_LINE_SEARCH): the stage sat the instance out, so its point is
+// where the step found it.  The right-hand side in h->rhs is the outer point's and the residual and
+// the refinement read nothing of the point; the step update does, so the handle is in its entered
+// state for it ((x, y) name the outer point's vectors, as while a single handle's Globalized step is
+// in flight) and leaves the repaired clipped direction.  Then the handle's own ls_search, exactly
+// what pgf_qp_sync runs behind a settled step.  Returns PGF_LINE_SEARCH when that finds no trial.
+static int batch_repair_instance(pgf_batch b, int i, double *diff_out, bool search) {
   pgf_handle h = b->hs[i];
   if (h->sparse || !h->guard.refine_mode) return PGF_SINGULAR;
   adopt_batch_factor(h, b->h_flags[3 * i + 2], b->h_flags[3 * i + 1], b->cond_last, b->cond_mp);
@@ -583,19 +628,28 @@ static int batch_repair_instance(pgf_batch b, int i, double *diff_out) {
   if (e != hipSuccess) return hip_fail(h, e, "batched repair");
   int rc = refine_if_needed(h, /*swapped=*/false, /*with_step=*/false);
   if (rc) return rc;
+  if (search) batch_ls_handle_enter(b, i);
   enqueue_step_update(h);  // (x, y) -> (xn, yn), dx, dy, ||d||
-  launch_copy(h->stream, h->x, h->xn, h->n);
-  launch_copy(h->stream, h->y, h->yn, h->m);
+  if (search) {
+    ls_leave(h);
+  } else {
+    launch_copy(h->stream, h->x, h->xn, h->n);
+    launch_copy(h->stream, h->y, h->yn, h->m);
+  }
   if ((e = hipMemcpyAsync(h->h_scal, h->scal, sizeof(double), hipMemcpyDeviceToHost, h->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(h->stream)) != hipSuccess)
     return hip_fail(h, e, "batched repair");
   if (ldlt_chain_check(f)) return fail(h, PGF_HIP_ERROR, k_chain_msg);
   *diff_out = h->h_scal[0];
+  if (search) {
+    b->ls.host_waits += 2;  // (the residual's and the step update's above)
+    rc = batch_ls_handle_search(b, i, diff_out);
+  }
   // (host-side view only.  In the batch, kb_step_final left ctl[1] = 0 and pgf_batch_sync keeps
   // all_factored false: the instance's next step assembles K again and launches the factorisation,
   // a Simplified step included)
   invalidate_factor(h);
-  return PGF_OK;
+  return search ? rc : PGF_OK;
 }
 
 int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
@@ -605,6 +659,12 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
   (void)hipSetDevice(b->device);
   if (b->band) return band_batch_sync(b, status, n_neg, diff);
   BHIPCHK(b, hipStreamSynchronize(b->stream));
+  const bool search = b->ls.pending;
+  b->ls.pending = false;
+  if (search) {
+    ++b->ls.host_waits;
+    b->ls.have_stats = true;
+  }
   bool all_ok = true, any_repaired = false;
   for (int i = 0; i < b->B; ++i) {
     // bit 2 alone: the factorisation went through but the sampled residual of the solve is too
@@ -613,7 +673,8 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
     // reports a failed step
     if (b->h_flags[3 * i] == 4) {
       double d = 0.0;
-      if (batch_repair_instance(b, i, &d) == PGF_OK) {
+      const int rrc = batch_repair_instance(b, i, &d, search);
+      if (rrc == PGF_OK || (search && rrc == PGF_LINE_SEARCH)) {
         b->h_flags[3 * i] = 0;
         b->h_diff[i] = d;
         b->eval_fresh = false;  // the instance moved after the evaluation made ahead
@@ -638,6 +699,8 @@ int pgf_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
     if (status) status[i] = bad ? PGF_SINGULAR : PGF_OK;
     if (n_neg) n_neg[i] = b->h_flags[3 * i + 1] + (b->cond_last ? b->m : 0);  // (+ the m pivots -delta)
     if (diff) diff[i] = b->h_diff[i];
+    // (the Globalized policy: the instance's search decides its status and the length of its step)
+    if (search && !bad) batch_ls_report(b, i, status, diff);
   }
   // a repaired instance holds no factor the batch can reuse (its ctl[1] is 0): a following
   // Simplified step must not skip the factor launch, or it would solve with the bare matrix

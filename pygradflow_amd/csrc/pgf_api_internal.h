@@ -16,6 +16,7 @@
 #include "../../include/pgf_hip.h"
 #include "pgf_band_batch.h"
 #include "pgf_batch.h"
+#include "pgf_batch_line_search.h"
 #include "pgf_ldlt.h"
 #include "pgf_lu.h"
 #include "pgf_sparse.h"
@@ -338,6 +339,8 @@ void band_measures_eval(pgf_handle h);                         // pgf_qp_measure
 
 // ---- the Globalized policy's line search (pgf_api_line_search.hip) -------------------------------
 void ls_free(pgf_handle h);                 // pgf_destroy
+int ls_reserve(pgf_handle h);               // ls_enter, batch_ls_attach
+void ls_enter_names(pgf_handle h);          // ls_enter, batch_ls_handle_enter
 int ls_enter(pgf_handle h);                 // pgf_qp_step_async, in front of enqueue_qp_step
 void ls_leave(pgf_handle h);                // pgf_qp_step_async (on an error), pgf_qp_sync
 int ls_search(pgf_handle h, double *diff);  // pgf_qp_sync, behind the settled step
@@ -460,6 +463,25 @@ struct pgf_batch_s {
   BandInst *rtab = nullptr;
   int *rctl = nullptr, *rcnt = nullptr;
   double *rrel = nullptr;
+  // created with PGF_BATCH_LINE_SEARCH (pgf_api_batch_line_search.hip): the Globalized policy.  otab /
+  // obtab: tab / btab over again, except that (x, y, g, c) name the instance's OUTER point
+  // (xhat, yhat and its handle's ls.ghat, ls.chat) -- the step's residual, right-hand side and
+  // update run on them; itab / ibtab (dense / band): (x, y, c, g, q, b) name (dx, dy, u, v, 0, 0),
+  // so that the batch's evaluation launches form the direction's images; ltab: what the ladder and
+  // the finish read; blk / h_blk: LSB_STRIDE doubles per instance and the pinned mirror; red: the
+  // instances' partial-sum slices; guard / h_guard: (guard on, refine_tol) per instance of a band
+  // batch, as the handles have them when the step is enqueued.  hat_fresh: g, c at the outer points
+  // are current for the outer step; pending: the step in flight carries the bit.
+  struct {
+    bool on = false;
+    double newton_tol = 1e-8;
+    BInst *otab = nullptr, *itab = nullptr;
+    BandInst *obtab = nullptr, *ibtab = nullptr;
+    LsInst *ltab = nullptr;
+    double *blk = nullptr, *h_blk = nullptr, *red = nullptr, *guard = nullptr, *h_guard = nullptr;
+    bool hat_fresh = false, pending = false, have_stats = false;
+    int stage_launches = 0, host_waits = 0;  // pgf_batch_debug_line_search_stats
+  } ls;
   PgfProfile prof;
   std::string err = "";
 };
@@ -493,6 +515,21 @@ void band_batch_enqueue_final(pgf_batch b);                                   //
 int band_batch_ctl_init(pgf_batch b);                                         // pgf_batch_ctl_init
 int band_batch_ctl_read(pgf_batch b);                                         // pgf_batch_ctl_read
 void band_batch_measures_eval(pgf_batch b);                                   // pgf_batch_measures
+// ---- the Globalized policy on a batch (pgf_api_batch_line_search.hip) -----------------------------
+int batch_ls_attach(pgf_batch b);                       // pgf_batch_create_ex
+void batch_ls_free(pgf_batch b);                        // pgf_batch_destroy
+// g, c at every instance's outer point, once per outer step (behind the evaluation at the current
+// points and in front of the mask, as ls_enter orders them on the handle)
+void batch_ls_eval_outer(pgf_batch b);                  // pgf_batch_step_async, band_batch_step_async
+// behind the step update: the images, the ladder, the finish, and the copy of the blocks
+int batch_ls_enqueue_stage(pgf_batch b);                // pgf_batch_step_async, band_batch_step_async
+// An instance the guard repairs on its handle: the handle's (x, y, g, c) name its outer point's
+// vectors for the repair's step update (enter / ls_leave); then ls_search on the handle, whose block
+// becomes the instance's.  PGF_OK, PGF_LINE_SEARCH, or an error.
+void batch_ls_handle_enter(pgf_batch b, int i);         // batch_repair_instance, band_batch_repair
+int batch_ls_handle_search(pgf_batch b, int i, double *diff);
+// after the step's wait: the instance's status and step length from its block
+void batch_ls_report(pgf_batch b, int i, int *status, double *diff);  // pgf_batch_sync, band_batch_sync
 // what it takes from pgf_api_band.hip: the guard's measure over nred residual pairs, and the hash
 // of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat_hash)
 double band_residual_rel_of(const double *pairs, int nred);

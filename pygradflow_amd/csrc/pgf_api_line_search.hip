@@ -12,8 +12,9 @@
 #include "pgf_kernels.h"
 #include "pgf_line_search.h"
 
-// the line search's vectors, on the first Globalized step of the handle
-static int ls_reserve(pgf_handle h) {
+// the line search's vectors, on the first Globalized step of the handle (or when it joins a batch
+// created with PGF_BATCH_LINE_SEARCH)
+int ls_reserve(pgf_handle h) {
   auto &ls = h->ls;
   if (ls.blk) return PGF_OK;
   const int n = h->n, m = h->m, nb = (n + m + 255) / 256;
@@ -52,9 +53,7 @@ static void ls_exchange(pgf_handle h) {
 // In front of enqueue_qp_step (g, c at the device point and its mask are enqueued): g, c at the
 // outer point -- once per outer step, qp_eval's own launches on the exchanged vectors -- and the
 // exchange.
-int ls_enter(pgf_handle h) {
-  int rc;
-  if ((rc = ls_reserve(h))) return rc;
+void ls_enter_names(pgf_handle h) {
   auto &ls = h->ls;
   ls.ox = h->xhat;
   ls.oy = h->yhat;
@@ -62,6 +61,13 @@ int ls_enter(pgf_handle h) {
   ls.oc = ls.chat;
   ls_exchange(h);
   ls.active = true;
+}
+
+int ls_enter(pgf_handle h) {
+  int rc;
+  if ((rc = ls_reserve(h))) return rc;
+  auto &ls = h->ls;
+  ls_enter_names(h);
   if (!ls.hat_fresh) {
     h->eval_fresh = false;
     drop_norm(h);

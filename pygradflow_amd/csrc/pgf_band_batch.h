@@ -161,8 +161,9 @@ void bandb_launch_wide_panel(hipStream_t s, const BandInst *tab, int B, const Ba
 void bandb_launch_wide_kept_solve(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
 // ---- step update, controller and refinement (pgf_sparse.hip) -------------------
 // (xn, yn), dx, dy and the partial sums; the new point replaces the old one, which stays in
-// (xn, yn), unless the instance met a bad pivot
-void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh);
+// (xn, yn), unless the instance met a bad pivot -- or move == false (a Globalized step on the table
+// that names the outer point): the current point stays, the line search's finish moves it
+void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool move = true);
 // The step finished per instance on the device, behind the step update (the device-resident
 // controller; what band_batch_sync does on the host): diff_out[i] the step length; flags_out[3 i]
 // bit 0 a zero or non-finite pivot, bit 2 the guard's measure above the instance's tolerance

@@ -101,8 +101,10 @@ void batch_launch_residual(hipStream_t s, const BInst *tab, int B, const BatchSc
 void batch_launch_cond_prep_fwd(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc);
 void batch_launch_cond_y(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc);
 // flags_out: [3 i] zero-pivot flag, [3 i + 1] negative pivots, [3 i + 2] |I| of instance i
+// move == false: (xn, yn), dx, dy and the length only; the current point stays (a Globalized step on
+// the table that names the outer point: the line search's finish moves the point)
 void batch_launch_step_update(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
-                              double *diff_out, int *flags_out);
+                              double *diff_out, int *flags_out, bool move = true);
 void batch_launch_res_norm(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
                            double *norm_out);
 void batch_launch_measures(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,

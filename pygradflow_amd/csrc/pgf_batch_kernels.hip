@@ -158,15 +158,16 @@ __global__ __launch_bounds__(256) void kb_assemble(const BInst *__restrict__ tab
 }
 
 __global__ __launch_bounds__(256) void kb_step_update(const BInst *__restrict__ tab, int n,
-                                                      int m) {
+                                                      int m, int move) {
   const BInst &I = tab[blockIdx.z];
   if (I.ctl[3]) return;
   b_step_update(n, m, I.counts[0], I.ps[BPS_FACT], I.ps[BPS_RHO], I.x, I.y, I.lb, I.ub, I.mask, I.pos, I.b0full, I.F,
                 I.sol, I.dx, I.dy, I.xn, I.yn, I.red);
   // the new point replaces the current one in place (each lane re-reads its own entry) -- unless
   // the sampled residual of the solve failed: the host repairs such an instance from the point it
-  // started at (batch_repair_instance, pgf_api_batch.hip)
-  if (I.flags[3]) return;
+  // started at (batch_repair_instance, pgf_api_batch.hip).  move == 0 (a Globalized step, whose
+  // table names the outer point): only the clipped direction is wanted, kb_ls_finish moves the point
+  if (I.flags[3] || !move) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n)
     I.x[i] = I.xn[i];
@@ -539,11 +540,11 @@ void batch_launch_cond_y(hipStream_t s, const BInst *tab, int B, const BatchScal
 }
 
 void batch_launch_step_update(hipStream_t s, const BInst *tab, int B, const BatchScalars &sc,
-                              double *diff_out, int *flags_out) {
+                              double *diff_out, int *flags_out, bool move) {
   const int nb = step_update_blocks(sc.n, sc.m);
   hipLaunchKernelGGL(kb_sample_residual, dim3(KB_NSAMPLE / 4, 1, B), dim3(256), 0, s, tab, sc.m);
   if (nb)
-    hipLaunchKernelGGL(kb_step_update, dim3(nb, 1, B), dim3(256), 0, s, tab, sc.n, sc.m);
+    hipLaunchKernelGGL(kb_step_update, dim3(nb, 1, B), dim3(256), 0, s, tab, sc.n, sc.m, move ? 1 : 0);
   hipLaunchKernelGGL(kb_step_final, dim3(1, 1, B), dim3(256), 0, s, tab, nb, diff_out, flags_out);
 }
 

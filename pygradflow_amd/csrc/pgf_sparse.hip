@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void kbb_band_residual(const BandInst *__restr
 
 // ---------------------------------------------------------------- step update
 __global__ __launch_bounds__(256) void kbb_band_step_update(const BandInst *__restrict__ tab,
-                                                            BandShape sh) {
+                                                            BandShape sh, int move) {
   INST(I);
   b_band_step_update(sh.n, sh.m, sh.pos, I.brhs, I.ps[BPS_FACT], I.ps[BPS_RHO], I.x, I.y, I.lb, I.ub, I.F,
                      I.dx, I.dy, I.xn, I.yn, I.stat + 2 * sh.nred);
@@ -562,8 +562,9 @@ __global__ __launch_bounds__(256) void kbb_band_step_update(const BandInst *__re
   // A zero or non-finite pivot: the point stays where it was.  Otherwise the new point replaces the
   // current one and the old one stays in (xn, yn), as after the pointer swap of a single handle: the
   // host repairs an instance whose residual misses the tolerance from there (each lane re-reads its
-  // own entries).
-  if (bad) return;
+  // own entries).  move == 0 (a Globalized step, whose table names the outer point): only the clipped
+  // direction is wanted, kb_ls_finish moves the point.
+  if (bad || !move) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < sh.n) {
     const double v = I.xn[i];
@@ -703,8 +704,8 @@ void bandb_launch_solve(hipStream_t s, const BandInst *tab, int B, const BandSha
   if (residual) hipLaunchKernelGGL(kbb_band_residual, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh);
 }
 
-void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh) {
-  if (sh.N) hipLaunchKernelGGL(kbb_band_step_update, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh);
+void bandb_launch_step_update(hipStream_t s, const BandInst *tab, int B, const BandShape &sh, bool move) {
+  if (sh.N) hipLaunchKernelGGL(kbb_band_step_update, gy(sh.N, 256, B), dim3(256), 0, s, tab, sh, move ? 1 : 0);
 }
 
 void bandb_launch_step_final(hipStream_t s, const BandInst *tab, int B, const BandShape &sh,
