@@ -34,7 +34,10 @@ NO_CONTRACT = [
     "pgf_api_unsym.hip",
     "pgf_api_batch.hip",
     "pgf_api_band_batch.hip",
+    "pgf_api_batch_ctl.hip",
     "pgf_api_batch_line_search.hip",
+    "pgf_api_batch_read.hip",
+    "pgf_api_comm.hip",
     "pgf_api_aux.hip",
 ]
 # The factorisations and the wide band contract freely; what must be bit-exact inside them switches

@@ -178,11 +178,7 @@ int pgf_set_outer(pgf_handle h, const double *xhat, const double *yhat, double d
   if ((rc = up(h, h->xhat, xhat, h->n * sizeof(double)))) return rc;
   if ((rc = up(h, h->yhat, yhat, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->dt = dt;
-  h->lamb = 1.0 / dt;
-  h->rho = rho;
-  h->fact = 1.0 / (1.0 + h->lamb * rho);
-  h->delta = h->lamb / (1.0 + h->lamb * rho);
+  set_outer_scalars(h, dt, rho);
   launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   h->outer_set = true;
   h->mask_set = false;

@@ -6,8 +6,7 @@
 // every instance -- the batched twins of the banded kernels (pgf_sparse.hip, pgf_band_wide.hip for
 // the wide reduction, pgf_border.hip for a border) around the vector kernels the dense batch
 // already has -- one host synchronisation per step (pgf_batch_sync) and one status copy for the whole
-// batch.
-#include <algorithm>
+// batch.  The banded steps of the device-resident controller's loop: pgf_api_batch_ctl.hip.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -32,11 +31,11 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
   for (int i = 0; i < count; ++i) {
     const pgf_handle h = handles[i];
     if (!h) return PGF_INVALID;
+    const char *msg = nullptr;
+    int rc;
     if (!h->sparse || !h0->sparse)
       return fail(h, PGF_INVALID, "batch: dense and banded handles cannot share a batch");
-    if (h->n != h0->n || h->m != h0->m || h->device != h0->device)
-      return fail(h, PGF_INVALID, "batch: instances must share n, m and the device");
-    if (h->unsym.form) return fail(h, PGF_INVALID, "batch: the Symmetric formulation only");
+    if ((rc = batch_check_shape(h, h0, &msg))) return fail(h, rc, msg);
     const SparseDev &sp = h->sp;
     if (!sp.active || !sp.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
@@ -62,198 +61,91 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     // allocated: sp_cyclic_solve)
     if (sp.B != s0.B || (sp.B > 8 && (sp.split != s0.split || (sp.bMr != nullptr) != (s0.bMr != nullptr))))
       return fail(h, PGF_INVALID, "batch: banded instances must share the block size and the factor / solve split");
-    if (!h->qp_mode || !h->bounds_set || !h->point_set)
-      return fail(h, PGF_NOT_READY, "batch: pgf_set_bounds, pgf_qp_set_vectors, pgf_qp_set_point first");
-    if (h->step_pending) return fail(h, PGF_NOT_READY, "batch: a step is pending");
+    if ((rc = batch_check_state(h, /*band=*/true, &msg))) return fail(h, rc, msg);
   }
   pgf_batch b = new (std::nothrow) pgf_batch_s();
   if (!b) return PGF_INVALID;
-  b->band = true;
-  b->band_ctl = (flags & PGF_BATCH_BAND_CTL) != 0;
-  b->ctl_refine = b->band_ctl && (flags & PGF_BATCH_CTL_REFINE) != 0;
-  b->hs.assign(handles, handles + count);
-  b->B = count;
-  b->n = h0->n;
-  b->m = h0->m;
-  b->device = h0->device;
-  b->sc.n = b->n;
-  b->sc.m = b->m;
-  b->frozen.assign(count, 0);
-  b->last_neg.assign(count, 0);
+  auto &bd = b->band;
+  bd.on = true;
+  bd.ctl = (flags & PGF_BATCH_BAND_CTL) != 0;
+  bd.refine = bd.ctl && (flags & PGF_BATCH_CTL_REFINE) != 0;
+  hipError_t e = batch_begin(b, handles, count);
+  bd.frozen.assign(count, 0);
+  bd.last_neg.assign(count, 0);
   const int N = b->n + b->m;
-  BandShape &sh = b->bsh;
-  const SparseDev &s0 = h0->sp;
+  BandShape &sh = bd.sh;
   // the sizes every instance shares, a border's included (bk was compared; bkp, Nb, bnchunk, nred
-  // follow from it and N), the status block with the handle's own stride 3 nred + 4
-  sh = band_shape_of(s0, N);
+  // follow from it and N), the status block with the handle's own stride
+  sh = band_shape_of(h0->sp, N);
   sh.n = b->n;
   sh.m = b->m;
-  const size_t cnt = (size_t)count, S = (size_t)3 * sh.nred + 4;
-  (void)hipSetDevice(b->device);
-  hipError_t e;
-  if ((e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking)) != hipSuccess ||
-      (e = hipMalloc((void **)&b->tab, cnt * sizeof(BInst))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->btab, cnt * sizeof(BandInst))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->ctl, cnt * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->wcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->bcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->norm_out, cnt * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->red4, cnt * 4 * ((size_t)(N + 255) / 256 + 1) * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->meas_out, cnt * 4 * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->ps, cnt * BPS_STRIDE * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_ps, cnt * BPS_STRIDE * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->bytes, cnt)) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_bytes, cnt)) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_meas, cnt * 4 * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_flags, cnt * 3 * sizeof(int))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_norm, cnt * sizeof(double))) != hipSuccess ||
-      (e = hipMalloc((void **)&b->bstat, cnt * S * sizeof(double))) != hipSuccess ||
-      (e = hipHostMalloc((void **)&b->h_bstat, cnt * S * sizeof(double))) != hipSuccess) {
-    pgf_batch_destroy(b);
-    return PGF_HIP_ERROR + (int)e;
-  }
+  const size_t cnt = (size_t)count, S = band_stat_stride(sh);
+  batch_alloc(b, &e, &b->tab, cnt);
+  batch_alloc(b, &e, &bd.tab, cnt);
+  batch_alloc(b, &e, &b->ctl, cnt * BCTL_STRIDE, BA_ZERO);
+  batch_alloc(b, &e, &bd.wcnt, cnt * 2, BA_ZERO);
+  batch_alloc(b, &e, &bd.bcnt, cnt * 2, BA_ZERO);
+  batch_alloc(b, &e, &b->out.norm, cnt);
+  batch_alloc(b, &e, &b->out.red4, cnt * 4 * ((size_t)(N + 255) / 256 + 1));
+  batch_alloc(b, &e, &b->out.meas, cnt * 4);
+  batch_alloc(b, &e, &b->ps, cnt * BPS_STRIDE, BA_ZERO);
+  batch_alloc(b, &e, &b->h_ps, cnt * BPS_STRIDE, BA_PINNED | BA_ZERO);
+  batch_alloc(b, &e, &b->bytes, cnt);
+  batch_alloc(b, &e, &b->h_bytes, cnt, BA_PINNED);
+  batch_alloc(b, &e, &b->out.h_meas, cnt * 4, BA_PINNED);
+  batch_alloc(b, &e, &b->out.h_flags, cnt * BFL_STRIDE, BA_PINNED | BA_ZERO);
+  batch_alloc(b, &e, &b->out.h_norm, cnt, BA_PINNED);
+  batch_alloc(b, &e, &bd.stat, cnt * S, BA_ZERO);
+  batch_alloc(b, &e, &bd.h_stat, cnt * S, BA_PINNED);
   // what kbb_step_final writes for kb_dctl_mid / kb_dctl_end (zeroed: the guard is off and nothing
   // is counted until pgf_batch_ctl_init)
-  if (b->band_ctl &&
-      ((e = hipMalloc((void **)&b->flags_out, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->diff_out, cnt * sizeof(double))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->band_guard, cnt * BG_STRIDE * sizeof(double))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->band_rejects, cnt * 2 * sizeof(int))) != hipSuccess ||
-       (e = hipMemset(b->flags_out, 0, (cnt * 3 + 1) * sizeof(int))) != hipSuccess ||
-       (e = hipMemset(b->diff_out, 0, cnt * sizeof(double))) != hipSuccess ||
-       (e = hipMemset(b->band_guard, 0, cnt * BG_STRIDE * sizeof(double))) != hipSuccess ||
-       (e = hipMemset(b->band_rejects, 0, cnt * 2 * sizeof(int))) != hipSuccess)) {
-    pgf_batch_destroy(b);
-    return PGF_HIP_ERROR + (int)e;
+  if (bd.ctl) {
+    batch_alloc(b, &e, &b->out.flags, cnt * BFL_STRIDE + 1, BA_ZERO);
+    batch_alloc(b, &e, &b->out.diff, cnt, BA_ZERO);
+    batch_alloc(b, &e, &bd.guard, cnt * BG_STRIDE, BA_ZERO);
+    batch_alloc(b, &e, &bd.rejects, cnt * 2, BA_ZERO);
   }
-  // the refinement rounds' table, control words (written by each round's decision kernel before
-  // anything reads them), measure and counters
-  if (b->ctl_refine &&
-      ((e = hipMalloc((void **)&b->rtab, cnt * sizeof(BandInst))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->rctl, cnt * 4 * sizeof(int))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->rcnt, cnt * 2 * sizeof(int))) != hipSuccess ||
-       (e = hipMalloc((void **)&b->rrel, cnt * sizeof(double))) != hipSuccess ||
-       (e = hipMemset(b->rctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
-       (e = hipMemset(b->rcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
-       (e = hipMemset(b->rrel, 0, cnt * sizeof(double))) != hipSuccess)) {
-    pgf_batch_destroy(b);
-    return PGF_HIP_ERROR + (int)e;
+  // the refinement rounds' control words (written by each round's decision kernel before anything
+  // reads them), measure and counters
+  if (bd.refine) {
+    batch_alloc(b, &e, &bd.rctl, cnt * BCTL_STRIDE, BA_ZERO);
+    batch_alloc(b, &e, &bd.rcnt, cnt * 2, BA_ZERO);
+    batch_alloc(b, &e, &bd.rrel, cnt, BA_ZERO);
   }
-  std::memset(b->h_flags, 0, cnt * 3 * sizeof(int));
-  std::vector<BInst> tab(count);
-  std::vector<BandInst> btab(count);
-  std::memset(tab.data(), 0, cnt * sizeof(BInst));
-  for (int i = 0; i < count; ++i) {
+  b->htab.resize(cnt);  // (zeros: no dense matrix, no factor)
+  bd.htab.resize(cnt);
+  for (int i = 0; i < count && e == hipSuccess; ++i) {
     const pgf_handle h = handles[i];
     (void)hipStreamSynchronize(h->stream);
-    const SparseDev &sp = h->sp;
-    // what the vector kernels shared with the dense batch read (no dense matrix, no factor)
-    BInst &t = tab[i];
-    t.lb = h->lb;
-    t.ub = h->ub;
-    t.q = h->q;
-    t.b = h->b;
-    t.slb = h->slb;
-    t.sub = h->sub;
-    t.xhat = h->xhat;
-    t.yhat = h->yhat;
-    t.x = h->x;
-    t.y = h->y;
-    t.xn = h->xn;
-    t.yn = h->yn;
-    t.g = h->g;
-    t.c = h->c;
-    t.F = h->F;
-    t.b0full = h->b0full;
-    t.rhs = h->rhs;
-    t.sol = h->sol;
-    t.dx = h->dx;
-    t.dy = h->dy;
-    t.w = h->w;
-    t.tmpn = h->tmpn;
-    t.partial = h->partial;
-    t.red = h->red;
-    t.mask = h->mask;
-    t.mask_new = h->mask_new;
-    t.idxI = h->idxI;
-    t.idxA = h->idxA;
-    t.pos = h->pos;
-    t.counts = h->counts;
-    t.ctl = b->ctl + 4 * i;
-    t.ps = b->ps + (size_t)BPS_STRIDE * i;
-    t.flags = h->fac.flags;
-    BandInst &u = btab[i];
-    u = band_inst_of(sp, h->fac.flags, b->bstat + S * i);
-    u.wcnt = b->wcnt + 2 * i;
-    u.bcnt = b->bcnt + 2 * i;
-    u.lb = h->lb;
-    u.ub = h->ub;
-    u.q = h->q;
-    u.b = h->b;
-    u.x = h->x;
-    u.y = h->y;
-    u.xn = h->xn;
-    u.yn = h->yn;
-    u.g = h->g;
-    u.c = h->c;
-    u.w = h->w;
-    u.F = h->F;
-    u.b0full = h->b0full;
-    u.dx = h->dx;
-    u.dy = h->dy;
-    u.tmpn = h->tmpn;
-    u.mask = h->mask;
-    u.counts = h->counts;
-    u.ctl = b->ctl + 4 * i;
-    u.ps = b->ps + (size_t)BPS_STRIDE * i;
-    // the batch owns the device-side state of the handle from here on
-    h->mask_set = false;
-    h->eval_fresh = false;
-    h->sp.stat_pending = false;
-    h->sp.kept = 0;  // (the batch's reductions write the handle's block arrays)
-    invalidate_factor(h);
+    // what the vector kernels shared with the dense batch read
+    batch_fill_vectors(b, i, b->htab[i]);
+    BandInst &u = bd.htab[i];
+    u = band_inst_of(h->sp, h->fac.flags, bd.stat + S * i);
+    u.wcnt = bd.wcnt + 2 * i;
+    u.bcnt = bd.bcnt + 2 * i;
+    batch_fill_vectors(b, i, u);
+    batch_own_handle(h);
   }
-  std::memset(b->h_ps, 0, cnt * BPS_STRIDE * sizeof(double));
-  if ((e = hipMemcpy(b->tab, tab.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(b->btab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemset(b->ctl, 0, cnt * 4 * sizeof(int))) != hipSuccess ||
-      (e = hipMemset(b->wcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
-      (e = hipMemset(b->bcnt, 0, cnt * 2 * sizeof(int))) != hipSuccess ||
-      (e = hipMemset(b->bstat, 0, cnt * S * sizeof(double))) != hipSuccess ||
-      (e = hipMemcpy(b->ps, b->h_ps, cnt * BPS_STRIDE * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) {
+  if (e == hipSuccess) e = hipMemcpy(b->tab, b->htab.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(bd.tab, bd.htab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice);
+  // the refinement rounds' table
+  if (bd.refine)
+    batch_renamed_table(b, &e, &bd.rtab, bd.htab, [&](BandInst &u, size_t i) { u.ctl = bd.rctl + BCTL_STRIDE * i; });
+  if (e != hipSuccess) {
     pgf_batch_destroy(b);
     return PGF_HIP_ERROR + (int)e;
-  }
-  if (b->ctl_refine) {
-    for (int i = 0; i < count; ++i) btab[i].ctl = b->rctl + 4 * i;
-    if ((e = hipMemcpy(b->rtab, btab.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice)) != hipSuccess) {
-      pgf_batch_destroy(b);
-      return PGF_HIP_ERROR + (int)e;
-    }
   }
   *out = b;
   return PGF_OK;
 }
 
-void band_batch_free(pgf_batch b) {
-  if (b->btab) (void)hipFree(b->btab);
-  if (b->wcnt) (void)hipFree(b->wcnt);
-  if (b->bcnt) (void)hipFree(b->bcnt);
-  if (b->bstat) (void)hipFree(b->bstat);
-  if (b->h_bstat) (void)hipHostFree(b->h_bstat);
-  if (b->band_guard) (void)hipFree(b->band_guard);
-  if (b->band_rejects) (void)hipFree(b->band_rejects);
-  if (b->rtab) (void)hipFree(b->rtab);
-  if (b->rctl) (void)hipFree(b->rctl);
-  if (b->rcnt) (void)hipFree(b->rcnt);
-  if (b->rrel) (void)hipFree(b->rrel);
-}
-
 // c = A x - b ; w = rho c + y ; g = Q x + (q + A' w) at every instance's point
-void band_batch_eval(pgf_batch b) { bandb_launch_eval(b->stream, b->btab, b->B, b->bsh); }
+void band_batch_eval(pgf_batch b) { bandb_launch_eval(b->stream, b->band.tab, b->B, b->band.sh); }
 
 // c = A x - b and F = Q x + q + A' y for the termination measures (no rho term)
-void band_batch_measures_eval(pgf_batch b) { bandb_launch_measures_eval(b->stream, b->btab, b->B, b->bsh); }
+void band_batch_measures_eval(pgf_batch b) {
+  bandb_launch_measures_eval(b->stream, b->band.tab, b->B, b->band.sh);
+}
 
 // The step sequence of batch_enqueue_step for banded instances: eval, mask, rhs, assembly where
 // needed, reduction, residual, step update, the evaluation made ahead of the sync, and the copy
@@ -278,50 +170,48 @@ void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean
   // update on the tables that name the outer points, nothing moved
   const bool search = (policy & PGF_STEP_LINE_SEARCH) != 0;
   hipStream_t s = b->stream;
-  if (!b->eval_fresh) {
-    band_batch_eval(b);
-    b->eval_fresh = true;
-  }
+  auto &bd = b->band;
+  batch_eval(b);
   if (search) batch_ls_eval_outer(b);
   batch_launch_mask(s, b->tab, b->B, b->sc, recompute ? (force ? 2 : 1) : 0, tau);
   b->have_mask = true;
   b->stepped = true;
   batch_launch_residual(s, search ? b->ls.otab : b->tab, b->B, b->sc);
-  bandb_launch_rhs(s, b->btab, b->B, b->bsh);
+  bandb_launch_rhs(s, bd.tab, b->B, bd.sh);
   // instances whose band is still valid return at once (ctl[0] == 0); when the host knows that
   // none assembles (a Simplified step behind a good one), the launches are skipped
-  if (b->bsh.bk) {
+  if (bd.sh.bk) {
     // The factor phase's workgroups return at once where the band, Y and the factor of S are still
     // valid; when the host knows that no instance factors, all its launches are left out.
     if (recompute || !lean_allowed) {
-      borderb_launch_factor(s, b->btab, b->B, b->bsh);
-      ++b->stat_band_assemblies;
+      borderb_launch_factor(s, bd.tab, b->B, bd.sh);
+      ++b->dbg.band_assemblies;
     } else {
-      ++b->stat_band_lean;
+      ++b->dbg.band_lean;
     }
-    borderb_launch_solve(s, b->btab, b->B, b->bsh);
-    ++b->stat_band_reductions;
-    bandb_launch_step_update(s, b->btab, b->B, b->bsh);
+    borderb_launch_solve(s, bd.tab, b->B, bd.sh);
+    ++b->dbg.band_reductions;
+    bandb_launch_step_update(s, bd.tab, b->B, bd.sh);
     b->eval_fresh = false;
     return;
   }
   if (recompute || !lean_allowed) {
-    bandb_launch_assemble(s, b->btab, b->B, b->bsh);
-    ++b->stat_band_assemblies;
+    bandb_launch_assemble(s, bd.tab, b->B, bd.sh);
+    ++b->dbg.band_assemblies;
   }
-  if (b->bsh.B > 8) {
+  if (bd.sh.B > 8) {
     // With the split on, an instance whose band is still valid solves against its kept factors.  When
     // the host knows that none reduces (a Simplified step behind a good one) the inversion launches
     // are left out: their workgroups would all return.
-    const bool lean = b->bsh.split && !recompute && lean_allowed;
-    bandb_launch_wide_solve(s, b->btab, b->B, b->bsh, lean);
-    if (lean && b->bsh.N) ++b->stat_band_lean;
+    const bool lean = bd.sh.split && !recompute && lean_allowed;
+    bandb_launch_wide_solve(s, bd.tab, b->B, bd.sh, lean);
+    if (lean && bd.sh.N) ++b->dbg.band_lean;
   } else {
     // (the 8 x 8 reduction keeps no factors: every step runs it, on the band as it stands)
-    bandb_launch_solve(s, b->btab, b->B, b->bsh);
+    bandb_launch_solve(s, bd.tab, b->B, bd.sh);
   }
-  ++b->stat_band_reductions;
-  bandb_launch_step_update(s, search ? b->ls.obtab : b->btab, b->B, b->bsh, /*move=*/!search);
+  ++b->dbg.band_reductions;
+  bandb_launch_step_update(s, search ? b->ls.obtab : bd.tab, b->B, bd.sh, /*move=*/!search);
   b->eval_fresh = false;
 }
 
@@ -332,11 +222,9 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
   if (policy & PGF_STEP_LINE_SEARCH)
     if (int rc = batch_ls_enqueue_stage(b)) return rc;
   // g and c at the new points, ahead of the host synchronisation (as pgf_batch_step_async)
-  if (eval_ahead()) {
-    band_batch_eval(b);
-    b->eval_fresh = true;
-  }
-  BHIPCHK(b, hipMemcpyAsync(b->h_bstat, b->bstat, (size_t)b->B * ((size_t)3 * b->bsh.nred + 4) * sizeof(double),
+  if (eval_ahead()) batch_eval(b);
+  BHIPCHK(b, hipMemcpyAsync(b->band.h_stat, b->band.stat,
+                            (size_t)b->B * band_stat_stride(b->band.sh) * sizeof(double),
                             hipMemcpyDeviceToHost, s));
   BHIPCHK(b, hipGetLastError());
   b->step_pending = true;
@@ -375,7 +263,7 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
   pgf_handle h = b->hs[i];
   SparseDev &sp = h->sp;
   hipStream_t s = h->stream;
-  const size_t S = (size_t)3 * sp.nred + 4;
+  const size_t S = band_stat_stride(b->band.sh);  // (the handle's own stride: create compared the shapes)
   if (!search) {
     launch_copy(s, h->x, h->xn, h->n);
     launch_copy(s, h->y, h->yn, h->m);
@@ -383,7 +271,7 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
   std::memcpy(sp.h_bred, st, S * sizeof(double));
   sp.guarded = true;
   h->mask_set = true;
-  sp.kept = b->bsh.split ? 2 : 0;
+  sp.kept = b->band.sh.split ? 2 : 0;
   if (search) batch_ls_handle_enter(b, i);
   const int refined = h->guard.stat_refined;
   int rc = band_refine(h, /*swapped=*/false, /*with_step=*/true);
@@ -407,30 +295,26 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
 
 int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
   BHIPCHK(b, hipStreamSynchronize(b->stream));
-  const bool search = b->ls.pending;
-  b->ls.pending = false;
-  if (search) {
-    ++b->ls.host_waits;
-    b->ls.have_stats = true;
-  }
-  const int nred = b->bsh.nred;
-  const size_t S = (size_t)3 * nred + 4;
+  const bool search = batch_ls_begin_sync(b);
+  auto &bd = b->band;
+  const int nred = bd.sh.nred;
+  const size_t S = band_stat_stride(bd.sh);
   bool all_ok = true;
   for (int i = 0; i < b->B; ++i) {
     pgf_handle h = b->hs[i];
-    if (b->frozen[i]) {  // no step was taken
+    if (bd.frozen[i]) {  // no step was taken
       all_ok = false;    // (whether its band is valid is the device's knowledge: ctl[1])
       if (status) status[i] = PGF_OK;
-      if (n_neg) n_neg[i] = b->last_neg[i];
+      if (n_neg) n_neg[i] = bd.last_neg[i];
       if (diff) diff[i] = 0.0;
       continue;
     }
-    const double *st = b->h_bstat + S * i;
+    const double *st = bd.h_stat + S * i;
     int rc = PGF_OK;
     double d = 0.0;
-    if (b->bsh.N > 0) {
+    if (bd.sh.N > 0) {
       const int bad = (int)st[3 * nred];
-      b->last_neg[i] = (int)st[3 * nred + 1];
+      bd.last_neg[i] = (int)st[3 * nred + 1];
       if (bad) {
         rc = fail(h, PGF_SINGULAR, k_zero_pivot);  // (the step update left the point alone)
       } else {
@@ -443,168 +327,18 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
           rc = band_batch_repair(b, i, st, &d, search);
           b->eval_fresh = false;  // the instance moved after the evaluation made ahead
           if (search && rc == PGF_LINE_SEARCH) rc = PGF_OK;  // (repaired; its block says the rest)
-          if (rc == PGF_OK) ++b->repaired;
+          if (rc == PGF_OK) ++b->dbg.repaired;
           else if (rc != PGF_SINGULAR) return bfail(b, rc, pgf_last_error(h));
         }
       }
     }
     if (rc) all_ok = false;
     if (status) status[i] = rc ? PGF_SINGULAR : PGF_OK;
-    if (n_neg) n_neg[i] = b->last_neg[i];
+    if (n_neg) n_neg[i] = bd.last_neg[i];
     if (diff) diff[i] = rc ? 0.0 : d;
     // (the Globalized policy: the instance's search decides its status and the length of its step)
     if (search && !rc) batch_ls_report(b, i, status, diff);
   }
   b->all_factored = all_ok;
-  return PGF_OK;
-}
-
-// ---- the device-resident controller on a band batch (PGF_BATCH_BAND_CTL) ------------------------
-// The loop itself is pgf_batch_ctl_iterate's; a banded step in it is band_batch_enqueue_step and,
-// where band_batch_sync would finish the step on the host, kbb_step_final on the device.
-void band_batch_enqueue_final(pgf_batch b) {
-  bandb_launch_step_final(b->stream, b->btab, b->B, b->bsh, b->band_guard, b->diff_out, b->flags_out,
-                          b->band_rejects, b->ctl_refine ? b->rctl : nullptr);
-}
-
-// PGF_BATCH_CTL_REFINE, between the step update and kbb_step_final: band_batch_sync ->
-// band_batch_repair -> band_refine on the device, for the instances whose measure asks for it.  The
-// host cannot know which: both rounds are enqueued, every launch of a round on the refinement table,
-// whose ctl[3] the round's decision kernel has set for every instance that does not refine -- its
-// workgroups return at once.  ctl[0] is 0 there: nothing assembles, a wide band with the split on
-// solves against its kept factors (the step left them clean, or the instance would not refine), and
-// the step update writes no ctl[1].  A round, per route, is band_refine's loop body: the copies,
-// sp_cyclic_solve(guard = false), the axpy, sp_cyclic_residual, and the step taken again from the
-// point it started from (which the load kernel has put back).  No factor phase is touched, so a
-// lean second step stays lean; the round's solve counts as a solve phase in wcnt / bcnt (split off:
-// as a reduction).
-void band_batch_enqueue_refine(pgf_batch b) {
-  hipStream_t s = b->stream;
-  const BandShape &sh = b->bsh;
-  const BandInst *rt = b->rtab;
-  for (int round = 0; round < 2; ++round) {
-    bandb_launch_refine_decide(s, b->btab, b->B, sh, b->band_guard, b->rctl, b->rrel, b->rcnt, round);
-    bandb_launch_refine_load(s, rt, b->B, sh);
-    if (sh.bk) {
-      borderb_launch_solve(s, rt, b->B, sh, /*guard=*/false);
-      bandb_launch_refine_axpy(s, rt, b->B, sh);
-      borderb_launch_residual(s, rt, b->B, sh);
-    } else if (sh.B > 8) {
-      if (sh.split)
-        bandb_launch_wide_kept_solve(s, rt, b->B, sh);
-      else
-        bandb_launch_wide_solve(s, rt, b->B, sh, /*lean=*/false, /*guard=*/false);
-      bandb_launch_refine_axpy(s, rt, b->B, sh);
-      bandb_launch_wide_residual(s, rt, b->B, sh);
-    } else {
-      bandb_launch_solve(s, rt, b->B, sh, /*residual=*/false, /*save_rhs=*/false);
-      bandb_launch_refine_axpy(s, rt, b->B, sh);
-      bandb_launch_residual(s, rt, b->B, sh);
-    }
-    bandb_launch_step_update(s, rt, b->B, sh);
-  }
-}
-
-// the guard's setting of every handle, as it stands now (pgf_set_refinement), for kbb_step_final
-// and the refinement rounds
-int band_batch_ctl_init(pgf_batch b) {
-  std::vector<double> g((size_t)BG_STRIDE * b->B);
-  for (int i = 0; i < b->B; ++i) {
-    g[BG_STRIDE * (size_t)i] = b->hs[i]->guard.refine_mode ? 1.0 : 0.0;
-    g[BG_STRIDE * (size_t)i + 1] = b->hs[i]->guard.refine_tol;
-    g[BG_STRIDE * (size_t)i + 2] = b->hs[i]->guard.refine_fail;
-  }
-  BHIPCHK(b, hipMemcpyAsync(b->band_guard, g.data(), g.size() * sizeof(double), hipMemcpyHostToDevice,
-                            b->stream));
-  BHIPCHK(b, hipStreamSynchronize(b->stream));
-  return PGF_OK;
-}
-
-// Behind the loop, stream idle: the host's view follows the device's.  The instances the controller
-// froze in the last iteration stay frozen until the next pgf_batch_advance_outer*, so a host-driven
-// pgf_batch_step_async right behind reports them as band_batch_sync reports frozen instances, with
-// the inertia of the last step they took.  (No chain helpers here: the sticky word stays unused.)
-int band_batch_ctl_read(pgf_batch b) {
-  std::vector<int> ctl((size_t)4 * b->B), fl((size_t)3 * b->B);
-  BHIPCHK(b, hipMemcpy(ctl.data(), b->ctl, ctl.size() * sizeof(int), hipMemcpyDeviceToHost));
-  BHIPCHK(b, hipMemcpy(fl.data(), b->flags_out, fl.size() * sizeof(int), hipMemcpyDeviceToHost));
-  for (int i = 0; i < b->B; ++i) {
-    b->frozen[i] = ctl[4 * (size_t)i + 3] ? 1 : 0;
-    if (b->dctl_logged > 0) b->last_neg[i] = fl[3 * (size_t)i + 1];
-  }
-  b->all_factored = false;
-  return PGF_OK;
-}
-
-extern "C" int pgf_batch_debug_ctl_stats(pgf_batch b, int *pivot_rejects, int *guard_rejects) {
-  if (!b) return PGF_INVALID;
-  if (!pivot_rejects && !guard_rejects) return PGF_OK;
-  std::vector<int> cnt((size_t)2 * b->B, 0);
-  if (b->band_rejects) {
-    (void)hipSetDevice(b->device);
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    BHIPCHK(b, hipMemcpy(cnt.data(), b->band_rejects, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  for (int i = 0; i < b->B; ++i) {
-    if (pivot_rejects) pivot_rejects[i] = cnt[2 * (size_t)i];
-    if (guard_rejects) guard_rejects[i] = cnt[2 * (size_t)i + 1];
-  }
-  return PGF_OK;
-}
-
-extern "C" int pgf_batch_debug_ctl_refine_stats(pgf_batch b, int *refined_steps, int *rounds) {
-  if (!b) return PGF_INVALID;
-  if (!refined_steps && !rounds) return PGF_OK;
-  std::vector<int> cnt((size_t)2 * b->B, 0);
-  if (b->rcnt) {
-    (void)hipSetDevice(b->device);
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    BHIPCHK(b, hipMemcpy(cnt.data(), b->rcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  for (int i = 0; i < b->B; ++i) {
-    if (refined_steps) refined_steps[i] = cnt[2 * (size_t)i];
-    if (rounds) rounds[i] = cnt[2 * (size_t)i + 1];
-  }
-  return PGF_OK;
-}
-
-extern "C" int pgf_batch_debug_band_stats(pgf_batch b, int *reductions, int *assemblies) {
-  if (!b) return PGF_INVALID;
-  if (reductions) *reductions = b->stat_band_reductions;
-  if (assemblies) *assemblies = b->stat_band_assemblies;
-  return PGF_OK;
-}
-
-extern "C" int pgf_batch_debug_band_wide_stats(pgf_batch b, int *reductions, int *solve_phases,
-                                               int *lean_steps) {
-  if (!b) return PGF_INVALID;
-  if (lean_steps) *lean_steps = b->stat_band_lean;
-  if (!reductions && !solve_phases) return PGF_OK;
-  std::vector<int> cnt((size_t)2 * b->B, 0);
-  if (b->band && b->wcnt) {
-    (void)hipSetDevice(b->device);
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    BHIPCHK(b, hipMemcpy(cnt.data(), b->wcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  for (int i = 0; i < b->B; ++i) {
-    if (reductions) reductions[i] = cnt[2 * i];
-    if (solve_phases) solve_phases[i] = cnt[2 * i + 1];
-  }
-  return PGF_OK;
-}
-
-extern "C" int pgf_batch_debug_border_stats(pgf_batch b, int *factor_phases, int *solve_phases) {
-  if (!b) return PGF_INVALID;
-  if (!factor_phases && !solve_phases) return PGF_OK;
-  std::vector<int> cnt((size_t)2 * b->B, 0);
-  if (b->band && b->bsh.bk && b->bcnt) {
-    (void)hipSetDevice(b->device);
-    BHIPCHK(b, hipStreamSynchronize(b->stream));
-    BHIPCHK(b, hipMemcpy(cnt.data(), b->bcnt, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
-  }
-  for (int i = 0; i < b->B; ++i) {
-    if (factor_phases) factor_phases[i] = cnt[2 * (size_t)i];
-    if (solve_phases) solve_phases[i] = cnt[2 * (size_t)i + 1];
-  }
   return PGF_OK;
 }

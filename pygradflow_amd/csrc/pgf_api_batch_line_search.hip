@@ -20,43 +20,53 @@ int batch_ls_attach(pgf_batch b) {
   auto &ls = b->ls;
   const size_t cnt = (size_t)b->B;
   const int n = b->n, m = b->m, nb = (n + m + 255) / 256;
+  const bool band = b->band.on;
   (void)hipSetDevice(b->device);
   for (pgf_handle h : b->hs) {
     if (int rc = ls_reserve(h)) return bfail(b, rc, pgf_last_error(h));
     h->ls.hat_fresh = false;  // (the batch evaluates into the handle's ghat, chat from here on)
     BHIPCHK(b, hipStreamSynchronize(h->stream));
   }
-  std::vector<BInst> tab(cnt);
-  BHIPCHK(b, hipMemcpy(tab.data(), b->tab, cnt * sizeof(BInst), hipMemcpyDeviceToHost));
-  BHIPCHK(b, hipMalloc((void **)&ls.otab, cnt * sizeof(BInst)));
-  BHIPCHK(b, hipMalloc((void **)&ls.ltab, cnt * sizeof(LsInst)));
-  BHIPCHK(b, dalloc(&ls.blk, cnt * LSB_STRIDE));
-  BHIPCHK(b, dalloc(&ls.red, cnt * LS_TERMS * ((size_t)nb + 1)));
-  BHIPCHK(b, hipHostMalloc((void **)&ls.h_blk, cnt * LSB_STRIDE * sizeof(double)));
-  BHIPCHK(b, hipMemset(ls.blk, 0, cnt * LSB_STRIDE * sizeof(double)));  // (the tickets start at zero)
-  std::memset(ls.h_blk, 0, cnt * LSB_STRIDE * sizeof(double));
-  if (b->band) {
-    BHIPCHK(b, dalloc(&ls.guard, cnt * 2));
-    BHIPCHK(b, hipHostMalloc((void **)&ls.h_guard, cnt * 2 * sizeof(double)));
-    BHIPCHK(b, hipMemset(ls.guard, 0, cnt * 2 * sizeof(double)));
+  hipError_t e = hipSuccess;
+  batch_alloc(b, &e, &ls.ltab, cnt);
+  batch_alloc(b, &e, &ls.blk, cnt * LSB_STRIDE, BA_ZERO);  // (the tickets start at zero)
+  batch_alloc(b, &e, &ls.red, cnt * LS_TERMS * ((size_t)nb + 1));
+  batch_alloc(b, &e, &ls.h_blk, cnt * LSB_STRIDE, BA_PINNED | BA_ZERO);
+  if (band) {
+    batch_alloc(b, &e, &ls.guard, cnt * 2, BA_ZERO);
+    batch_alloc(b, &e, &ls.h_guard, cnt * 2, BA_PINNED);
   }
-  std::vector<LsInst> lt(cnt);
-  std::vector<BInst> ot(tab), it(tab);
-  for (size_t i = 0; i < cnt; ++i) {
+  // the tables that name the outer point's vectors and the direction with its images: the same
+  // renaming for the BInst and the BandInst of an instance
+  const std::vector<BInst> &tab = b->htab;
+  auto outer = [&](auto &o, size_t i) {
     const pgf_handle h = b->hs[i];
-    const BInst &t = tab[i];
-    BInst &o = ot[i];
-    o.x = t.xhat;
-    o.y = t.yhat;
+    o.x = tab[i].xhat;
+    o.y = tab[i].yhat;
     o.g = h->ls.ghat;
     o.c = h->ls.chat;
-    BInst &d = it[i];
-    d.x = t.dx;
-    d.y = t.dy;
+  };
+  auto images = [&](auto &d, size_t i) {
+    const pgf_handle h = b->hs[i];
+    d.x = tab[i].dx;
+    d.y = tab[i].dy;
     d.c = h->ls.u;
     d.g = h->ls.v;
     d.q = h->ls.zero;
     d.b = h->ls.zero;
+  };
+  batch_renamed_table(b, &e, &ls.otab, tab, outer);
+  if (band) {
+    batch_renamed_table(b, &e, &ls.obtab, b->band.htab, outer);
+    batch_renamed_table(b, &e, &ls.ibtab, b->band.htab, images);
+  } else {
+    batch_renamed_table(b, &e, &ls.itab, tab, images);
+  }
+  BHIPCHK(b, e);
+  std::vector<LsInst> lt(cnt);
+  for (size_t i = 0; i < cnt; ++i) {
+    const pgf_handle h = b->hs[i];
+    const BInst &t = tab[i];
     LsInst &l = lt[i];
     l.x = t.x;
     l.y = t.y;
@@ -76,57 +86,22 @@ int batch_ls_attach(pgf_batch b) {
     l.blk = ls.blk + i * LSB_STRIDE;
     l.ctl = t.ctl;
     l.ps = t.ps;
-    // dense: the instance's word of flags_out, which kb_step_final has written by then (pivot,
+    // dense: the instance's word of out.flags, which kb_step_final has written by then (pivot,
     // hand-over and sampled-residual bits); band: its pivot flags, final behind the reduction
-    l.bad = b->band ? h->fac.flags : b->flags_out + 3 * i;
-    l.stat = b->band ? b->bstat + i * ((size_t)3 * b->bsh.nred + 4) : nullptr;
-    l.guard = b->band ? ls.guard + 2 * i : nullptr;
+    l.bad = band ? h->fac.flags : b->out.flags + BFL_STRIDE * i + BFL_BAD;
+    l.stat = band ? b->band.stat + i * band_stat_stride(b->band.sh) : nullptr;
+    l.guard = band ? ls.guard + 2 * i : nullptr;
   }
-  BHIPCHK(b, hipMemcpy(ls.otab, ot.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice));
   BHIPCHK(b, hipMemcpy(ls.ltab, lt.data(), cnt * sizeof(LsInst), hipMemcpyHostToDevice));
-  if (b->band) {
-    std::vector<BandInst> bt(cnt);
-    BHIPCHK(b, hipMemcpy(bt.data(), b->btab, cnt * sizeof(BandInst), hipMemcpyDeviceToHost));
-    std::vector<BandInst> obt(bt), ibt(bt);
-    for (size_t i = 0; i < cnt; ++i) {
-      const pgf_handle h = b->hs[i];
-      obt[i].x = tab[i].xhat;
-      obt[i].y = tab[i].yhat;
-      obt[i].g = h->ls.ghat;
-      obt[i].c = h->ls.chat;
-      ibt[i].x = tab[i].dx;
-      ibt[i].y = tab[i].dy;
-      ibt[i].c = h->ls.u;
-      ibt[i].g = h->ls.v;
-      ibt[i].q = h->ls.zero;
-      ibt[i].b = h->ls.zero;
-    }
-    BHIPCHK(b, hipMalloc((void **)&ls.obtab, cnt * sizeof(BandInst)));
-    BHIPCHK(b, hipMalloc((void **)&ls.ibtab, cnt * sizeof(BandInst)));
-    BHIPCHK(b, hipMemcpy(ls.obtab, obt.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice));
-    BHIPCHK(b, hipMemcpy(ls.ibtab, ibt.data(), cnt * sizeof(BandInst), hipMemcpyHostToDevice));
-  } else {
-    BHIPCHK(b, hipMalloc((void **)&ls.itab, cnt * sizeof(BInst)));
-    BHIPCHK(b, hipMemcpy(ls.itab, it.data(), cnt * sizeof(BInst), hipMemcpyHostToDevice));
-  }
   ls.on = true;
   return PGF_OK;
-}
-
-void batch_ls_free(pgf_batch b) {
-  auto &ls = b->ls;
-  for (void *p : {(void *)ls.otab, (void *)ls.itab, (void *)ls.obtab, (void *)ls.ibtab, (void *)ls.ltab,
-                  (void *)ls.blk, (void *)ls.red, (void *)ls.guard})
-    if (p) (void)hipFree(p);
-  if (ls.h_blk) (void)hipHostFree(ls.h_blk);
-  if (ls.h_guard) (void)hipHostFree(ls.h_guard);
 }
 
 void batch_ls_eval_outer(pgf_batch b) {
   auto &ls = b->ls;
   if (ls.hat_fresh) return;
-  if (b->band)
-    bandb_launch_eval(b->stream, ls.obtab, b->B, b->bsh);
+  if (b->band.on)
+    bandb_launch_eval(b->stream, ls.obtab, b->B, b->band.sh);
   else
     batch_launch_eval(b->stream, ls.otab, b->B, b->sc, PGF_GEMVT_PARTS);
   ls.hat_fresh = true;
@@ -140,7 +115,7 @@ int batch_ls_enqueue_stage(pgf_batch b) {
   hipStream_t s = b->stream;
   const int n = b->n, m = b->m;
   int launches = 0;
-  if (b->band) {
+  if (b->band.on) {
     // (the guard's setting of every handle as it stands now, for the instances that sit the stage
     // out above their tolerance; the pinned pair is free: the last step was awaited)
     for (int i = 0; i < b->B; ++i) {
@@ -148,13 +123,13 @@ int batch_ls_enqueue_stage(pgf_batch b) {
       ls.h_guard[2 * i + 1] = b->hs[i]->guard.refine_tol;
     }
     BHIPCHK(b, hipMemcpyAsync(ls.guard, ls.h_guard, (size_t)b->B * 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    bandb_launch_eval(s, ls.ibtab, b->B, b->bsh);
+    bandb_launch_eval(s, ls.ibtab, b->B, b->band.sh);
     launches += (m ? 1 : 0) + (n ? 1 : 0);
   } else if (n) {
     batch_launch_eval(s, ls.itab, b->B, b->sc, PGF_GEMVT_PARTS);
     launches += m ? 5 : 2;
   }
-  batch_launch_ls_ladder(s, ls.ltab, b->B, n, m, b->band ? b->bsh.nred : 0, ls.newton_tol);
+  batch_launch_ls_ladder(s, ls.ltab, b->B, n, m, b->band.on ? b->band.sh.nred : 0, ls.newton_tol);
   batch_launch_ls_finish(s, ls.ltab, b->B, n, m);
   if (n + m) launches += 2;
   ls.stage_launches = launches;
@@ -198,10 +173,10 @@ int batch_ls_handle_search(pgf_batch b, int i, double *diff) {
 void batch_ls_report(pgf_batch b, int i, int *status, double *diff) {
   const double *blk = b->ls.h_blk + (size_t)LSB_STRIDE * i;
   if (blk[LSB_SAT_OUT] != 0.0) return;  // frozen, or a failed direction: reported by the step
-  const bool failed = blk[34] != 0.0;
+  const bool failed = blk[LS_STATUS] != 0.0;
   if (failed) b->hs[i]->err = "Line search failed to converge";
   if (status) status[i] = failed ? PGF_LINE_SEARCH : PGF_OK;
-  if (diff) diff[i] = failed ? 0.0 : blk[35];
+  if (diff) diff[i] = failed ? 0.0 : blk[LS_DIFF];
 }
 
 extern "C" {
@@ -224,11 +199,11 @@ int pgf_batch_line_search_stats(pgf_batch b, double *alpha, int *trials, double 
   if (!b->ls.have_stats) return bfail(b, PGF_NOT_READY, "no step with PGF_STEP_LINE_SEARCH yet");
   for (int i = 0; i < b->B; ++i) {
     const double *blk = b->ls.h_blk + (size_t)LSB_STRIDE * i;
-    if (alpha) alpha[i] = blk[0];
-    if (trials) trials[i] = (int)blk[1];
-    if (merit0) merit0[i] = blk[2];
-    if (slope) slope[i] = blk[3];
-    if (trial_merits) std::memcpy(trial_merits + (size_t)LS_TRIALS * i, blk + 4, LS_TRIALS * sizeof(double));
+    if (alpha) alpha[i] = blk[LS_ALPHA];
+    if (trials) trials[i] = (int)blk[LS_NTRIALS];
+    if (merit0) merit0[i] = blk[LS_MERIT0];
+    if (slope) slope[i] = blk[LS_SLOPE];
+    if (trial_merits) std::memcpy(trial_merits + (size_t)LS_TRIALS * i, blk + LS_MERITS, LS_TRIALS * sizeof(double));
   }
   return PGF_OK;
 }

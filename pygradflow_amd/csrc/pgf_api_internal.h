@@ -3,7 +3,10 @@
 // order, Gram matrix); pgf_api_guard.hip: its accuracy guard; pgf_api_step.hip: the Newton step and
 // the device-resident LQ mode; pgf_api_line_search.hip: the Globalized policy's line search around that
 // step; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the
-// unsymmetric formulations; pgf_api_batch.hip: the batch driver; pgf_api_aux.hip: profiling read-out,
+// unsymmetric formulations; pgf_api_batch.hip: the batch driver (lifecycle, outer step, host-driven
+// step) with pgf_api_band_batch.hip its banded half, pgf_api_batch_ctl.hip its device-resident
+// controller, pgf_api_batch_line_search.hip its Globalized policy and pgf_api_batch_read.hip its
+// read-outs; pgf_api_comm.hip: the RCCL communicator; pgf_api_aux.hip: profiling read-out,
 // the stand-alone linear solver and the pgf_debug_* hooks -- the handles, the error helpers and
 // the small interfaces between the files.
 #pragma once
@@ -397,74 +400,101 @@ int chain_recover(pgf_handle h, bool swapped);      // pgf_newton_solve, pgf_qp_
 bool step_spec();                                   // refresh_index_sets
 #pragma GCC visibility pop
 
-// ---- the batch (pgf_api_batch.hip: the dense half and the dispatch; pgf_api_band_batch.hip: the
-// banded half) ----------------------------------------------------------------------------------
+// ---- the batch ---------------------------------------------------------------------------------
+// pgf_api_batch.hip: lifecycle, the outer step and the host-driven Newton step (the dense half and
+// the dispatch); pgf_api_band_batch.hip: the banded half of those; pgf_api_batch_ctl.hip: the
+// device-resident controller, both halves; pgf_api_batch_line_search.hip: the Globalized policy;
+// pgf_api_batch_read.hip: read-outs and hooks; pgf_api_comm.hip: the RCCL communicator.
 struct pgf_batch_s {
   std::vector<pgf_handle> hs;
   int B = 0, n = 0, m = 0, device = 0;
   hipStream_t stream = nullptr;
+  // the instances' BInst records on the device and as create wrote them (the renamed tables of the
+  // refinement and the line search are copies of the host's); ctl: BCTL_STRIDE ints per instance
   BInst *tab = nullptr;
-  int *ctl = nullptr, *flags_out = nullptr, *h_flags = nullptr;
-  double *diff_out = nullptr, *norm_out = nullptr, *h_diff = nullptr, *h_norm = nullptr;
-  double *red4 = nullptr, *meas_out = nullptr, *h_meas = nullptr;
+  std::vector<BInst> htab;
+  int *ctl = nullptr;
   double *ps = nullptr, *h_ps = nullptr;      // per-instance [dt, lambda, rho, fact, delta, ...]
   uint8_t *bytes = nullptr, *h_bytes = nullptr;  // accept / frozen flags on their way to the device
   BatchScalars sc{};
   bool outer_set = false, eval_fresh = false, step_pending = false, have_mask = false;
   bool all_factored = false;
-  // condensed order (constraint block eliminated first, as condensed_wanted for one instance):
-  // cond_ok = the panels exist and the batch runs one of the chain schedules; cond_wanted = the
+  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond.last
+  // everything batch_alloc gave out (pointer, pinned), freed by pgf_batch_destroy
+  std::vector<std::pair<void *, bool>> mem;
+  PgfProfile prof;
+  std::string err = "";
+
+  // ---- what a step or a read-out leaves, and the pinned mirrors (pgf_api_batch.hip; the read-outs:
+  // pgf_api_batch_read.hip) ---- flags / h_flags: BFL_STRIDE ints per instance (pgf_batch.h)
+  struct {
+    int *flags = nullptr, *h_flags = nullptr;
+    double *diff = nullptr, *norm = nullptr, *h_diff = nullptr, *h_norm = nullptr;
+    double *red4 = nullptr, *meas = nullptr, *h_meas = nullptr;
+  } out;
+
+  // ---- the condensed order (pgf_api_batch.hip) ----
+  // (constraint block eliminated first, as condensed_wanted for one instance):
+  // ok = the panels exist and the batch runs one of the chain schedules; wanted = the
   // growth bound holds for every instance's delta (decided per outer step on the host: the
   // device-resident controller, which moves lambda on the device, keeps the natural order);
-  // cond_last = how the factors the instances hold were made; cond_free = the next step
+  // last = how the factors the instances hold were made; free = the next step
   // refactorises every instance anyway and may choose
-  bool cond_ok = false, cond_wanted = false, cond_last = false, cond_free = true;
-  bool stepped = false;  // a step was enqueued: the instances hold factors made in order cond_last
-  int cond_mp = 0;
-  int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
-  int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
-  // device-resident step controller (pgf_batch_ctl_*): per-instance state, constants, and a
-  // log of (lambda used, lambda next, accepted) per outer iteration and instance
-  double *dctl_cs = nullptr, *dctl_cp = nullptr, *dctl_log = nullptr;
-  int dctl_log_cap = 0, dctl_logged = 0;
-  // A banded batch (pgf_api_band_batch.hip): banded handles of one pattern, all narrow or all wide.  btab: the
-  // instances' BandInst records beside the BInst ones in tab; bsh: what they share; bstat / h_bstat:
-  // ONE status block for the whole batch, 3 nred + 4 doubles per instance (residual pairs, partial
-  // sums of the step update, pivot flags) and its pinned mirror, read with one copy per step;
-  // frozen / last_neg: the host's view of pgf_batch_set_frozen and of the inertia last reported.
-  bool band = false;
-  BandInst *btab = nullptr;
-  BandShape bsh{};
-  double *bstat = nullptr, *h_bstat = nullptr;
-  std::vector<uint8_t> frozen;
-  std::vector<int> last_neg;
-  int stat_band_reductions = 0, stat_band_assemblies = 0;  // pgf_batch_debug_band_stats
-  // wide route: per instance (reductions, solve phases) counted on the device, and the steps enqueued
-  // without inversion launches (pgf_batch_debug_band_wide_stats)
-  int *wcnt = nullptr;
-  int stat_band_lean = 0;
-  // bordered narrow route: per instance (factor phases, solve phases) counted on the device
-  // (pgf_batch_debug_border_stats); stat_band_lean counts the steps enqueued without factor-phase launches
-  int *bcnt = nullptr;
-  // created with PGF_BATCH_BAND_CTL: the device-resident controller is open to this band batch.
-  // flags_out / diff_out are allocated as for a dense batch and written by kbb_step_final;
-  // band_guard: per instance (guard on, refine_tol) as pgf_batch_ctl_init found them on the handles;
-  // band_rejects: per instance, steps the loop rejected for a pivot / by the guard
-  bool band_ctl = false;
-  double *band_guard = nullptr;
-  int *band_rejects = nullptr;
-  // created with PGF_BATCH_CTL_REFINE besides: band_guard has a third double per instance
-  // (refine_fail), and every banded step of the loop enqueues two refinement rounds on rtab -- btab
-  // over again, except that ctl points at the instance's refinement words in rctl ([0] stays 0: no
-  // assembly, kept factors, no write of ctl[1]; [1] a round ran in this step; [2] the step missed
-  // refine_tol as it came out of the solve; [3] sits this round out) -- rrel: the measure the next
-  // round has to beat; rcnt: per instance (steps refined, rounds run)
-  bool ctl_refine = false;
-  BandInst *rtab = nullptr;
-  int *rctl = nullptr, *rcnt = nullptr;
-  double *rrel = nullptr;
-  // created with PGF_BATCH_LINE_SEARCH (pgf_api_batch_line_search.hip): the Globalized policy.  otab /
-  // obtab: tab / btab over again, except that (x, y, g, c) name the instance's OUTER point
+  struct {
+    bool ok = false, wanted = false, last = false, free = true;
+    int mp = 0;
+  } cond;
+
+  // ---- the device-resident step controller (pgf_api_batch_ctl.hip) ----
+  // per-instance state, constants, and a log of (lambda used, lambda next, accepted) per outer
+  // iteration and instance
+  struct {
+    double *cs = nullptr, *cp = nullptr, *log = nullptr;
+    int log_cap = 0, logged = 0;
+  } dctl;
+
+  // ---- a banded batch (pgf_api_band_batch.hip; ctl, refine and what follows each:
+  // pgf_api_batch_ctl.hip) ----
+  // Banded handles of one pattern, all narrow or all wide.  tab / htab: the instances' BandInst
+  // records beside the BInst ones; sh: what they share; stat / h_stat: ONE status block for the whole
+  // batch, band_stat_stride(sh) doubles per instance (residual pairs, partial sums of the step
+  // update, pivot flags) and its pinned mirror, read with one copy per step; frozen / last_neg: the
+  // host's view of pgf_batch_set_frozen and of the inertia last reported.
+  struct {
+    bool on = false;
+    BandInst *tab = nullptr;
+    std::vector<BandInst> htab;
+    BandShape sh{};
+    double *stat = nullptr, *h_stat = nullptr;
+    std::vector<uint8_t> frozen;
+    std::vector<int> last_neg;
+    // wide route: per instance (reductions, solve phases) counted on the device
+    // (pgf_batch_debug_band_wide_stats)
+    int *wcnt = nullptr;
+    // bordered narrow route: per instance (factor phases, solve phases) counted on the device
+    // (pgf_batch_debug_border_stats)
+    int *bcnt = nullptr;
+    // created with PGF_BATCH_BAND_CTL: the device-resident controller is open to this band batch.
+    // out.flags / out.diff are allocated as for a dense batch and written by kbb_step_final;
+    // guard: per instance (guard on, refine_tol) as pgf_batch_ctl_init found them on the handles;
+    // rejects: per instance, steps the loop rejected for a pivot / by the guard
+    bool ctl = false;
+    double *guard = nullptr;
+    int *rejects = nullptr;
+    // created with PGF_BATCH_CTL_REFINE besides: guard has a third double per instance
+    // (refine_fail), and every banded step of the loop enqueues two refinement rounds on rtab -- tab
+    // over again, except that ctl points at the instance's refinement words in rctl ([0] stays 0: no
+    // assembly, kept factors, no write of ctl[1]; [1] a round ran in this step; [2] the step missed
+    // refine_tol as it came out of the solve; [3] sits this round out) -- rrel: the measure the next
+    // round has to beat; rcnt: per instance (steps refined, rounds run)
+    bool refine = false;
+    BandInst *rtab = nullptr;
+    int *rctl = nullptr, *rcnt = nullptr;
+    double *rrel = nullptr;
+  } band;
+
+  // ---- the Globalized policy (pgf_api_batch_line_search.hip; created with PGF_BATCH_LINE_SEARCH) ----
+  // otab / obtab: tab / band.tab over again, except that (x, y, g, c) name the instance's OUTER point
   // (xhat, yhat and its handle's ls.ghat, ls.chat) -- the step's residual, right-hand side and
   // update run on them; itab / ibtab (dense / band): (x, y, c, g, q, b) name (dx, dy, u, v, 0, 0),
   // so that the batch's evaluation launches form the direction's images; ltab: what the ladder and
@@ -482,8 +512,16 @@ struct pgf_batch_s {
     bool hat_fresh = false, pending = false, have_stats = false;
     int stage_launches = 0, host_waits = 0;  // pgf_batch_debug_line_search_stats
   } ls;
-  PgfProfile prof;
-  std::string err = "";
+
+  // ---- counters and hooks read or set only by pgf_api_batch_read.hip ----
+  struct {
+    int repaired = 0;  // instances whose step the host-side guard repaired (pgf_batch_refinement_stats)
+    int inject_helper_failure = 0;  // test hook: instance 0's next factorisation reports failed helpers
+    int band_reductions = 0, band_assemblies = 0;  // pgf_batch_debug_band_stats
+    // steps enqueued without inversion launches (wide route) / without factor-phase launches
+    // (bordered): pgf_batch_debug_band_wide_stats
+    int band_lean = 0;
+  } dbg;
 };
 
 static inline int bfail(pgf_batch b, int code, const char *msg) {
@@ -500,27 +538,78 @@ static inline int bfail(pgf_batch b, int code, const char *msg) {
     }                                                                    \
   } while (0)
 
+// doubles per instance of a band batch's status block: the handle's own stride
+static inline size_t band_stat_stride(const BandShape &sh) { return (size_t)3 * sh.nred + 4; }
 
-// The banded half, each beside the entry point that hands over to it in one line.
+// a handle's host-side view of its outer step: lambda and what a step derives from it and rho
+static inline void set_outer_scalars(pgf_handle h, double dt, double rho) {
+  h->dt = dt;
+  h->lamb = 1.0 / dt;
+  h->rho = rho;
+  h->fact = 1.0 / (1.0 + h->lamb * rho);
+  h->delta = h->lamb / (1.0 + h->lamb * rho);
+}
+
+#pragma GCC visibility push(hidden)
+// ---- pgf_api_batch.hip, for every file of the batch ----------------------------------------------
+// One allocation of the batch: count elements, device memory or (BA_PINNED) pinned host memory,
+// zeroed with BA_ZERO; pgf_batch_destroy frees it.  A create is a list of these behind one
+// hipError_t: a call is a no-op once *e holds an error, so the list has a single failure exit.
+enum { BA_DEVICE = 0, BA_PINNED = 1, BA_ZERO = 2 };
+void batch_alloc_bytes(pgf_batch b, hipError_t *e, void **p, size_t bytes, unsigned kind);
+template <typename T>
+static inline void batch_alloc(pgf_batch b, hipError_t *e, T **p, size_t count, unsigned kind = BA_DEVICE) {
+  batch_alloc_bytes(b, e, (void **)p, count * sizeof(T), kind);
+}
+// a device copy of the host table src with rename(entry, i) applied to every entry (band.rtab and
+// the line search's tables)
+template <typename T, typename F>
+static inline void batch_renamed_table(pgf_batch b, hipError_t *e, T **dst, const std::vector<T> &src, F rename) {
+  std::vector<T> t(src);
+  for (size_t i = 0; i < t.size(); ++i) rename(t[i], i);
+  batch_alloc(b, e, dst, t.size());
+  if (*e == hipSuccess) *e = hipMemcpy(*dst, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+// What both creates ask of every handle, in two parts: the kind's own checks go between them.  0, or
+// the refusal's code with its text in *msg.
+int batch_check_shape(pgf_handle h, pgf_handle h0, const char **msg);   // pgf_batch_create_ex, band_batch_create
+int batch_check_state(pgf_handle h, bool band, const char **msg);       // pgf_batch_create_ex, band_batch_create
+// the new batch's scalars from its first handle, and its stream
+hipError_t batch_begin(pgf_batch b, const pgf_handle *handles, int count);  // pgf_batch_create_ex, band_batch_create
+// the vector part of instance i's records from its handle and its batch slots (the dense create
+// adds the matrices and the factor's arrays; band_inst_of has filled the band's own)
+void batch_fill_vectors(pgf_batch b, int i, BInst &t);     // pgf_batch_create_ex, band_batch_create
+void batch_fill_vectors(pgf_batch b, int i, BandInst &u);  // band_batch_create
+// the batch owns the device-side state of the handle from here on
+void batch_own_handle(pgf_handle h);                        // pgf_batch_create_ex, band_batch_create
+void batch_eval(pgf_batch b);  // band_batch_enqueue_step, band_batch_step_async, pgf_batch_ctl_iterate, the read-outs
+// everything of one dense Newton step, enqueued
+void batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool host_knows_factored);  // ctl_enqueue_step
+// behind the step's wait: whether the step carried PGF_STEP_LINE_SEARCH, its counters settled
+bool batch_ls_begin_sync(pgf_batch b);                      // pgf_batch_sync, band_batch_sync
+// a chain helper or a chained solve failed its hand-over: both go off for the process, the
+// publication halves of instance i (i < 0: of every instance) get their sentinels back, and the
+// sticky word behind out.flags is cleared -- all enqueued on the batch's stream
+hipError_t batch_chain_off(pgf_batch b, int i);             // pgf_batch_sync, pgf_batch_ctl_read
+// ---- pgf_api_batch_read.hip ----
+// two ints per instance, counted on the device in pairs (null: zeros), split into the two outputs
+int batch_read_pairs(pgf_batch b, const int *pairs, int *first, int *second);  // the pgf_batch_debug_*_stats of both files
+
+// ---- the banded half (pgf_api_band_batch.hip), each beside the entry point that hands over to it
+// in one line ----
 int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out);  // pgf_batch_create_ex
-void band_batch_free(pgf_batch b);                                            // pgf_batch_destroy
 void band_batch_eval(pgf_batch b);                                            // batch_eval
 int band_batch_step_async(pgf_batch b, unsigned policy, double tau);          // pgf_batch_step_async
 int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff);      // pgf_batch_sync
 // the launches of one banded step, without the evaluation made ahead and the status copy;
 // lean_allowed: the caller knows that every instance still live holds a clean factor of its band
-void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed);  // pgf_batch_ctl_iterate
-void band_batch_enqueue_refine(pgf_batch b);                                  // pgf_batch_ctl_iterate
-void band_batch_enqueue_final(pgf_batch b);                                   // pgf_batch_ctl_iterate
-int band_batch_ctl_init(pgf_batch b);                                         // pgf_batch_ctl_init
-int band_batch_ctl_read(pgf_batch b);                                         // pgf_batch_ctl_read
+void band_batch_enqueue_step(pgf_batch b, unsigned policy, double tau, bool lean_allowed);  // ctl_enqueue_step
 void band_batch_measures_eval(pgf_batch b);                                   // pgf_batch_measures
 // ---- the Globalized policy on a batch (pgf_api_batch_line_search.hip) -----------------------------
 int batch_ls_attach(pgf_batch b);                       // pgf_batch_create_ex
-void batch_ls_free(pgf_batch b);                        // pgf_batch_destroy
 // g, c at every instance's outer point, once per outer step (behind the evaluation at the current
 // points and in front of the mask, as ls_enter orders them on the handle)
-void batch_ls_eval_outer(pgf_batch b);                  // pgf_batch_step_async, band_batch_step_async
+void batch_ls_eval_outer(pgf_batch b);                  // batch_enqueue_step, band_batch_enqueue_step
 // behind the step update: the images, the ladder, the finish, and the copy of the blocks
 int batch_ls_enqueue_stage(pgf_batch b);                // pgf_batch_step_async, band_batch_step_async
 // An instance the guard repairs on its handle: the handle's (x, y, g, c) name its outer point's
@@ -530,6 +619,7 @@ void batch_ls_handle_enter(pgf_batch b, int i);         // batch_repair_instance
 int batch_ls_handle_search(pgf_batch b, int i, double *diff);
 // after the step's wait: the instance's status and step length from its block
 void batch_ls_report(pgf_batch b, int i, int *status, double *diff);  // pgf_batch_sync, band_batch_sync
+#pragma GCC visibility pop
 // what it takes from pgf_api_band.hip: the guard's measure over nred residual pairs, and the hash
 // of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat_hash)
 double band_residual_rel_of(const double *pairs, int nred);

@@ -121,14 +121,14 @@ int ls_search(pgf_handle h, double *diff) {
   ++h->dbg.stat_host_syncs;
   float ms = 0.f;
   if (timed && hipEventElapsedTime(&ms, ls.ev0, ls.ev1) == hipSuccess) ls.stage_ms = ms;
-  if (n + m == 0) ls.h_blk[0] = 1.0;
+  if (n + m == 0) ls.h_blk[LS_ALPHA] = 1.0;
   ls.have_stats = true;
-  if (ls.h_blk[34] != 0.0) return fail(h, PGF_LINE_SEARCH, "Line search failed to converge");
+  if (ls.h_blk[LS_STATUS] != 0.0) return fail(h, PGF_LINE_SEARCH, "Line search failed to converge");
   swap_point(h);
   h->eval_fresh = false;
   drop_norm(h);
-  h->h_scal[0] = ls.h_blk[35];
-  if (diff) *diff = ls.h_blk[35];
+  h->h_scal[0] = ls.h_blk[LS_DIFF];
+  if (diff) *diff = ls.h_blk[LS_DIFF];
   return PGF_OK;
 }
 
@@ -146,11 +146,11 @@ int pgf_qp_line_search_stats(pgf_handle h, double *alpha, int *trials, double *m
   if (!h) return PGF_INVALID;
   if (!h->ls.have_stats) return fail(h, PGF_NOT_READY, "no step with PGF_STEP_LINE_SEARCH yet");
   const double *b = h->ls.h_blk;
-  if (alpha) *alpha = b[0];
-  if (trials) *trials = (int)b[1];
-  if (merit0) *merit0 = b[2];
-  if (slope) *slope = b[3];
-  if (trial_merits) std::memcpy(trial_merits, b + 4, LS_TRIALS * sizeof(double));
+  if (alpha) *alpha = b[LS_ALPHA];
+  if (trials) *trials = (int)b[LS_NTRIALS];
+  if (merit0) *merit0 = b[LS_MERIT0];
+  if (slope) *slope = b[LS_SLOPE];
+  if (trial_merits) std::memcpy(trial_merits, b + LS_MERITS, LS_TRIALS * sizeof(double));
   return PGF_OK;
 }
 

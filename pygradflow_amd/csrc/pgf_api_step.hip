@@ -500,11 +500,7 @@ int pgf_qp_advance_outer(pgf_handle h, double dt, double rho) {
   }
   if (rho != h->rho) h->eval_fresh = false;  // g depends on rho
   drop_norm(h);                              // (the norm on the outer point and dt besides)
-  h->dt = dt;
-  h->lamb = 1.0 / dt;
-  h->rho = rho;
-  h->fact = 1.0 / (1.0 + h->lamb * rho);
-  h->delta = h->lamb / (1.0 + h->lamb * rho);
+  set_outer_scalars(h, dt, rho);
   if (one)
     launch_advance_outer(h->stream, h->n, h->m, h->lamb, h->x, h->y, h->lb, h->ub, h->xhat, h->yhat, h->slb,
                          h->sub);

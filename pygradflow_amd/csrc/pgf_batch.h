@@ -34,7 +34,7 @@ struct BInst {
   double *xpub;
   int *cctl;
   int capblk;
-  // condensed order (pgf_api_batch.hip, pgf_batch_s::cond_wanted): the instance's panel V = J_I^T
+  // condensed order (pgf_api_batch.hip, pgf_batch_s::cond): the instance's panel V = J_I^T
   // ((n + 1) x ldv, row nI = the constraint part of the right-hand side) and its scaling -1 / delta
   double *V;
   int64_t ldv;
@@ -55,6 +55,14 @@ struct BatchScalars {
 #define BPS_NORM_J1 6
 #define BPS_NORM_JINF 7
 #define BPS_STRIDE 8
+// ctl: BCTL_STRIDE ints per instance (the words above).  flags_out of the step update and its pinned
+// mirror: BFL_STRIDE ints per instance; on the device one sticky word behind the last instance's
+// (a chain helper or a chained solve failed its hand-over in some step since it was cleared)
+#define BCTL_STRIDE 4
+#define BFL_BAD 0  // bit 0 zero pivot, bit 1 failed hand-over, bit 2 sampled residual too large
+#define BFL_NEG 1  // negative pivots
+#define BFL_NI 2   // |I|
+#define BFL_STRIDE 3
 
 // device-resident step controller: per-instance state (cs) and constants (cp)
 #define DCS_LAMB 0      // lambda of the next outer iteration

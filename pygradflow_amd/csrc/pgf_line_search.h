@@ -10,6 +10,13 @@
 // the full step without a trial), [2] merit0, [3] slope, [4, 34) the trial merits, [34] status
 // (0 accepted, 1 no trial accepted), [35] ||(dx, alpha dy)|| of the step taken (k_ls_finish);
 // behind what the host reads: [36] the two tickets of the last-workgroup reductions.
+#define LS_ALPHA 0
+#define LS_NTRIALS 1
+#define LS_MERIT0 2
+#define LS_SLOPE 3
+#define LS_MERITS 4  // LS_TRIALS doubles
+#define LS_STATUS 34
+#define LS_DIFF 35
 #define LS_COPY 36
 #define LS_ALLOC 37
 

@@ -105,7 +105,7 @@ __device__ __forceinline__ void b_ls_ladder(int bid, unsigned nblk, int n, int m
     tot[tid] = w;
   }
   __syncthreads();
-  if (tid < LS_TRIALS) blk[4 + tid] = 0.5 * tot[tid];
+  if (tid < LS_TRIALS) blk[LS_MERITS + tid] = 0.5 * tot[tid];
   if (tid != 0) return;
   const double merit0 = 0.5 * tot[LS_TRIALS], slope = tot[LS_TRIALS + 1];
   double alpha = 1.0, status = 0.0;
@@ -126,11 +126,11 @@ __device__ __forceinline__ void b_ls_ladder(int bid, unsigned nblk, int n, int m
       a *= 0.5;
     }
   }
-  blk[0] = alpha;
-  blk[1] = (double)trials;
-  blk[2] = merit0;
-  blk[3] = slope;
-  blk[34] = status;
+  blk[LS_ALPHA] = alpha;
+  blk[LS_NTRIALS] = (double)trials;
+  blk[LS_MERIT0] = merit0;
+  blk[LS_SLOPE] = slope;
+  blk[LS_STATUS] = status;
   *ticket = 0u;
 }
 
@@ -143,8 +143,8 @@ __device__ __forceinline__ void b_ls_finish(int bid, unsigned nblk, int n, int m
     const double *__restrict__ lb, const double *__restrict__ ub, double *__restrict__ xn,
     double *__restrict__ yn, double *red, double *blk, unsigned *ticket) {
   __shared__ double part[4];
-  if (blk[34] != 0.0) return;  // no trial accepted: the point stays
-  const double alpha = blk[0];
+  if (blk[LS_STATUS] != 0.0) return;  // no trial accepted: the point stays
+  const double alpha = blk[LS_ALPHA];
   const int tid = threadIdx.x;
   const int i = bid * 256 + tid;
   double sq = 0.0;
@@ -181,7 +181,7 @@ __device__ __forceinline__ void b_ls_finish(int bid, unsigned nblk, int n, int m
   if ((tid & 63) == 0) part[tid >> 6] = s;
   __syncthreads();
   if (tid == 0) {
-    blk[35] = sqrt((part[0] + part[1]) + (part[2] + part[3]));
+    blk[LS_DIFF] = sqrt((part[0] + part[1]) + (part[2] + part[3]));
     *ticket = 0u;
   }
 }

@@ -1,6 +1,6 @@
 """Bordered band batches under the device-resident step controller (PGF_BATCH_BORDER_CTL with
 PGF_BATCH_BORDER | PGF_BATCH_BAND_CTL; on a wide remainder PGF_BATCH_WIDE_BAND | PGF_BATCH_WIDE_BORDER
-besides): the loop of csrc/pgf_api_batch.hip around the bordered step of csrc/pgf_border.hip, finished
+besides): the loop of csrc/pgf_api_batch_ctl.hip around the bordered step of csrc/pgf_border.hip, finished
 per instance by kbb_step_final.
 
 The reference and the bars are those of test_band_batch_ctl_gpu.py, whose helpers are used: the

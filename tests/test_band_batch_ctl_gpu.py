@@ -1,5 +1,5 @@
 """The device-resident step controller on band batches (PGF_BATCH_BAND_CTL; kbb_step_final in
-csrc/pgf_sparse.hip, the loop in csrc/pgf_api_batch.hip): k outer iterations of every instance
+csrc/pgf_sparse.hip, the loop in csrc/pgf_api_batch_ctl.hip): k outer iterations of every instance
 enqueued back to back, the banded step finished per instance on the device.
 
 The reference is the host-driven ``BatchedDistanceRatioController`` on a twin batch without the flag,

@@ -1,5 +1,5 @@
 """Refinement inside the device-resident controller's loop on band batches (PGF_BATCH_CTL_REFINE
-with PGF_BATCH_BAND_CTL; band_batch_enqueue_refine in csrc/pgf_api_band_batch.hip): an instance whose
+with PGF_BATCH_BAND_CTL; band_batch_enqueue_refine in csrc/pgf_api_batch_ctl.hip): an instance whose
 solve misses its handle's refine_tol is refined on the device, by the device functions and in the
 order of band_refine on its handle, instead of rejected with 2 lambda.
 
