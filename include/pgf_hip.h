@@ -184,6 +184,20 @@ int pgf_sparse_set_factor_split(pgf_handle h, int on);
  * for dense handles.  With PGF_BORDER_MULTI=0 in the environment Y is formed by k single
  * banded solves also at block size 8 (the only route at 16, 32, 64). */
 int pgf_sparse_set_border(pgf_handle h, int k);
+/* Large border: 65 <= k <= 1024 border nodes, after pgf_sparse_set_pattern, on a banded handle whose
+ * remainder runs the wide route -- block size 16, 32 or 64 (pgf_sparse_set_block_size) with the
+ * factor / solve split on.  The store is that of pgf_sparse_set_border with kp = k rounded up to a
+ * multiple of 64.  Per assembled matrix: B is factorised once (the kept factors of the wide
+ * reduction), Y = inv(B) C is one panel solve whose launches carry kp / 64 column slices, C' Y is
+ * formed on the FP64 matrix pipes in 64 x 64 tiles over row chunks whose partial sums are added in
+ * chunk order, and S = D - C' Y is factorised by a dense L D L' of size kp whose status the factor
+ * phase awaits; a solve phase adds no host wait (csrc/pgf_border_large.hip).  Steps, line search,
+ * pgf_linear_solve(_multi), the accuracy guard and the measures run as on any bordered handle.
+ * PGF_INVALID: k outside 65..1024, a dense handle, block size 8, the split off; afterwards
+ * pgf_sparse_set_factor_split(h, 0) and a change to block size 8 are PGF_INVALID, and
+ * pgf_batch_create refuses the handle ("batch: a large border ...").  pgf_sparse_set_border(h, 0)
+ * removes the border.  PGF_BORDER_MULTI=0 forms Y by k single solves, as above. */
+int pgf_sparse_set_border_large(pgf_handle h, int k);
 /* values of H = lag_hess(x, y) and J = cons_jac(x) in pattern order (update_derivs) */
 int pgf_sparse_set_values(pgf_handle h, const double *Hval, const double *Jval);
 /* q and b of a linear-quadratic problem whose Q, A were given through the sparse pattern */
@@ -692,6 +706,19 @@ int pgf_debug_update_plan(int N, int nrows, int vdepth, int budget, int cap, int
 /* the handle's border size and the factor / solve phases of the bordered route enqueued since
  * pgf_sparse_set_border (tests: a step that keeps its factor runs the solve phase only) */
 int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int *border_solves);
+/* large border: C and Y = inv(B) C (Nb x kp each, row-major, Nb = n + m - k) and G = C' Y (kp x kp,
+ * lower triangle, zero above) of the last factor phase.  Any pointer may be NULL.  PGF_NOT_READY
+ * before the first factor phase, PGF_INVALID without a large border. */
+int pgf_debug_border_gram(pgf_handle h, double *C, double *Y, double *G);
+/* large border: the Gram kernel's launch plan on this handle -- rows per chunk, row chunks and
+ * 64 x 64 tiles of the lower triangle; the grid is tiles x chunks.  Any pointer may be NULL.
+ * PGF_INVALID without a large border. */
+int pgf_debug_border_gram_plan(pgf_handle h, int *rows, int *chunks, int *tiles);
+/* measurement (tools/time_border.py): device time in ms per launch, over `reps` launches, of the
+ * Gram launch alone on the C and Y of the last factor phase of a bordered handle whose kp is a
+ * multiple of 64 -- *ms_mfma: the large border's MFMA kernel; *ms_fma: the small border's FMA
+ * kernel (kp = 64 only, -1 beyond).  Production at kp <= 64 runs the FMA kernel. */
+int pgf_debug_border_gram_time(pgf_handle h, int reps, double *ms_mfma, double *ms_fma);
 /* phases of the wide band (B = 16, 32, 64) enqueued on the handle since its creation: reductions
  * (fused or factor-only), solve phases for one right-hand side against kept factors, panel
  * solves.  Any pointer may be NULL. */

@@ -67,6 +67,7 @@ SIGNATURES = {
     "pgf_sparse_set_block_size": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_factor_split": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_border": (C.c_int, [_h, C.c_int]),
+    "pgf_sparse_set_border_large": (C.c_int, [_h, C.c_int]),
     "pgf_sparse_set_values": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_vectors": (C.c_int, [_h, _dp, _dp]),
     "pgf_qp_set_problem": (C.c_int, [_h, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
@@ -135,6 +136,9 @@ SIGNATURES = {
     "pgf_debug_update_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip,
                                         _ip, C.c_int, _ip, _ip, _ip]),
     "pgf_debug_border_stats": (C.c_int, [_h, _ip, _ip, _ip]),
+    "pgf_debug_border_gram": (C.c_int, [_h, _dp, _dp, _dp]),
+    "pgf_debug_border_gram_plan": (C.c_int, [_h, _ip, _ip, _ip]),
+    "pgf_debug_border_gram_time": (C.c_int, [_h, C.c_int, _dp, _dp]),
     "pgf_debug_band_stats": (C.c_int, [_h, _ip, _ip, _ip]),
     "pgf_batch_refinement_stats": (C.c_int, [_h, _ip]),
     "pgf_batch_debug_band_stats": (C.c_int, [_h, _ip, _ip]),

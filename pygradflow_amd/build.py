@@ -24,6 +24,7 @@ NO_CONTRACT = [
     "pgf_line_search.hip",
     "pgf_batch_line_search.hip",
     "pgf_border.hip",
+    "pgf_border_large.hip",
     "pgf_unsym.hip",
     "pgf_api.hip",
     "pgf_api_factor.hip",

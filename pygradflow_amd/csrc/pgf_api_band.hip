@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <new>
 #include <utility>
 
 #include "pgf_api_internal.h"
@@ -388,6 +389,17 @@ static void sp_border_free(SparseDev &sp) {
     (void)hipFree(sp.bsflags);
     sp.bsflags = nullptr;
   }
+  if (sp.bG) {  // large border: the kept C' Y and the dense factor of S
+    (void)hipFree(sp.bG);
+    sp.bG = nullptr;
+  }
+  if (sp.blf) {
+    ldlt_free(*sp.blf);
+    delete sp.blf;
+    sp.blf = nullptr;
+  }
+  sp.bgrows = sp.bgchunks = 0;
+  sp.bgram_ready = false;
   sp.bk = sp.bkp = sp.Nb = sp.bnchunk = 0;
   sp.bC = sp.bDd = nullptr;
   sp.stat_bfactor = sp.stat_bsolve = 0;
@@ -418,9 +430,14 @@ void band_free(pgf_handle h) {
   void *sps[] = {sp.pos, sp.Hptr, sp.Hrow, sp.Hcol, sp.Hslot, sp.Jptr, sp.Jcol, sp.Jslot, sp.JTptr,
                  sp.JTrow, sp.JTmap, sp.Hval, sp.Jval, sp.band, sp.brhs, sp.Hb0, sp.Jb0,
                  sp.bD, sp.bL, sp.bU, sp.bDinv, sp.bF, sp.bneg, sp.brhs0, sp.bres, sp.bsol,
-                 sp.bred, sp.bMr, sp.bMl, sp.bP, sp.bredm, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags};
+                 sp.bred, sp.bMr, sp.bMl, sp.bP, sp.bredm, sp.bY, sp.bS, sp.bpart, sp.bpartv, sp.brb, sp.bz, sp.bsflags,
+                 sp.bG};
   for (void *q : sps)
     if (q) (void)hipFree(q);
+  if (sp.blf) {
+    ldlt_free(*sp.blf);
+    delete sp.blf;
+  }
 }
 
 extern "C" {
@@ -566,12 +583,103 @@ int pgf_debug_border_stats(pgf_handle h, int *k, int *border_factorisations, int
   return PGF_OK;
 }
 
+int pgf_sparse_set_border_large(pgf_handle h, int k) {
+  if (!h) return PGF_INVALID;
+  if (!h->sparse) return fail(h, PGF_INVALID, "pgf_sparse_set_border_large: banded handles only");
+  if (k < 65 || k > 1024) return fail(h, PGF_INVALID, "large border size must be 65..1024");
+  if (!h->sp.active) return fail(h, PGF_NOT_READY, "pgf_sparse_set_pattern first");
+  const int N = h->n + h->m;
+  if (k >= N) return fail(h, PGF_INVALID, "the border must leave at least one band row");
+  SparseDev &sp = h->sp;
+  if (sp.B <= 8) return fail(h, PGF_INVALID, "a large border needs a wide remainder (block size 16, 32 or 64)");
+  if (!(sp.split && sp.bMr)) return fail(h, PGF_INVALID, "a large border needs the factor / solve split");
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  sp_border_free(sp);
+  invalidate_factor(h);
+  const int Nb = N - k, kp = (k + 63) / 64 * 64;
+  const size_t band_doubles = (size_t)(Nb + 1) * sp.ldb;
+  // band, C and D in one array: the plan's slots index it as a whole
+  (void)hipFree(sp.band);
+  sp.band = nullptr;
+  if (band_doubles + (size_t)Nb * kp + (size_t)kp * kp > (size_t)INT32_MAX)
+    return fail(h, PGF_INVALID, "band and border store exceed 2^31 entries");
+  HIPCHK(h, dalloc(&sp.band, band_doubles + (size_t)Nb * kp + (size_t)kp * kp));
+  sp.bk = k;
+  sp.bkp = kp;
+  sp.Nb = Nb;
+  sp.bC = sp.band + band_doubles;
+  sp.bDd = sp.bC + (size_t)Nb * kp;
+  sp.bnchunk = (Nb + SP_BORDER_CHUNK - 1) / SP_BORDER_CHUNK;
+  sp_borderL_gram_plan(Nb, kp, &sp.bgrows, &sp.bgchunks);
+  const size_t ntiles = (size_t)(kp / 64) * (kp / 64 + 1) / 2;
+  HIPCHK(h, dalloc(&sp.bY, ((size_t)Nb + 64) * kp));
+  HIPCHK(h, dalloc(&sp.bS, (size_t)kp));  // here: the right-hand side of the solve with S
+  HIPCHK(h, dalloc(&sp.bpart, (size_t)sp.bgchunks * ntiles * 4096));
+  HIPCHK(h, dalloc(&sp.bpartv, (size_t)sp.bnchunk * 3 * kp));
+  HIPCHK(h, dalloc(&sp.brb, (size_t)kp));
+  HIPCHK(h, dalloc(&sp.bz, (size_t)kp));
+  HIPCHK(h, dalloc(&sp.bG, (size_t)kp * kp));
+  HIPCHK(h, hipMalloc((void **)&sp.bsflags, 4 * sizeof(int)));
+  HIPCHK(h, hipMemsetAsync(sp.bsflags, 0, 4 * sizeof(int), h->stream));
+  HIPCHK(h, hipMemsetAsync(sp.brb, 0, (size_t)kp * sizeof(double), h->stream));  // padding stays zero
+  sp.blf = new (std::nothrow) DenseLdlt();
+  if (!sp.blf) return fail(h, PGF_INVALID, "out of memory");
+  HIPCHK(h, ldlt_alloc(*sp.blf, kp, h->stream));
+  sp.blf->chain_solves = false;  // (no host synchronisation of its own behind a solve phase)
+  HIPCHK(h, hipMemsetAsync(sp.blf->K, 0, ((size_t)kp + 1 + PGF_NB) * sp.blf->ldk * sizeof(double), h->stream));
+  // the residual pairs: one per 256 band rows and one per 256 border rows
+  int rc;
+  if ((rc = sp_alloc_bred(h, std::max((N + 255) / 256, (Nb + 255) / 256 + (k + 255) / 256)))) return rc;
+  HIPCHK(h, hipMemsetAsync(sp.bred, 0, ((size_t)3 * sp.nred + 4) * sizeof(double), h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PGF_OK;
+}
+
+int pgf_debug_border_gram(pgf_handle h, double *Cout, double *Yout, double *Gout) {
+  if (!h) return PGF_INVALID;
+  const SparseDev &sp = h->sp;
+  if (!h->sparse || !sp_border_large(sp)) return fail(h, PGF_INVALID, "pgf_debug_border_gram: no large border");
+  if (!sp.bgram_ready) return fail(h, PGF_NOT_READY, "no factor phase has run on this border yet");
+  (void)hipSetDevice(h->device);
+  const size_t panel = (size_t)sp.Nb * sp.bkp * sizeof(double);
+  int rc;
+  if (Cout && (rc = down(h, Cout, sp.bC, panel))) return rc;
+  if (Yout && (rc = down(h, Yout, sp.bY, panel))) return rc;
+  if (Gout && (rc = down(h, Gout, sp.bG, (size_t)sp.bkp * sp.bkp * sizeof(double)))) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return PGF_OK;
+}
+
+int pgf_debug_border_gram_plan(pgf_handle h, int *rows, int *chunks, int *tiles) {
+  if (!h) return PGF_INVALID;
+  const SparseDev &sp = h->sp;
+  if (!h->sparse || !sp_border_large(sp)) return fail(h, PGF_INVALID, "pgf_debug_border_gram_plan: no large border");
+  if (rows) *rows = sp.bgrows;
+  if (chunks) *chunks = sp.bgchunks;
+  if (tiles) *tiles = (sp.bkp / 64) * (sp.bkp / 64 + 1) / 2;
+  return PGF_OK;
+}
+
+int pgf_debug_border_gram_time(pgf_handle h, int reps, double *ms_mfma, double *ms_fma) {
+  if (!h || !ms_mfma || !ms_fma || reps < 1) return PGF_INVALID;
+  const SparseDev &sp = h->sp;
+  if (!h->sparse || !sp.bk || sp.bkp % 64) return fail(h, PGF_INVALID, "pgf_debug_border_gram_time: a border with kp a multiple of 64");
+  if (!sp.stat_bfactor) return fail(h, PGF_NOT_READY, "no factor phase has run on this border yet");
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, sp_borderL_gram_time(h->stream, sp, reps, ms_mfma, ms_fma));
+  return PGF_OK;
+}
+
 int pgf_sparse_set_factor_split(pgf_handle h, int on) {
   if (!h) return PGF_INVALID;
   if (!h->sparse) return fail(h, PGF_INVALID, "pgf_sparse_set_factor_split: banded handles only");
   SparseDev &sp = h->sp;
   const bool want = on != 0;
   if (want == sp.split) return PGF_OK;
+  if (!want && sp_border_large(sp))
+    return fail(h, PGF_INVALID, "a large border needs the factor / solve split");
   (void)hipSetDevice(h->device);
   HIPCHK(h, hipStreamSynchronize(h->stream));
   sp.split = want;
@@ -608,6 +716,8 @@ int pgf_sparse_set_block_size(pgf_handle h, int B) {
   (void)hipSetDevice(h->device);
   const int want = B ? B : auto_block_size(h->sp.bw);
   if (want == h->sp.B) return PGF_OK;
+  if (want == 8 && sp_border_large(h->sp))
+    return fail(h, PGF_INVALID, "a large border needs a wide remainder (block size 16, 32 or 64)");
   int rc;
   if ((rc = sp_alloc_blocks(h, want))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));

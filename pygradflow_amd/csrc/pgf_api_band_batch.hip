@@ -39,6 +39,8 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
     const SparseDev &sp = h->sp;
     if (!sp.active || !sp.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
+    if (sp_border_large(sp))
+      return fail(h, PGF_INVALID, "batch: a large border (more than 64 nodes) cannot join a device batch");
     if (sp.bk && !border_ok) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
     if (sp.bk != h0->sp.bk) return fail(h, PGF_INVALID, "batch: banded instances must share the border size");
     if (sp.bk && sp.B != 8 && !wide_border_ok)

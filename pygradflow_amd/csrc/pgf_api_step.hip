@@ -662,7 +662,15 @@ static int qp_sync_step(pgf_handle h, int *n_neg, double *diff) {
     if (st == 2) return fail(h, PGF_HIP_ERROR, k_helper_msg);
   }
   if (st < 0) return hip_fail(h, e, "step");
-  if (st == 1) return fail(h, PGF_SINGULAR, "zero or non-finite pivot in LDL^T of the KKT matrix");
+  if (st == 1) {
+    // large border: the discarded step's point goes back (its solve phase ran on a factor of S that
+    // does not exist; the other routes leave the new point, as they always have)
+    if (h->sparse && sp_border_large(h->sp) && !h->ls.want) {
+      swap_point(h);
+      h->eval_fresh = false;
+    }
+    return fail(h, PGF_SINGULAR, "zero or non-finite pivot in LDL^T of the KKT matrix");
+  }
   // (swapped: (x, y) is already the new point -- not with PGF_STEP_LINE_SEARCH, whose point moves later)
   if ((rc = chain_recover(h, !h->ls.want))) return rc;
   if ((rc = refine_if_needed(h, !h->ls.want))) return rc;

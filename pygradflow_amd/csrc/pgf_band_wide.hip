@@ -149,11 +149,12 @@ __global__ __launch_bounds__(BW_THREADS) void k_bw_x0(const double *__restrict__
 template <int B>
 __global__ __launch_bounds__(BW_THREADS) void k_bw_fwd_panel(const double *__restrict__ Mr,
                                                              const double *__restrict__ Ml,
-                                                             double *__restrict__ P, int kp, int nb,
-                                                             int s) {
+                                                             double *__restrict__ P, int ld, int kp,
+                                                             int nb, int s) {
   const int i = blockIdx.x * 2 * s;
   if (i >= nb) return;
-  bw_fwd_panel_block<B>(Mr, Ml, P, kp, nb, s, i);
+  // slice blockIdx.y: columns [64 y, 64 y + kp) of a panel with row stride ld
+  bw_fwd_panel_block<B>(Mr, Ml, P + 64 * blockIdx.y, ld, kp, nb, s, i);
 }
 
 // X_e = inv(D_e) (F_e - L_e X_{e-s} - U_e X_{e+s}) for e = first, first + stride, ...; s == 0: the
@@ -162,12 +163,12 @@ template <int B>
 __global__ __launch_bounds__(BW_THREADS) void k_bw_back_panel(const double *__restrict__ Dinv,
                                                               const double *__restrict__ L,
                                                               const double *__restrict__ U,
-                                                              double *__restrict__ P, int kp, int nb,
-                                                              int s, int first, int stride) {
+                                                              double *__restrict__ P, int ld, int kp,
+                                                              int nb, int s, int first, int stride) {
   __shared__ double T[B * 65];
   const int e = first + blockIdx.x * stride;
   if (e >= nb) return;
-  bw_back_panel_block<B>(Dinv, L, U, P, kp, nb, s, e, T);
+  bw_back_panel_block<B>(Dinv, L, U, P + 64 * blockIdx.y, ld, kp, nb, s, e, T);
 }
 // Accuracy guard for bw <= 64 (bw_residual_rows)
 __global__ __launch_bounds__(256) void k_bw_residual(const double *__restrict__ band, int ldb, int bw,
@@ -251,18 +252,22 @@ static void bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P,
   const int nb = (N + B - 1) / B;
   const dim3 blk(BW_THREADS);
   ++sp.stat_bw_panel;
+  // a panel wider than 64 columns (a multiple of 64 then): one 64-column slice per blockIdx.y, in
+  // the same launches -- the slices share the factors and nothing else
+  const int ld = kp, kw = kp > 64 ? 64 : kp;
+  const unsigned ns = (unsigned)((kp + 63) / 64);
   int levels[32], nlev = 0;
   for (int st = 1; st < nb; st *= 2) {
     const int nk = (nb + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_fwd_panel<B>, dim3(nk), blk, 0, s, sp.bMr, sp.bMl, P, kp, nb, st);
+    hipLaunchKernelGGL(k_bw_fwd_panel<B>, dim3(nk, ns), blk, 0, s, sp.bMr, sp.bMl, P, ld, kw, nb, st);
     levels[nlev++] = st;
   }
-  hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(1), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, kp, nb, 0, 0, 1);
+  hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(1, ns), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, ld, kw, nb, 0, 0, 1);
   for (int q = nlev - 1; q >= 0; --q) {
     const int st = levels[q];
     const int ne = (nb - st + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, kp, nb, st, st,
-                       2 * st);
+    hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(ne, ns), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, ld, kw, nb, st,
+                       st, 2 * st);
   }
 }
 
@@ -334,8 +339,9 @@ void sp_launch_bw_residual_to(hipStream_t s, const SparseDev &sp, int N, const i
                      sp.brhs, sp.brhs0, sp.bres, pairs, flags, sp.nred);
 }
 
-// Solve phase for a panel: P is (nb B) x kp row-major, kp a multiple of 16 and at most 64, rows >= N
-// zero on entry; the solutions replace the right-hand sides.
+// Solve phase for a panel: P is (nb B) x kp row-major, kp a multiple of 16 up to 64 or a multiple
+// of 64 beyond (64-column slices on blockIdx.y of the same launches), rows >= N zero on entry; the
+// solutions replace the right-hand sides.
 void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp) {
   if (N == 0) return;
   switch (sp.B) {
@@ -503,7 +509,7 @@ __global__ __launch_bounds__(BW_THREADS) void kbw_fwd_panel(const BandInst *__re
   if (I.ctl[0] == 0) return;
   const int i = blockIdx.x * 2 * s;
   if (i >= sh.nb) return;
-  bw_fwd_panel_block<B>(I.bMr, I.bMl, I.bY, sh.bkp, sh.nb, s, i);
+  bw_fwd_panel_block<B>(I.bMr, I.bMl, I.bY, sh.bkp, sh.bkp, sh.nb, s, i);
 }
 
 template <int B>
@@ -514,7 +520,7 @@ __global__ __launch_bounds__(BW_THREADS) void kbw_back_panel(const BandInst *__r
   __shared__ double T[B * 65];
   const int e = first + blockIdx.x * stride;
   if (e >= sh.nb) return;
-  bw_back_panel_block<B>(I.bDinv, I.bL, I.bU, I.bY, sh.bkp, sh.nb, s, e, T);
+  bw_back_panel_block<B>(I.bDinv, I.bL, I.bU, I.bY, sh.bkp, sh.bkp, sh.nb, s, e, T);
 }
 
 // the walk of bw_solve / bw_backsolve (pgf_band_wide.hip), every launch with the instances in grid.y;

@@ -381,19 +381,20 @@ __device__ __forceinline__ void bw_x0_block(const double *__restrict__ Dinv, con
 }
 
 // ---- solve phase against the kept factors, a panel of kp right-hand sides (row-major, row stride
-// kp, a block's B x kp rows contiguous; kp a multiple of 16, at most 64), in place, on
+// ld >= kp; kp a multiple of 16, at most 64: a wider panel is solved as 64-column slices, P
+// pointing at the slice's first column), in place, on
 // v_mfma_f64_16x16x4_f64: (B / 16) (kp / 16) <= 16 output tiles, at most four per wavefront.
 // Forward step of one level for the kept block i: P_i -= Mr[i-s] P_{i-s} + Ml[i+s] P_{i+s}.
 template <int B>
 __device__ __forceinline__ void bw_fwd_panel_block(const double *__restrict__ Mr,
                                                    const double *__restrict__ Ml, double *__restrict__ P,
-                                                   int kp, int nb, int s, int i) {
+                                                   int ld, int kp, int nb, int s, int i) {
   constexpr int BB = B * B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l4 = lane >> 4, l15 = lane & 15;
   const int le = i - s, ri = i + s;
   const int tc = kp / 16, nt = (B / 16) * tc;
-  double *Pi = P + (int64_t)i * B * kp;
+  double *Pi = P + (int64_t)i * B * ld;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int tt = wave + 4 * t;
@@ -401,13 +402,13 @@ __device__ __forceinline__ void bw_fwd_panel_block(const double *__restrict__ Mr
     const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
     bw_double4 acc;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
+    for (int g = 0; g < 4; ++g) acc[g] = Pi[(int64_t)(r0 + l4 + 4 * g) * ld + c0 + l15];
     if (le >= 0)
-      acc = bw_tile<B>(Mr + (int64_t)le * BB, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
+      acc = bw_tile<B>(Mr + (int64_t)le * BB, B, P + (int64_t)le * B * ld, ld, r0, c0, acc, lane, true);
     if (ri < nb)
-      acc = bw_tile<B>(Ml + (int64_t)ri * BB, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+      acc = bw_tile<B>(Ml + (int64_t)ri * BB, B, P + (int64_t)ri * B * ld, ld, r0, c0, acc, lane, true);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) Pi[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+    for (int g = 0; g < 4; ++g) Pi[(int64_t)(r0 + l4 + 4 * g) * ld + c0 + l15] = acc[g];
   }
 }
 
@@ -417,7 +418,7 @@ template <int B>
 __device__ __forceinline__ void bw_back_panel_block(const double *__restrict__ Dinv,
                                                     const double *__restrict__ L,
                                                     const double *__restrict__ U, double *__restrict__ P,
-                                                    int kp, int nb, int s, int e, double *T) {
+                                                    int ld, int kp, int nb, int s, int e, double *T) {
   constexpr int BB = B * B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l4 = lane >> 4, l15 = lane & 15;
@@ -425,7 +426,7 @@ __device__ __forceinline__ void bw_back_panel_block(const double *__restrict__ D
   const bool hl = s > 0 && le >= 0, hr = s > 0 && ri < nb;
   const int tc = kp / 16, nt = (B / 16) * tc;
   const int64_t be = (int64_t)e * BB;
-  double *Pe = P + (int64_t)e * B * kp;
+  double *Pe = P + (int64_t)e * B * ld;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int tt = wave + 4 * t;
@@ -433,9 +434,9 @@ __device__ __forceinline__ void bw_back_panel_block(const double *__restrict__ D
     const int r0 = (tt / tc) * 16, c0 = (tt % tc) * 16;
     bw_double4 acc;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) acc[g] = Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15];
-    if (hl) acc = bw_tile<B>(L + be, B, P + (int64_t)le * B * kp, kp, r0, c0, acc, lane, true);
-    if (hr) acc = bw_tile<B>(U + be, B, P + (int64_t)ri * B * kp, kp, r0, c0, acc, lane, true);
+    for (int g = 0; g < 4; ++g) acc[g] = Pe[(int64_t)(r0 + l4 + 4 * g) * ld + c0 + l15];
+    if (hl) acc = bw_tile<B>(L + be, B, P + (int64_t)le * B * ld, ld, r0, c0, acc, lane, true);
+    if (hr) acc = bw_tile<B>(U + be, B, P + (int64_t)ri * B * ld, ld, r0, c0, acc, lane, true);
 #pragma unroll
     for (int g = 0; g < 4; ++g) T[(r0 + l4 + 4 * g) * ldt + c0 + l15] = acc[g];
   }
@@ -448,7 +449,7 @@ __device__ __forceinline__ void bw_back_panel_block(const double *__restrict__ D
     bw_double4 acc = {0.0, 0.0, 0.0, 0.0};
     acc = bw_tile<B>(Dinv + be, B, T, ldt, r0, c0, acc, lane, false);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) Pe[(int64_t)(r0 + l4 + 4 * g) * kp + c0 + l15] = acc[g];
+    for (int g = 0; g < 4; ++g) Pe[(int64_t)(r0 + l4 + 4 * g) * ld + c0 + l15] = acc[g];
   }
 }
 

@@ -1,6 +1,7 @@
 // Bordered band: K = [[B, C], [C', D]] up to the plan's permutation, B banded (half-bandwidth <= 64,
 // the existing cyclic reductions take it), C the Nb x k coupling to a border of k <= 64 KKT nodes
 // (dense rows / columns: a budget constraint, a global parameter), D the k x k border block.
+// 65 <= k <= 1024 (the large border): pgf_border_large.hip behind the same entry points.
 //
 // Block elimination of B first:
 //   factor, once per assembled matrix:  Y = inv(B) C,  S = D - C' Y,  S = L D L'
@@ -175,33 +176,57 @@ __global__ void k_border_bflags(int *__restrict__ flags, int *__restrict__ sflag
   }
 }
 
+// Wide remainder under wide_kept, first half of the factor phase (both border sizes): the
+// factor-only KEEP reduction of B, its flags parked, Y = inv(B) C as one panel (kp <= 64, or 64-column
+// slices of the same launches beyond) or, PGF_BORDER_MULTI=0, column by column.
+void sp_border_wide_Y(hipStream_t s, const SparseDev &sp, int *flags) {
+  static const bool multi = env_on("PGF_BORDER_MULTI");
+  const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
+  sp_launch_bw_factor(s, sp, Nb, flags);  // (reads sp.brhs, writes none of it)
+  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 1);
+  const int nbB = (Nb + sp.B - 1) / sp.B * sp.B;  // Y in whole B-row blocks, the padding rows zero
+  if (multi) {
+    (void)hipMemcpyAsync(sp.bY, sp.bC, (size_t)Nb * kp * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (nbB > Nb)
+      (void)hipMemsetAsync(sp.bY + (size_t)Nb * kp, 0, (size_t)(nbB - Nb) * kp * sizeof(double), s);
+    sp_launch_bw_panel_solve(s, sp, Nb, sp.bY, kp);
+  } else {
+    (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemsetAsync(sp.bY, 0, (size_t)nbB * kp * sizeof(double), s);
+    for (int j = 0; j < k; ++j) {
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bC, sp.brhs, 0);
+      sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.brhs, sp.bY, 1);
+    }
+    (void)hipMemcpyAsync(sp.brhs, sp.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+  }
+}
+
+// the small border's Gram launch alone (tools: timed against the MFMA kernel at kp = 64)
+void sp_border_gram_fma(hipStream_t s, const SparseDev &sp) {
+  hipLaunchKernelGGL(k_border_gram, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.bY, sp.Nb, sp.bkp, sp.bpart);
+}
+
+// ... and of the solve phase: v = inv(B) ra against the kept factors; flags <- pivots of B as kept
+void sp_border_wide_v(hipStream_t s, const SparseDev &sp, int *flags) {
+  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 0);
+  sp_launch_bw_backsolve(s, sp, sp.Nb, flags, /*guard=*/false);
+}
+
 void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
   const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
   ++sp.stat_bfactor;
+  if (sp_border_large(sp)) {  // 65 .. 1024 border nodes: pgf_border_large.hip
+    sp_borderL_factor(s, sp, flags);
+    return;
+  }
   // PGF_BORDER_MULTI=0: Y column by column through the single-right-hand-side solves at every B:
   // slower, and an independent check of the panel kernels
   static const bool multi = env_on("PGF_BORDER_MULTI");
   if (sp.B == 8 && multi) {
     mbcr_solve(s, sp);
   } else if (wide_kept(sp)) {
-    sp_launch_bw_factor(s, sp, Nb, flags);  // (reads sp.brhs, writes none of it)
-    hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 1);
-    const int nbB = (Nb + sp.B - 1) / sp.B * sp.B;  // Y in whole B-row blocks, the padding rows zero
-    if (multi) {
-      (void)hipMemcpyAsync(sp.bY, sp.bC, (size_t)Nb * kp * sizeof(double), hipMemcpyDeviceToDevice, s);
-      if (nbB > Nb)
-        (void)hipMemsetAsync(sp.bY + (size_t)Nb * kp, 0, (size_t)(nbB - Nb) * kp * sizeof(double), s);
-      sp_launch_bw_panel_solve(s, sp, Nb, sp.bY, kp);
-    } else {
-      (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-      (void)hipMemsetAsync(sp.bY, 0, (size_t)nbB * kp * sizeof(double), s);
-      for (int j = 0; j < k; ++j) {
-        hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bC, sp.brhs, 0);
-        sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
-        hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.brhs, sp.bY, 1);
-      }
-      (void)hipMemcpyAsync(sp.brhs, sp.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-    }
+    sp_border_wide_Y(s, sp, flags);
   } else {
     // the band solves work in sp.brhs: whatever right-hand side waits there moves out of the way
     (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
@@ -219,6 +244,10 @@ void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
 }
 
 void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags) {
+  if (sp_border_large(sp)) {
+    sp_borderL_residual(s, sp, flags);
+    return;
+  }
   hipLaunchKernelGGL(k_border_ctv, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.brhs, sp.Nb, sp.bkp, sp.bpartv);
   hipLaunchKernelGGL(k_border_residual, dim3(sp.nred), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, sp.Nb, sp.bk,
                      sp.bkp, sp.bC, sp.bDd, sp.bpartv, sp.bnchunk, sp.brhs, sp.brhs0, sp.bres, sp.bred, flags,
@@ -228,13 +257,16 @@ void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags) {
 void sp_border_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard) {
   const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
   ++sp.stat_bsolve;
+  if (sp_border_large(sp)) {
+    sp_borderL_solve(s, sp, flags, guard);
+    return;
+  }
   // (the band solve writes whole blocks: the border entries behind Nb do not survive it)
   (void)hipMemcpyAsync(sp.brb, sp.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (guard)
     (void)hipMemcpyAsync(sp.brhs0, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-  if (wide_kept(sp)) {  // v = inv(B) ra against the kept factors; flags <- pivots of B as kept
-    hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 0);
-    sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
+  if (wide_kept(sp)) {
+    sp_border_wide_v(s, sp, flags);
   } else {
     band_solve(s, sp, Nb, flags);  // v = inv(B) ra; flags <- pivots of B
   }

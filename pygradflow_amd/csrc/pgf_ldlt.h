@@ -80,6 +80,10 @@ struct DenseLdlt {
   int vdepth = 0;  // multiple of 32 (zero-padded columns)
   int vneg = 0;
   size_t vcap = 0, vdcap = 0;  // allocated doubles
+  // false: the triangular solves of this factor always take the per-block kernels, never the
+  // chained single-launch ones -- for an owner that has no host synchronisation of its own behind a
+  // solve at which ldlt_chain_check could run (the large border's S, pgf_border_large.hip)
+  bool chain_solves = true;
   int inject_chain_failure = 0;  // test hook: the next chained solve reports a failure
   int inject_helper_failure = 0;  // test hook: the next factorisation reports failed helpers
   // Status words of a dense Newton step (pgf_api_step.hip): flags_zeroed -- the caller's assembly

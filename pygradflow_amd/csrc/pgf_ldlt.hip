@@ -707,6 +707,7 @@ static bool use_chain() {
   static const bool on = env_on("PGF_TRSV_CHAIN");
   return on && !g_chain_off;
 }
+static bool use_chain(const DenseLdlt &f) { return f.chain_solves && use_chain(); }
 
 void ldlt_chain_set_enabled(bool on) { g_chain_off = !on; }
 
@@ -759,7 +760,7 @@ hipError_t ldlt_backsolve_async(DenseLdlt &f, const double *w, double *sol) {
   const int N = f.N;
   hipStream_t s = f.stream;
   if (N == 0) return hipSuccess;
-  if (use_chain()) {
+  if (use_chain(f)) {
     const int nblk = (N + 63) / 64;
     hipLaunchKernelGGL(k_trsv_bwd_chain, dim3(8 * nblk), dim3(256), 0, s, f.K, f.ldk, f.Linv, w, sol,
                        N, f.xpub, f.chain_stride, f.chain + 2 * f.chain_stride);
@@ -781,7 +782,7 @@ hipError_t ldlt_solve_async(DenseLdlt &f, const double *rhs, double *sol) {
   hipStream_t s = f.stream;
   if (N == 0) return hipSuccess;
   // forward: L y = rhs  (y lands in sol)
-  if (use_chain()) {
+  if (use_chain(f)) {
     const int nblk = (N + 63) / 64;
     hipLaunchKernelGGL(k_trsv_fwd_chain, dim3(8 * nblk), dim3(256), 0, s, f.K, f.ldk, f.LinvT, rhs,
                        sol, N, f.xpub, f.chain_stride, f.chain + 2 * f.chain_stride);

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct DenseLdlt;
+
 struct SparseDev {
   bool active = false;
   int bw = 0, ldb = 0;
@@ -62,7 +64,19 @@ struct SparseDev {
   int *bsflags = nullptr;                    // [0] bad pivot in S, [1] negative pivots of S
   int bnchunk = 0;                           // chunks of SP_BORDER_CHUNK rows
   mutable int stat_bfactor = 0, stat_bsolve = 0;  // factor / solve phases enqueued (pgf_debug_border_stats)
+  // Large border (pgf_border_large.hip), 65 <= bk <= 1024: bkp = bk rounded up to 64, S = D - C' Y
+  // factorised by a dense L D L' of its own on the handle's stream (blf; bS, bpart's small-border
+  // use and the one-workgroup kernels of S are not used).  bG: kp x kp, the lower triangle of
+  // C' Y (zero above), which survives the factorisation (pgf_debug_border_gram; S itself goes into
+  // blf->K alone and is formed again from bpart and D when a factorisation is repeated);
+  // bpart: bgchunks partial sums of bgrows rows for each 64 x 64 tile of C' Y's lower triangle.
+  DenseLdlt *blf = nullptr;
+  double *bG = nullptr;
+  int bgrows = 0, bgchunks = 0;
+  mutable bool bgram_ready = false;  // a factor phase has run since the border was declared
 };
+// sp.bkp > 64: the large border's route behind the four entry points below
+static inline bool sp_border_large(const SparseDev &sp) { return sp.bkp > 64; }
 #define SP_BORDER_CHUNK 512
 
 void sp_launch_spmv(hipStream_t s, int rows, const int *ptr, const int *col, const double *val,
@@ -111,8 +125,8 @@ void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, b
 // the KEEP reduction without a right-hand side (factors and pivot flags only)
 void sp_launch_bw_factor(hipStream_t s, const SparseDev &sp, int N, int *flags);
 // solve phase against the kept factors: the right-hand side in sp.brhs / a row-major panel P of kp
-// columns (a multiple of 16, at most 64; whole blocks, rows >= N zero), in place.  The pivot flags
-// are left as the reduction reported them.
+// columns (a multiple of 16 up to 64, a multiple of 64 beyond; whole blocks, rows >= N zero), in
+// place.  The pivot flags are left as the reduction reported them.
 void sp_launch_bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard);
 void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp);
 // column j of a panel: P[pos[i]][j] = in[i] / out[g] = P[g][j]; the residual of sp.brhs against
@@ -139,3 +153,19 @@ void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags);
 // guard: keep the right-hand side and finish with the residual over all Nb + bk rows.
 void sp_border_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard);
 void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags);
+// ---- large border (pgf_border_large.hip): the same three phases for sp.bkp > 64, reached through
+// the entry points above (assembly is shared: the store has the same shape)
+// the wide remainder's halves of the two phases, shared with pgf_border.hip: the kept factors of B
+// with its flags parked and Y = inv(B) C / v = inv(B) ra in sp.brhs with the flags of B put back
+void sp_border_wide_Y(hipStream_t s, const SparseDev &sp, int *flags);
+void sp_border_wide_v(hipStream_t s, const SparseDev &sp, int *flags);
+void sp_borderL_factor(hipStream_t s, const SparseDev &sp, int *flags);
+void sp_borderL_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard);
+void sp_borderL_residual(hipStream_t s, const SparseDev &sp, const int *flags);
+// rows per chunk and chunks of the Gram kernel for Nb rows and kp columns (the partial sums stay
+// below 256 MB)
+void sp_borderL_gram_plan(int Nb, int kp, int *rows, int *chunks);
+void sp_border_gram_fma(hipStream_t s, const SparseDev &sp);  // k_border_gram alone (kp <= 64)
+// device time per launch of the two Gram kernels on the last factor phase's C and Y (kp % 64 == 0;
+// *ms_fma = -1 for kp > 64)
+hipError_t sp_borderL_gram_time(hipStream_t s, const SparseDev &sp, int reps, double *ms_mfma, double *ms_fma);

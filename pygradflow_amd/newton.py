@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib
 from .errors import LinearSolverError, LineSearchError, StepSolverError  # noqa: F401
 from .params import enum_name
-from .sparse import MAX_BANDWIDTH, BandPlan, apply_band_split, border_key
+from .sparse import MAX_BANDWIDTH, BandPlan, apply_band_split, border_key, effective_band_split
 from .step_solver import DENSE_LIMIT, POOL, HipStepSolver, residency_key, same_key
 
 
@@ -202,6 +202,7 @@ class DeviceNewton:
         self.dt, self.rho = float(dt), float(rho)
         self.tau = math.nan if tau is None else float(tau)
         border = getattr(problem, "pgf_border", None)  # a bordered band (sparse.BandPlan)
+        border_limit = getattr(problem, "pgf_border_limit", None)  # up to 1024 nodes (None: 64)
         self.sparse = (not problem.is_dense) and (
             bool(getattr(problem, "pgf_force_band", False)) or border is not None
             or self.n + self.m > DENSE_LIMIT)
@@ -228,17 +229,20 @@ class DeviceNewton:
         key = residency_key(problem)
         stale = not same_key(key, self._hd.derivs_key)
         block = getattr(problem, "pgf_band_block", None)
-        if self.sparse:
-            apply_band_split(lib, h, problem)
-        replan = self._hd.plan is not None and (
+        dropped = self.sparse and apply_band_split(lib, h, problem)
+        if dropped:  # a large border left the handle with the split: nothing on it is current
+            self._hd.plan = None
+            self._hd.derivs_key = self._hd.qp_key = None
+            stale = True
+        replan = dropped or (self._hd.plan is not None and (
             self._hd.plan.block != (int(block) if block else None)
-            or self._hd.plan.border_spec != border_key(border))
+            or self._hd.plan.border_spec != border_key(border, border_limit)))
         # q and b are resident for the problem THIS class uploaded last: a HipStepSolver that had the
         # pooled handle in between makes derivs_key current for its problem without sending q, b
         loaded = same_key(key, getattr(self._hd, "qp_key", None))
         if self.sparse and (stale or replan or not loaded):
             plan = BandPlan(problem.hess_sparse(), problem.jac_sparse(), self.n, self.m, block=block,
-                            border=border)
+                            border=border, border_limit=border_limit, split=effective_band_split(problem))
             if not plan.supported:
                 tried = "" if border is None else f" with a border of {plan.k} nodes"
                 raise NotImplementedError(

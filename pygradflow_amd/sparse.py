@@ -24,7 +24,8 @@ from scipy.sparse.csgraph import reverse_cuthill_mckee
 from . import _lib
 
 MAX_BANDWIDTH = 64  # widest block of the cyclic reduction (csrc/pgf_band_wide.hip)
-MAX_BORDER = 64     # most border nodes of a bordered band (csrc/pgf_border.hip: S in 32 KB of LDS)
+MAX_BORDER = 64     # most border nodes without asking (csrc/pgf_border.hip: S in 32 KB of LDS, one workgroup)
+MAX_LARGE_BORDER = 1024  # ... with problem.pgf_border_limit (csrc/pgf_border_large.hip: S by the dense LDL^T)
 BLOCK_SIZES = (8, 16, 32, 64)
 
 
@@ -56,19 +57,32 @@ def _rcm_positions(pat):
     return pos
 
 
-def select_border(pat):
+def border_limit_of(limit):
+    """A border limit as BandPlan and select_border take it: None is MAX_BORDER (the small border,
+    as ever), otherwise an integer in MAX_BORDER .. MAX_LARGE_BORDER."""
+    if limit is None:
+        return MAX_BORDER
+    if isinstance(limit, (bool, np.bool_)) or not isinstance(limit, (int, np.integer)) \
+            or not MAX_BORDER <= limit <= MAX_LARGE_BORDER:
+        raise ValueError(f"pgf_border_limit: {limit!r} (an integer in {MAX_BORDER} .. {MAX_LARGE_BORDER})")
+    return int(limit)
+
+
+def select_border(pat, limit=MAX_BORDER):
     """The automatic border of a symmetric KKT pattern (diagonal present): every node whose degree
     exceeds 2 * MAX_BANDWIDTH -- it fits no band of that half-width -- and then, while reverse
     Cuthill-McKee of the remainder still gives a wider band, the remainder's node of highest
     degree (the highest index among equals: where thousands of nodes tie, as in a uniform band,
     the choice is arbitrary, and what RCM makes of the remainder can depend on it).  Returns (sorted border nodes, fits): fits is False
-    when MAX_BORDER nodes do not bring the remainder's bandwidth down to MAX_BANDWIDTH."""
+    when ``limit`` nodes (MAX_BORDER unless given) do not bring the remainder's bandwidth down to
+    MAX_BANDWIDTH."""
+    limit = border_limit_of(limit)
     N = pat.shape[0]
     pat = sps.csr_matrix(pat)
     deg = np.diff(pat.indptr) - 1
     border = [int(i) for i in np.nonzero(deg > 2 * MAX_BANDWIDTH)[0]]
-    if len(border) > MAX_BORDER:
-        return sorted(border[:MAX_BORDER]), False
+    if len(border) > limit:
+        return sorted(border[:limit]), False
     while True:
         keep = np.ones(N, dtype=bool)
         keep[border] = False
@@ -76,7 +90,7 @@ def select_border(pat):
         sub = pat[rem, :][:, rem]
         if rem.size == 0 or _bandwidth(sub, _rcm_positions(sub)) <= MAX_BANDWIDTH:
             return sorted(border), True
-        if len(border) >= MAX_BORDER or rem.size <= 1:
+        if len(border) >= limit or rem.size <= 1:
             return sorted(border), False
         deg = np.diff(sub.indptr)
         border.append(int(rem[np.nonzero(deg == deg.max())[0][-1]]))
@@ -90,9 +104,16 @@ class BandPlan:
     -- at positions ``Nb .. Nb + k - 1``.  The entries that touch a border node get slots in a
     border store directly behind the band array, which the scatter kernels write like any other
     slot: C as ``Nb x kp`` row-major at ``base_C = (Nb + 1) ldb``, then the lower triangle of D as
-    ``kp x kp`` at ``base_D = base_C + Nb kp``; ``kp`` is ``k`` rounded up to a multiple of 16."""
+    ``kp x kp`` at ``base_D = base_C + Nb kp``; ``kp`` is ``k`` rounded up to a multiple of 16.
 
-    def __init__(self, hess, jac, n, m, block=None, border=None):
+    ``border_limit`` (``problem.pgf_border_limit``): the most border nodes, None (64) or 64 .. 1024.
+    A border of more than 64 nodes is a LARGE border (csrc/pgf_border_large.hip): ``kp`` is ``k``
+    rounded up to a multiple of 64, the store is otherwise the same, and the remainder always
+    runs the wide route with the factor / solve split -- block size max(16, block_size_for(bw))
+    unless 16, 32 or 64 is forced; a forced 8 and ``split`` = False (``problem.pgf_band_split``) are
+    errors."""
+
+    def __init__(self, hess, jac, n, m, block=None, border=None, border_limit=None, split=None):
         if block and int(block) not in BLOCK_SIZES:
             raise ValueError(f"band block size {block}: must be one of {BLOCK_SIZES}")
         self.block = int(block) if block else None  # forced block size (problem.pgf_band_block)
@@ -110,26 +131,32 @@ class BandPlan:
         Hp = sps.csr_matrix((np.ones(H.nnz), H.indices, H.indptr), shape=(n, n))
         Jp = sps.csr_matrix((np.ones(J.nnz), J.indices, J.indptr), shape=(m, n))
         pat = sps.bmat([[Hp + Hp.T + sps.identity(n), Jp.T], [Jp, sps.identity(m)]], format="csr")
-        self.border_spec = border_key(border)
+        self.border_limit = limit = border_limit_of(border_limit)
+        self.border_spec = border_key(border, border_limit)
         self._border_fits = True
         if border is None:
             nodes = np.zeros(0, dtype=np.int64)
         elif isinstance(border, str):
             if border != "auto":
                 raise ValueError(f"pgf_border: {border!r} (\"auto\" or a sequence of KKT node indices)")
-            found, self._border_fits = select_border(pat)
+            found, self._border_fits = select_border(pat, limit)
             nodes = np.asarray(found, dtype=np.int64)
         else:
             nodes = np.unique(np.asarray(list(border), dtype=np.int64))
             if nodes.size != len(list(border)) or nodes.size == 0 or nodes[0] < 0 or nodes[-1] >= N:
                 raise ValueError("pgf_border: distinct KKT node indices in [0, n + m) expected")
-            if nodes.size > MAX_BORDER:
-                raise ValueError(f"pgf_border: {nodes.size} nodes, at most {MAX_BORDER}")
+            if nodes.size > limit:
+                raise ValueError(f"pgf_border: {nodes.size} nodes, at most {limit}")
             if nodes.size >= N:
                 raise ValueError("pgf_border: the border must leave a band")
         self.border = nodes.astype(np.int32)
         self.k = k = int(nodes.size)
-        self.kp = kp = (k + 15) // 16 * 16
+        self.large = k > MAX_BORDER
+        self.kp = kp = (k + 63) // 64 * 64 if self.large else (k + 15) // 16 * 16
+        if self.large and self.block == 8:
+            raise ValueError("pgf_band_block: a border of more than 64 nodes needs block size 16, 32 or 64")
+        if self.large and split is not None and not split:
+            raise ValueError("pgf_band_split: a border of more than 64 nodes needs the factor / solve split")
         self.Nb = Nb = N - k
         if k == 0:
             pos = _rcm_positions(pat)
@@ -196,8 +223,9 @@ class BandPlan:
 
     @property
     def block_size(self):
-        """Block size the solve runs with (block_size_for)."""
-        return block_size_for(self.bw, self.block)
+        """Block size the solve runs with (block_size_for; at least 16 under a large border)."""
+        B = block_size_for(self.bw, self.block)
+        return max(16, B) if self.large and B else B
 
     def values(self, hess, jac):
         """Values of H, J in plan order; raises if the pattern differs from the plan's."""
@@ -252,6 +280,11 @@ class BandPlan:
             ip(self.Hslot), self.nnzJ, ip(self.Jptr), ip(self.Jcol), ip(self.Jslot), ip(self.JTptr),
             ip(self.JTrow), ip(self.JTmap))
         _lib.check(rc, handle, "pgf_sparse_set_pattern")
+        if self.large:  # the wide route first: the large border is declared on it
+            rc = lib.pgf_sparse_set_block_size(handle, self.block_size)
+            _lib.check(rc, handle, f"pgf_sparse_set_block_size (half-bandwidth {self.bw})")
+            _lib.check(lib.pgf_sparse_set_border_large(handle, self.k), handle, "pgf_sparse_set_border_large")
+            return
         if self.k:
             _lib.check(lib.pgf_sparse_set_border(handle, self.k), handle, "pgf_sparse_set_border")
         rc = lib.pgf_sparse_set_block_size(handle, self.block or 0)
@@ -281,20 +314,37 @@ def _band_split_default():
         return False  # (atoi of a non-number is 0)
 
 
+def effective_band_split(problem):
+    """The split the problem's handle will run with: ``problem.pgf_band_split`` or, if not set, the
+    library's default.  What BandPlan(split=...) needs to refuse a large border in time."""
+    want = band_split(problem)
+    return _band_split_default() if want is None else want
+
+
 def apply_band_split(lib, handle, problem):
     """Set the handle's split to what the problem asks for, or back to the default: pooled handles
-    keep what their last user set."""
+    keep what their last user set.  A handle that still carries a LARGE border cannot run without
+    the split: the border is removed first and True returned -- the caller's plan for the handle is
+    stale and is built again (which raises, if it is a large border that the split was switched off
+    under)."""
     want = band_split(problem)
     on = _band_split_default() if want is None else want
+    dropped = False
+    if not on:
+        k = C.c_int(0)
+        _lib.check(lib.pgf_debug_border_stats(handle, C.byref(k), None, None), handle, "pgf_debug_border_stats")
+        if k.value > MAX_BORDER:
+            _lib.check(lib.pgf_sparse_set_border(handle, 0), handle, "pgf_sparse_set_border")
+            dropped = True
     _lib.check(lib.pgf_sparse_set_factor_split(handle, int(on)), handle, "pgf_sparse_set_factor_split")
+    return dropped
 
 
-def border_key(border):
-    """Hashable form of a ``problem.pgf_border`` setting (None, "auto" or node indices): a handle's
-    plan is rebuilt when it differs."""
-    if border is None or isinstance(border, str):
-        return border
-    return tuple(int(i) for i in border)
+def border_key(border, limit=None):
+    """Hashable form of a ``problem.pgf_border`` setting (None, "auto" or node indices) and, if one is
+    set, of ``problem.pgf_border_limit``: a handle's plan is rebuilt when it differs."""
+    key = border if border is None or isinstance(border, str) else tuple(int(i) for i in border)
+    return key if limit is None else ("limit", int(limit), key)
 
 
 def wants_band(problem, hess, n, m, dense_limit=20000):

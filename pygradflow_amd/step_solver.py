@@ -25,7 +25,7 @@ import scipy.sparse as sps
 from . import _lib
 from .errors import LinearSolverError, StepSolverError
 from .linear_solver import HipLinearSolver
-from .sparse import BandPlan, MAX_BANDWIDTH, apply_band_split, border_key
+from .sparse import BandPlan, MAX_BANDWIDTH, apply_band_split, border_key, effective_band_split
 
 DENSE_LIMIT = 20000  # n + m above which sparse derivatives take the banded path
 DENSE_MAX = 60000    # largest n + m the dense path accepts (pgf_create; 28.8 GB of KKT matrix)
@@ -266,6 +266,8 @@ class HipStepSolver:
         self.formulation = int(formulation)
         # ``problem.pgf_border`` ("auto" or KKT node indices): a bordered band (sparse.BandPlan)
         self._border = getattr(problem, "pgf_border", None)
+        # ``problem.pgf_border_limit``: up to 1024 border nodes (None: 64)
+        self._border_limit = getattr(problem, "pgf_border_limit", None)
         self._border_tried = None  # size of an automatic border that did not fit
         self.sparse = not self.formulation and (
             bool(getattr(problem, "pgf_force_band", False)) or self._border is not None
@@ -449,13 +451,15 @@ class HipStepSolver:
         hess = sps.csr_matrix(self._hess)
         jac = sps.csr_matrix(self._jac) if self.m else sps.csr_matrix((0, self.n))
         block = getattr(self.problem, "pgf_band_block", None)
-        apply_band_split(self._lib, hd.h, self.problem)
+        if apply_band_split(self._lib, hd.h, self.problem):
+            hd.plan = None  # (a large border left the handle with the split: upload again)
         if hd.plan is not None and (hd.plan.block != (int(block) if block else None)
-                                    or hd.plan.border_spec != border_key(self._border)):
+                                    or hd.plan.border_spec != border_key(self._border, self._border_limit)):
             hd.plan = None  # a different block size or border was asked for: upload again
         for attempt in (0, 1):
             if hd.plan is None:
-                plan = BandPlan(hess, jac, self.n, self.m, block=block, border=self._border)
+                plan = BandPlan(hess, jac, self.n, self.m, block=block, border=self._border,
+                                border_limit=self._border_limit, split=effective_band_split(self.problem))
                 if not plan.supported:
                     self._border_tried = plan.k if self._border is not None else None
                     return False
