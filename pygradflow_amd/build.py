@@ -31,6 +31,7 @@ NO_CONTRACT = [
     "pgf_api_guard.hip",
     "pgf_api_step.hip",
     "pgf_api_band.hip",
+    "pgf_api_band_setup.hip",
     "pgf_api_line_search.hip",
     "pgf_api_unsym.hip",
     "pgf_api_batch.hip",

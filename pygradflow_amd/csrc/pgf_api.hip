@@ -86,7 +86,7 @@ int pgf_create(int n, int m, int device, unsigned flags, pgf_handle *out) {
   h->h_scal = h->h_stat + 8;
   h->h_counts = reinterpret_cast<int *>(h->h_stat + 12);
   h->sparse = sparse;
-  h->sp.split = band_split_default();
+  h->sp.blk.split = band_split_default();
   if (sparse) {
     // banded mode: no dense N x N storage; only the factor's flag words are shared
     h->fac.stream = h->stream;
@@ -404,7 +404,7 @@ int pgf_reduced_dims(pgf_handle h, int *n_inactive, int *n_reduced) {
 
 int check_ready(pgf_handle h) {
   if (!h->outer_set) return fail(h, PGF_NOT_READY, "pgf_set_outer first");
-  if (h->sparse ? !h->sp.values_set : !h->derivs_set)
+  if (h->sparse ? !h->sp.pat.values_set : !h->derivs_set)
     return fail(h, PGF_NOT_READY, "pgf_set_derivs_* / pgf_sparse_set_values first");
   if (!h->mask_set) return fail(h, PGF_NOT_READY, "pgf_set_active_set first");
   return PGF_OK;

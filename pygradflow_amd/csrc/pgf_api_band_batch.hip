@@ -14,8 +14,6 @@
 #include "pgf_api_internal.h"
 #include "pgf_kernels.h"
 
-static const char *const k_zero_pivot = "zero or non-finite pivot in the banded KKT factorisation";
-
 int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_batch *out) {
   const bool wide_ok = (flags & PGF_BATCH_WIDE_BAND) != 0;
   const bool border_ok = (flags & PGF_BATCH_BORDER) != 0;
@@ -37,31 +35,31 @@ int band_batch_create(const pgf_handle *handles, int count, unsigned flags, pgf_
       return fail(h, PGF_INVALID, "batch: dense and banded handles cannot share a batch");
     if ((rc = batch_check_shape(h, h0, &msg))) return fail(h, rc, msg);
     const SparseDev &sp = h->sp;
-    if (!sp.active || !sp.values_set)
+    if (!sp.active || !sp.pat.values_set)
       return fail(h, PGF_NOT_READY, "batch: pgf_sparse_set_pattern and pgf_sparse_set_values first");
     if (sp_border_large(sp))
       return fail(h, PGF_INVALID, "batch: a large border (more than 64 nodes) cannot join a device batch");
-    if (sp.bk && !border_ok) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
-    if (sp.bk != h0->sp.bk) return fail(h, PGF_INVALID, "batch: banded instances must share the border size");
-    if (sp.bk && sp.B != 8 && !wide_border_ok)
+    if (sp.bor.bk && !border_ok) return fail(h, PGF_INVALID, "batch: a bordered band cannot join a device batch");
+    if (sp.bor.bk != h0->sp.bor.bk) return fail(h, PGF_INVALID, "batch: banded instances must share the border size");
+    if (sp.bor.bk && sp.blk.B != 8 && !wide_border_ok)
       return fail(h, PGF_INVALID,
                   "batch: a bordered band joins a device batch on the narrow route only (block size 8)");
     // (pgf_batch_create_ex has seen to it that PGF_BATCH_BORDER_CTL comes with the other two)
-    if (sp.bk && (flags & PGF_BATCH_BAND_CTL) && !(flags & PGF_BATCH_BORDER_CTL))
+    if (sp.bor.bk && (flags & PGF_BATCH_BAND_CTL) && !(flags & PGF_BATCH_BORDER_CTL))
       return fail(h, PGF_INVALID, "batch: the device-resident controller does not drive a bordered band batch");
     // (the wide border's phases are those of the handle under wide_kept, pgf_border.hip: B factorised
     // once, every solve against the kept factors)
-    if (sp.bk && sp.B != 8 && !(sp.split && sp.bMr))
+    if (sp.bor.bk && sp.blk.B != 8 && !(sp.blk.split && sp.blk.bMr))
       return fail(h, PGF_INVALID, "batch: a bordered wide band needs the factor / solve split");
-    if (sp.B != 8 && !wide_ok)
+    if (sp.blk.B != 8 && !wide_ok)
       return fail(h, PGF_INVALID, "batch: a wide band (block size above 8) cannot join a device batch");
     const SparseDev &s0 = h0->sp;
-    if (sp.pat_hash != s0.pat_hash || sp.bw != s0.bw || sp.ldb != s0.ldb || sp.nnzH != s0.nnzH ||
-        sp.nnzJ != s0.nnzJ)
+    if (sp.pat.hash != s0.pat.hash || sp.pat.bw != s0.pat.bw || sp.pat.ldb != s0.pat.ldb || sp.pat.nnzH != s0.pat.nnzH ||
+        sp.pat.nnzJ != s0.pat.nnzJ)
       return fail(h, PGF_INVALID, "batch: banded instances must share one sparsity pattern");
     // (the split matters on the wide route only, and is in force only where the multipliers are
     // allocated: sp_cyclic_solve)
-    if (sp.B != s0.B || (sp.B > 8 && (sp.split != s0.split || (sp.bMr != nullptr) != (s0.bMr != nullptr))))
+    if (sp.blk.B != s0.blk.B || (sp.blk.B > 8 && (sp.blk.split != s0.blk.split || (sp.blk.bMr != nullptr) != (s0.blk.bMr != nullptr))))
       return fail(h, PGF_INVALID, "batch: banded instances must share the block size and the factor / solve split");
     if ((rc = batch_check_state(h, /*band=*/true, &msg))) return fail(h, rc, msg);
   }
@@ -234,18 +232,18 @@ int band_batch_step_async(pgf_batch b, unsigned policy, double tau) {
 }
 
 // An instance whose normwise backward error misses refine_tol, on its own handle: the handle's
-// buffers ARE the instance's, the band is intact, the solution is in sp.brhs and its residual in
-// sp.bres.  The step update left the point the step started from in (xn, yn): it goes back, and
+// buffers ARE the instance's, the band is intact, the solution is in sp.vec.brhs and its residual in
+// sp.vec.bres.  The step update left the point the step started from in (xn, yn): it goes back, and
 // band_refine corrects the solution and takes the step again from there.  The batch's stream is
 // idle (band_batch_sync).  On the wide route with the split on, the handle holds the factors the
-// batch's reduction left (the instance's flags were clean, or it would not be here): sp.kept says so
+// batch's reduction left (the instance's flags were clean, or it would not be here): sp.blk.kept says so
 // for the length of the repair, and the corrections are solve phases against the instance's own
 // multipliers, as the single handle's would be.  With a border, band_refine -> sp_cyclic_solve ->
 // sp_border_solve and sp_cyclic_residual -> sp_border_residual run the solve phase against the
 // handle's bY, bS and bsflags, which ARE the instance's and hold what the batch's factor phase left
 // (valid: the instance's flags were clean); nothing on that path tests fac.factored or assembles
 // again (read: band_refine, sp_cyclic_solve, sp_border_solve).  With a border on a wide remainder
-// sp_cyclic_solve takes its sp.bk branch before it looks at sp.kept, and sp_border_solve takes
+// sp_cyclic_solve takes its sp.bor.bk branch before it looks at sp.blk.kept, and sp_border_solve takes
 // wide_kept(sp) -- B > 8, split on, multipliers allocated: what band_batch_create admitted -- which
 // puts the flags of B back from bsflags[2, 4) and runs sp_launch_bw_backsolve against bMr, bMl, bL,
 // bU, bDinv: load, forward, x_0, backward, no inversion and no reduction of B (sp_launch_bw_factor
@@ -270,10 +268,10 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
     launch_copy(s, h->x, h->xn, h->n);
     launch_copy(s, h->y, h->yn, h->m);
   }
-  std::memcpy(sp.h_bred, st, S * sizeof(double));
-  sp.guarded = true;
+  std::memcpy(sp.vec.h_bred, st, S * sizeof(double));
+  sp.vec.guarded = true;
   h->mask_set = true;
-  sp.kept = b->band.sh.split ? 2 : 0;
+  sp.blk.kept = b->band.sh.split ? 2 : 0;
   if (search) batch_ls_handle_enter(b, i);
   const int refined = h->guard.stat_refined;
   int rc = band_refine(h, /*swapped=*/false, /*with_step=*/true);
@@ -281,7 +279,7 @@ static int band_batch_repair(pgf_batch b, int i, const double *st, double *diff_
     ls_leave(h);
     b->ls.host_waits += h->guard.stat_refined - refined;  // (one wait per round)
   }
-  sp.kept = 0;  // (outside a repair the handle's own view stays: no factors of its making)
+  sp.blk.kept = 0;  // (outside a repair the handle's own view stays: no factors of its making)
   h->mask_set = false;
   if (rc) {
     (void)hipStreamSynchronize(s);  // (the point the step started from is back in place)
@@ -318,7 +316,7 @@ int band_batch_sync(pgf_batch b, int *status, int *n_neg, double *diff) {
       const int bad = (int)st[3 * nred];
       bd.last_neg[i] = (int)st[3 * nred + 1];
       if (bad) {
-        rc = fail(h, PGF_SINGULAR, k_zero_pivot);  // (the step update left the point alone)
+        rc = fail(h, PGF_SINGULAR, k_band_zero_pivot);  // (the step update left the point alone)
       } else {
         double sum = 0.0;
         for (int k = 0; k < nred; ++k) sum += st[2 * nred + k];

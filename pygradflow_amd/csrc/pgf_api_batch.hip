@@ -130,13 +130,13 @@ void batch_fill_vectors(pgf_batch b, int i, BInst &t) {
   t.flags = h->fac.flags;
 }
 
-// (sp.stat_pending, sp.kept: the banded handle's -- the batch's reductions write its block arrays;
+// (sp.vec.stat_pending, sp.blk.kept: the banded handle's -- the batch's reductions write its block arrays;
 // unb.lists_ready and the norm: the dense handle's.  Each is at rest on a handle of the other kind.)
 void batch_own_handle(pgf_handle h) {
   h->mask_set = false;
   h->eval_fresh = false;
-  h->sp.stat_pending = false;
-  h->sp.kept = 0;
+  h->sp.vec.stat_pending = false;
+  h->sp.blk.kept = 0;
   h->unb.lists_ready = false;
   drop_norm(h);
   invalidate_factor(h);

@@ -2,7 +2,8 @@
 // lifecycle, uploads, index sets and linear solves; pgf_api_factor.hip: its factorisation (condensed
 // order, Gram matrix); pgf_api_guard.hip: its accuracy guard; pgf_api_step.hip: the Newton step and
 // the device-resident LQ mode; pgf_api_line_search.hip: the Globalized policy's line search around that
-// step; pgf_api_band.hip: the banded driver; pgf_api_unsym.hip: the
+// step; pgf_api_band.hip: the banded solve driver with pgf_api_band_setup.hip its configuration and
+// lifetimes (pattern, values, block size, split, borders); pgf_api_unsym.hip: the
 // unsymmetric formulations; pgf_api_batch.hip: the batch driver (lifecycle, outer step, host-driven
 // step) with pgf_api_band_batch.hip its banded half, pgf_api_batch_ctl.hip its device-resident
 // controller, pgf_api_batch_line_search.hip its Globalized policy and pgf_api_batch_read.hip its
@@ -240,6 +241,7 @@ struct pgf_linsolver {
 static const char *const k_no_handle = "null handle";
 static const char *const k_chain_msg = "chained triangular solve failed its placement / timeout check "
                                        "and so did the per-block solve that replaced it";
+static const char *const k_band_zero_pivot = "zero or non-finite pivot in the banded KKT factorisation";
 static const char *const k_helper_msg =
     "the dense factorisation failed its hand-over checks with and without helper workgroups";
 // internal: the factorisation just awaited must be repeated (its chain helpers failed their
@@ -273,12 +275,20 @@ static inline hipError_t dalloc(T **p, size_t count) {
   return hipMalloc((void **)p, (count ? count : 1) * sizeof(T));
 }
 
+// free what is set and null it: device memory (any number of pointers) / pinned host memory
+template <typename... T>
+static inline void dev_free(T *&...p) {
+  ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
+}
+template <typename T>
+static inline void pinned_free(T *&p) {
+  if (p) (void)hipHostFree(p);
+  p = nullptr;
+}
+
 template <typename T>
 static inline int up_new(pgf_handle h, T **dst, const T *src, size_t count) {
-  if (*dst) {
-    (void)hipFree(*dst);
-    *dst = nullptr;
-  }
+  dev_free(*dst);
   HIPCHK(h, dalloc(dst, count));
   if (count) HIPCHK(h, hipMemcpyAsync(*dst, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
   return PGF_OK;
@@ -323,9 +333,18 @@ static inline void invalidate_factor(pgf_handle h) {
   h->unsym.ulu_ok = false;
 }
 
-// ---- the banded driver (pgf_api_band.hip), for handles created with PGF_CREATE_SPARSE ----------
-// Each is the banded half of the dense function named beside it, which hands over in one line.
+// ---- the banded driver, for handles created with PGF_CREATE_SPARSE ------------------------------
+// pgf_api_band.hip: the solve driver (route dispatch, factor, step, refinement, linear solves,
+// evaluation); pgf_api_band_setup.hip: the pgf_sparse_* setters, the debug hooks and the lifetimes
+// of SparseDev's groups.  Each is the banded half of the dense function named beside it, which
+// hands over in one line.
+// doubles of a banded status block (SparseDev::vec.bred, a batch's slice): nred residual pairs, nred
+// partial sums of the step update, four pivot flags
+static inline size_t band_stat_stride(int nred) { return (size_t)3 * nred + 4; }
+// (pgf_api_band_setup.hip)
 void band_free(pgf_handle h);                                  // pgf_destroy
+bool band_split_default();                                     // pgf_create (PGF_BW_SPLIT)
+// (pgf_api_band.hip)
 int band_factor_async(pgf_handle h);                           // factor_async
 int band_step_async(pgf_handle h, bool *did_factor);           // newton_core_async
 int band_status_sync(pgf_handle h);                            // factor_finish, pgf_qp_sync (no-op on dense handles)
@@ -336,7 +355,6 @@ bool band_multi_panel(pgf_handle h);
 int band_linear_solve_multi(pgf_handle h, const double *rhs, int nrhs, int64_t ld, double *sol);
 // after a sync that brought the pivot flags to fac.h_flags: settle the wide band's kept factors
 void band_kept_resolve(pgf_handle h);                          // finish_factor_state
-bool band_split_default();                                     // pgf_create (PGF_BW_SPLIT)
 void band_eval(pgf_handle h);                                  // qp_eval
 void band_measures_eval(pgf_handle h);                         // pgf_qp_measures
 
@@ -398,6 +416,8 @@ void adopt_batch_factor(pgf_handle h, int nI, int n_neg_reported, bool condensed
 int chain_recover(pgf_handle h, bool swapped);      // pgf_newton_solve, pgf_qp_sync
 // pgf_api_step.hip
 bool step_spec();                                   // refresh_index_sets
+// pgf_api_band_setup.hip, for pgf_api_band.hip
+int band_panel_reserve(pgf_handle h);               // band_linear_solve_multi
 #pragma GCC visibility pop
 
 // ---- the batch ---------------------------------------------------------------------------------
@@ -539,7 +559,7 @@ static inline int bfail(pgf_batch b, int code, const char *msg) {
   } while (0)
 
 // doubles per instance of a band batch's status block: the handle's own stride
-static inline size_t band_stat_stride(const BandShape &sh) { return (size_t)3 * sh.nred + 4; }
+static inline size_t band_stat_stride(const BandShape &sh) { return band_stat_stride(sh.nred); }
 
 // a handle's host-side view of its outer step: lambda and what a step derives from it and rho
 static inline void set_outer_scalars(pgf_handle h, double dt, double rho) {
@@ -620,6 +640,7 @@ int batch_ls_handle_search(pgf_batch b, int i, double *diff);
 // after the step's wait: the instance's status and step length from its block
 void batch_ls_report(pgf_batch b, int i, int *status, double *diff);  // pgf_batch_sync, band_batch_sync
 #pragma GCC visibility pop
-// what it takes from pgf_api_band.hip: the guard's measure over nred residual pairs, and the hash
-// of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat_hash)
+// what it takes from pgf_api_band.hip, the guard's measure over nred residual pairs, and from
+// pgf_api_band_setup.hip the hash
+// of a pattern as pgf_sparse_set_pattern receives it (kept in SparseDev::pat.hash)
 double band_residual_rel_of(const double *pairs, int nred);

@@ -101,10 +101,10 @@ int ls_search(pgf_handle h, double *diff) {
   if (timed) (void)hipEventRecord(ls.ev0, s);
   if (h->sparse) {
     const SparseDev &sp = h->sp;
-    sp_launch_spmv(s, m, sp.Jptr, sp.Jcol, sp.Jval, h->dx, ls.zero, 1.0, ls.u);
+    sp_launch_spmv(s, m, sp.pat.Jptr, sp.pat.Jcol, sp.pat.Jval, h->dx, ls.zero, 1.0, ls.u);
     launch_mult_vec(s, m, h->rho, ls.u, h->dy, h->w);
-    sp_launch_spmvT(s, n, sp.JTptr, sp.JTrow, sp.JTmap, sp.Jval, h->w, ls.zero, h->tmpn);
-    sp_launch_spmv(s, n, sp.Hptr, sp.Hcol, sp.Hval, h->dx, h->tmpn, 1.0, ls.v);
+    sp_launch_spmvT(s, n, sp.pat.JTptr, sp.pat.JTrow, sp.pat.JTmap, sp.pat.Jval, h->w, ls.zero, h->tmpn);
+    sp_launch_spmv(s, n, sp.pat.Hptr, sp.pat.Hcol, sp.pat.Hval, h->dx, h->tmpn, 1.0, ls.v);
   } else {
     launch_gemv_rows(s, m, n, h->J, h->ldj, h->dx, ls.zero, 1.0, ls.u);
     launch_mult_vec(s, m, h->rho, ls.u, h->dy, h->w);

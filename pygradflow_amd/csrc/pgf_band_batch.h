@@ -21,8 +21,8 @@
 struct BandInst {
   const double *Hval, *Jval;
   double *band, *brhs, *brhs0, *bres;
-  double *bsol;  // the solution a refinement round keeps (PGF_BATCH_CTL_REFINE; SparseDev::bsol)
-  double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev; wide: one)
+  double *bsol;  // the solution a refinement round keeps (PGF_BATCH_CTL_REFINE; SparseDev::vec.bsol)
+  double *bD, *bL, *bU, *bDinv, *bF;  // two block sets, bstride blocks apart (SparseDev::blk; wide: one)
   double *bMr, *bMl;                  // wide route with the factor / solve split: the kept multipliers
   int *bneg, *flags;
   int *wcnt;  // wide route: [0] reductions, [1] solve phases this instance's workgroups ran
@@ -33,7 +33,7 @@ struct BandInst {
   double *bC, *bDd, *bY, *bS, *bpart, *bpartv, *brb, *bz;
   int *bsflags, *bcnt;
   // the instance's slice of the batch's status block: [0, 2 nred) residual pairs, [2 nred, 3 nred)
-  // partial sums of the step update, [3 nred, 3 nred + 4) pivot flags (as SparseDev::bred)
+  // partial sums of the step update, [3 nred, 3 nred + 4) pivot flags (as SparseDev::vec.bred)
   double *stat;
   const double *lb, *ub, *q, *b;
   double *x, *y, *xn, *yn, *g, *c, *w, *F, *b0full, *dx, *dy, *tmpn;
@@ -52,69 +52,69 @@ struct BandShape {
   const int *pos, *Hptr, *Hrow, *Hcol, *Hslot, *Jptr, *Jcol, *Jslot, *JTptr, *JTrow, *JTmap;
 };
 // The SparseDev part of a BandInst: the arrays of one handle.  flags: where the reduction reports
-// its pivots; stat: where the residual pairs go (SparseDev::bred, or a batch's status slice).  The
+// its pivots; stat: where the residual pairs go (SparseDev::vec.bred, or a batch's status slice).  The
 // vectors of the step, ctl, ps and the counters stay null: band_batch_create adds them.
 inline BandInst band_inst_of(const SparseDev &sp, int *flags, double *stat) {
   BandInst u{};
-  u.Hval = sp.Hval;
-  u.Jval = sp.Jval;
-  u.band = sp.band;
-  u.brhs = sp.brhs;  // (SparseDev::bX is brhs: the back-substitution writes the solution there)
-  u.brhs0 = sp.brhs0;
-  u.bres = sp.bres;
-  u.bsol = sp.bsol;
-  u.bD = sp.bD;
-  u.bL = sp.bL;
-  u.bU = sp.bU;
-  u.bDinv = sp.bDinv;
-  u.bF = sp.bF;
-  u.bMr = sp.bMr;
-  u.bMl = sp.bMl;
-  u.bneg = sp.bneg;
+  u.Hval = sp.pat.Hval;
+  u.Jval = sp.pat.Jval;
+  u.band = sp.pat.band;
+  u.brhs = sp.vec.brhs;  // (the back-substitution writes the solution there)
+  u.brhs0 = sp.vec.brhs0;
+  u.bres = sp.vec.bres;
+  u.bsol = sp.vec.bsol;
+  u.bD = sp.blk.bD;
+  u.bL = sp.blk.bL;
+  u.bU = sp.blk.bU;
+  u.bDinv = sp.blk.bDinv;
+  u.bF = sp.blk.bF;
+  u.bMr = sp.blk.bMr;
+  u.bMl = sp.blk.bMl;
+  u.bneg = sp.blk.bneg;
   u.flags = flags;
-  u.bC = sp.bC;
-  u.bDd = sp.bDd;
-  u.bY = sp.bY;
-  u.bS = sp.bS;
-  u.bpart = sp.bpart;
-  u.bpartv = sp.bpartv;
-  u.brb = sp.brb;
-  u.bz = sp.bz;
-  u.bsflags = sp.bsflags;
+  u.bC = sp.bor.bC;
+  u.bDd = sp.bor.bDd;
+  u.bY = sp.bor.bY;
+  u.bS = sp.bor.bS;
+  u.bpart = sp.bor.bpart;
+  u.bpartv = sp.bor.bpartv;
+  u.brb = sp.bor.brb;
+  u.bz = sp.bor.bz;
+  u.bsflags = sp.bor.bsflags;
   u.stat = stat;
   return u;
 }
 // The SparseDev part of a BandShape for a reduction over N rows (n + m, or the Nb band rows under a
 // border); n and m are the caller's.  split: the factor / solve split is in force only where the
-// multipliers are allocated.  sp.B is the block size of a pattern that is set (8, 16, 32 or 64), never
+// multipliers are allocated.  sp.blk.B is the block size of a pattern that is set (8, 16, 32 or 64), never
 // the 0 of a fresh SparseDev.
 inline BandShape band_shape_of(const SparseDev &sp, int N) {
   BandShape sh{};
   sh.N = N;
-  sh.B = sp.B;
-  sh.split = (sp.B > 8 && sp.split && sp.bMr) ? 1 : 0;
-  sh.nb = (N + sp.B - 1) / sp.B;
-  sh.bw = sp.bw;
-  sh.ldb = sp.ldb;
-  sh.nnzH = sp.nnzH;
-  sh.nnzJ = sp.nnzJ;
-  sh.nred = sp.nred;
-  sh.bk = sp.bk;
-  sh.bkp = sp.bkp;
-  sh.Nb = sp.bk ? sp.Nb : N;
-  sh.bnchunk = sp.bnchunk;
-  sh.bstride = sp.bstride;
-  sh.pos = sp.pos;
-  sh.Hptr = sp.Hptr;
-  sh.Hrow = sp.Hrow;
-  sh.Hcol = sp.Hcol;
-  sh.Hslot = sp.Hslot;
-  sh.Jptr = sp.Jptr;
-  sh.Jcol = sp.Jcol;
-  sh.Jslot = sp.Jslot;
-  sh.JTptr = sp.JTptr;
-  sh.JTrow = sp.JTrow;
-  sh.JTmap = sp.JTmap;
+  sh.B = sp.blk.B;
+  sh.split = (sp.blk.B > 8 && sp.blk.split && sp.blk.bMr) ? 1 : 0;
+  sh.nb = (N + sp.blk.B - 1) / sp.blk.B;
+  sh.bw = sp.pat.bw;
+  sh.ldb = sp.pat.ldb;
+  sh.nnzH = sp.pat.nnzH;
+  sh.nnzJ = sp.pat.nnzJ;
+  sh.nred = sp.vec.nred;
+  sh.bk = sp.bor.bk;
+  sh.bkp = sp.bor.bkp;
+  sh.Nb = sp.bor.bk ? sp.bor.Nb : N;
+  sh.bnchunk = sp.bor.bnchunk;
+  sh.bstride = sp.blk.bstride;
+  sh.pos = sp.pat.pos;
+  sh.Hptr = sp.pat.Hptr;
+  sh.Hrow = sp.pat.Hrow;
+  sh.Hcol = sp.pat.Hcol;
+  sh.Hslot = sp.pat.Hslot;
+  sh.Jptr = sp.pat.Jptr;
+  sh.Jcol = sp.pat.Jcol;
+  sh.Jslot = sp.pat.Jslot;
+  sh.JTptr = sp.pat.JTptr;
+  sh.JTrow = sp.pat.JTrow;
+  sh.JTmap = sp.pat.JTmap;
   return sh;
 }
 // ---- narrow route and the vector kernels (pgf_sparse.hip) ----------------------

@@ -183,8 +183,8 @@ __global__ __launch_bounds__(256) void k_bw_residual(const double *__restrict__ 
 
 void sp_launch_bw_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
   if (N == 0) return;
-  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, N,
-                     sp.brhs, sp.brhs0, sp.bres, sp.bred, flags, sp.nred);
+  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, N,
+                     sp.vec.brhs, sp.vec.brhs0, sp.vec.bres, sp.vec.bred, flags, sp.vec.nred);
 }
 
 // the fused reduction (+ solve when with_rhs); keep: the KEEP variant, which leaves the factors
@@ -193,34 +193,34 @@ static void bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool
                      bool with_rhs) {
   const int nb = (N + B - 1) / B;
   const dim3 blk(BW_THREADS);
-  ++sp.stat_bw_reduce;
+  ++sp.cnt.stat_bw_reduce;
   // (the extraction always fills F; a factor-only reduction just does not carry it along)
-  hipLaunchKernelGGL(k_bw_extract<B>, dim3(nb), blk, 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N, nb, sp.bD,
-                     sp.bL, sp.bU, sp.bF, guard ? sp.brhs0 : nullptr, flags);
+  hipLaunchKernelGGL(k_bw_extract<B>, dim3(nb), blk, 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, sp.vec.brhs, N, nb, sp.blk.bD,
+                     sp.blk.bL, sp.blk.bU, sp.blk.bF, guard ? sp.vec.brhs0 : nullptr, flags);
   int levels[32], nlev = 0;
   for (int st = 1; st < nb; st *= 2) {
     const int ne = (nb - st + 2 * st - 1) / (2 * st);  // eliminated: st, 3st, ...
     const int nk = (nb + 2 * st - 1) / (2 * st);       // kept: 0, 2st, ...
-    hipLaunchKernelGGL(k_bw_invert<B>, dim3(ne), blk, 0, s, sp.bD, sp.bDinv, nb, st, 2 * st, flags, sp.bneg);
+    hipLaunchKernelGGL(k_bw_invert<B>, dim3(ne), blk, 0, s, sp.blk.bD, sp.blk.bDinv, nb, st, 2 * st, flags, sp.blk.bneg);
     if (!with_rhs)
-      hipLaunchKernelGGL((k_bw_reduce<B, true, false>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
-                         sp.bDinv, sp.bMr, sp.bMl, nb, st);
+      hipLaunchKernelGGL((k_bw_reduce<B, true, false>), dim3(nk), blk, 0, s, sp.blk.bD, sp.blk.bL, sp.blk.bU, sp.blk.bF,
+                         sp.blk.bDinv, sp.blk.bMr, sp.blk.bMl, nb, st);
     else if (keep)
-      hipLaunchKernelGGL((k_bw_reduce<B, true, true>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
-                         sp.bDinv, sp.bMr, sp.bMl, nb, st);
+      hipLaunchKernelGGL((k_bw_reduce<B, true, true>), dim3(nk), blk, 0, s, sp.blk.bD, sp.blk.bL, sp.blk.bU, sp.blk.bF,
+                         sp.blk.bDinv, sp.blk.bMr, sp.blk.bMl, nb, st);
     else
-      hipLaunchKernelGGL((k_bw_reduce<B, false, true>), dim3(nk), blk, 0, s, sp.bD, sp.bL, sp.bU, sp.bF,
-                         sp.bDinv, nullptr, nullptr, nb, st);
+      hipLaunchKernelGGL((k_bw_reduce<B, false, true>), dim3(nk), blk, 0, s, sp.blk.bD, sp.blk.bL, sp.blk.bU, sp.blk.bF,
+                         sp.blk.bDinv, nullptr, nullptr, nb, st);
     levels[nlev++] = st;
   }
   // (factor-only: the last block's product goes to the spare block behind F and is not used)
-  hipLaunchKernelGGL(k_bw_last<B>, dim3(1), blk, 0, s, sp.bD, sp.bDinv, sp.bF,
-                     with_rhs ? sp.bX : sp.bF + (int64_t)nb * B, nb, flags, sp.bneg);
+  hipLaunchKernelGGL(k_bw_last<B>, dim3(1), blk, 0, s, sp.blk.bD, sp.blk.bDinv, sp.blk.bF,
+                     with_rhs ? sp.vec.brhs : sp.blk.bF + (int64_t)nb * B, nb, flags, sp.blk.bneg);
   if (!with_rhs) return;
   for (int q = nlev - 1; q >= 0; --q) {
     const int st = levels[q];
     const int ne = (nb - st + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, sp.bF, sp.bX, nb, st);
+    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, sp.blk.bF, sp.vec.brhs, nb, st);
   }
   if (guard) sp_launch_bw_residual(s, sp, N, flags);
 }
@@ -229,20 +229,20 @@ template <int B>
 static void bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard) {
   const int nb = (N + B - 1) / B;
   const dim3 blk(BW_THREADS);
-  ++sp.stat_bw_solve;
-  hipLaunchKernelGGL(k_bw_load, dim3((nb * B + 255) / 256), dim3(256), 0, s, sp.brhs, N, nb * B, sp.bF,
-                     guard ? sp.brhs0 : nullptr);
+  ++sp.cnt.stat_bw_solve;
+  hipLaunchKernelGGL(k_bw_load, dim3((nb * B + 255) / 256), dim3(256), 0, s, sp.vec.brhs, N, nb * B, sp.blk.bF,
+                     guard ? sp.vec.brhs0 : nullptr);
   int levels[32], nlev = 0;
   for (int st = 1; st < nb; st *= 2) {
     const int nk = (nb + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_fwd<B>, dim3(nk), blk, 0, s, sp.bMr, sp.bMl, sp.bF, nb, st);
+    hipLaunchKernelGGL(k_bw_fwd<B>, dim3(nk), blk, 0, s, sp.blk.bMr, sp.blk.bMl, sp.blk.bF, nb, st);
     levels[nlev++] = st;
   }
-  hipLaunchKernelGGL(k_bw_x0<B>, dim3(1), blk, 0, s, sp.bDinv, sp.bF, sp.bX);
+  hipLaunchKernelGGL(k_bw_x0<B>, dim3(1), blk, 0, s, sp.blk.bDinv, sp.blk.bF, sp.vec.brhs);
   for (int q = nlev - 1; q >= 0; --q) {
     const int st = levels[q];
     const int ne = (nb - st + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.bDinv, sp.bL, sp.bU, sp.bF, sp.bX, nb, st);
+    hipLaunchKernelGGL(k_bw_back<B>, dim3(ne), blk, 0, s, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, sp.blk.bF, sp.vec.brhs, nb, st);
   }
   if (guard) sp_launch_bw_residual(s, sp, N, flags);
 }
@@ -251,7 +251,7 @@ template <int B>
 static void bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp) {
   const int nb = (N + B - 1) / B;
   const dim3 blk(BW_THREADS);
-  ++sp.stat_bw_panel;
+  ++sp.cnt.stat_bw_panel;
   // a panel wider than 64 columns (a multiple of 64 then): one 64-column slice per blockIdx.y, in
   // the same launches -- the slices share the factors and nothing else
   const int ld = kp, kw = kp > 64 ? 64 : kp;
@@ -259,53 +259,53 @@ static void bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P,
   int levels[32], nlev = 0;
   for (int st = 1; st < nb; st *= 2) {
     const int nk = (nb + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_fwd_panel<B>, dim3(nk, ns), blk, 0, s, sp.bMr, sp.bMl, P, ld, kw, nb, st);
+    hipLaunchKernelGGL(k_bw_fwd_panel<B>, dim3(nk, ns), blk, 0, s, sp.blk.bMr, sp.blk.bMl, P, ld, kw, nb, st);
     levels[nlev++] = st;
   }
-  hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(1, ns), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, ld, kw, nb, 0, 0, 1);
+  hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(1, ns), blk, 0, s, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, P, ld, kw, nb, 0, 0, 1);
   for (int q = nlev - 1; q >= 0; --q) {
     const int st = levels[q];
     const int ne = (nb - st + 2 * st - 1) / (2 * st);
-    hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(ne, ns), blk, 0, s, sp.bDinv, sp.bL, sp.bU, P, ld, kw, nb, st,
+    hipLaunchKernelGGL(k_bw_back_panel<B>, dim3(ne, ns), blk, 0, s, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, P, ld, kw, nb, st,
                        st, 2 * st);
   }
 }
 
-// Solve the banded system in sp.band / sp.brhs with B = sp.B x sp.B blocks (16, 32, 64); the
-// solution replaces sp.brhs (which holds whole blocks: sp.bX).  flags[0] zero pivot, flags[1]
+// Solve the banded system in sp.pat.band / sp.vec.brhs with B = sp.blk.B x sp.blk.B blocks (16, 32, 64); the
+// solution replaces sp.vec.brhs (which holds whole blocks).  flags[0] zero pivot, flags[1]
 // negative pivots; guard: keep the right-hand side and finish with the residual (bres, bred).
-// keep: also leave the forward multipliers in sp.bMr / sp.bMl (the same solution, bit for bit).
+// keep: also leave the forward multipliers in sp.blk.bMr / sp.blk.bMl (the same solution, bit for bit).
 void sp_launch_bw_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard, bool keep) {
   if (N == 0) {
     (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
     return;
   }
-  switch (sp.B) {
+  switch (sp.blk.B) {
     case 16: bw_solve<16>(s, sp, N, flags, guard, keep, true); break;
     case 32: bw_solve<32>(s, sp, N, flags, guard, keep, true); break;
     default: bw_solve<64>(s, sp, N, flags, guard, keep, true); break;
   }
 }
 
-// The KEEP reduction without a right-hand side: factors and pivot flags only; sp.brhs survives.
+// The KEEP reduction without a right-hand side: factors and pivot flags only; sp.vec.brhs survives.
 void sp_launch_bw_factor(hipStream_t s, const SparseDev &sp, int N, int *flags) {
   if (N == 0) {
     (void)hipMemsetAsync(flags, 0, 4 * sizeof(int), s);
     return;
   }
-  switch (sp.B) {
+  switch (sp.blk.B) {
     case 16: bw_solve<16>(s, sp, N, flags, false, true, false); break;
     case 32: bw_solve<32>(s, sp, N, flags, false, true, false); break;
     default: bw_solve<64>(s, sp, N, flags, false, true, false); break;
   }
 }
 
-// Solve phase against the factors a KEEP reduction left, for the right-hand side in sp.brhs: load,
+// Solve phase against the factors a KEEP reduction left, for the right-hand side in sp.vec.brhs: load,
 // one forward launch per level, x_0, one backward launch per level (2 levels + 3 launches with the
 // guard's residual; no inversion, no MFMA).  The pivot flags stay what the reduction reported.
 void sp_launch_bw_backsolve(hipStream_t s, const SparseDev &sp, int N, const int *flags, bool guard) {
   if (N == 0) return;
-  switch (sp.B) {
+  switch (sp.blk.B) {
     case 16: bw_backsolve<16>(s, sp, N, flags, guard); break;
     case 32: bw_backsolve<32>(s, sp, N, flags, guard); break;
     default: bw_backsolve<64>(s, sp, N, flags, guard); break;
@@ -327,16 +327,16 @@ __global__ __launch_bounds__(256) void k_bw_panel_get(int N, const double *__res
 }
 void sp_launch_bw_panel_put(hipStream_t s, const SparseDev &sp, int N, const double *in, double *P, int kp,
                             int j) {
-  if (N) hipLaunchKernelGGL(k_bw_panel_put, dim3((N + 255) / 256), dim3(256), 0, s, N, sp.pos, in, P, kp, j);
+  if (N) hipLaunchKernelGGL(k_bw_panel_put, dim3((N + 255) / 256), dim3(256), 0, s, N, sp.pat.pos, in, P, kp, j);
 }
 void sp_launch_bw_panel_get(hipStream_t s, int N, const double *P, int kp, int j, double *out) {
   if (N) hipLaunchKernelGGL(k_bw_panel_get, dim3((N + 255) / 256), dim3(256), 0, s, N, P, kp, j, out);
 }
-// the guard's residual of sp.brhs against sp.brhs0 with the pairs written to `pairs`
+// the guard's residual of sp.vec.brhs against sp.vec.brhs0 with the pairs written to `pairs`
 void sp_launch_bw_residual_to(hipStream_t s, const SparseDev &sp, int N, const int *flags, double *pairs) {
   if (N == 0) return;
-  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, N,
-                     sp.brhs, sp.brhs0, sp.bres, pairs, flags, sp.nred);
+  hipLaunchKernelGGL(k_bw_residual, dim3((N + 255) / 256), dim3(256), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, N,
+                     sp.vec.brhs, sp.vec.brhs0, sp.vec.bres, pairs, flags, sp.vec.nred);
 }
 
 // Solve phase for a panel: P is (nb B) x kp row-major, kp a multiple of 16 up to 64 or a multiple
@@ -344,7 +344,7 @@ void sp_launch_bw_residual_to(hipStream_t s, const SparseDev &sp, int N, const i
 // solutions replace the right-hand sides.
 void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double *P, int kp) {
   if (N == 0) return;
-  switch (sp.B) {
+  switch (sp.blk.B) {
     case 16: bw_panel_solve<16>(s, sp, N, P, kp); break;
     case 32: bw_panel_solve<32>(s, sp, N, P, kp); break;
     default: bw_panel_solve<64>(s, sp, N, P, kp); break;
@@ -364,7 +364,7 @@ void sp_launch_bw_panel_solve(hipStream_t s, const SparseDev &sp, int N, double 
 // on (BandShape::split), ctl[0] == 0 for an instance that is not frozen means: its matrix did not
 // change and the last reduction of its band was clean (kbb_band_step_update sets ctl[1], kb_mask_adopt
 // and kb_advance clear it) -- the situation in which one handle runs the solve phase against its kept
-// factors (SparseDev::kept == 2).  So every twin branches on ctl[0]:
+// factors (SparseDev::blk.kept == 2).  So every twin branches on ctl[0]:
 //
 //   twin of    ctl[0] != 0, or split off            ctl[0] == 0 and split on
 //   extract    whole extraction                     right-hand side part only (k_bw_load's work)

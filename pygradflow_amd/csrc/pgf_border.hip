@@ -27,10 +27,10 @@
 
 static inline dim3 g1(int n, int b = 256) { return dim3((n + b - 1) / b); }
 
-// the banded solve of B: sp.brhs[0, N) <- inv(B) sp.brhs[0, N) (the solution is written in whole
+// the banded solve of B: sp.vec.brhs[0, N) <- inv(B) sp.vec.brhs[0, N) (the solution is written in whole
 // blocks: up to 63 entries behind N are overwritten)
 static void band_solve(hipStream_t s, const SparseDev &sp, int N, int *flags) {
-  if (sp.B > 8)
+  if (sp.blk.B > 8)
     sp_launch_bw_solve(s, sp, N, flags, /*guard=*/false);
   else
     sp_launch_bcr_solve(s, sp, N, flags, /*guard=*/false);
@@ -48,10 +48,10 @@ __global__ void k_border_set_diag(int n, int m, const int *__restrict__ pos,
 
 void sp_border_assemble(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
                         double lamb, double delta) {
-  const size_t total = (size_t)(sp.Nb + 1) * sp.ldb + (size_t)sp.Nb * sp.bkp + (size_t)sp.bkp * sp.bkp;
-  (void)hipMemsetAsync(sp.band, 0, total * sizeof(double), s);
-  hipLaunchKernelGGL(k_border_set_diag, g1(n + m + sp.bkp - sp.bk), dim3(256), 0, s, n, m, sp.pos, mask, lamb,
-                     delta, sp.band, sp.ldb, sp.Nb, sp.bDd, sp.bk, sp.bkp);
+  const size_t total = (size_t)(sp.bor.Nb + 1) * sp.pat.ldb + (size_t)sp.bor.Nb * sp.bor.bkp + (size_t)sp.bor.bkp * sp.bor.bkp;
+  (void)hipMemsetAsync(sp.pat.band, 0, total * sizeof(double), s);
+  hipLaunchKernelGGL(k_border_set_diag, g1(n + m + sp.bor.bkp - sp.bor.bk), dim3(256), 0, s, n, m, sp.pat.pos, mask, lamb,
+                     delta, sp.pat.band, sp.pat.ldb, sp.bor.Nb, sp.bor.bDd, sp.bor.bk, sp.bor.bkp);
   sp_launch_scatter(s, sp, mask);
 }
 
@@ -84,18 +84,18 @@ __global__ __launch_bounds__(64) void k_mbcr_back(const double *__restrict__ D, 
 }
 
 static void mbcr_solve(hipStream_t s, const SparseDev &sp) {
-  const int N = sp.Nb, R = sp.bkp, nb = (N + 7) / 8;
-  hipLaunchKernelGGL(k_mbcr_extract, dim3(nb), dim3(64), 0, s, sp.band, sp.ldb, sp.bw, sp.bC, R, N, nb, sp.bD,
-                     sp.bL, sp.bU, sp.bY);
+  const int N = sp.bor.Nb, R = sp.bor.bkp, nb = (N + 7) / 8;
+  hipLaunchKernelGGL(k_mbcr_extract, dim3(nb), dim3(64), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, sp.bor.bC, R, N, nb, sp.blk.bD,
+                     sp.blk.bL, sp.blk.bU, sp.bor.bY);
   int st = 1;
   for (; st < nb; st *= 2) {
     const int nk = (nb + 2 * st - 1) / (2 * st);  // kept: 0, 2 st, ...
-    hipLaunchKernelGGL(k_mbcr_level, dim3(nk), dim3(64), 0, s, sp.bD, sp.bL, sp.bU, sp.bDinv, sp.bY, R, nb, st);
+    hipLaunchKernelGGL(k_mbcr_level, dim3(nk), dim3(64), 0, s, sp.blk.bD, sp.blk.bL, sp.blk.bU, sp.blk.bDinv, sp.bor.bY, R, nb, st);
   }
-  hipLaunchKernelGGL(k_mbcr_back, dim3(1), dim3(64), 0, s, sp.bD, sp.bDinv, sp.bL, sp.bU, sp.bY, R, nb, 0);
+  hipLaunchKernelGGL(k_mbcr_back, dim3(1), dim3(64), 0, s, sp.blk.bD, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, sp.bor.bY, R, nb, 0);
   for (st /= 2; st >= 1; st /= 2) {
     const int ne = (nb - st + 2 * st - 1) / (2 * st);  // eliminated: st, 3 st, ...
-    hipLaunchKernelGGL(k_mbcr_back, dim3(ne), dim3(64), 0, s, sp.bD, sp.bDinv, sp.bL, sp.bU, sp.bY, R, nb, st);
+    hipLaunchKernelGGL(k_mbcr_back, dim3(ne), dim3(64), 0, s, sp.blk.bD, sp.blk.bDinv, sp.blk.bL, sp.blk.bU, sp.bor.bY, R, nb, st);
   }
 }
 
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void k_border_residual(
 // Wide remainder (B = 16, 32, 64) with the factor / solve split on: B is factorised ONCE per
 // assembled matrix (the factor-only KEEP reduction of pgf_band_wide.hip), and every solve with B --
 // the kp columns of Y as one panel, v of each solve phase -- runs against the kept factors.
-static bool wide_kept(const SparseDev &sp) { return sp.B > 8 && sp.split && sp.bMr; }
+static bool wide_kept(const SparseDev &sp) { return sp.blk.B > 8 && sp.blk.split && sp.blk.bMr; }
 
 // The solve phase of the wide band leaves the pivot flags alone, and k_border_small_solve ADDS
 // those of S to them: the flags of B are parked in bsflags[2, 4) by the factor phase (save) and
@@ -181,41 +181,41 @@ __global__ void k_border_bflags(int *__restrict__ flags, int *__restrict__ sflag
 // slices of the same launches beyond) or, PGF_BORDER_MULTI=0, column by column.
 void sp_border_wide_Y(hipStream_t s, const SparseDev &sp, int *flags) {
   static const bool multi = env_on("PGF_BORDER_MULTI");
-  const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
-  sp_launch_bw_factor(s, sp, Nb, flags);  // (reads sp.brhs, writes none of it)
-  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 1);
-  const int nbB = (Nb + sp.B - 1) / sp.B * sp.B;  // Y in whole B-row blocks, the padding rows zero
+  const int Nb = sp.bor.Nb, k = sp.bor.bk, kp = sp.bor.bkp;
+  sp_launch_bw_factor(s, sp, Nb, flags);  // (reads sp.vec.brhs, writes none of it)
+  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bor.bsflags, 1);
+  const int nbB = (Nb + sp.blk.B - 1) / sp.blk.B * sp.blk.B;  // Y in whole B-row blocks, the padding rows zero
   if (multi) {
-    (void)hipMemcpyAsync(sp.bY, sp.bC, (size_t)Nb * kp * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sp.bor.bY, sp.bor.bC, (size_t)Nb * kp * sizeof(double), hipMemcpyDeviceToDevice, s);
     if (nbB > Nb)
-      (void)hipMemsetAsync(sp.bY + (size_t)Nb * kp, 0, (size_t)(nbB - Nb) * kp * sizeof(double), s);
-    sp_launch_bw_panel_solve(s, sp, Nb, sp.bY, kp);
+      (void)hipMemsetAsync(sp.bor.bY + (size_t)Nb * kp, 0, (size_t)(nbB - Nb) * kp * sizeof(double), s);
+    sp_launch_bw_panel_solve(s, sp, Nb, sp.bor.bY, kp);
   } else {
-    (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-    (void)hipMemsetAsync(sp.bY, 0, (size_t)nbB * kp * sizeof(double), s);
+    (void)hipMemcpyAsync(sp.vec.bres, sp.vec.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemsetAsync(sp.bor.bY, 0, (size_t)nbB * kp * sizeof(double), s);
     for (int j = 0; j < k; ++j) {
-      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bC, sp.brhs, 0);
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bor.bC, sp.vec.brhs, 0);
       sp_launch_bw_backsolve(s, sp, Nb, flags, /*guard=*/false);
-      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.brhs, sp.bY, 1);
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.vec.brhs, sp.bor.bY, 1);
     }
-    (void)hipMemcpyAsync(sp.brhs, sp.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sp.vec.brhs, sp.vec.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
   }
 }
 
 // the small border's Gram launch alone (tools: timed against the MFMA kernel at kp = 64)
 void sp_border_gram_fma(hipStream_t s, const SparseDev &sp) {
-  hipLaunchKernelGGL(k_border_gram, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.bY, sp.Nb, sp.bkp, sp.bpart);
+  hipLaunchKernelGGL(k_border_gram, dim3(sp.bor.bnchunk), dim3(256), 0, s, sp.bor.bC, sp.bor.bY, sp.bor.Nb, sp.bor.bkp, sp.bor.bpart);
 }
 
 // ... and of the solve phase: v = inv(B) ra against the kept factors; flags <- pivots of B as kept
 void sp_border_wide_v(hipStream_t s, const SparseDev &sp, int *flags) {
-  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bsflags, 0);
-  sp_launch_bw_backsolve(s, sp, sp.Nb, flags, /*guard=*/false);
+  hipLaunchKernelGGL(k_border_bflags, dim3(1), dim3(64), 0, s, flags, sp.bor.bsflags, 0);
+  sp_launch_bw_backsolve(s, sp, sp.bor.Nb, flags, /*guard=*/false);
 }
 
 void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
-  const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
-  ++sp.stat_bfactor;
+  const int Nb = sp.bor.Nb, k = sp.bor.bk, kp = sp.bor.bkp;
+  ++sp.cnt.stat_bfactor;
   if (sp_border_large(sp)) {  // 65 .. 1024 border nodes: pgf_border_large.hip
     sp_borderL_factor(s, sp, flags);
     return;
@@ -223,24 +223,24 @@ void sp_border_factor(hipStream_t s, const SparseDev &sp, int *flags) {
   // PGF_BORDER_MULTI=0: Y column by column through the single-right-hand-side solves at every B:
   // slower, and an independent check of the panel kernels
   static const bool multi = env_on("PGF_BORDER_MULTI");
-  if (sp.B == 8 && multi) {
+  if (sp.blk.B == 8 && multi) {
     mbcr_solve(s, sp);
   } else if (wide_kept(sp)) {
     sp_border_wide_Y(s, sp, flags);
   } else {
-    // the band solves work in sp.brhs: whatever right-hand side waits there moves out of the way
-    (void)hipMemcpyAsync(sp.bres, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
-    (void)hipMemsetAsync(sp.bY, 0, (size_t)Nb * kp * sizeof(double), s);
+    // the band solves work in sp.vec.brhs: whatever right-hand side waits there moves out of the way
+    (void)hipMemcpyAsync(sp.vec.bres, sp.vec.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemsetAsync(sp.bor.bY, 0, (size_t)Nb * kp * sizeof(double), s);
     for (int j = 0; j < k; ++j) {
-      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bC, sp.brhs, 0);
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.bor.bC, sp.vec.brhs, 0);
       band_solve(s, sp, Nb, flags);
-      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.brhs, sp.bY, 1);
+      hipLaunchKernelGGL(k_border_col, g1(Nb), dim3(256), 0, s, Nb, kp, j, sp.vec.brhs, sp.bor.bY, 1);
     }
-    (void)hipMemcpyAsync(sp.brhs, sp.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sp.vec.brhs, sp.vec.bres, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
   }
-  hipLaunchKernelGGL(k_border_gram, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.bY, Nb, kp, sp.bpart);
-  hipLaunchKernelGGL(k_border_factor_S, dim3(1), dim3(256), 0, s, sp.bDd, sp.bpart, sp.bnchunk, kp, sp.bS,
-                     sp.bsflags);
+  hipLaunchKernelGGL(k_border_gram, dim3(sp.bor.bnchunk), dim3(256), 0, s, sp.bor.bC, sp.bor.bY, Nb, kp, sp.bor.bpart);
+  hipLaunchKernelGGL(k_border_factor_S, dim3(1), dim3(256), 0, s, sp.bor.bDd, sp.bor.bpart, sp.bor.bnchunk, kp, sp.bor.bS,
+                     sp.bor.bsflags);
 }
 
 void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags) {
@@ -248,32 +248,32 @@ void sp_border_residual(hipStream_t s, const SparseDev &sp, const int *flags) {
     sp_borderL_residual(s, sp, flags);
     return;
   }
-  hipLaunchKernelGGL(k_border_ctv, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.brhs, sp.Nb, sp.bkp, sp.bpartv);
-  hipLaunchKernelGGL(k_border_residual, dim3(sp.nred), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, sp.Nb, sp.bk,
-                     sp.bkp, sp.bC, sp.bDd, sp.bpartv, sp.bnchunk, sp.brhs, sp.brhs0, sp.bres, sp.bred, flags,
-                     sp.nred);
+  hipLaunchKernelGGL(k_border_ctv, dim3(sp.bor.bnchunk), dim3(256), 0, s, sp.bor.bC, sp.vec.brhs, sp.bor.Nb, sp.bor.bkp, sp.bor.bpartv);
+  hipLaunchKernelGGL(k_border_residual, dim3(sp.vec.nred), dim3(256), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, sp.bor.Nb, sp.bor.bk,
+                     sp.bor.bkp, sp.bor.bC, sp.bor.bDd, sp.bor.bpartv, sp.bor.bnchunk, sp.vec.brhs, sp.vec.brhs0, sp.vec.bres, sp.vec.bred, flags,
+                     sp.vec.nred);
 }
 
 void sp_border_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard) {
-  const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
-  ++sp.stat_bsolve;
+  const int Nb = sp.bor.Nb, k = sp.bor.bk, kp = sp.bor.bkp;
+  ++sp.cnt.stat_bsolve;
   if (sp_border_large(sp)) {
     sp_borderL_solve(s, sp, flags, guard);
     return;
   }
   // (the band solve writes whole blocks: the border entries behind Nb do not survive it)
-  (void)hipMemcpyAsync(sp.brb, sp.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
+  (void)hipMemcpyAsync(sp.bor.brb, sp.vec.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (guard)
-    (void)hipMemcpyAsync(sp.brhs0, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sp.vec.brhs0, sp.vec.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (wide_kept(sp)) {
     sp_border_wide_v(s, sp, flags);
   } else {
     band_solve(s, sp, Nb, flags);  // v = inv(B) ra; flags <- pivots of B
   }
-  hipLaunchKernelGGL(k_border_ctv, dim3(sp.bnchunk), dim3(256), 0, s, sp.bC, sp.brhs, Nb, kp, sp.bpartv);
-  hipLaunchKernelGGL(k_border_small_solve, dim3(1), dim3(64), 0, s, sp.bS, k, kp, sp.brb, sp.bpartv, sp.bnchunk,
-                     sp.bsflags, sp.bz, sp.brhs + Nb, flags);
-  hipLaunchKernelGGL(k_border_update, g1(Nb), dim3(256), 0, s, Nb, k, kp, sp.bY, sp.bz, sp.brhs);
+  hipLaunchKernelGGL(k_border_ctv, dim3(sp.bor.bnchunk), dim3(256), 0, s, sp.bor.bC, sp.vec.brhs, Nb, kp, sp.bor.bpartv);
+  hipLaunchKernelGGL(k_border_small_solve, dim3(1), dim3(64), 0, s, sp.bor.bS, k, kp, sp.bor.brb, sp.bor.bpartv, sp.bor.bnchunk,
+                     sp.bor.bsflags, sp.bor.bz, sp.vec.brhs + Nb, flags);
+  hipLaunchKernelGGL(k_border_update, g1(Nb), dim3(256), 0, s, Nb, k, kp, sp.bor.bY, sp.bor.bz, sp.vec.brhs);
   if (guard) sp_border_residual(s, sp, flags);
 }
 

@@ -148,9 +148,9 @@ void sp_borderL_gram_plan(int Nb, int kp, int *rows, int *chunks) {
 // Device time of the Gram launch alone, the mean over reps launches between two events, on
 // the C and Y of the handle's last factor phase (tools/time_border.py): the MFMA kernel into a
 // scratch buffer of its own, and for kp <= 64 the small border's FMA kernel (k_border_gram) into
-// sp.bpart, which the factor phase has consumed.  kp must be a multiple of 64.
+// sp.bor.bpart, which the factor phase has consumed.  kp must be a multiple of 64.
 hipError_t sp_borderL_gram_time(hipStream_t s, const SparseDev &sp, int reps, double *ms_mfma, double *ms_fma) {
-  const int Nb = sp.Nb, kp = sp.bkp, nt = kp / BL_T, ntiles = nt * (nt + 1) / 2;
+  const int Nb = sp.bor.Nb, kp = sp.bor.bkp, nt = kp / BL_T, ntiles = nt * (nt + 1) / 2;
   int rows, chunks;
   sp_borderL_gram_plan(Nb, kp, &rows, &chunks);
   double *part = nullptr;
@@ -168,7 +168,7 @@ hipError_t sp_borderL_gram_time(hipStream_t s, const SparseDev &sp, int reps, do
     for (int it = -2; it < reps; ++it) {  // two warm-up launches
       if (it == 0) (void)hipEventRecord(e0, s);
       if (variant == 0)
-        hipLaunchKernelGGL(k_borderL_gram, dim3(ntiles, chunks), dim3(256), 0, s, sp.bC, sp.bY, Nb, kp, rows, part);
+        hipLaunchKernelGGL(k_borderL_gram, dim3(ntiles, chunks), dim3(256), 0, s, sp.bor.bC, sp.bor.bY, Nb, kp, rows, part);
       else
         sp_border_gram_fma(s, sp);
     }
@@ -372,12 +372,12 @@ __global__ void k_borderL_sflags(int *__restrict__ sflags, int bad, int neg) {
 
 // ---------------------------------------------------------------- phases
 void sp_borderL_factor(hipStream_t s, const SparseDev &sp, int *flags) {
-  const int Nb = sp.Nb, kp = sp.bkp;
-  DenseLdlt &f = *sp.blf;
+  const int Nb = sp.bor.Nb, kp = sp.bor.bkp;
+  DenseLdlt &f = *sp.bor.blf;
   sp_border_wide_Y(s, sp, flags);  // the factors of B, its flags parked, Y = inv(B) C
   const int nt = kp / BL_T, ntiles = nt * (nt + 1) / 2;
-  hipLaunchKernelGGL(k_borderL_gram, dim3(ntiles, sp.bgchunks), dim3(256), 0, s, sp.bC, sp.bY, Nb, kp, sp.bgrows,
-                     sp.bpart);
+  hipLaunchKernelGGL(k_borderL_gram, dim3(ntiles, sp.bor.bgchunks), dim3(256), 0, s, sp.bor.bC, sp.bor.bY, Nb, kp, sp.bor.bgrows,
+                     sp.bor.bpart);
   // S into the dense factor and its L D L'; the status is awaited here, once per assembled matrix
   // (a solve phase never waits).  Status 2 -- the diagonal chain's helper workgroups failed their
   // checks and are off now -- means nothing of that factor is to be trusted: S is formed again from
@@ -385,43 +385,43 @@ void sp_borderL_factor(hipStream_t s, const SparseDev &sp, int *flags) {
   int st = -1;
   for (int attempt = 0; attempt < 2; ++attempt) {
     hipLaunchKernelGGL(k_borderL_schur, dim3((unsigned)(((int64_t)kp * kp + 255) / 256)), dim3(256), 0, s,
-                       sp.bpart, sp.bgchunks, kp, sp.bDd, sp.bG, f.K, f.ldk);
+                       sp.bor.bpart, sp.bor.bgchunks, kp, sp.bor.bDd, sp.bor.bG, f.K, f.ldk);
     hipError_t e = ldlt_factor_async(f, kp, kp);
     st = e == hipSuccess ? ldlt_finish(f, &e) : -1;
     if (st != 2) break;
   }
-  sp.bgram_ready = true;
+  sp.bor.gram_ready = true;
   // Anything but a clean factor reaches the caller as a bad pivot at its next look at the flags --
   // intended also for a HIP error (st < 0) and for helpers that failed twice (st == 2), which
   // pgf_ls_create_dense reports as PGF_HIP_ERROR: this function has no return path of its own (the
   // four entry points are void and enqueue), the step is rejected either way, and a HIP error on the
   // stream comes back as such from the caller's own synchronisation right behind.
-  hipLaunchKernelGGL(k_borderL_sflags, dim3(1), dim3(64), 0, s, sp.bsflags, st == 0 ? 0 : 1, st == 0 ? f.n_neg : 0);
+  hipLaunchKernelGGL(k_borderL_sflags, dim3(1), dim3(64), 0, s, sp.bor.bsflags, st == 0 ? 0 : 1, st == 0 ? f.n_neg : 0);
 }
 
 void sp_borderL_residual(hipStream_t s, const SparseDev &sp, const int *flags) {
-  hipLaunchKernelGGL(k_borderL_ctv, dim3(sp.bnchunk, sp.bkp / 64), dim3(256), 0, s, sp.bC, sp.brhs, sp.Nb, sp.bkp,
-                     sp.bpartv);
-  hipLaunchKernelGGL(k_borderL_residual, dim3(sp.nred), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, sp.Nb, sp.bk,
-                     sp.bkp, sp.bC, sp.bDd, sp.bpartv, sp.bnchunk, sp.brhs, sp.brhs0, sp.bres, sp.bred, flags,
-                     sp.nred);
+  hipLaunchKernelGGL(k_borderL_ctv, dim3(sp.bor.bnchunk, sp.bor.bkp / 64), dim3(256), 0, s, sp.bor.bC, sp.vec.brhs, sp.bor.Nb, sp.bor.bkp,
+                     sp.bor.bpartv);
+  hipLaunchKernelGGL(k_borderL_residual, dim3(sp.vec.nred), dim3(256), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, sp.bor.Nb, sp.bor.bk,
+                     sp.bor.bkp, sp.bor.bC, sp.bor.bDd, sp.bor.bpartv, sp.bor.bnchunk, sp.vec.brhs, sp.vec.brhs0, sp.vec.bres, sp.vec.bred, flags,
+                     sp.vec.nred);
 }
 
 void sp_borderL_solve(hipStream_t s, const SparseDev &sp, int *flags, bool guard) {
-  const int Nb = sp.Nb, k = sp.bk, kp = sp.bkp;
-  DenseLdlt &f = *sp.blf;
+  const int Nb = sp.bor.Nb, k = sp.bor.bk, kp = sp.bor.bkp;
+  DenseLdlt &f = *sp.bor.blf;
   // (the band solve writes whole blocks: the border entries behind Nb do not survive it)
-  (void)hipMemcpyAsync(sp.brb, sp.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
+  (void)hipMemcpyAsync(sp.bor.brb, sp.vec.brhs + Nb, (size_t)k * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (guard)
-    (void)hipMemcpyAsync(sp.brhs0, sp.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(sp.vec.brhs0, sp.vec.brhs, (size_t)(Nb + k) * sizeof(double), hipMemcpyDeviceToDevice, s);
   sp_border_wide_v(s, sp, flags);  // v = inv(B) ra against the kept factors; flags <- pivots of B as kept
-  hipLaunchKernelGGL(k_borderL_ctv, dim3(sp.bnchunk, kp / 64), dim3(256), 0, s, sp.bC, sp.brhs, Nb, kp, sp.bpartv);
-  hipLaunchKernelGGL(k_borderL_rhs, dim3((kp + 255) / 256), dim3(256), 0, s, kp, sp.brb, sp.bpartv, sp.bnchunk,
-                     sp.bS);
+  hipLaunchKernelGGL(k_borderL_ctv, dim3(sp.bor.bnchunk, kp / 64), dim3(256), 0, s, sp.bor.bC, sp.vec.brhs, Nb, kp, sp.bor.bpartv);
+  hipLaunchKernelGGL(k_borderL_rhs, dim3((kp + 255) / 256), dim3(256), 0, s, kp, sp.bor.brb, sp.bor.bpartv, sp.bor.bnchunk,
+                     sp.bor.bS);
   // (a factor that failed is reported through the flags; the solve then runs on whatever is there,
   // as the small route's does, and its result is discarded with the step)
-  (void)ldlt_solve_async(f, sp.bS, sp.bz);
-  hipLaunchKernelGGL(k_borderL_update, dim3((Nb + 63) / 64), dim3(256), 0, s, Nb, k, kp, sp.bY, sp.bz, sp.brhs,
-                     sp.bsflags, flags);
+  (void)ldlt_solve_async(f, sp.bor.bS, sp.bor.bz);
+  hipLaunchKernelGGL(k_borderL_update, dim3((Nb + 63) / 64), dim3(256), 0, s, Nb, k, kp, sp.bor.bY, sp.bor.bz, sp.vec.brhs,
+                     sp.bor.bsflags, flags);
   if (guard) sp_borderL_residual(s, sp, flags);
 }

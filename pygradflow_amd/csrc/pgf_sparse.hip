@@ -117,29 +117,29 @@ void sp_launch_spmvT(hipStream_t s, int cols, const int *tptr, const int *trow, 
 
 void sp_launch_eval(hipStream_t s, const SparseDev &sp, int n, int m, const double *x, const double *y,
                     const double *b, const double *q, double rho, double *c, double *w, double *g) {
-  if (m) hipLaunchKernelGGL(k_sp_eval_c, g1(m), dim3(256), 0, s, m, sp.Jptr, sp.Jcol, sp.Jval, x, b, rho, y, c, w);
+  if (m) hipLaunchKernelGGL(k_sp_eval_c, g1(m), dim3(256), 0, s, m, sp.pat.Jptr, sp.pat.Jcol, sp.pat.Jval, x, b, rho, y, c, w);
   if (n)
-    hipLaunchKernelGGL(k_sp_eval_g, g1(n), dim3(256), 0, s, n, sp.Hptr, sp.Hcol, sp.Hval, sp.JTptr, sp.JTrow,
-                       sp.JTmap, sp.Jval, x, w, q, g);
+    hipLaunchKernelGGL(k_sp_eval_g, g1(n), dim3(256), 0, s, n, sp.pat.Hptr, sp.pat.Hcol, sp.pat.Hval, sp.pat.JTptr, sp.pat.JTrow,
+                       sp.pat.JTmap, sp.pat.Jval, x, w, q, g);
 }
 
 void sp_launch_assemble(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
                         double lamb, double delta) {
   const int N = n + m;
-  (void)hipMemsetAsync(sp.band, 0, (size_t)(N + 1) * sp.ldb * sizeof(double), s);
-  hipLaunchKernelGGL(k_band_set_diag, g1(N), dim3(256), 0, s, n, m, sp.pos, mask, lamb, delta,
-                     sp.band, sp.ldb);
+  (void)hipMemsetAsync(sp.pat.band, 0, (size_t)(N + 1) * sp.pat.ldb * sizeof(double), s);
+  hipLaunchKernelGGL(k_band_set_diag, g1(N), dim3(256), 0, s, n, m, sp.pat.pos, mask, lamb, delta,
+                     sp.pat.band, sp.pat.ldb);
   sp_launch_scatter(s, sp, mask);
 }
 
 // the stored entries of H and J into their slots (band, or the border store behind it)
 void sp_launch_scatter(hipStream_t s, const SparseDev &sp, const uint8_t *mask) {
-  if (sp.nnzH)
-    hipLaunchKernelGGL(k_band_scatter_H, g1(sp.nnzH), dim3(256), 0, s, sp.nnzH, sp.Hrow, sp.Hcol,
-                       sp.Hval, sp.Hslot, mask, sp.band);
-  if (sp.nnzJ)
-    hipLaunchKernelGGL(k_band_scatter_J, g1(sp.nnzJ), dim3(256), 0, s, sp.nnzJ, sp.Jcol, sp.Jval,
-                       sp.Jslot, mask, sp.band);
+  if (sp.pat.nnzH)
+    hipLaunchKernelGGL(k_band_scatter_H, g1(sp.pat.nnzH), dim3(256), 0, s, sp.pat.nnzH, sp.pat.Hrow, sp.pat.Hcol,
+                       sp.pat.Hval, sp.pat.Hslot, mask, sp.pat.band);
+  if (sp.pat.nnzJ)
+    hipLaunchKernelGGL(k_band_scatter_J, g1(sp.pat.nnzJ), dim3(256), 0, s, sp.pat.nnzJ, sp.pat.Jcol, sp.pat.Jval,
+                       sp.pat.Jslot, mask, sp.pat.band);
 }
 
 void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8_t *mask,
@@ -147,13 +147,13 @@ void sp_launch_rhs(hipStream_t s, const SparseDev &sp, int n, int m, const uint8
   (void)Hb0;
   (void)Jb0;
   if (n + m)
-    hipLaunchKernelGGL(k_band_rhs_fused, g1(n + m), dim3(256), 0, s, n, m, mask, F, b0full, sp.Hptr, sp.Hcol,
-                       sp.Hval, sp.Jptr, sp.Jcol, sp.Jval, fact, sp.pos, sp.brhs);
+    hipLaunchKernelGGL(k_band_rhs_fused, g1(n + m), dim3(256), 0, s, n, m, mask, F, b0full, sp.pat.Hptr, sp.pat.Hcol,
+                       sp.pat.Hval, sp.pat.Jptr, sp.pat.Jcol, sp.pat.Jval, fact, sp.pat.pos, sp.vec.brhs);
 }
 
 void sp_launch_permute(hipStream_t s, const SparseDev &sp, int N, const double *in, double *out,
                        int gather) {
-  if (N) hipLaunchKernelGGL(k_band_permute, g1(N), dim3(256), 0, s, N, sp.pos, in, out, gather);
+  if (N) hipLaunchKernelGGL(k_band_permute, g1(N), dim3(256), 0, s, N, sp.pat.pos, in, out, gather);
 }
 
 void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, double fact,
@@ -162,7 +162,7 @@ void sp_launch_step_update(hipStream_t s, const SparseDev &sp, int n, int m, dou
                            double *yn, double *red) {
   const int nb = (n + m + 255) / 256;
   if (nb)
-    hipLaunchKernelGGL(k_band_step_update, dim3(nb), dim3(256), 0, s, n, m, sp.pos, sp.brhs, fact,
+    hipLaunchKernelGGL(k_band_step_update, dim3(nb), dim3(256), 0, s, n, m, sp.pat.pos, sp.vec.brhs, fact,
                        rho, x, y, lb, ub, F, dx, dy, xn, yn, red);
 }
 
@@ -276,8 +276,8 @@ __global__ __launch_bounds__(256) void k_band_residual(const double *__restrict_
 
 void sp_launch_band_residual(hipStream_t s, const SparseDev &sp, int N, const int *flags) {
   if (N == 0) return;
-  hipLaunchKernelGGL(k_band_residual, g1(N), dim3(256), 0, s, sp.band, sp.ldb, sp.bw, N, sp.brhs, sp.brhs0,
-                     sp.bres, sp.bred, flags, sp.nred);
+  hipLaunchKernelGGL(k_band_residual, g1(N), dim3(256), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, N, sp.vec.brhs, sp.vec.brhs0,
+                     sp.vec.bres, sp.vec.bred, flags, sp.vec.nred);
 }
 
 // x = saved + correction (refinement step of the guard)
@@ -325,8 +325,8 @@ BcrPlan sp_bcr_plan(int nb) {
   return p;
 }
 
-// Solve the banded system in sp.band / sp.brhs by block cyclic reduction; the solution
-// replaces sp.brhs.  flags[0] zero pivot, flags[1] negative pivots.
+// Solve the banded system in sp.pat.band / sp.vec.brhs by block cyclic reduction; the solution
+// replaces sp.vec.brhs.  flags[0] zero pivot, flags[1] negative pivots.
 // guard: keep the right-hand side and finish with the residual of the solution (bres, bred);
 // a correction solve of the refinement runs without.
 void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, bool guard) {
@@ -335,53 +335,53 @@ void sp_launch_bcr_solve(hipStream_t s, const SparseDev &sp, int N, int *flags, 
     return;
   }
   const int nb = (N + 7) / 8;
-  hipLaunchKernelGGL(k_bcr_extract, dim3(nb), dim3(64), 0, s, sp.band, sp.ldb, sp.bw, sp.brhs, N, nb,
-                     sp.bD, sp.bL, sp.bU, sp.bF, guard ? sp.brhs0 : nullptr, flags);
+  hipLaunchKernelGGL(k_bcr_extract, dim3(nb), dim3(64), 0, s, sp.pat.band, sp.pat.ldb, sp.pat.bw, sp.vec.brhs, N, nb,
+                     sp.blk.bD, sp.blk.bL, sp.blk.bU, sp.blk.bF, guard ? sp.vec.brhs0 : nullptr, flags);
   const BcrPlan plan = sp_bcr_plan(nb);
-  auto Dp = [&](int set) { return sp.bD + (size_t)set * sp.bstride * 64; };
-  auto Lp = [&](int set) { return sp.bL + (size_t)set * sp.bstride * 64; };
-  auto Up = [&](int set) { return sp.bU + (size_t)set * sp.bstride * 64; };
-  auto Fp = [&](int set) { return sp.bF + (size_t)set * sp.bstride * 8; };
+  auto Dp = [&](int set) { return sp.blk.bD + (size_t)set * sp.blk.bstride * 64; };
+  auto Lp = [&](int set) { return sp.blk.bL + (size_t)set * sp.blk.bstride * 64; };
+  auto Up = [&](int set) { return sp.blk.bU + (size_t)set * sp.blk.bstride * 64; };
+  auto Fp = [&](int set) { return sp.blk.bF + (size_t)set * sp.blk.bstride * 8; };
   for (int q = 0; q < plan.nlev; ++q) {
     const int st = plan.lev[q].s, cur = plan.lev[q].set;
     if (plan.lev[q].pair_set2 >= 0) {
       hipLaunchKernelGGL(k_bcr_level2, dim3(bcr_pair_groups(nb, st)), dim3(192), 0, s, Dp(cur), Lp(cur),
-                         Up(cur), Fp(cur), Dp(cur ^ 1), Lp(cur ^ 1), Up(cur ^ 1), Fp(cur ^ 1), sp.bDinv, nb,
-                         st, flags, sp.bneg);
+                         Up(cur), Fp(cur), Dp(cur ^ 1), Lp(cur ^ 1), Up(cur ^ 1), Fp(cur ^ 1), sp.blk.bDinv, nb,
+                         st, flags, sp.blk.bneg);
       continue;
     }
     const int nk = bcr_kept(nb, st);
     if (plan.fused) {
       hipLaunchKernelGGL(k_bcr_level, dim3(nk), dim3(64), 0, s, Dp(cur), Lp(cur), Up(cur), Fp(cur),
-                         sp.bDinv, nb, st, flags, sp.bneg);
+                         sp.blk.bDinv, nb, st, flags, sp.blk.bneg);
     } else {
       const int ne = bcr_eliminated(nb, st);
       if (ne > 0)
-        hipLaunchKernelGGL(k_bcr_invert, dim3(ne), dim3(64), 0, s, Dp(cur), sp.bDinv, nb, st, st,
-                           2 * st, flags, sp.bneg);
+        hipLaunchKernelGGL(k_bcr_invert, dim3(ne), dim3(64), 0, s, Dp(cur), sp.blk.bDinv, nb, st, st,
+                           2 * st, flags, sp.blk.bneg);
       hipLaunchKernelGGL(k_bcr_reduce, dim3(nk), dim3(64), 0, s, Dp(cur), Lp(cur), Up(cur), Fp(cur),
-                         sp.bDinv, nb, st);
+                         sp.blk.bDinv, nb, st);
     }
   }
   const int cur = plan.tail_set;
-  hipLaunchKernelGGL(k_bcr_tail, dim3(1), dim3(1024), 0, s, Dp(cur), Lp(cur), Up(cur), Fp(cur), sp.bX, nb,
-                     plan.tail_s, flags, sp.bneg);
+  hipLaunchKernelGGL(k_bcr_tail, dim3(1), dim3(1024), 0, s, Dp(cur), Lp(cur), Up(cur), Fp(cur), sp.vec.brhs, nb,
+                     plan.tail_s, flags, sp.blk.bneg);
   for (int q = plan.nlev - 1; q >= 0; --q) {
     const int bs = plan.lev[q].s;
     if (plan.lev[q].pair_set2 >= 0) {
       const int s2 = plan.lev[q].pair_set2, s1 = plan.lev[q].set;
       const int nj = bcr_back_pair_groups(nb, bs);
       if (nj > 0)
-        hipLaunchKernelGGL(k_bcr_back2, dim3(nj), dim3(128), 0, s, sp.bDinv, Lp(s1), Up(s1), Fp(s1),
-                           Lp(s2), Up(s2), Fp(s2), sp.bX, nb, bs);
+        hipLaunchKernelGGL(k_bcr_back2, dim3(nj), dim3(128), 0, s, sp.blk.bDinv, Lp(s1), Up(s1), Fp(s1),
+                           Lp(s2), Up(s2), Fp(s2), sp.vec.brhs, nb, bs);
       continue;
     }
     const int ne = bcr_eliminated(nb, bs);
     if (ne > 0)
-      hipLaunchKernelGGL(k_bcr_back, dim3(ne), dim3(64), 0, s, sp.bDinv, Lp(plan.lev[q].set),
-                         Up(plan.lev[q].set), Fp(plan.lev[q].set), sp.bX, nb, bs, bs, 2 * bs);
+      hipLaunchKernelGGL(k_bcr_back, dim3(ne), dim3(64), 0, s, sp.blk.bDinv, Lp(plan.lev[q].set),
+                         Up(plan.lev[q].set), Fp(plan.lev[q].set), sp.vec.brhs, nb, bs, bs, 2 * bs);
   }
-  // (sp.bX IS sp.brhs: the back-substitution writes the solution where the caller reads it)
+  // (the back-substitution has written the solution into sp.vec.brhs, where the caller reads it)
   if (guard) sp_launch_band_residual(s, sp, N, flags);
 }
 
@@ -468,7 +468,7 @@ __global__ void kbb_band_scatter_J(const BandInst *__restrict__ tab, BandShape s
 }
 
 // ---------------------------------------------------------------- block cyclic reduction
-// set: which of the instance's two block sets (SparseDev::bstride blocks apart)
+// set: which of the instance's two block sets (SparseDev::blk.bstride blocks apart)
 #define SETP(I, arr, set, w) ((I).arr + (size_t)(set) * sh.bstride * (w))
 
 __global__ __launch_bounds__(64) void kbb_bcr_extract(const BandInst *__restrict__ tab, BandShape sh) {

@@ -304,7 +304,7 @@ def band_split(problem):
 
 
 def _band_split_default():
-    """The library's default (``PGF_BW_SPLIT=0`` switches it off; pgf_api_band.hip reads it alike)."""
+    """The library's default (``PGF_BW_SPLIT=0`` switches it off; pgf_api_band_setup.hip reads it alike)."""
     v = os.environ.get("PGF_BW_SPLIT")
     if v is None:
         return True
