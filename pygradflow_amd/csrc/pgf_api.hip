@@ -178,6 +178,7 @@ int pgf_set_outer(pgf_handle h, const double *xhat, const double *yhat, double d
   if ((rc = up(h, h->xhat, xhat, h->n * sizeof(double)))) return rc;
   if ((rc = up(h, h->yhat, yhat, h->m * sizeof(double)))) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (rho != h->rho) h->eval_fresh = false;  // g depends on rho (as pgf_qp_advance_outer; the point may stay)
   set_outer_scalars(h, dt, rho);
   launch_scale_bounds(h->stream, h->n, h->lamb, h->lb, h->ub, h->slb, h->sub);
   h->outer_set = true;
